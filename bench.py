@@ -8,7 +8,12 @@ SWMatcherKonolige::compute (bm-sw.cpp:33-38) runs.  A "step" is one rtdm_bm_comp
 over a batch of --batch synthetic pairs (default 1024, the stream length of BASELINE config 4) that are
 already resident in HBM.  `value` is measured over EXACTLY --steps steps.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR]
+
+--dump-outputs DIR writes what the last timed step returned to its caller, so that two builds run with the same arguments
+(same seeded inputs) can be compared output for output: DIR/disparity.npy, float32 [n, H, W], the int16 disparity maps of
+n frames of rank 0's batch (all of them, or a fixed seeded sample when the batch is over DUMP_MAX_BYTES), and
+DIR/frame_index.npy, float64 [n], the stream index of each of those frames.
 
 After the headline region, on rank 0 and outside `value`:
   * "sustained": the same step repeated until >= 2 s have passed (a region long enough for an outside sampler to see);
@@ -73,6 +78,8 @@ CONFIGS = [
 # roif = (max x, max y, min w, min h) of ROI1/ROI2 of backup/1280x720/extrinsics.yml:56-57 (main.cpp:80-85)
 REF_CROP = (192, 177, 934, 404)
 REF_ROI1 = (300, 90, 320, 200)   # a union-of-objects box as find_relevant_matching_region would return (estimator.cpp:53)
+DUMP_MAX_BYTES = 64 * 10**6      # --dump-outputs: everything written stays under this, .npy headers included
+DUMP_SEED = 0x5EED               # --dump-outputs: picks the sampled frames; fixed, so every run dumps the same frames
 
 
 def kernel_source_sha():
@@ -83,6 +90,18 @@ def kernel_source_sha():
         if f.endswith((".hip", ".h")):
             h.update(f.encode()); h.update(open(os.path.join(d, f), "rb").read())
     return h.hexdigest()[:16]
+
+
+def dump_outputs(dirname, disp):
+    """--dump-outputs: rank 0's disparity batch [n, H, W] (frame i of it is frame i of the stream) as float32, whole frames: all
+    of them when they fit DUMP_MAX_BYTES, else a fixed seeded sample.  int16 disparities are exact in float32."""
+    import numpy as np
+    n_all, h, w = disp.shape
+    n = min(n_all, (DUMP_MAX_BYTES - 8 * n_all - 1024) // (4 * h * w))
+    idx = np.arange(n_all) if n == n_all else np.sort(np.random.default_rng(DUMP_SEED).choice(n_all, n, replace=False))
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "disparity.npy"), disp[idx.tolist()].float().cpu().numpy())
+    np.save(os.path.join(dirname, "frame_index.npy"), idx.astype(np.float64))
 
 
 def free_port():
@@ -479,6 +498,8 @@ def rccl_stream(args, pkg, torch, dist, rank, local_rank, world, backend):
     el = torch.tensor([time.perf_counter() - t0], dtype=torch.float64, device=dev if backend == "nccl" else "cpu")
     dist.all_reduce(el, op=dist.ReduceOp.MAX)
     el = float(el.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
     # one more pass with events around every scatter / compute / gather (outside the timed region: the scatter's end event makes
     # the side stream wait for it, which the timed passes do not): what overlaps on the first real xGMI run shows up here
     tm = sh.new_timings()
@@ -572,7 +593,12 @@ def main():
                     help="BASELINE config 4 instead of the headline: rank 0 owns FRAMES pairs, scatter -> compute -> gather "
                          "over torch.distributed (RCCL); reports root-sourced pairs/s")
     ap.add_argument("--chunk", type=int, default=128, help="--rccl-stream: frames per scatter/gather per rank (128: 60 k pairs/s at world size 1, 64: 55 k)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the disparity maps of the last timed step (rank 0; a fixed seeded sample of whole frames when "
+                         "the batch is over 64 MB as float32) to DIR/disparity.npy, their stream indices to DIR/frame_index.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.headline_only:
         args.no_cpu_baseline = args.no_single_frame = args.no_configs = True
 
@@ -645,6 +671,8 @@ def main():
     elapsed = allmax(time.perf_counter() - t0)
     stages = m.stage_times()
     m.set_profiling(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dD)
 
     # the same step, repeated until the GPU has been busy for >= 2 s in one stretch: long enough for a sampler outside this
     # process to see it.  Its own figure ("sustained"); `value` stays the K-step region above.

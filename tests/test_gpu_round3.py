@@ -252,6 +252,27 @@ def test_bench_two_ranks_keep_cpu_baseline_and_roofline():
     assert out["roofline"]["achieved"] > 0
 
 
+def test_bench_dump_outputs_repeat_and_are_what_the_timed_path_computed(oracle, synth, tmp_path):
+    # 32 frames of 720p as float32 are over the 64 MB budget: a fixed seeded sample of whole frames, the same in every run
+    args = ["--headline-only", "--steps", "2", "--warmup", "1", "--batch", "32"]
+    dumps = []
+    for name in ("a", "b"):
+        d = tmp_path / name
+        out = _bench(args + ["--dump-outputs", str(d)])
+        assert out["steps"] == 2 and out["ms_per_step"] > 0 and out["parity_ok"] is True
+        assert sorted(os.listdir(d)) == ["disparity.npy", "frame_index.npy"]
+        assert sum(os.path.getsize(d / f) for f in os.listdir(d)) <= 64 * 10**6
+        disp, idx = np.load(d / "disparity.npy"), np.load(d / "frame_index.npy")
+        assert disp.dtype == np.float32 and idx.dtype == np.float64
+        dumps.append((disp, idx))
+    (disp, idx), (disp2, idx2) = dumps
+    assert 0 < len(idx) < 32 and disp.shape == (len(idx), 720, 1280)
+    assert np.array_equal(idx, idx2) and np.array_equal(disp, disp2)
+    for k in (0, len(idx) - 1):
+        L, R = synth.make_pair(synth.STREAM_SEED + int(idx[k]), 1280, 720, 64)
+        assert_same(disp[k].astype(np.int16), oracle.bm_compute(L, R, nthreads=8, numDisparities=64, blockSize=9))
+
+
 def test_two_gpus_over_rccl_when_the_box_has_them():
     """Multi-rank RCCL execution: runs only where torch sees >= 2 GPUs (the driver's 8-GPU node); a one-GPU box skips.  No
     scaling curve is produced or simulated here."""
