@@ -41,7 +41,8 @@ typedef struct rtdm_bm_params {
     int preFilterCap;      /* 1..63 */
     int blockSize;         /* odd, 5..255, smaller than min(width,height) */
     int minDisparity;      /* >= -2047 and minDisparity + numDisparities <= 2047: the x16 output is 16 bits wide */
-    int numDisparities;    /* > 0, multiple of 16 */
+    int numDisparities;    /* > 0, multiple of 16, minDisparity + numDisparities <= 2047 (so up to 4080); every such value is
+                            * served -- the only RTDM_ERR_UNSUPPORTED left for BlockMatcher is max_width > 4096 */
     int textureThreshold;  /* >= 0 */
     int uniquenessRatio;   /* >= 0 */
     int speckleWindowSize; /* <= 0 disables the speckle filter */
@@ -124,6 +125,12 @@ int rtdm_bm_get_tuner_stats(const rtdm_bm* bm, long* shapes_measured, long* timi
  * lanes per pixel where that form of the ring kernel exists; -1 (default): the library's choice (environment RTDM_RING=0/1 and
  * RTDM_RING_LPP=2/4 override it).  Results never depend on it. */
 void rtdm_debug_search_kernel(int mode);
+/* Diagnostic switch, process wide: 0 (default): the library picks the SAD-search kernel and, for the disparity-sliced one
+ * ("generic_dslice_*": configurations whose column sums do not fit the generic kernel's LDS, numDisparities > 256 among
+ * them), its slice width.  dt > 0: EVERY configuration is searched by the disparity-sliced kernel with slices of dt
+ * reversed disparity indices (rounded up to a multiple of 16, capped by numDisparities and by what fits in LDS).  Results
+ * never depend on it; it exists so that tests can put slice boundaries anywhere. */
+void rtdm_debug_disparity_slice(int dt);
 
 /* ---- VideoFilterDevice (morphological open + close, 10x10 ellipse) -----------------------
  * rtdm_morph_create      <- SWMorphologicalFilter::SWMorphologicalFilter (filter/mf-sw.cpp:10-17)

@@ -459,13 +459,16 @@ static int chunk_front(rtdm_bm* bm, const Lane& ln, int n, Plane8 L, Plane8 R, i
     // (+ the speckle filter's run counts = 0); the fill rides in the prefilter's launch
     const FillJob fill{disp, g.cx0, g.cx1, g.vy0, g.vy1, g.filtered, (p.speckleRange >= 0 && p.speckleWindowSize > 0) ? ln.dRowCnt : nullptr};
     StageEvent ev;
-    const bool fast = fast_search_supported(g);
     bool u16 = false;
-    if (!generic_search_supported(g, &u16)) return RTDM_ERR_UNSUPPORTED;
+    // what k_search_generic cannot hold in LDS (D > 256, large windows at large D) -- or everything, when
+    // rtdm_debug_disparity_slice forces it -- is searched by the disparity-sliced kernel over the whole range
+    const bool dslice = !generic_search_supported(g, &u16) || dslice_forced();
+    const bool fast = !dslice && fast_search_supported(g);
     {
         const bool ring = fast && ring_search_supported(g);
         const int lpp = ring ? ring_lanes_per_pixel(g) : 0;
-        bm->variant = ring ? (lpp == 16 ? "fast_ring16_qsad" : lpp == 8 ? "fast_ring8_qsad" : lpp == 4 ? "fast_ring4_qsad" : "fast_ring_qsad") : fast ? "fast_qsad" : (u16 ? "generic_u16" : "generic_u32");
+        bm->variant = dslice ? (u16 ? "generic_dslice_u16" : "generic_dslice_u32")
+                    : ring ? (lpp == 16 ? "fast_ring16_qsad" : lpp == 8 ? "fast_ring8_qsad" : lpp == 4 ? "fast_ring4_qsad" : "fast_ring_qsad") : fast ? "fast_qsad" : (u16 ? "generic_u16" : "generic_u32");
         Plane8W Lp{ln.dLp, bm->ppitch, bm->ppitch * (size_t)H}, Rp{ln.dRp, bm->ppitch, bm->ppitch * (size_t)H};
         stage_begin(bm, RTDM_STAGE_PREFILTER, n, s, &ev);
         launch_prefilter(L, R, Lp, Rp, W, H, p.preFilterCap, n, s, &fill);
@@ -507,6 +510,8 @@ static int chunk_front(rtdm_bm* bm, const Lane& ln, int n, Plane8 L, Plane8 R, i
                 launch_search_generic(Lpr, Rpr, disp, ln.dCost, g, n, s, lx0, lx1);
                 launch_search_generic(Lpr, Rpr, disp, ln.dCost, g, n, s, rx0, rx1);
             }
+        } else if (dslice) {
+            launch_search_dslice(Lpr, Rpr, disp, ln.dCost, g, n, s, g.cx0 - g.lofs, g.cx1 - g.lofs);
         } else {
             launch_search_generic(Lpr, Rpr, disp, ln.dCost, g, n, s, g.cx0 - g.lofs, g.cx1 - g.lofs);
         }
@@ -832,6 +837,7 @@ int rtdm_bm_get_tuner_stats(const rtdm_bm* bm, long* shapes_measured, long* timi
     return RTDM_OK;
 }
 void rtdm_debug_search_kernel(int mode) { ring_set_mode(mode); }
+void rtdm_debug_disparity_slice(int dt) { dslice_set_width(dt); }
 
 // ---- VideoFilterDevice ---------------------------------------------------------------------
 int rtdm_morph_create(int width, int height, int max_batch, int device, rtdm_morph** out)

@@ -77,12 +77,21 @@ void launch_fill16(Plane16W disp, int x0, int x1, int y0, int y1, int n, int val
 void launch_fill_frame(Plane16W disp, int W, int H, int cx0, int cx1, int vy0, int vy1, int n, int value, int32_t* rowcnt,
                        hipStream_t stream);
 
-// K2 (generic variant): any D <= 256, any odd w, LDS column sums; writes disp (+ int32 cost).
-// Returns false if the configuration does not fit (caller reports RTDM_ERR_UNSUPPORTED).
+// K2 (generic variant): D <= 256 and any odd w whose column sums fit LDS; writes disp (+ int32 cost).
+// Returns false if the configuration does not fit (the caller runs launch_search_dslice instead).
 bool generic_search_supported(const BMGeom& g, bool* use16);
 // [gx0, gx1) restricts the output-column range (gx1 < 0: all of [0, width1)).
 void launch_search_generic(Plane8 Lp, Plane8 Rp, Plane16W disp, void* cost, const BMGeom& g,
                            int n, hipStream_t stream, int gx0 = 0, int gx1 = -1);
+
+// K2 (disparity-sliced generic variant, k_search_dslice.hip): every valid configuration (D a multiple of 16 up to 4080,
+// any odd w); the reversed disparity range is walked in slices whose results are folded in index order per pixel.  Same
+// outputs as launch_search_generic, bit for bit.  [gx0, gx1) as there.
+void launch_search_dslice(Plane8 Lp, Plane8 Rp, Plane16W disp, void* cost, const BMGeom& g,
+                          int n, hipStream_t stream, int gx0 = 0, int gx1 = -1);
+int dslice_width(const BMGeom& g, bool use16, int TC);   // the slice width a launch uses
+void dslice_set_width(int dt);   // rtdm_debug_disparity_slice
+bool dslice_forced();            // a slice width is forced: every configuration goes to launch_search_dslice
 
 // K2 (fast variant): packed-u8 quad-SAD kernel for the common configurations.  Works on the
 // prefiltered planes and covers the output columns whose window needs no border clamping; the

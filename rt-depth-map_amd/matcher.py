@@ -15,6 +15,8 @@ from . import binding as B
 
 
 class HIPMatcher:
+    """numOfDisparities: any multiple of 16 with minDisparity + numOfDisparities <= 2047 (up to 4080), any odd blockSize
+    5..255 -- the parameters go to rtdm_bm_create unchanged; only frames wider than 4096 are refused."""
     def __init__(self, roi1=None, roi2=None, preFilterCap=31, blockSize=13, minDisparity=0, textureThreshold=10,
                  numOfDisparities=64, maxDisparity=None, uniquenessRatio=10, speckleWindowSize=100,
                  speckleRange=32, disp12MaxDiff=1, width=1280, height=720, max_batch=1, device=0, legacy_right_clamp=0):
