@@ -168,7 +168,8 @@ typedef struct rtdm_sgm_params {
                             * it does is refused by the compute call (RTDM_ERR_UNSUPPORTED; it takes nearly every pixel of a
                             * window at the maximum pixel cost), and rtdm_sgm_compute_device synchronises its stream to tell */
     int minDisparity;
-    int numDisparities;    /* multiple of 16, <= 256 */
+    int numDisparities;    /* multiple of 16 (any: above 256 the path passes run on the wide-line kernel, k_sgm_wide.hip, and
+                            * the cost volumes cover the column domain only, max_width + min(minD, 0) - max(minD + D, 0)) */
     int P1, P2;            /* as the library: P1 <= 0 -> 2, P2 <= 0 -> 5, P2 >= P1 + 1 */
     int uniquenessRatio;   /* <= 100; < 0 -> 10 */
     int speckleWindowSize; /* <= 0 disables the speckle filter */
@@ -193,6 +194,15 @@ int rtdm_sgm_compute_device(rtdm_sgm* sg, int n, const uint8_t* d_left, const ui
  * each: k_sgm_sweep), *gave_up = 1 once such a pass has given up waiting for a neighbouring strip (the call that finds this
  * returns RTDM_ERR_HIP once; from then on the handle runs one pass per direction).  Either pointer may be NULL. */
 int rtdm_sgm_get_pass_stats(const rtdm_sgm* sg, long* sweeps, int* gave_up);
+/* Name of the path-pass form this handle's last call ran: "sweep" (row-synchronous sweeps), "half" (half-wave lines), "wave",
+ * "block" (the A/B forms), "wide_w1" / "wide_w4" (the wide-line pass, one wave / four waves per line: numDisparities > 256 or
+ * forced); "" before the first call. */
+const char* rtdm_sgm_path_variant(const rtdm_sgm* sg);
+/* Diagnostic switch, process wide: 0 (default): the library's choice (numDisparities > 256 runs the wide-line pass, one wave
+ * per line up to 1024 disparities, four above).  1: EVERY numDisparities runs the wide-line pass, one wave per line where that
+ * holds the line (<= 1024), four waves above.  4: every numDisparities runs the wide-line pass with four waves per line.
+ * Other values mean 0.  Results never depend on it; it exists so that tests can put lane and wave boundaries anywhere. */
+void rtdm_debug_sgm_wide_paths(int lines_per_wave_or_waves);
 
 /* ---- the step after the matcher, kept on the device ------------
  * rtdm_bm_compute_depth <- estimator.cpp:56 + 75-77: bm->compute(...); left_disp /= 16.;

@@ -374,7 +374,7 @@ __device__ __forceinline__ void st_pack(uint16_t* p, const int* l)
 // uniqueness vote, S[d* +- 1] by v_readlane, quadratic sub-pixel in lane 0 -- and S is neither written back nor read again
 // (424 MB of HBM traffic per 720p D = 128 pair, and the select kernel's launch).  What leaves is 8 bytes per pixel:
 // {x16 disparity or INV, integer winner + minD or minD - 1, minimum cost, 0} for k_sgm_lrfinal.
-struct SgmWin { int16_t d16, bd; uint16_t mins, pad; };
+// (SgmWin: rtdm_kernels.h)
 
 template <int NPL, int PF, bool LAST>
 __global__ __launch_bounds__(256) void k_sgm_path_w(const uint16_t* C, uint16_t* S, SGMGeom g, int dx, int dy, int P1, int P2,
@@ -1159,9 +1159,12 @@ static bool launch_sweep(bool last, const SGMGeom& g, const SGMBuffers& b, int d
     }
 }
 
-void launch_sgm(Plane8 L, Plane8 R, Plane16W disp, const SGMGeom& g, const SGMBuffers& b, int blockSize, int P1, int P2,
-                int uniq, int disp12MaxDiff, int speckleWindowSize, int speckleRange, int paths, int n, hipStream_t stream,
-                int cost_limit)
+static void sgm_finish(Plane16W disp, const SGMGeom& g, const SGMBuffers& b, int disp12MaxDiff, int speckleWindowSize,
+                       int speckleRange, int n, hipStream_t stream, const SgmWin* win, bool fused, int uniq);
+
+const char* launch_sgm(Plane8 L, Plane8 R, Plane16W disp, const SGMGeom& g, const SGMBuffers& b, int blockSize, int P1, int P2,
+                       int uniq, int disp12MaxDiff, int speckleWindowSize, int speckleRange, int paths, int n, hipStream_t stream,
+                       int cost_limit)
 {
     dim3 blk(256);
     hipLaunchKernelGGL(k_sgm_bounds, dim3((g.W + 255) / 256, g.H, 2 * n), blk, 0, stream, L, R, (uint2*)b.gl, (uint2*)b.gr, g.W, g.H, n);
@@ -1193,6 +1196,19 @@ void launch_sgm(Plane8 L, Plane8 R, Plane16W disp, const SGMGeom& g, const SGMBu
     }
     }
     static const int dirs[8][2] = {{1, 0}, {-1, 0}, {0, 1}, {0, -1}, {1, 1}, {-1, 1}, {1, -1}, {-1, -1}};
+    const int last_dir = paths == 5 ? 5 : 7;
+    SgmWin* win = (SgmWin*)b.gr;                     // the right image's bounds are dead once the pixel costs exist: 8 bytes per pixel
+    // D > 256 (or rtdm_debug_sgm_wide_paths): one wide pass per direction (k_sgm_wide.hip), the last one deciding the winners;
+    // none of the forms below, whatever the A/B switches say -- they hold at most 256 disparities per line
+    if (g.D > 256 || sgm_wide_mode()) {
+        for (int k = 0; k < 8; ++k) {
+            if (paths == 5 && dirs[k][1] < 0) continue;
+            launch_sgm_wide(g, b.C, b.S, dirs[k][0], dirs[k][1], P1, P2, k == 0 ? 1 : 0, k == last_dir, n, win, uniq, stream);
+        }
+        sgm_finish(disp, g, b, disp12MaxDiff, speckleWindowSize, speckleRange, n, stream, win, true, uniq);
+        return sgm_wide_waves(g.D) == 1 ? "wide_w1" : "wide_w4";
+    }
+    const char* variant = "block";
     const int threads = (g.D + 63) & ~63;
     int npl = (g.D + 63) / 64;                       // disparities per lane of the wave-per-line kernel: must divide D
     if (g.D % npl) npl = 4;
@@ -1204,8 +1220,6 @@ void launch_sgm(Plane8 L, Plane8 R, Plane16W disp, const SGMGeom& g, const SGMBu
     // RTDM_SGM_FUSE_SELECT=0 (A/B): the last direction writes S like the others and k_sgm_select reads it back
     static const int fuse_env = env_int("RTDM_SGM_FUSE_SELECT", 1);
     const bool fuse_select = fuse_env && wave_paths && aligned && g.D <= 256;
-    const int last_dir = paths == 5 ? 5 : 7;
-    SgmWin* win = (SgmWin*)b.gr;                     // the right image's bounds are dead once the pixel costs exist: 8 bytes per pixel
     // RTDM_SGM_SWEEP=0 (A/B): one pass per direction for the six that advance a row per step as well
     static const int sweep_env = env_int("RTDM_SGM_SWEEP", 1);
     bool sweep = sweep_env && half_paths && wave_paths && aligned16 && fuse_select && b.ring && b.abortf && *b.abortf == 0;
@@ -1213,6 +1227,7 @@ void launch_sgm(Plane8 L, Plane8 R, Plane16W disp, const SGMGeom& g, const SGMBu
     // RTDM_SGM_DUAL=0 (A/B): the two horizontal directions one after the other (the second adds to S) instead of side by side
     static const int dual_env = env_int("RTDM_SGM_DUAL", 1);
     bool s2_pending = false;                         // S2 holds the (-1, 0) direction's L_r and has not been added to S yet
+    bool swept = false;                              // a row-synchronous sweep ran (the variant this call reports)
     for (int k = 0; k < 8; ++k) {
         const int dx = dirs[k][0], dy = dirs[k][1];
         if (paths == 5 && dy < 0) continue;          // MODE_SGBM's five directions: nothing runs upwards
@@ -1223,6 +1238,7 @@ void launch_sgm(Plane8 L, Plane8 R, Plane16W disp, const SGMGeom& g, const SGMBu
 #define RTDM_PATHD(N) hipLaunchKernelGGL((k_sgm_path_h<N, 8, false>), hgrid, blk, 0, stream, b.C, b.S, g, 1, 0, P1, P2, 1, g.H, win, uniq, b.S2)
             if (g.D <= 64) RTDM_PATHD(1); else if (g.D <= 128) RTDM_PATHD(2); else RTDM_PATHD(4);
 #undef RTDM_PATHD
+            variant = "half";
             s2_pending = true;
             continue;
         }
@@ -1233,7 +1249,7 @@ void launch_sgm(Plane8 L, Plane8 R, Plane16W disp, const SGMGeom& g, const SGMBu
             if (done) continue;
             if (sweep && (k == 2 || k == 3)) {
                 const bool last_sweep = paths == 5 || dy < 0;
-                if (launch_sweep(last_sweep, g, b, dy, P1, P2, n, win, uniq, stream, s2_pending ? b.S2 : nullptr)) { done = true; s2_pending = false; continue; }
+                if (launch_sweep(last_sweep, g, b, dy, P1, P2, n, win, uniq, stream, s2_pending ? b.S2 : nullptr)) { done = true; s2_pending = false; swept = true; continue; }
                 sweep = false;                       // not launched: this and the remaining directions run as passes of their own
             }
             if (s2_pending) {                        // (the sweep that was to add S2 could not be launched)
@@ -1252,6 +1268,7 @@ void launch_sgm(Plane8 L, Plane8 R, Plane16W disp, const SGMGeom& g, const SGMBu
                               else hipLaunchKernelGGL((k_sgm_path_h<N, P, false>), hgrid, blk, 0, stream, b.C, b.S, g, dx, dy, P1, P2, first, lines, win, uniq, (uint16_t*)nullptr); } while (0)
             if (g.D <= 64) RTDM_PATHH(1, 8); else if (g.D <= 128) RTDM_PATHH(2, 8); else RTDM_PATHH(4, 8);
 #undef RTDM_PATHH
+            variant = "half";
         } else if (wave_paths && aligned && g.D <= 256) {
             const dim3 wgrid((lines + 3) / 4, n);
             const int first = k == 0 ? 1 : 0;
@@ -1264,16 +1281,26 @@ void launch_sgm(Plane8 L, Plane8 R, Plane16W disp, const SGMGeom& g, const SGMBu
                 default: RTDM_PATHW(4, 8); break;
             }
 #undef RTDM_PATHW
+            if (variant[0] == 'b') variant = "wave";
         } else {
             hipLaunchKernelGGL(k_sgm_path, dim3(lines, n), dim3(threads), 0, stream, b.C, b.S, g, dx, dy, P1, P2, k == 0 ? 1 : 0);
         }
     }
+    sgm_finish(disp, g, b, disp12MaxDiff, speckleWindowSize, speckleRange, n, stream, win, fuse_select, uniq);
+    return swept ? "sweep" : variant;
+}
+
+// the winners (k_sgm_lrfinal where the last path pass decided them, else k_sgm_select), the median and the speckle filter
+static void sgm_finish(Plane16W disp, const SGMGeom& g, const SGMBuffers& b, int disp12MaxDiff, int speckleWindowSize,
+                       int speckleRange, int n, hipStream_t stream, const SgmWin* win, bool fused, int uniq)
+{
+    dim3 blk(256);
     const bool speckle = speckleWindowSize > 0;                           // R11
     const size_t lds = (size_t)g.W * (8 + 2 + 2 + 2);
     // select -> a temporary plane (the bounds buffer of the left image is free again), median -> the caller's plane
     int16_t* tmp = (int16_t*)b.gl;
     const Plane16W tplane{tmp, (size_t)g.W, (size_t)g.W * g.H};
-    if (fuse_select) hipLaunchKernelGGL(k_sgm_lrfinal, dim3(1, g.H, n), blk, lds, stream, win, tplane, g, disp12MaxDiff);
+    if (fused) hipLaunchKernelGGL(k_sgm_lrfinal, dim3(1, g.H, n), blk, lds, stream, win, tplane, g, disp12MaxDiff);
     else launch_select<false>((g.D + 63) / 64, dim3(1, g.H, n), lds, stream, b.S, tplane, g, uniq, disp12MaxDiff, b, 0);
     const size_t mlds = (size_t)g.W * 6;
     const int INV = (g.minD - 1) * 16;

@@ -1015,6 +1015,7 @@ struct rtdm_sgm {
     uint32_t sweep_epoch;          // launches of k_sgm_sweep (tags of its edge ring)
     int sweep_cap[36];             // workgroups the device holds at once, per instantiation (0 = not asked yet)
     bool sweep_reported;           // a give-up of the sweep has been returned to the caller
+    const char* path_variant;      // the path-pass form of the last call (launch_sgm), "" before the first
 };
 
 // The row-synchronous sweep waits on its neighbours with a bound; a pass that gave up has produced garbage and has said so in a
@@ -1064,7 +1065,7 @@ int rtdm_sgm_create(const rtdm_sgm_params* params, int max_width, int max_height
     if (p.uniquenessRatio < 0) p.uniquenessRatio = 10;
     if (p.disp12MaxDiff <= 0) p.disp12MaxDiff = 1;         // the library's left-right check cannot be switched off
     if (max_width <= 0 || max_height <= 0 || max_batch <= 0) return RTDM_ERR_BAD_SIZE;
-    if (p.numDisparities > 256 || max_width > 4096) return RTDM_ERR_UNSUPPORTED;
+    if (max_width > 4096) return RTDM_ERR_UNSUPPORTED;
     // 16-bit costs: a path cost is at most block cost + P2 (pixel cost <= 30 + 63); above 32767 the library's short
     // arithmetic wraps, which is not restated: windows that CAN get there (> 17 at P2 = 2400) run with a check of the block
     // costs and refuse the frame that does (RTDM_ERR_UNSUPPORTED from the compute call; it takes nearly every pixel of a
@@ -1077,15 +1078,21 @@ int rtdm_sgm_create(const rtdm_sgm_params* params, int max_width, int max_height
     if (!sg) return RTDM_ERR_NOMEM;
     sg->p = p; sg->maxW = max_width; sg->maxH = max_height; sg->maxB = max_batch; sg->device = device;
     sg->cost_limit = cost_limit;
+    sg->path_variant = "";
     const size_t px = (size_t)max_width * max_height * max_batch;
-    const size_t vol = px * p.numDisparities;
+    // D <= 256: volumes on max_width columns, as always.  D > 256 (the wide path pass): on the widest column domain a frame can
+    // have, W1max = max_width + min(minD, 0) - max(minD + D, 0) -- at D = 4080 on 4096 columns that is 16 columns instead of
+    // 4096 -- and no S2 (the side-by-side horizontal passes are off there); W1max <= 0: every frame is all-invalid, no volumes.
+    const bool wide = p.numDisparities > 256;
+    const long w1max = (long)max_width + std::min(p.minDisparity, 0) - std::max(p.minDisparity + p.numDisparities, 0);
+    const size_t vol = wide ? (w1max > 0 ? (size_t)w1max * max_height * max_batch * p.numDisparities : 0) : px * p.numDisparities;
     hipError_t e = hipStreamCreateWithFlags(&sg->stream, hipStreamNonBlocking);
     void** ptrs[] = {(void**)&sg->dInL, (void**)&sg->dInR, (void**)&sg->dOut, (void**)&sg->b.gl, (void**)&sg->b.gr,
                      (void**)&sg->b.pix, (void**)&sg->b.C, (void**)&sg->b.S, (void**)&sg->b.label, (void**)&sg->b.size,
                      (void**)&sg->b.runs, (void**)&sg->b.rowcnt, (void**)&sg->b.headmap};
     const size_t sizes[] = {px, px, px * 2, px * 8, px * 8, vol, vol * 2, vol * 2, px * 4, px * 4, px * 4,
                             (size_t)max_batch * max_height * 4, px * 2};
-    for (int i = 0; i < 13 && e == hipSuccess; ++i) e = hipMalloc(ptrs[i], sizes[i]);
+    for (int i = 0; i < 13 && e == hipSuccess; ++i) if (sizes[i]) e = hipMalloc(ptrs[i], sizes[i]);
     if (e == hipSuccess) e = hipMalloc((void**)&sg->b.ovf, sizeof(int32_t));
     if (e == hipSuccess) e = hipMemset(sg->b.ovf, 0, sizeof(int32_t));
     if (e == hipSuccess) e = hipHostMalloc((void**)&sg->hOvf, sizeof(int32_t), hipHostMallocDefault);
@@ -1093,7 +1100,7 @@ int rtdm_sgm_create(const rtdm_sgm_params* params, int max_width, int max_height
     if (e == hipSuccess) e = hipMalloc((void**)&sg->b.ring, sg->b.ring_words * sizeof(unsigned long long));
     if (e == hipSuccess) e = hipMemset(sg->b.ring, 0, sg->b.ring_words * sizeof(unsigned long long));
     if (e == hipSuccess) e = hipHostMalloc((void**)&sg->b.abortf, sizeof(int32_t), hipHostMallocMapped);
-    if (e == hipSuccess && hipMalloc((void**)&sg->b.S2, vol * 2) != hipSuccess) { (void)hipGetLastError(); sg->b.S2 = nullptr; }   // (optional: without it the horizontal passes run one after the other)
+    if (e == hipSuccess && !wide && hipMalloc((void**)&sg->b.S2, vol * 2) != hipSuccess) { (void)hipGetLastError(); sg->b.S2 = nullptr; }   // (optional: without it the horizontal passes run one after the other)
     if (e == hipSuccess) *sg->b.abortf = 0;
     sg->b.epoch = &sg->sweep_epoch; sg->b.sweep_cap = sg->sweep_cap;
     if (e == hipSuccess) e = hipEventCreateWithFlags((hipEvent_t*)&sg->b.ev_in, hipEventDisableTiming);
@@ -1134,8 +1141,8 @@ static int sgm_chunk(rtdm_sgm* sg, int n, Plane8 L, Plane8 R, int W, int H, Plan
     g.x0 = std::max(g.minD + g.D, 0);
     g.W1 = (W + std::min(g.minD, 0)) - g.x0;
     if (g.W1 <= 0) { launch_fill16(disp, 0, W, 0, H, n, (g.minD - 1) * 16, s); return RTDM_OK; }
-    launch_sgm(L, R, disp, g, sg->b, p.blockSize, p.P1, p.P2, p.uniquenessRatio, p.disp12MaxDiff, p.speckleWindowSize,
-               p.speckleRange, p.paths, n, s, sg->cost_limit);
+    sg->path_variant = launch_sgm(L, R, disp, g, sg->b, p.blockSize, p.P1, p.P2, p.uniquenessRatio, p.disp12MaxDiff,
+                                  p.speckleWindowSize, p.speckleRange, p.paths, n, s, sg->cost_limit);
     HIPC(hipGetLastError());
     return RTDM_OK;
 }
@@ -1187,6 +1194,9 @@ int rtdm_sgm_get_pass_stats(const rtdm_sgm* sg, long* sweeps, int* gave_up)
     if (gave_up) *gave_up = sg->b.abortf && *sg->b.abortf ? 1 : 0;
     return RTDM_OK;
 }
+
+const char* rtdm_sgm_path_variant(const rtdm_sgm* sg) { return sg ? sg->path_variant : ""; }
+void rtdm_debug_sgm_wide_paths(int lines_per_wave_or_waves) { sgm_wide_set_mode(lines_per_wave_or_waves); }
 
 // ---- rectification in front of the matcher (estimator.cpp:29-39) ----------------------------------------------
 struct rtdm_rectify {

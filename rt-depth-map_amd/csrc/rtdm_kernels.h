@@ -167,10 +167,22 @@ struct SGMBuffers {
     void *ev_in, *ev_out;    // hipEvent_t: the caller's stream -> the process's sweep stream -> the caller's stream
 };
 size_t sgm_ring_words(int maxW, int D, int max_batch);
+// What the last path pass leaves per pixel for k_sgm_lrfinal: {x16 disparity or INV, integer winner + minD or minD - 1,
+// minimum cost, 0}
+struct SgmWin { int16_t d16, bd; uint16_t mins, pad; };
+// The path pass for wide lines (k_sgm_wide.hip): every D from 16 to 4080, one direction per launch, S (+)= L_r or (last) the
+// winners -> win.  sgm_wide_waves(D): waves per line it runs with (1 or 4).  sgm_wide_set_mode: rtdm_debug_sgm_wide_paths.
+void launch_sgm_wide(const SGMGeom& g, const uint16_t* C, uint16_t* S, int dx, int dy, int P1, int P2, int first, bool last, int n,
+                     SgmWin* win, int uniq, hipStream_t stream);
+int sgm_wide_waves(int D);
+void sgm_wide_set_mode(int m);
+int sgm_wide_mode();
 // cost_limit > 0: block costs above it set *b.ovf (the caller reads it back: rtdm_api.hip)
-void launch_sgm(Plane8 L, Plane8 R, Plane16W disp, const SGMGeom& g, const SGMBuffers& b, int blockSize, int P1, int P2,
-                int uniq, int disp12MaxDiff, int speckleWindowSize, int speckleRange, int paths, int n, hipStream_t stream,
-                int cost_limit = 0);
+// Returns the name of the path-pass form the call ran ("sweep", "half", "wave", "block", "wide_w1", "wide_w4").  D > 256 (or a
+// forced wide mode) runs the wide pass for every direction, whatever the A/B environment switches say.
+const char* launch_sgm(Plane8 L, Plane8 R, Plane16W disp, const SGMGeom& g, const SGMBuffers& b, int blockSize, int P1, int P2,
+                       int uniq, int disp12MaxDiff, int speckleWindowSize, int speckleRange, int paths, int n, hipStream_t stream,
+                       int cost_limit = 0);
 
 // Depth statistics after the matcher (estimator.cpp:75-77, 206-263).  q = the 4x4 reprojection matrix Q, row major.
 struct DepthQ { double q[16]; };

@@ -135,7 +135,8 @@ class HIPMatcher:
 class HIPSemiGlobalMatcher:
     """BlockMatcher over rtdm_sgm_*; constructor shape of SWSemiGlobalMatcher
     (include/stereo-matcher/sgbm-sw.h:27-28): blockSize, minDisparity, numOfDisparities, uniquenessRatio,
-    speckleWindowSize, speckleRange, disp12MaxDiff; P1/P2 are the literals of sgbm-sw.cpp:17-18."""
+    speckleWindowSize, speckleRange, disp12MaxDiff; P1/P2 are the literals of sgbm-sw.cpp:17-18.  numOfDisparities is
+    any multiple of 16, as in cv::StereoSGBM (above 256 the path passes run on the wide-line kernel); the library checks it."""
 
     def __init__(self, blockSize=5, minDisparity=0, numOfDisparities=128, uniquenessRatio=10, speckleWindowSize=100,
                  speckleRange=32, disp12MaxDiff=1, P1=600, P2=2400, width=1280, height=720, max_batch=1, device=0, paths=8):
@@ -180,6 +181,11 @@ class HIPSemiGlobalMatcher:
         sw, gu = C.c_long(0), C.c_int(0)
         B.check(B.lib().rtdm_sgm_get_pass_stats(self._h, C.byref(sw), C.byref(gu)), "rtdm_sgm_get_pass_stats")
         return sw.value, bool(gu.value)
+
+    @property
+    def path_variant(self):
+        """the path-pass form of the last call: "sweep", "half", "wave", "block", "wide_w1", "wide_w4" -- rtdm_sgm_path_variant"""
+        return B.lib().rtdm_sgm_path_variant(self._h).decode()
 
     def compute_device(self, d_left, d_right, d_disp, stream=None):
         n, H, W = d_left.shape
