@@ -550,13 +550,19 @@ __global__ __launch_bounds__(256, (RingBounds<D, WS, LPP, FUSE>::WAVES)) void k_
             // Selection is skipped for a wave none of whose pixels can produce a disparity here (untextured, outside the
             // tile, masked): exact, such a pixel is FILTERED and writes no cost whatever its SADs are.
             const int tsum = *ptw_own;                               // the texture sum of the row this lane owns
-            const bool dead = !active || !row_ok || masked_col || tsum < g.tex;
+            // (bitwise: one lane mask for the vote, no branch around the texture read)
+            const bool dead = !active | !row_ok | masked_col | (tsum < g.tex);
             if (__builtin_amdgcn_ballot_w64(!dead) == 0) {
                 if (active && row_ok) *(int16_t*)(db + dof) = (int16_t)g.filtered;
             } else {
                 int m1; bool fail;
                 int out;
-                if constexpr (SPLIT && RING_ABL == 0) {
+                if constexpr (SPLIT && MINREC && RING_ABL == 0) {
+                    int uq = g.uniq;
+                    asm volatile("" : "+s"(uq));                     // (tested here, on the scalar unit, not hoisted as a lane mask)
+                    out = gsel.finish(tsum, g, uq > 0, scr, &m1, &fail);
+                    RING_STAMP(5);
+                } else if constexpr (SPLIT && RING_ABL == 0) {
                     out = gsel.finish(tsum, g, scr, &m1, &fail);
                     RING_STAMP(5);
                 } else {
@@ -779,6 +785,8 @@ bool ring_search_supported(const BMGeom& g)
     const int sw = ring_mode(), mode = sw >= 0 ? sw : env;
     if (mode == 0) return false;
     if (2L * g.cap * g.w * g.w > 32766) return false;       // packed u16 sums + the T+1 <= 32767 argument of the selection
+    if (2L * g.cap * g.w * g.w >= 0x7C00) return false;     // ... and positive finite f16 for the group minima (sel_pk_min3_h; cap <= 63
+                                                            //     keeps every ring form below: 2 * 63 * 15^2 = 28350)
     if (ring_rows_cap(g) < 2) return false;
     if (!ring_range(g, nullptr, nullptr)) return false;
     if ((size_t)g.H * (size_t)g.Ws * 2 >= ((size_t)1 << 32)) return false;   // 32-bit byte offsets inside a frame (pitch <= Ws)

@@ -27,6 +27,16 @@ __device__ __forceinline__ uint32_t sel_pk_sub_sat(uint32_t a, uint32_t b)
 { return __builtin_bit_cast(uint32_t, __builtin_elementwise_sub_sat(__builtin_bit_cast(sel_us2, a), __builtin_bit_cast(sel_us2, b))); }
 __device__ __forceinline__ uint32_t sel_pk_add_sat(uint32_t a, uint32_t b)
 { return __builtin_bit_cast(uint32_t, __builtin_elementwise_add_sat(__builtin_bit_cast(sel_us2, a), __builtin_bit_cast(sel_us2, b))); }
+// min3 of packed pairs of window sums, read as f16 (v_pk_minimum3_f16): a sum < 0x7C00 is a positive finite f16, never NaN or
+// Inf, and the f16 order of such values is their u16 order -- denormals included, which the kernels keep (float denorm mode
+// 16/64 = 3, not flushed; tests/test_gpu_select_min3.py checks the order on the GPU for every pair).  The result is one of
+// the inputs, bit for bit.
+typedef _Float16 sel_h2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ uint32_t sel_pk_min3_h(uint32_t a, uint32_t b, uint32_t c)
+{
+    const sel_h2 x = __builtin_bit_cast(sel_h2, a), y = __builtin_bit_cast(sel_h2, b), z = __builtin_bit_cast(sel_h2, c);
+    return __builtin_bit_cast(uint32_t, __builtin_elementwise_minimum(__builtin_elementwise_minimum(x, y), z));
+}
 
 // The sub-pixel term of A.3b, trunc((p - n) * 256 / den) with den = p + n - 2 m + |p - n| (0 if den == 0), for m <= min(p, n):
 // den = 2 (max(p, n) - m) and |p - n| <= max(p, n) - m, so the magnitude is floor(|p - n| * 128 / u) <= 128 with
@@ -415,8 +425,8 @@ struct GroupSelect {
 
 // GroupSelectRec: GroupSelect with the group minima kept in the OWNER's record as well (D <= 64: the D/8 packed u16 minima
 // are D/16 <= 4 dwords and live in the four padding dwords behind the D/2 SAD dwords).  A lane's part of a row shrinks to
-// the packed minima of its groups (3 v_pk_min + one SDWA minimum per group, written with ds_write_b16) and NOTHING crosses
-// between the lanes any more: the owner reads the minima of all D/8 groups back with one 16-byte read and builds the keys
+// the packed minima of its groups (v_pk_minimum3_f16 + v_pk_min + one SDWA minimum per group, written with ds_write_b16)
+// and NOTHING crosses between the lanes any more: the owner reads the minima of all D/8 groups back with one 16-byte read and builds the keys
 // (v_perm, v_min3: 12 instructions at D = 64 against 16 per-row key instructions + an 8-instruction lane reduction), and
 // evaluates test (A) itself as a second sum identity over those minima (8 packed instructions against a 9-instruction
 // broadcast of T+1, 16 compares in the other lanes and a 10-instruction reduction).  Per 64 pixel-rows at D = 64, four lanes per pixel: about 45 VALU instructions
@@ -461,13 +471,15 @@ struct GroupSelectRec {
         for (int i = 0; i < NRL; i += 4) st4(wr + i, u4{sv[i], sv[i + 1], sv[i + 2], sv[i + 3]});
 #pragma unroll
         for (int gq = 0; gq < NGH; ++gq) {
-            const uint32_t m = sel_pk_min(sel_pk_min(sv[4 * gq], sv[4 * gq + 1]), sel_pk_min(sv[4 * gq + 2], sv[4 * gq + 3]));
+            // two packed minima per group of eight instead of three (window sums < 0x7C00: k_search_ring's ring_search_supported)
+            const uint32_t m = sel_pk_min(sel_pk_min3_h(sv[4 * gq], sv[4 * gq + 1], sv[4 * gq + 2]), sv[4 * gq + 3]);
             wm[gq] = (unsigned short)min(m & 0xffffu, m >> 16);
         }
     }
 
-    // after the LPP rows: the result for the row this lane owns (rec_own = its record)
-    __device__ __forceinline__ int finish(int tsum, const BMGeom& g, const uint32_t* rec_own, int* minsad, bool* rejected)
+    // after the LPP rows: the result for the row this lane owns (rec_own = its record); uniq = g.uniq > 0, held wave-uniform
+    // by the caller
+    __device__ __forceinline__ int finish(int tsum, const BMGeom& g, bool uniq, const uint32_t* rec_own, int* minsad, bool* rejected)
     {
         uint32_t mn[4 * NGQ];                                        // minima of the groups 2q (low half) and 2q + 1 (high half)
 #pragma unroll
@@ -497,12 +509,12 @@ struct GroupSelectRec {
         // the neighbour's group contribute -- any other group with a minimum <= T adds a positive term.  Groups 2q / 2q+1
         // sit in the low / high halves, so the (adjacent) winner and neighbour groups fall into different halves: a half that
         // saturates (65535) holds more than its one expected term (<= 32767) -- the total stays above the expected total.
-        uint32_t T1 = 0, zg = 0;
-        if (g.uniq > 0) {
+        uint32_t T1 = 0, T1pk = 0, zg = 0;
+        if (uniq) {
             uint32_t T = (uint32_t)m1 + ((uint32_t)m1 * (uint32_t)g.uniq) / 100u;
             T = min(T, 32766u);
             T1 = T + 1u;
-            const uint32_t T1pk = T1 * 0x00010001u;
+            T1pk = T1 * 0x00010001u;
             uint32_t z2[2] = {0, 0};
 #pragma unroll
             for (int q = 0; q < NGD; ++q) z2[q & 1] = sel_pk_add_sat(z2[q & 1], sel_pk_sub_sat(T1pk, mn[q]));   // unused halves (0xffff) add 0
@@ -520,21 +532,25 @@ struct GroupSelectRec {
         const int e = (int)(min(k3[0], k3[1]) & 0xffu);
         const int a = 8 * gs + e;
         const bool has_n = a > 0, has_p = a + 1 < D;
-        const unsigned short* sv = (const unsigned short*)rec_own;
-        const int n_real = sv[max(a - 1, 0)];                        // (sad[a] itself where the neighbour does not exist)
-        const int p_real = sv[min(a + 1, D - 1)];
+        // sad[a-1] and sad[a+1] from one address: where a neighbour does not exist the read lands on the u16 in front of the
+        // record (a = 0: the previous record's last word, or this wave's staging area) or on the first minimum behind the
+        // SADs (a = D-1) -- inside the workgroup's LDS either way, and never used
+        const unsigned short* sv = (const unsigned short*)rec_own + (a - 1);
+        const int n_real = sv[0];
+        const int p_real = sv[2];
         bool fail = tsum < g.tex;
-        if (g.uniq > 0) {
+        if (uniq) {
             // the group a-1 or a+1 falls into, if that is not the winner's
             const int nbq = (e == 0 && has_n) ? gs - 1 : (e == 7 && has_p) ? gs + 1 : gs;
             const bool has_nb = nbq != gs;
             const u4 nbg = ld4(rec_own + 4 * nbq);
-            const uint32_t nbmin = sv[D + nbq];                      // its minimum, from the minima behind the SADs
-            const uint32_t T1pk = T1 * 0x00010001u, nbmask = has_nb ? 0xffffffffu : 0u;
+            const uint32_t nbmin = ((const unsigned short*)rec_own)[D + nbq];   // its minimum, from the minima behind the SADs
+            // without a neighbour group its four registers count against a threshold of 0: max(0 - sad, 0) = 0, exactly
+            const uint32_t T1nb = has_nb ? T1pk : 0u;
             uint32_t zz[4];
 #pragma unroll
             for (int q = 0; q < 4; ++q)
-                zz[q] = sel_pk_add_sat(sel_pk_sub_sat(T1pk, grp[q]), sel_pk_sub_sat(T1pk, nbg[q]) & nbmask);
+                zz[q] = sel_pk_add_sat(sel_pk_sub_sat(T1pk, grp[q]), sel_pk_sub_sat(T1nb, nbg[q]));
             const uint32_t zp = sel_pk_add_sat(sel_pk_add_sat(zz[0], zz[1]), sel_pk_add_sat(zz[2], zz[3]));
             // a 16-bit half saturates at 65535, more than the (at most two) terms of {a-1, a, a+1} it can hold add up to:
             // the total stays >= the expected total, with equality only if nothing saturated and nothing else contributed
