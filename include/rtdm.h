@@ -154,16 +154,20 @@ int rtdm_morph_run_device(rtdm_morph* mf, int n, const uint8_t* d_in, size_t in_
 /* ---- SWSemiGlobalMatcher counterpart: cv::StereoSGBM (rows S / f4, BASELINE config 5) -------------------
  * rtdm_sgm_create   <- SWSemiGlobalMatcher::SWSemiGlobalMatcher (stereo-matcher/sgbm-sw.cpp:12-25):
  *                      StereoSGBM::create(0, numDisparities, blockSize), P1 = 600, P2 = 2400 (:17-18),
- *                      then the five setters (:19-24).  preFilterCap stays 0 (=> clip at +-15), mode MODE_SGBM.
+ *                      then the five setters (:19-24).  preFilterCap starts at 0 (=> clip at +-15; rtdm_sgm_set_prefilter_cap
+ *                      changes it), mode MODE_SGBM.
  * rtdm_sgm_compute  <- SWSemiGlobalMatcher::compute (sgbm-sw.cpp:32-37); setROI1/2 are no-ops in the
- *                      reference (sgbm-sw.h:32-33), so there is no ROI entry point.
+ *                      reference (sgbm-sw.h:32-33), so there is no ROI entry point.  rtdm_sgm_compute_cn also takes
+ *                      interleaved three-channel pairs (CV_8UC3), as cv::StereoSGBM::compute does.
  * The algorithm is the restatement of cv::StereoSGBM::compute in oracle/sgm_oracle.c (rules R1-R12 there: pixel cost,
  * block sum, 5 or 8 path directions, saturating sum, winner / uniqueness / sub-pixel, the always-on left-right check,
  * 3x3 median, speckle filter), integer arithmetic, bit-exact against that oracle; parity against the library itself is
  * unpinned (OpenCV is not available where this was built). */
 typedef struct rtdm_sgm_params {
     int blockSize;         /* 1..255; an even size runs as the next odd one, as in the library (window = blockSize / 2 either
-                            * side).  Where 93 * window^2 + P2 > 32767 (window > 17 at P2 = 2400) a block cost + P2 CAN pass
+                            * side).  A pixel cost is at most M = channels * (2 ftzero + 63), ftzero = max(preFilterCap, 15) | 1
+                            * (93 for gray at preFilterCap 0).  Where M * window^2 + P2 > 32767 (gray at preFilterCap 0: window
+                            * > 17 at P2 = 2400) a block cost + P2 CAN pass
                             * 32767, where the library's 16-bit costs wrap around -- which is not reproduced: a frame in which
                             * it does is refused by the compute call (RTDM_ERR_UNSUPPORTED; it takes nearly every pixel of a
                             * window at the maximum pixel cost), and rtdm_sgm_compute_device synchronises its stream to tell */
@@ -203,6 +207,25 @@ const char* rtdm_sgm_path_variant(const rtdm_sgm* sg);
  * holds the line (<= 1024), four waves above.  4: every numDisparities runs the wide-line pass with four waves per line.
  * Other values mean 0.  Results never depend on it; it exists so that tests can put lane and wave boundaries anywhere. */
 void rtdm_debug_sgm_wide_paths(int lines_per_wave_or_waves);
+/* cv::StereoSGBM::setPreFilterCap, from the next compute call on: R1's gradient clip ftzero = max(preFilterCap, 15) | 1
+ * (0 and 15 -> 15, 16 -> 17, 63 -> 63).  preFilterCap >= 128: RTDM_ERR_UNSUPPORTED (the library's 8-bit clip table wraps
+ * there).  Where a pixel cost can pass 255 (ftzero >= 97, or colour) the cost stage runs on 16-bit pixel costs. */
+int rtdm_sgm_set_prefilter_cap(rtdm_sgm* sg, int preFilterCap);
+/* rtdm_sgm_compute / rtdm_sgm_compute_device for channels = 1 (exactly those) or 3: interleaved colour, a row holds
+ * channels * width bytes, pitches in bytes.  The pixel cost is summed over the channels (R1 generalised: for every channel the
+ * clipped x-gradient and the raw value, Birchfield-Tomasi each; cost = sum BT(gradient) + sum (BT(raw) >> 2)), which restates
+ * the library's calcPixelCostBT from memory -- parity with the library itself is unpinned.  Other channel counts:
+ * RTDM_ERR_BAD_PARAM.  The first colour call of a handle allocates its colour buffers (24 bytes per pixel and image of
+ * max_width x max_height x max_batch, plus the host entry point's staging). */
+int rtdm_sgm_compute_cn(rtdm_sgm* sg, int channels, const uint8_t* left, size_t left_pitch, const uint8_t* right,
+                        size_t right_pitch, int width, int height, int16_t* disp, size_t disp_pitch);
+int rtdm_sgm_compute_device_cn(rtdm_sgm* sg, int channels, int n, const uint8_t* d_left, const uint8_t* d_right,
+                               size_t pitch, size_t frame_stride, int width, int height,
+                               int16_t* d_disp, size_t disp_pitch, size_t disp_frame_stride, void* hip_stream);
+/* Diagnostic switch, process wide: 1 runs the 16-bit pixel-cost forms on gray frames as well (0, the default: only where a
+ * pixel cost can pass 255).  Results never depend on it; it exists so that tests can hold the 16-bit forms against the 8-bit
+ * ones. */
+void rtdm_debug_sgm_cost16(int on);
 
 /* ---- the step after the matcher, kept on the device ------------
  * rtdm_bm_compute_depth <- estimator.cpp:56 + 75-77: bm->compute(...); left_disp /= 16.;

@@ -5,10 +5,11 @@
 // cv::StereoSGBM is unpinned).  Cost volumes live on the column domain [x0, x1) = [minD+D, W+min(minD,0)) and are laid
 // out [frame][y][x - x0][d] with d fastest, so a wavefront's lanes = consecutive disparities = one coalesced line per pixel.
 //
-//   k_sgm_bounds x-Sobel (vertical edge replication) clipped to +-15, + 15, and the BT bounds of it and of the
-//                intensity (border columns overwritten with 15, R1), per pixel          (HBM bound)
+//   k_sgm_bounds x-Sobel (vertical edge replication) clipped to +-ftzero, + ftzero, and the BT bounds of it and of the
+//                intensity (border columns overwritten with ftzero, R1), per pixel and channel  (HBM bound)
 //   k_sgm_pixbox Birchfield-Tomasi pixel cost (gradient + (intensity >> 2), u8, kept in LDS) and the blockSize x blockSize sum
 //                with clamped coordinates -> C (u16), windows <= 7; larger windows: k_sgm_pix (u8 volume) + k_sgm_box / _any
+//                (colour frames and ftzero >= 97, where a pixel cost passes 255: the u16 forms k_sgm_pixbox16, k_sgm_pix16)
 //   k_sgm_path_h one HALF-WAVE per path line, packed u16 recurrence: L_r, S = min(S + L_r, 32767) (R5); the two horizontal
 //                directions in one launch (-> S, <- S2)
 //   k_sgm_sweep  the three directions that advance a row per step in one row-synchronous pass (adds S2; the last sweep decides
@@ -20,21 +21,26 @@
 #include "rtdm_kernels.h"
 #include "rtdm_device.h"
 
+#include <atomic>
 #include <cstdlib>
 #include <mutex>
 
 namespace rtdm {
 
-static constexpr int FTZ = 15;
-
+// R1's ftzero = max(preFilterCap, 15) | 1 comes in at run time: 15 at the default preFilterCap 0, at most 127 (the caller
+// refuses preFilterCap >= 128), so every gradient value, 0 .. 2 ftzero, and every raw value still fits a byte.
+//
 // Per pixel and image, once: the Birchfield-Tomasi bounds (value, min and max against the half-way points to the two
 // neighbours) of the clipped x-gradient and of the raw intensity, packed as two uchar4 -- the pixel-cost kernel then
-// needs one 8-byte load per (pixel, image) instead of six byte loads per (pixel, disparity, image).
-__device__ __forceinline__ int sgm_grad(const uint8_t* r0, const uint8_t* r1, const uint8_t* r2, int x, int W)
+// needs one 8-byte load per (pixel, image) instead of six byte loads per (pixel, disparity, image).  CN = 3 (interleaved
+// colour, CV_8UC3): one such uint2 per channel, a 24-byte record per pixel ([f][y][x][c]).
+template <int CN>
+__device__ __forceinline__ int sgm_grad(const uint8_t* r0, const uint8_t* r1, const uint8_t* r2, int x, int W, int ftz)
 {
-    if (x <= 0 || x >= W - 1) return FTZ;
-    const int g = ((int)r1[x + 1] - (int)r1[x - 1]) * 2 + ((int)r0[x + 1] - (int)r0[x - 1]) + ((int)r2[x + 1] - (int)r2[x - 1]);
-    return min(max(g, -FTZ), FTZ) + FTZ;
+    if (x <= 0 || x >= W - 1) return ftz;
+    const int a = (x + 1) * CN, b = (x - 1) * CN;
+    const int g = ((int)r1[a] - (int)r1[b]) * 2 + ((int)r0[a] - (int)r0[b]) + ((int)r2[a] - (int)r2[b]);
+    return min(max(g, -ftz), ftz) + ftz;
 }
 __device__ __forceinline__ uint32_t bt_pack(int v, int m, int p, bool has_m, bool has_p)
 {
@@ -42,7 +48,8 @@ __device__ __forceinline__ uint32_t bt_pack(int v, int m, int p, bool has_m, boo
     return (uint32_t)v | ((uint32_t)min(min(l, r), v) << 8) | ((uint32_t)max(max(l, r), v) << 16);
 }
 
-__global__ __launch_bounds__(256) void k_sgm_bounds(Plane8 L, Plane8 R, uint2* bl, uint2* br, int W, int H, int n)
+template <int CN>
+__global__ __launch_bounds__(256) void k_sgm_bounds(Plane8 L, Plane8 R, uint2* bl, uint2* br, int W, int H, int n, int ftz)
 {
     const int x = blockIdx.x * 256 + threadIdx.x;
     if (x >= W) return;
@@ -52,16 +59,19 @@ __global__ __launch_bounds__(256) void k_sgm_bounds(Plane8 L, Plane8 R, uint2* b
     if (right) f -= n;
     const Plane8 S = right ? R : L;
     const uint8_t* img = S.base + (size_t)f * S.frame;
-    const uint8_t* r1 = img + (size_t)y * S.pitch;
-    const uint8_t* r0 = img + (size_t)(y > 0 ? y - 1 : y) * S.pitch;
-    const uint8_t* r2 = img + (size_t)(y < H - 1 ? y + 1 : y) * S.pitch;
     const bool hm = x > 0, hp = x < W - 1;
-    const uint32_t gb = bt_pack(sgm_grad(r0, r1, r2, x, W), hm ? sgm_grad(r0, r1, r2, x - 1, W) : 0,
-                                hp ? sgm_grad(r0, r1, r2, x + 1, W) : 0, hm, hp);
-    // R1: the library overwrites columns 0 and W-1 of the raw-intensity row with ftzero as well, before the bounds are taken
-    const auto raw = [&](int i) -> int { return (i <= 0 || i >= W - 1) ? FTZ : (int)r1[i]; };
-    const uint32_t rb = bt_pack(raw(x), hm ? raw(x - 1) : 0, hp ? raw(x + 1) : 0, hm, hp);
-    (right ? br : bl)[((size_t)f * H + y) * W + x] = make_uint2(gb, rb);
+#pragma unroll
+    for (int c = 0; c < CN; ++c) {
+        const uint8_t* r1 = img + (size_t)y * S.pitch + c;
+        const uint8_t* r0 = img + (size_t)(y > 0 ? y - 1 : y) * S.pitch + c;
+        const uint8_t* r2 = img + (size_t)(y < H - 1 ? y + 1 : y) * S.pitch + c;
+        const uint32_t gb = bt_pack(sgm_grad<CN>(r0, r1, r2, x, W, ftz), hm ? sgm_grad<CN>(r0, r1, r2, x - 1, W, ftz) : 0,
+                                    hp ? sgm_grad<CN>(r0, r1, r2, x + 1, W, ftz) : 0, hm, hp);
+        // R1: the library overwrites columns 0 and W-1 of the raw-intensity row with ftzero as well, before the bounds are taken
+        const auto raw = [&](int i) -> int { return (i <= 0 || i >= W - 1) ? ftz : (int)r1[i * CN]; };
+        const uint32_t rb = bt_pack(raw(x), hm ? raw(x - 1) : 0, hp ? raw(x + 1) : 0, hm, hp);
+        (right ? br : bl)[(((size_t)f * H + y) * W + x) * CN + c] = make_uint2(gb, rb);
+    }
 }
 
 __device__ __forceinline__ int bt_cost(uint32_t a, uint32_t b)
@@ -123,10 +133,17 @@ __global__ __launch_bounds__(256) void k_sgm_pix(const uint2* bl, const uint2* b
     *(uint32_t*)(pix + (((size_t)f * g.H + y) * g.W1 + xi) * g.D + d) = __builtin_amdgcn_perm(c[1], c[0], 0x06040200u);
 }
 
+// four consecutive pixel costs (u8 volume: one dword, u16 volume: one qword) added to s[0..3]
+__device__ __forceinline__ void sgm_acc4(const uint8_t* p, int* s)
+{ const uint32_t w = *(const uint32_t*)p; s[0] += w & 0xff; s[1] += (w >> 8) & 0xff; s[2] += (w >> 16) & 0xff; s[3] += w >> 24; }
+__device__ __forceinline__ void sgm_acc4(const uint16_t* p, int* s)
+{ const uint2 w = *(const uint2*)p; s[0] += w.x & 0xffff; s[1] += w.x >> 16; s[2] += w.y & 0xffff; s[3] += w.y >> 16; }
+
 // block cost: thread = (x, four consecutive d); walks down a strip of rows keeping the last 2R+1 horizontal sums in
-// registers, so every pixel-cost element is read (2R+1) times instead of (2R+1)^2 times
-template <int R>
-__global__ __launch_bounds__(256) void k_sgm_box(const uint8_t* pix, uint16_t* C, SGMGeom g, int rows_per_strip, int cost_limit, int32_t* ovf)
+// registers, so every pixel-cost element is read (2R+1) times instead of (2R+1)^2 times.  T: the pixel-cost volume's type
+// (uint8_t, or uint16_t where a pixel cost can pass 255: colour, preFilterCap >= 96)
+template <int R, typename T>
+__global__ __launch_bounds__(256) void k_sgm_box(const T* pix, uint16_t* C, SGMGeom g, int rows_per_strip, int cost_limit, int32_t* ovf)
 {
     const int dq = g.D >> 2;
     const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;          // over W1 * D/4
@@ -134,19 +151,16 @@ __global__ __launch_bounds__(256) void k_sgm_box(const uint8_t* pix, uint16_t* C
     const int d = (int)(idx % dq) * 4, xi = (int)(idx / dq);
     const int f = blockIdx.z;
     const int y0 = blockIdx.y * rows_per_strip, y1 = min(y0 + rows_per_strip, g.H);
-    const uint8_t* base = pix + (size_t)f * g.H * g.W1 * g.D + d;
+    const T* base = pix + (size_t)f * g.H * g.W1 * g.D + d;
     int xs[2 * R + 1];
 #pragma unroll
     for (int k = 0; k <= 2 * R; ++k) xs[k] = min(max(xi + k - R, 0), g.W1 - 1) * g.D;
     struct Sum4 { int v[4]; };
     const auto hsum = [&](int y) -> Sum4 {
-        const uint8_t* row = base + (size_t)min(max(y, 0), g.H - 1) * g.W1 * g.D;
+        const T* row = base + (size_t)min(max(y, 0), g.H - 1) * g.W1 * g.D;
         Sum4 s = {{0, 0, 0, 0}};
 #pragma unroll
-        for (int k = 0; k <= 2 * R; ++k) {
-            const uint32_t w = *(const uint32_t*)(row + xs[k]);
-            s.v[0] += w & 0xff; s.v[1] += (w >> 8) & 0xff; s.v[2] += (w >> 16) & 0xff; s.v[3] += w >> 24;
-        }
+        for (int k = 0; k <= 2 * R; ++k) sgm_acc4(row + xs[k], s.v);
         return s;
     };
     Sum4 ring[2 * R + 1];
@@ -254,7 +268,8 @@ __global__ __launch_bounds__(256) void k_sgm_pixbox(const uint2* bl, const uint2
 // Any window (R > 8: the register ring of k_sgm_box<R> would not fit): the running vertical sum gains the entering row's
 // horizontal sum and loses the leaving row's, both recomputed -- 2 (2R + 1) loads per output instead of 2R + 1.  Sums are
 // 32-bit; a block cost above cost_limit (> 0) sets *ovf and is stored truncated (the caller refuses the frame).
-__global__ __launch_bounds__(256) void k_sgm_box_any(const uint8_t* pix, uint16_t* C, SGMGeom g, int R, int rows_per_strip, int cost_limit, int32_t* ovf)
+template <typename T>
+__global__ __launch_bounds__(256) void k_sgm_box_any(const T* pix, uint16_t* C, SGMGeom g, int R, int rows_per_strip, int cost_limit, int32_t* ovf)
 {
     const int dq = g.D >> 2;
     const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;          // over W1 * D/4
@@ -262,15 +277,12 @@ __global__ __launch_bounds__(256) void k_sgm_box_any(const uint8_t* pix, uint16_
     const int d = (int)(idx % dq) * 4, xi = (int)(idx / dq);
     const int f = blockIdx.z;
     const int y0 = blockIdx.y * rows_per_strip, y1 = min(y0 + rows_per_strip, g.H);
-    const uint8_t* base = pix + (size_t)f * g.H * g.W1 * g.D + d;
+    const T* base = pix + (size_t)f * g.H * g.W1 * g.D + d;
     struct Sum4 { int v[4]; };
     const auto hsum = [&](int y) -> Sum4 {
-        const uint8_t* row = base + (size_t)min(max(y, 0), g.H - 1) * g.W1 * g.D;
+        const T* row = base + (size_t)min(max(y, 0), g.H - 1) * g.W1 * g.D;
         Sum4 s = {{0, 0, 0, 0}};
-        for (int k = -R; k <= R; ++k) {
-            const uint32_t w = *(const uint32_t*)(row + (size_t)min(max(xi + k, 0), g.W1 - 1) * g.D);
-            s.v[0] += w & 0xff; s.v[1] += (w >> 8) & 0xff; s.v[2] += (w >> 16) & 0xff; s.v[3] += w >> 24;
-        }
+        for (int k = -R; k <= R; ++k) sgm_acc4(row + (size_t)min(max(xi + k, 0), g.W1 - 1) * g.D, s.v);
         return s;
     };
     int sum[4] = {0, 0, 0, 0};
@@ -283,6 +295,120 @@ __global__ __launch_bounds__(256) void k_sgm_box_any(const uint8_t* pix, uint16_
         const Sum4 a = hsum(y + R + 1), b = hsum(y - R);
         for (int j = 0; j < 4; ++j) sum[j] += a.v[j] - b.v[j];
     }
+}
+
+// ---- 16-bit pixel costs: colour (CN = 3) at any preFilterCap, gray at ftzero >= 97 --------------------------------------------
+// A pixel cost is at most M = CN (2 ftzero + 63): 93 for gray at preFilterCap 0, 255 for gray at ftzero 96, 279 .. 951 for colour.
+// Past 255 it no longer fits the u8 forms above; these keep their packed-u16 Birchfield-Tomasi arithmetic (bt_cost2) and sum the
+// CN channels in it (<= 951 per half: no carry).  The pixel-cost volume, where there is one, is u16 and lives in S (dead until
+// the first path pass writes it).
+
+// packed u16 pixel cost of one left record a against two right records (low half: lo, high half: hi)
+__device__ __forceinline__ uint32_t sgm_cost2(uint2 a, uint2 lo, uint2 hi)
+{
+    const auto rep = [](uint32_t w, int k) -> uint32_t { return ((w >> (8 * k)) & 0xffu) * 0x00010001u; };
+    const uint32_t cg = bt_cost2(rep(a.x, 0), rep(a.x, 1), rep(a.x, 2), __builtin_amdgcn_perm(hi.x, lo.x, 0x0C040C00u),
+                                 __builtin_amdgcn_perm(hi.x, lo.x, 0x0C050C01u), __builtin_amdgcn_perm(hi.x, lo.x, 0x0C060C02u));
+    const uint32_t cr = bt_cost2(rep(a.y, 0), rep(a.y, 1), rep(a.y, 2), __builtin_amdgcn_perm(hi.y, lo.y, 0x0C040C00u),
+                                 __builtin_amdgcn_perm(hi.y, lo.y, 0x0C050C01u), __builtin_amdgcn_perm(hi.y, lo.y, 0x0C060C02u));
+    return cg + ((cr >> 2) & 0x003f003fu);
+}
+
+// pixel costs of left column x against right columns xr, xr - 1, xr - 2, xr - 3 (disparities d .. d + 3), summed over the CN
+// channels: {(d, d + 1), (d + 2, d + 3)} as packed u16.  row = (f * H + y) * W.
+template <int CN>
+__device__ __forceinline__ uint2 sgm_cost4(const uint2* bl, const uint2* br, size_t row, int x, int xr)
+{
+    uint32_t c0 = 0u, c1 = 0u;
+#pragma unroll
+    for (int c = 0; c < CN; ++c) {
+        const uint2 a = bl[(row + x) * CN + c];
+        uint2 b[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) b[j] = br[(row + xr - j) * CN + c];
+        c0 += sgm_cost2(a, b[0], b[1]);
+        c1 += sgm_cost2(a, b[2], b[3]);
+    }
+    return make_uint2(c0, c1);
+}
+
+// k_sgm_pix with u16 pixel costs: one thread per (x, four consecutive d) -> pix [n][H][W1][D]
+template <int CN>
+__global__ __launch_bounds__(256) void k_sgm_pix16(const uint2* bl, const uint2* br, uint16_t* pix, SGMGeom g)
+{
+    const int dq = g.D >> 2;
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;          // over W1 * D/4
+    if (idx >= (size_t)g.W1 * dq) return;
+    const int d = (int)(idx % dq) * 4, xi = (int)(idx / dq);
+    const int y = blockIdx.y, f = blockIdx.z;
+    const int x = g.x0 + xi, xr = x - (d + g.minD);
+    const size_t row = ((size_t)f * g.H + y) * g.W;
+    *(uint2*)(pix + (((size_t)f * g.H + y) * g.W1 + xi) * g.D + d) = sgm_cost4<CN>(bl, br, row, x, xr);
+}
+
+// k_sgm_pixbox with u16 pixel costs (same tiling, strips and ring; the LDS tile holds four u16 per (column, quad)).  Block sums
+// stay below 49 * 951 < 65536, so the packed u16 ring is exact; unlike k_sgm_pixbox this form checks them against cost_limit
+// (> 0 where a block cost + P2 can pass 32767) and sets *ovf.
+template <int CN, int R, int DQ>
+__global__ __launch_bounds__(256) void k_sgm_pixbox16(const uint2* bl, const uint2* br, uint16_t* C, SGMGeom g, int rows_per_strip,
+                                                      int cost_limit, int32_t* ovf)
+{
+    constexpr int CG = 256 / DQ, TX = 4 * CG, TW = TX + 2 * R, NP = (TW + CG - 1) / CG, W1R = 2 * R + 1, PU = CN == 1 ? NP : 1;
+    __shared__ uint2 tile[2][TW][DQ];                       // [row parity][tile column][disparity quad]: four u16 pixel costs
+    const int dqi = threadIdx.x % DQ, cg = threadIdx.x / DQ, d = dqi * 4;
+    const int xt0 = blockIdx.x * TX;
+    const int f = blockIdx.z;
+    const int y0 = blockIdx.y * rows_per_strip, y1 = min(y0 + rows_per_strip, g.H);
+    uint32_t ring[4][W1R][2], sum[4][2];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { sum[i][0] = sum[i][1] = 0u; for (int k = 0; k < W1R; ++k) ring[i][k][0] = ring[i][k][1] = 0u; }
+    bool over = false;
+    const int nsrc = (y1 - y0) + 2 * R;
+    for (int base = 0; base < nsrc; base += W1R) {
+#pragma unroll
+        for (int k = 0; k < W1R; ++k) {
+            const int t = base + k;
+            if (t < nsrc) {                                 // workgroup-uniform
+                const int par = t & 1;
+                const int ysrc = min(max(y0 - R + t, 0), g.H - 1);
+                const size_t row = ((size_t)f * g.H + ysrc) * g.W;
+                // (colour: this loop stays rolled, or the whole body of the unrolled k loop grows past what the compiler unrolls,
+                // and then ring[][k] goes to scratch)
+#pragma unroll PU
+                for (int p = 0; p < NP; ++p) {
+                    const int tc = cg + p * CG;
+                    if (tc < TW) {
+                        const int xi = min(max(xt0 - R + tc, 0), g.W1 - 1);
+                        const int x = g.x0 + xi;
+                        tile[par][tc][dqi] = sgm_cost4<CN>(bl, br, row, x, x - (d + g.minD));
+                    }
+                }
+                __syncthreads();
+                const int yo = y0 - 2 * R + t;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int tcol = cg + i * CG;
+                    uint32_t h0 = 0u, h1 = 0u;
+#pragma unroll
+                    for (int q = 0; q < W1R; ++q) {
+                        const uint2 w = tile[par][tcol + q][dqi];
+                        h0 = sgm_add2(h0, w.x);
+                        h1 = sgm_add2(h1, w.y);
+                    }
+                    sum[i][0] = sgm_sub2(sgm_add2(sum[i][0], h0), ring[i][k][0]);
+                    sum[i][1] = sgm_sub2(sgm_add2(sum[i][1], h1), ring[i][k][1]);
+                    ring[i][k][0] = h0; ring[i][k][1] = h1;
+                    const int xo = xt0 + tcol;
+                    if (yo >= y0 && xo < g.W1) {
+                        *(uint2*)(C + (((size_t)f * g.H + yo) * g.W1 + xo) * g.D + d) = make_uint2(sum[i][0], sum[i][1]);
+                        const uint32_t m = sgm_max2(sum[i][0], sum[i][1]);
+                        over |= (int)max(m & 0xffffu, m >> 16) > cost_limit;
+                    }
+                }
+            }
+        }
+    }
+    if (cost_limit > 0 && over) *ovf = 1;
 }
 
 // wave-wide minimum (DPP), uniform result
@@ -1162,18 +1288,65 @@ static bool launch_sweep(bool last, const SGMGeom& g, const SGMBuffers& b, int d
 static void sgm_finish(Plane16W disp, const SGMGeom& g, const SGMBuffers& b, int disp12MaxDiff, int speckleWindowSize,
                        int speckleRange, int n, hipStream_t stream, const SgmWin* win, bool fused, int uniq);
 
+// rtdm_debug_sgm_cost16: the u16 cost forms for gray frames as well (they must give what the u8 forms give)
+static std::atomic<int> g_cost16{0};
+void sgm_cost16_set(int on) { g_cost16.store(on ? 1 : 0, std::memory_order_relaxed); }
+bool sgm_cost16_needed(int cn, int ftz) { return cn != 1 || 2 * ftz + 63 > 255 || g_cost16.load(std::memory_order_relaxed); }
+
+// pixel cost + block sum with u16 pixel costs -> C: fused (windows <= 7, D <= 256, k_sgm_pixbox16, which checks cost_limit
+// itself) or k_sgm_pix16 into the u16 volume (S) + k_sgm_box / _any over it
+static void launch_cost16(const SGMGeom& g, const SGMBuffers& b, int blockSize, int cn, bool fused, int cost_limit, int n,
+                          hipStream_t stream)
+{
+    const dim3 blk(256);
+    const uint2 *bl = (const uint2*)(cn == 3 ? b.cl : b.gl), *br = (const uint2*)(cn == 3 ? b.cr : b.gr);
+    const int Rw = blockSize / 2, dq = g.D / 4, rps = 48, strips = (g.H + rps - 1) / rps;
+    if (fused) {
+        const int tx = 4 * (256 / dq);
+        const dim3 pgrid((g.W1 + tx - 1) / tx, strips, n);
+#define RTDM_PB(CC, RR, QQ) hipLaunchKernelGGL((k_sgm_pixbox16<CC, RR, QQ>), pgrid, blk, 0, stream, bl, br, b.C, g, rps, cost_limit, b.ovf)
+#define RTDM_PBQ(CC, RR) do { switch (dq) { case 4: RTDM_PB(CC, RR, 4); break; case 8: RTDM_PB(CC, RR, 8); break; \
+                                            case 16: RTDM_PB(CC, RR, 16); break; case 32: RTDM_PB(CC, RR, 32); break; \
+                                            default: RTDM_PB(CC, RR, 64); break; } } while (0)
+#define RTDM_PBR(CC) do { switch (Rw) { case 0: RTDM_PBQ(CC, 0); break; case 1: RTDM_PBQ(CC, 1); break; \
+                                        case 2: RTDM_PBQ(CC, 2); break; default: RTDM_PBQ(CC, 3); break; } } while (0)
+        if (cn == 3) RTDM_PBR(3); else RTDM_PBR(1);
+#undef RTDM_PBR
+#undef RTDM_PBQ
+#undef RTDM_PB
+        return;
+    }
+    const unsigned nxd = (unsigned)(((size_t)g.W1 * dq + 255) / 256);
+    uint16_t* pix = b.S;                                 // u16 pixel costs: S is not written before the first path pass
+    if (cn == 3) hipLaunchKernelGGL(k_sgm_pix16<3>, dim3(nxd, g.H, n), blk, 0, stream, bl, br, pix, g);
+    else hipLaunchKernelGGL(k_sgm_pix16<1>, dim3(nxd, g.H, n), blk, 0, stream, bl, br, pix, g);
+    const dim3 bgrid(nxd, strips, n);
+    switch (Rw) {
+        // (windows <= 13: the register ring of k_sgm_box<R> holds 64-bit loads as well; above it would spill)
+#define RTDM_BOX(RR) case RR: hipLaunchKernelGGL((k_sgm_box<RR, uint16_t>), bgrid, blk, 0, stream, (const uint16_t*)pix, b.C, g, rps, cost_limit, b.ovf); break;
+        RTDM_BOX(0) RTDM_BOX(1) RTDM_BOX(2) RTDM_BOX(3) RTDM_BOX(4) RTDM_BOX(5) RTDM_BOX(6)
+        default: hipLaunchKernelGGL(k_sgm_box_any<uint16_t>, bgrid, blk, 0, stream, (const uint16_t*)pix, b.C, g, Rw, rps, cost_limit, b.ovf); break;
+#undef RTDM_BOX
+    }
+}
+
 const char* launch_sgm(Plane8 L, Plane8 R, Plane16W disp, const SGMGeom& g, const SGMBuffers& b, int blockSize, int P1, int P2,
                        int uniq, int disp12MaxDiff, int speckleWindowSize, int speckleRange, int paths, int n, hipStream_t stream,
-                       int cost_limit)
+                       int cost_limit, int cn, int ftz)
 {
     dim3 blk(256);
-    hipLaunchKernelGGL(k_sgm_bounds, dim3((g.W + 255) / 256, g.H, 2 * n), blk, 0, stream, L, R, (uint2*)b.gl, (uint2*)b.gr, g.W, g.H, n);
+    const dim3 bnd((g.W + 255) / 256, g.H, 2 * n);
+    if (cn == 3) hipLaunchKernelGGL(k_sgm_bounds<3>, bnd, blk, 0, stream, L, R, (uint2*)b.cl, (uint2*)b.cr, g.W, g.H, n, ftz);
+    else hipLaunchKernelGGL(k_sgm_bounds<1>, bnd, blk, 0, stream, L, R, (uint2*)b.gl, (uint2*)b.gr, g.W, g.H, n, ftz);
     const unsigned nxd = (unsigned)(((size_t)g.W1 * (g.D / 4) + 255) / 256);       // D is a multiple of 16
     // RTDM_SGM_PIXBOX=0 (A/B): pixel cost and block sum as two kernels with the u8 volume between them, for every window
     static const int pixbox_env = env_int("RTDM_SGM_PIXBOX", 1);
     const int Rw = blockSize / 2, dq = g.D / 4;
-    const bool pixbox = pixbox_env && Rw <= 3 && (dq == 4 || dq == 8 || dq == 16 || dq == 32 || dq == 64) && !cost_limit;
-    if (pixbox) {
+    const bool dq_ok = dq == 4 || dq == 8 || dq == 16 || dq == 32 || dq == 64;
+    const bool pixbox = pixbox_env && Rw <= 3 && dq_ok && !cost_limit;
+    if (sgm_cost16_needed(cn, ftz)) {
+        launch_cost16(g, b, blockSize, cn, pixbox_env && Rw <= 3 && dq_ok, cost_limit, n, stream);
+    } else if (pixbox) {
         const int rps = 48, strips = (g.H + rps - 1) / rps, tx = 4 * (256 / dq);
         const dim3 pgrid((g.W1 + tx - 1) / tx, strips, n);
 #define RTDM_PB(RR, QQ) hipLaunchKernelGGL((k_sgm_pixbox<RR, QQ>), pgrid, blk, 0, stream, (const uint2*)b.gl, (const uint2*)b.gr, b.C, g, rps)
@@ -1188,9 +1361,9 @@ const char* launch_sgm(Plane8 L, Plane8 R, Plane16W disp, const SGMGeom& g, cons
         const int rps = 48, strips = (g.H + rps - 1) / rps;
         const dim3 bgrid(nxd, strips, n);
         switch (blockSize / 2) {                      // windows <= 17: the row sums of a strip stay in registers
-#define RTDM_BOX(RR) case RR: hipLaunchKernelGGL(k_sgm_box<RR>, bgrid, blk, 0, stream, b.pix, b.C, g, rps, cost_limit, b.ovf); break;
+#define RTDM_BOX(RR) case RR: hipLaunchKernelGGL((k_sgm_box<RR, uint8_t>), bgrid, blk, 0, stream, (const uint8_t*)b.pix, b.C, g, rps, cost_limit, b.ovf); break;
             RTDM_BOX(0) RTDM_BOX(1) RTDM_BOX(2) RTDM_BOX(3) RTDM_BOX(4) RTDM_BOX(5) RTDM_BOX(6) RTDM_BOX(7) RTDM_BOX(8)
-            default: hipLaunchKernelGGL(k_sgm_box_any, bgrid, blk, 0, stream, b.pix, b.C, g, blockSize / 2, rps, cost_limit, b.ovf); break;
+            default: hipLaunchKernelGGL(k_sgm_box_any<uint8_t>, bgrid, blk, 0, stream, (const uint8_t*)b.pix, b.C, g, blockSize / 2, rps, cost_limit, b.ovf); break;
 #undef RTDM_BOX
         }
     }

@@ -1008,9 +1008,12 @@ struct rtdm_sgm {
     int maxW, maxH, maxB, device;
     hipStream_t stream;
     uint8_t *dInL, *dInR;
+    uint8_t *dInL3, *dInR3;        // colour staging of rtdm_sgm_compute_cn (allocated by the first colour call)
     int16_t* dOut;
     SGMBuffers b;
-    int cost_limit;                // > 0 (windows > 17 at P2 = 2400): a block cost above it would wrap the library's 16-bit path costs
+    int prefilter_cap;             // rtdm_sgm_set_prefilter_cap: R1's ftzero = max(preFilterCap, 15) | 1
+    int cost_limit;                // of the current call, > 0 where a block cost + P2 can pass 32767: a block cost above it would
+                                   // wrap the library's 16-bit path costs (sgm_cost_limit)
     int32_t* hOvf;                 // page-locked copy of b.ovf
     uint32_t sweep_epoch;          // launches of k_sgm_sweep (tags of its edge ring)
     int sweep_cap[36];             // workgroups the device holds at once, per instantiation (0 = not asked yet)
@@ -1027,6 +1030,34 @@ static int sgm_sweep_check(rtdm_sgm* sg)
     g_hip_err = "StereoSGBM: a row-synchronous sweep gave up waiting for a neighbouring strip; the output of that call is invalid "
                 "(this handle runs one pass per direction from now on)";
     return RTDM_ERR_HIP;
+}
+
+// R1 generalised (oracle rule restated for colour in tests/sgm_cn_ref.py): a pixel cost is at most M = cn (2 ftzero + 63), a
+// block cost at most M blockSize^2; where that + P2 can pass 32767 the block costs are checked against 32767 - P2
+static int sgm_ftzero(const rtdm_sgm* sg) { return std::max(sg->prefilter_cap, 15) | 1; }
+static int sgm_cost_limit(const rtdm_sgm* sg, int cn)
+{
+    const long M = (long)cn * (2 * sgm_ftzero(sg) + 63);
+    return M * sg->p.blockSize * sg->p.blockSize + sg->p.P2 > 32767 ? 32767 - sg->p.P2 : 0;
+}
+
+// colour frames: the 24-byte bounds records (and, for the host entry point, the staging of the interleaved input)
+static int sgm_colour_buffers(rtdm_sgm* sg, bool host)
+{
+    const size_t px = (size_t)sg->maxW * sg->maxH * sg->maxB;
+    void** ptrs[] = {(void**)&sg->b.cl, (void**)&sg->b.cr, (void**)&sg->dInL3, (void**)&sg->dInR3};
+    const size_t sizes[] = {px * 24, px * 24, (size_t)sg->maxW * sg->maxH * 3, (size_t)sg->maxW * sg->maxH * 3};
+    for (int i = 0; i < (host ? 4 : 2); ++i) {
+        if (*ptrs[i]) continue;
+        const hipError_t e = hipMalloc(ptrs[i], sizes[i]);
+        if (e != hipSuccess) {
+            *ptrs[i] = nullptr;
+            (void)hipGetLastError();
+            g_hip_err = std::string("StereoSGBM colour buffers: ") + hipGetErrorString(e);
+            return e == hipErrorOutOfMemory ? RTDM_ERR_NOMEM : RTDM_ERR_HIP;
+        }
+    }
+    return RTDM_OK;
 }
 
 // windows whose block cost + P2 can pass 32767: the frame is refused if it does (what is not restated is the wrap-around)
@@ -1066,18 +1097,17 @@ int rtdm_sgm_create(const rtdm_sgm_params* params, int max_width, int max_height
     if (p.disp12MaxDiff <= 0) p.disp12MaxDiff = 1;         // the library's left-right check cannot be switched off
     if (max_width <= 0 || max_height <= 0 || max_batch <= 0) return RTDM_ERR_BAD_SIZE;
     if (max_width > 4096) return RTDM_ERR_UNSUPPORTED;
-    // 16-bit costs: a path cost is at most block cost + P2 (pixel cost <= 30 + 63); above 32767 the library's short
-    // arithmetic wraps, which is not restated: windows that CAN get there (> 17 at P2 = 2400) run with a check of the block
-    // costs and refuse the frame that does (RTDM_ERR_UNSUPPORTED from the compute call; it takes nearly every pixel of a
-    // window at the maximum pixel cost)
+    // 16-bit costs: a path cost is at most block cost + P2 (pixel cost <= M = cn (2 ftzero + 63), 93 for gray at preFilterCap
+    // 0); above 32767 the library's short arithmetic wraps, which is not restated: windows that CAN get there (gray at preFilterCap
+    // 0: > 17 at P2 = 2400) run with a check of the block costs and refuse the frame that does (RTDM_ERR_UNSUPPORTED from the
+    // compute call; it takes nearly every pixel of a window at the maximum pixel cost).  The limit is set per call
+    // (sgm_cost_limit): preFilterCap and the channel count change M.
     if (p.blockSize > 255 || p.P2 > 32000) return RTDM_ERR_UNSUPPORTED;
-    const int cost_limit = 93L * p.blockSize * p.blockSize + p.P2 > 32767 ? 32767 - p.P2 : 0;
     int rc = use_device(device);
     if (rc) return rc;
     rtdm_sgm* sg = new (std::nothrow) rtdm_sgm();
     if (!sg) return RTDM_ERR_NOMEM;
     sg->p = p; sg->maxW = max_width; sg->maxH = max_height; sg->maxB = max_batch; sg->device = device;
-    sg->cost_limit = cost_limit;
     sg->path_variant = "";
     const size_t px = (size_t)max_width * max_height * max_batch;
     // D <= 256: volumes on max_width columns, as always.  D > 256 (the wide path pass): on the widest column domain a frame can
@@ -1120,7 +1150,7 @@ void rtdm_sgm_destroy(rtdm_sgm* sg)
     (void)hipSetDevice(sg->device);
     if (sg->stream) (void)hipStreamSynchronize(sg->stream);
     void* bufs[] = {sg->dInL, sg->dInR, sg->dOut, sg->b.gl, sg->b.gr, sg->b.pix, sg->b.C, sg->b.S, sg->b.label, sg->b.size,
-                    sg->b.runs, sg->b.rowcnt, sg->b.headmap};
+                    sg->b.runs, sg->b.rowcnt, sg->b.headmap, sg->b.cl, sg->b.cr, sg->dInL3, sg->dInR3};
     for (void* b : bufs) if (b) (void)hipFree(b);
     if (sg->b.ovf) (void)hipFree(sg->b.ovf);
     if (sg->b.ring) (void)hipFree(sg->b.ring);
@@ -1133,7 +1163,7 @@ void rtdm_sgm_destroy(rtdm_sgm* sg)
     delete sg;
 }
 
-static int sgm_chunk(rtdm_sgm* sg, int n, Plane8 L, Plane8 R, int W, int H, Plane16W disp, hipStream_t s)
+static int sgm_chunk(rtdm_sgm* sg, int n, int cn, Plane8 L, Plane8 R, int W, int H, Plane16W disp, hipStream_t s)
 {
     const rtdm_sgm_params& p = sg->p;
     SGMGeom g;
@@ -1142,49 +1172,80 @@ static int sgm_chunk(rtdm_sgm* sg, int n, Plane8 L, Plane8 R, int W, int H, Plan
     g.W1 = (W + std::min(g.minD, 0)) - g.x0;
     if (g.W1 <= 0) { launch_fill16(disp, 0, W, 0, H, n, (g.minD - 1) * 16, s); return RTDM_OK; }
     sg->path_variant = launch_sgm(L, R, disp, g, sg->b, p.blockSize, p.P1, p.P2, p.uniquenessRatio, p.disp12MaxDiff,
-                                  p.speckleWindowSize, p.speckleRange, p.paths, n, s, sg->cost_limit);
+                                  p.speckleWindowSize, p.speckleRange, p.paths, n, s, sg->cost_limit, cn, sgm_ftzero(sg));
     HIPC(hipGetLastError());
     return RTDM_OK;
+}
+
+int rtdm_sgm_compute_device_cn(rtdm_sgm* sg, int channels, int n, const uint8_t* d_left, const uint8_t* d_right, size_t pitch,
+                               size_t frame_stride, int width, int height, int16_t* d_disp, size_t disp_pitch,
+                               size_t disp_frame_stride, void* hip_stream)
+{
+    if (!sg || !d_left || !d_right || !d_disp) return RTDM_ERR_NULL;
+    if (channels != 1 && channels != 3) return RTDM_ERR_BAD_PARAM;
+    if (n <= 0 || width <= 0 || height <= 0 || width > sg->maxW || height > sg->maxH) return RTDM_ERR_BAD_SIZE;
+    if (pitch < (size_t)width * channels || disp_pitch < (size_t)width * 2 || (disp_pitch & 1) || (disp_frame_stride & 1)) return RTDM_ERR_BAD_SIZE;
+    HIPC(hipSetDevice(sg->device));
+    if (channels == 3) { const int rc = sgm_colour_buffers(sg, false); if (rc) return rc; }
+    sg->cost_limit = sgm_cost_limit(sg, channels);
+    hipStream_t s = (hipStream_t)hip_stream;          // NULL = the HIP null stream
+    for (int i0 = 0; i0 < n; i0 += sg->maxB) {
+        const int m = std::min(sg->maxB, n - i0);
+        Plane8 L{d_left + (size_t)i0 * frame_stride, pitch, frame_stride}, R{d_right + (size_t)i0 * frame_stride, pitch, frame_stride};
+        Plane16W O{d_disp + (size_t)i0 * (disp_frame_stride / 2), disp_pitch / 2, disp_frame_stride / 2};
+        int rc = sgm_chunk(sg, m, channels, L, R, width, height, O, s);
+        if (rc) return rc;
+    }
+    int rc = sgm_overflow_check(sg, s);                // (where a block cost can overflow: this call then synchronises the stream)
+    return rc ? rc : sgm_sweep_check(sg);              // (asynchronous call: a give-up of this call's sweep shows in the next call)
 }
 
 int rtdm_sgm_compute_device(rtdm_sgm* sg, int n, const uint8_t* d_left, const uint8_t* d_right, size_t pitch,
                             size_t frame_stride, int width, int height, int16_t* d_disp, size_t disp_pitch,
                             size_t disp_frame_stride, void* hip_stream)
 {
-    if (!sg || !d_left || !d_right || !d_disp) return RTDM_ERR_NULL;
-    if (n <= 0 || width <= 0 || height <= 0 || width > sg->maxW || height > sg->maxH) return RTDM_ERR_BAD_SIZE;
-    if (pitch < (size_t)width || disp_pitch < (size_t)width * 2 || (disp_pitch & 1) || (disp_frame_stride & 1)) return RTDM_ERR_BAD_SIZE;
-    HIPC(hipSetDevice(sg->device));
-    hipStream_t s = (hipStream_t)hip_stream;          // NULL = the HIP null stream
-    for (int i0 = 0; i0 < n; i0 += sg->maxB) {
-        const int m = std::min(sg->maxB, n - i0);
-        Plane8 L{d_left + (size_t)i0 * frame_stride, pitch, frame_stride}, R{d_right + (size_t)i0 * frame_stride, pitch, frame_stride};
-        Plane16W O{d_disp + (size_t)i0 * (disp_frame_stride / 2), disp_pitch / 2, disp_frame_stride / 2};
-        int rc = sgm_chunk(sg, m, L, R, width, height, O, s);
-        if (rc) return rc;
-    }
-    int rc = sgm_overflow_check(sg, s);                // (windows > 17 only: this call then synchronises the stream)
-    return rc ? rc : sgm_sweep_check(sg);              // (asynchronous call: a give-up of this call's sweep shows in the next call)
+    return rtdm_sgm_compute_device_cn(sg, 1, n, d_left, d_right, pitch, frame_stride, width, height, d_disp, disp_pitch,
+                                      disp_frame_stride, hip_stream);
 }
 
-int rtdm_sgm_compute(rtdm_sgm* sg, const uint8_t* left, size_t left_pitch, const uint8_t* right, size_t right_pitch,
-                     int width, int height, int16_t* disp, size_t disp_pitch)
+int rtdm_sgm_compute_cn(rtdm_sgm* sg, int channels, const uint8_t* left, size_t left_pitch, const uint8_t* right,
+                        size_t right_pitch, int width, int height, int16_t* disp, size_t disp_pitch)
 {
     if (!sg || !left || !right || !disp) return RTDM_ERR_NULL;
+    if (channels != 1 && channels != 3) return RTDM_ERR_BAD_PARAM;
     if (width <= 0 || height <= 0 || width > sg->maxW || height > sg->maxH) return RTDM_ERR_BAD_SIZE;
-    if (left_pitch < (size_t)width || right_pitch < (size_t)width || disp_pitch < (size_t)width * 2) return RTDM_ERR_BAD_SIZE;
+    const size_t row = (size_t)width * channels;
+    if (left_pitch < row || right_pitch < row || disp_pitch < (size_t)width * 2) return RTDM_ERR_BAD_SIZE;
     HIPC(hipSetDevice(sg->device));
+    if (channels == 3) { const int rc = sgm_colour_buffers(sg, true); if (rc) return rc; }
+    sg->cost_limit = sgm_cost_limit(sg, channels);
     hipStream_t s = sg->stream;
-    HIPC(hipMemcpy2DAsync(sg->dInL, width, left, left_pitch, width, height, hipMemcpyHostToDevice, s));
-    HIPC(hipMemcpy2DAsync(sg->dInR, width, right, right_pitch, width, height, hipMemcpyHostToDevice, s));
-    Plane8 L{sg->dInL, (size_t)width, (size_t)width * height}, R{sg->dInR, (size_t)width, (size_t)width * height};
+    uint8_t* inL = channels == 3 ? sg->dInL3 : sg->dInL;
+    uint8_t* inR = channels == 3 ? sg->dInR3 : sg->dInR;
+    HIPC(hipMemcpy2DAsync(inL, row, left, left_pitch, row, height, hipMemcpyHostToDevice, s));
+    HIPC(hipMemcpy2DAsync(inR, row, right, right_pitch, row, height, hipMemcpyHostToDevice, s));
+    Plane8 L{inL, row, row * height}, R{inR, row, row * height};
     Plane16W O{sg->dOut, (size_t)width, (size_t)width * height};
-    int rc = sgm_chunk(sg, 1, L, R, width, height, O, s);
+    int rc = sgm_chunk(sg, 1, channels, L, R, width, height, O, s);
     if (rc) return rc;
     HIPC(hipMemcpy2DAsync(disp, disp_pitch, sg->dOut, (size_t)width * 2, (size_t)width * 2, height, hipMemcpyDeviceToHost, s));
     HIPC(hipStreamSynchronize(s));
     rc = sgm_overflow_check(sg, s);
     return rc ? rc : sgm_sweep_check(sg);
+}
+
+int rtdm_sgm_compute(rtdm_sgm* sg, const uint8_t* left, size_t left_pitch, const uint8_t* right, size_t right_pitch,
+                     int width, int height, int16_t* disp, size_t disp_pitch)
+{
+    return rtdm_sgm_compute_cn(sg, 1, left, left_pitch, right, right_pitch, width, height, disp, disp_pitch);
+}
+
+int rtdm_sgm_set_prefilter_cap(rtdm_sgm* sg, int preFilterCap)
+{
+    if (!sg) return RTDM_ERR_NULL;
+    if (preFilterCap >= 128) return RTDM_ERR_UNSUPPORTED;      // the library's 8-bit clip table wraps from here on
+    sg->prefilter_cap = preFilterCap;
+    return RTDM_OK;
 }
 
 int rtdm_sgm_get_pass_stats(const rtdm_sgm* sg, long* sweeps, int* gave_up)
@@ -1197,6 +1258,7 @@ int rtdm_sgm_get_pass_stats(const rtdm_sgm* sg, long* sweeps, int* gave_up)
 
 const char* rtdm_sgm_path_variant(const rtdm_sgm* sg) { return sg ? sg->path_variant : ""; }
 void rtdm_debug_sgm_wide_paths(int lines_per_wave_or_waves) { sgm_wide_set_mode(lines_per_wave_or_waves); }
+void rtdm_debug_sgm_cost16(int on) { sgm_cost16_set(on); }
 
 // ---- rectification in front of the matcher (estimator.cpp:29-39) ----------------------------------------------
 struct rtdm_rectify {

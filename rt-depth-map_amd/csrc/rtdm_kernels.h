@@ -154,6 +154,8 @@ void launch_morph_open_close(Plane8 in, Plane8W out, uint8_t* tmp0, uint8_t* tmp
 struct SGMGeom { int W, H, D, minD, x0, W1; };
 struct SGMBuffers {
     uint8_t *gl, *gr;        // Birchfield-Tomasi bounds of gradient and intensity, 2 x uchar4 per pixel  [n][H][W]
+    uint8_t *cl, *cr;        // the same for colour frames, one uint2 per channel: 24 bytes per pixel [n][H][W][3] (or null:
+                             // allocated by the first colour call)
     uint8_t* pix;            // pixel cost                 [n][H][W1][D]
     uint16_t *C, *S;         // block cost, aggregated     [n][H][W1][D]
     uint16_t* S2;            // the (-1, 0) direction's path costs where the two horizontal directions run side by side (or null)
@@ -177,12 +179,16 @@ void launch_sgm_wide(const SGMGeom& g, const uint16_t* C, uint16_t* S, int dx, i
 int sgm_wide_waves(int D);
 void sgm_wide_set_mode(int m);
 int sgm_wide_mode();
-// cost_limit > 0: block costs above it set *b.ovf (the caller reads it back: rtdm_api.hip)
+// cost_limit > 0: block costs above it set *b.ovf (the caller reads it back: rtdm_api.hip).  cn: 1 (gray) or 3 (interleaved
+// colour, reads b.cl / b.cr); ftz: R1's ftzero = max(preFilterCap, 15) | 1, at most 127.  Where a pixel cost can pass 255
+// (sgm_cost16_needed: colour, ftz >= 97, or rtdm_debug_sgm_cost16) the cost stage runs on u16 pixel costs.
 // Returns the name of the path-pass form the call ran ("sweep", "half", "wave", "block", "wide_w1", "wide_w4").  D > 256 (or a
 // forced wide mode) runs the wide pass for every direction, whatever the A/B environment switches say.
 const char* launch_sgm(Plane8 L, Plane8 R, Plane16W disp, const SGMGeom& g, const SGMBuffers& b, int blockSize, int P1, int P2,
                        int uniq, int disp12MaxDiff, int speckleWindowSize, int speckleRange, int paths, int n, hipStream_t stream,
-                       int cost_limit = 0);
+                       int cost_limit = 0, int cn = 1, int ftz = 15);
+bool sgm_cost16_needed(int cn, int ftz);
+void sgm_cost16_set(int on);
 
 // Depth statistics after the matcher (estimator.cpp:75-77, 206-263).  q = the 4x4 reprojection matrix Q, row major.
 struct DepthQ { double q[16]; };

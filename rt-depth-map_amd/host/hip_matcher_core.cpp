@@ -138,6 +138,18 @@ int HIPSGMCore::compute(const uint8_t* left, size_t leftStep, const uint8_t* rig
     status_ = rtdm_sgm_compute(sg_, left, leftStep, right, rightStep, cols, rows, out, outStep);
     return status_;
 }
+int HIPSGMCore::compute(int channels, const uint8_t* left, size_t leftStep, const uint8_t* right, size_t rightStep, int rows,
+                        int cols, int16_t* out, size_t outStep)
+{
+    if (!sg_) return status_ != RTDM_OK ? status_ : RTDM_ERR_NO_DEVICE;
+    status_ = rtdm_sgm_compute_cn(sg_, channels, left, leftStep, right, rightStep, cols, rows, out, outStep);
+    return status_;
+}
+int HIPSGMCore::setPreFilterCap(int preFilterCap)
+{
+    if (!sg_) return status_ != RTDM_OK ? status_ : RTDM_ERR_NO_DEVICE;
+    return rtdm_sgm_set_prefilter_cap(sg_, preFilterCap);
+}
 
 HIPMorphCore::HIPMorphCore(int w, int h, int bpp, int device) : width_(w), height_(h), bpp_(bpp)
 {

@@ -74,6 +74,11 @@ public:
     HIPSGMCore& operator=(const HIPSGMCore&) = delete;
     int compute(const uint8_t* left, size_t leftStep, const uint8_t* right, size_t rightStep,
                 int rows, int cols, int16_t* out, size_t outStep);
+    // channels = 1 (the call above) or 3: interleaved colour (CV_8UC3), steps in bytes
+    int compute(int channels, const uint8_t* left, size_t leftStep, const uint8_t* right, size_t rightStep,
+                int rows, int cols, int16_t* out, size_t outStep);
+    // cv::StereoSGBM::setPreFilterCap (0 .. 127), from the next compute on
+    int setPreFilterCap(int preFilterCap);
     int status() const { return status_; }
 
 private:

@@ -20,9 +20,9 @@ HIPSemiGlobalMatcher::~HIPSemiGlobalMatcher()
 int HIPSemiGlobalMatcher::compute(cv::InputArray left, cv::InputArray right, cv::OutputArray out)
 {
 	cv::Mat l = left.getMat(), r = right.getMat();
-	if (l.type() != CV_8UC1 || r.type() != CV_8UC1 || l.size() != r.size())
+	if ((l.type() != CV_8UC1 && l.type() != CV_8UC3) || r.type() != l.type() || l.size() != r.size())
 		return RTDM_ERR_BAD_SIZE;
 	out.create(l.size(), CV_16SC1);
 	cv::Mat d = out.getMat();
-	return core->compute(l.data, l.step, r.data, r.step, l.rows, l.cols, (int16_t*) d.data, d.step);
+	return core->compute(l.channels(), l.data, l.step, r.data, r.step, l.rows, l.cols, (int16_t*) d.data, d.step);
 }

@@ -4,7 +4,9 @@
  * Like SWSemiGlobalMatcher it is not selected by main.cpp unless the maintainer does so.  The device module runs
  * cv::StereoSGBM's MODE_SGBM as restated in oracle/sgm_oracle.c (bit-exact against that restatement; against the
  * library itself parity is unpinned); numOfDisparities is any multiple of 16, as in the library (checked by the device module,
- * not here; above 256 the path passes run on its wide-line kernel); an even blockSize runs as the next odd one (as in the library); with a window > 17 a frame whose block cost + P2 would pass 32767 (where the library's 16-bit costs wrap) makes compute return an error.
+ * not here; above 256 the path passes run on its wide-line kernel); an even blockSize runs as the next odd one (as in the library); where a window is large enough, a frame whose block cost + P2 would pass 32767 (where the library's 16-bit costs wrap) makes compute return an error.
+ * compute takes CV_8UC1 or CV_8UC3 pairs and setPreFilterCap takes 0 .. 127, as cv::StereoSGBM does (the colour pixel cost
+ * restates the library's from memory; parity unpinned).
  */
 #ifndef INCLUDE_BM_SGBM_HIP_H_
 #define INCLUDE_BM_SGBM_HIP_H_
@@ -19,6 +21,7 @@ public:
 			int speckleWindowSize, int speckleRange, int disp12MaxDiff, int width, int height);
 	~HIPSemiGlobalMatcher();
 	int compute(cv::InputArray left, cv::InputArray right, cv::OutputArray out);
+	int setPreFilterCap(int preFilterCap) { return core->setPreFilterCap(preFilterCap); }
 	void setROI1(cv::Rect roi1) {}
 	void setROI2(cv::Rect roi2) {}
 private:

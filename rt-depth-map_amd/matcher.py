@@ -136,16 +136,31 @@ class HIPSemiGlobalMatcher:
     """BlockMatcher over rtdm_sgm_*; constructor shape of SWSemiGlobalMatcher
     (include/stereo-matcher/sgbm-sw.h:27-28): blockSize, minDisparity, numOfDisparities, uniquenessRatio,
     speckleWindowSize, speckleRange, disp12MaxDiff; P1/P2 are the literals of sgbm-sw.cpp:17-18.  numOfDisparities is
-    any multiple of 16, as in cv::StereoSGBM (above 256 the path passes run on the wide-line kernel); the library checks it."""
+    any multiple of 16, as in cv::StereoSGBM (above 256 the path passes run on the wide-line kernel); the library checks it.
+    preFilterCap is cv::StereoSGBM's (0 .. 127, setPreFilterCap); compute / compute_device take gray (H x W) or
+    interleaved colour (H x W x 3) uint8 frames, as cv::StereoSGBM::compute takes CV_8UC1 and CV_8UC3."""
 
     def __init__(self, blockSize=5, minDisparity=0, numOfDisparities=128, uniquenessRatio=10, speckleWindowSize=100,
-                 speckleRange=32, disp12MaxDiff=1, P1=600, P2=2400, width=1280, height=720, max_batch=1, device=0, paths=8):
+                 speckleRange=32, disp12MaxDiff=1, P1=600, P2=2400, width=1280, height=720, max_batch=1, device=0, paths=8,
+                 preFilterCap=0):
         # paths: 5 = cv::StereoSGBM's default MODE_SGBM (what sgbm-sw.cpp:15 creates), 8 = MODE_HH (BASELINE config 5)
         self._h = C.c_void_p()
         self.params = B.SGMParams(blockSize, minDisparity, numOfDisparities, P1, P2, uniquenessRatio, speckleWindowSize,
                                   speckleRange, disp12MaxDiff, paths)
         B.check(B.lib().rtdm_sgm_create(C.byref(self.params), width, height, max_batch, device, C.byref(self._h)),
                 "rtdm_sgm_create")
+        self.preFilterCap = 0
+        if preFilterCap:
+            try:
+                self.setPreFilterCap(preFilterCap)
+            except B.RtdmError:
+                self.close()
+                raise
+
+    def setPreFilterCap(self, preFilterCap):
+        """cv::StereoSGBM::setPreFilterCap: applies from the next compute call; >= 128 is refused (RTDM_ERR_UNSUPPORTED)."""
+        B.check(B.lib().rtdm_sgm_set_prefilter_cap(self._h, int(preFilterCap)), "rtdm_sgm_set_prefilter_cap")
+        self.preFilterCap = int(preFilterCap)
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
@@ -167,13 +182,31 @@ class HIPSemiGlobalMatcher:
     def filtered(self):
         return (self.params.minDisparity - 1) * 16
 
+    @staticmethod
+    def _channels(shape, lead):
+        """channel count of a gray (lead + (H, W)) or colour (lead + (H, W, 3)) frame shape"""
+        if len(shape) == lead + 2:
+            return 1
+        if len(shape) == lead + 3 and shape[-1] == 3:
+            return 3
+        raise ValueError("StereoSGBM frames are %s x H x W (gray) or %s x H x W x 3 (interleaved colour) uint8; got shape %s"
+                         % (("n",) * lead or "", ("n",) * lead or "", tuple(shape)))
+
     def compute(self, left, right):
-        assert left.dtype == np.uint8 and right.dtype == np.uint8 and left.shape == right.shape
-        assert left.ndim == 2 and left.strides[1] == 1 and right.strides[1] == 1
-        H, W = left.shape
+        if not isinstance(left, np.ndarray) or not isinstance(right, np.ndarray):
+            raise TypeError("compute takes numpy arrays")
+        if left.dtype != np.uint8 or right.dtype != np.uint8:
+            raise TypeError("StereoSGBM frames are uint8; got %s and %s" % (left.dtype, right.dtype))
+        if left.shape != right.shape:
+            raise ValueError("left and right frames differ in shape: %s vs %s" % (left.shape, right.shape))
+        cn = self._channels(left.shape, 0)
+        H, W = left.shape[:2]
+        for a in (left, right):
+            if a.strides[1] != cn or (cn == 3 and a.strides[2] != 1):
+                raise ValueError("frame rows must be contiguous (pixels %d bytes apart); got strides %s" % (cn, a.strides))
         disp = np.empty((H, W), np.int16)
-        B.check(B.lib().rtdm_sgm_compute(self._h, left.ctypes.data, left.strides[0], right.ctypes.data,
-                                         right.strides[0], W, H, disp.ctypes.data, W * 2), "rtdm_sgm_compute")
+        B.check(B.lib().rtdm_sgm_compute_cn(self._h, cn, left.ctypes.data, left.strides[0], right.ctypes.data,
+                                            right.strides[0], W, H, disp.ctypes.data, W * 2), "rtdm_sgm_compute_cn")
         return disp
 
     def pass_stats(self):
@@ -188,9 +221,14 @@ class HIPSemiGlobalMatcher:
         return B.lib().rtdm_sgm_path_variant(self._h).decode()
 
     def compute_device(self, d_left, d_right, d_disp, stream=None):
-        n, H, W = d_left.shape
-        B.check(B.lib().rtdm_sgm_compute_device(self._h, n, d_left.data_ptr(), d_right.data_ptr(), W, W * H, W, H,
-                                                d_disp.data_ptr(), W * 2, W * H * 2, stream), "rtdm_sgm_compute_device")
+        """d_left, d_right: contiguous (n, H, W) or (n, H, W, 3) uint8 device tensors; d_disp: (n, H, W) int16."""
+        if tuple(d_left.shape) != tuple(d_right.shape):
+            raise ValueError("left and right frames differ in shape: %s vs %s" % (tuple(d_left.shape), tuple(d_right.shape)))
+        cn = self._channels(tuple(d_left.shape), 1)
+        n, H, W = d_left.shape[:3]
+        B.check(B.lib().rtdm_sgm_compute_device_cn(self._h, cn, n, d_left.data_ptr(), d_right.data_ptr(), W * cn, W * H * cn,
+                                                   W, H, d_disp.data_ptr(), W * 2, W * H * 2, stream),
+                "rtdm_sgm_compute_device_cn")
 
 
 class HIPMorphologicalFilter:
