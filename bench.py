@@ -8,14 +8,21 @@ SWMatcherKonolige::compute (bm-sw.cpp:33-38) runs.  A "step" is one rtdm_bm_comp
 over a batch of --batch synthetic pairs (default 1024, the stream length of BASELINE config 4) that are
 already resident in HBM.  `value` is measured over EXACTLY --steps steps.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR] [--full]
 
 --dump-outputs DIR writes what the last timed step returned to its caller, so that two builds run with the same arguments
 (same seeded inputs) can be compared output for output: DIR/disparity.npy, float32 [n, H, W], the int16 disparity maps of
 n frames of rank 0's batch (all of them, or a fixed seeded sample when the batch is over DUMP_MAX_BYTES), and
 DIR/frame_index.npy, float64 [n], the stream index of each of those frames.
 
-After the headline region, on rank 0 and outside `value`:
+A plain run does only what the headline figure needs: it sets up, warms up, times the K steps, writes --dump-outputs and
+prints the JSON line (with the roofline figures, which come from the timed steps' own stage times and the offline PMC
+file).  Its "parity_ok" is null: nothing is compared with the oracle.
+
+--full adds everything else, as listed below; --no-cpu-baseline, --no-single-frame, --no-configs and --headline-only trim
+it.  After the headline region, with --full:
+  * the parity self-check: three frames of every rank's last timed step against the CPU oracle (every rank);
+and on rank 0, outside `value`:
   * "sustained": the same step repeated until >= 2 s have passed (a region long enough for an outside sampler to see);
   * "configs": every other size north_star names -- 320x240 d=32 7x7, 640x480 d=64 9x9, 1280x720 d=128 11x11 + the
     morphological open/close (frame sizes: backup/{320x240,640x480,1280x720}/extrinsics.yml:56-57), and the reference's
@@ -34,9 +41,10 @@ line and exits with the ranks' status.  Under torchrun (WORLD_SIZE set) it is on
 Multi-GPU: frames are independent (estimator.cpp:18-82 carries nothing across iterations), so each
 rank synthesises and processes its own shard of the stream (weak scaling, no data-path collective);
 timing is barrier + synchronize on both sides and the MAX over ranks.  --rccl-stream FRAMES is
-BASELINE config 4 instead: rank 0 owns the frames, scatter -> compute -> gather over RCCL.
+BASELINE config 4 instead: rank 0 owns the frames, scatter -> compute -> gather over RCCL; that mode is a measurement of
+its own and always checks its output against the oracle and the direct call.
 
-Three frames of the last step's output of every timed workload are compared with the CPU oracle
+With --full, three frames of the last step's output of every timed workload are compared with the CPU oracle
 ("parity_ok"); a mismatch exits non-zero.
 """
 import argparse
@@ -583,12 +591,16 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=1024,
                     help="pairs per step per GPU (BASELINE config 4's stream length; 256 is 4 percent slower: tail effects of the search grid)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: the sustained region, the parity check against the CPU oracle, the other BASELINE "
+                         "configurations, single-frame latency and the CPU baseline (a plain run does none of these)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-single-frame", action="store_true",
-                    help="skip the single-frame latency measurement (profiling runs: its launches would mix into per-kernel averages)")
-    ap.add_argument("--no-configs", action="store_true", help="skip the other BASELINE configurations")
+                    help="--full: skip the single-frame latency measurement (profiling runs: its launches would mix into per-kernel averages)")
+    ap.add_argument("--no-configs", action="store_true", help="--full: skip the other BASELINE configurations")
     ap.add_argument("--headline-only", action="store_true",
-                    help="the K timed steps and nothing else (rocprofv3 runs: no sustained region, configs, single frames or CPU baseline)")
+                    help="--full: the K timed steps and their parity check, nothing else (no sustained region, configs, single "
+                         "frames or CPU baseline)")
     ap.add_argument("--rccl-stream", type=int, default=0, metavar="FRAMES",
                     help="BASELINE config 4 instead of the headline: rank 0 owns FRAMES pairs, scatter -> compute -> gather "
                          "over torch.distributed (RCCL); reports root-sourced pairs/s")
@@ -599,7 +611,7 @@ def main():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
-    if args.headline_only:
+    if args.headline_only or not args.full:
         args.no_cpu_baseline = args.no_single_frame = args.no_configs = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -677,7 +689,7 @@ def main():
     # the same step, repeated until the GPU has been busy for >= 2 s in one stretch: long enough for a sampler outside this
     # process to see it.  Its own figure ("sustained"); `value` stays the K-step region above.
     sustained = None
-    if not args.headline_only:
+    if args.full and not args.headline_only:
         n_s = max(args.steps, int(math.ceil(2.0 / max(elapsed / max(1, args.steps), 1e-6))))   # from the all-reduced time: same on every rank
         t0 = time.perf_counter()
         for _ in range(n_s):
@@ -686,18 +698,21 @@ def main():
         el_s = allmax(time.perf_counter() - t0)
         sustained = {"steps": n_s, "seconds": round(el_s, 3), "pairs_per_s": round(world * B * n_s / el_s, 1)}
 
-    # parity self-check of the timed path (this batch size, autotuned strips, side-stream border kernel): three frames of
-    # the last step's output against the CPU oracle, on every rank's own shard
-    import numpy as np
-    oracle_ready(rank, dist)
-    idx = sorted({0, B // 2, B - 1})
-    want = oracle_frames(dL, dR, idx, max(1, min(usable_cores() // max(1, min(world, torch.cuda.device_count())), 64)))
-    bad = [i for i, w in zip(idx, want) if not np.array_equal(dD[i].cpu().numpy(), w)]
-    parity_ok = not bad
-    if dist is not None:
-        flag = torch.tensor([0 if parity_ok else 1], dtype=torch.int32, device=dev if backend == "nccl" else "cpu")
-        dist.all_reduce(flag, op=dist.ReduceOp.MAX)
-        parity_ok = int(flag.item()) == 0
+    # parity self-check of the timed path (this batch size, autotuned strips, side-stream border kernel), --full only: three
+    # frames of the last step's output against the CPU oracle, on every rank's own shard.  A plain run reports null.
+    parity_ok, bad, checked = None, [], 0
+    if args.full:
+        import numpy as np
+        oracle_ready(rank, dist)
+        idx = sorted({0, B // 2, B - 1})
+        want = oracle_frames(dL, dR, idx, max(1, min(usable_cores() // max(1, min(world, torch.cuda.device_count())), 64)))
+        bad = [i for i, w in zip(idx, want) if not np.array_equal(dD[i].cpu().numpy(), w)]
+        parity_ok = not bad
+        checked = len(idx) * world
+        if dist is not None:
+            flag = torch.tensor([0 if parity_ok else 1], dtype=torch.int32, device=dev if backend == "nccl" else "cpu")
+            dist.all_reduce(flag, op=dist.ReduceOp.MAX)
+            parity_ok = int(flag.item()) == 0
 
     single = None
     if rank == 0 and world == 1 and not args.no_single_frame:
@@ -713,7 +728,7 @@ def main():
     floor = sad_issue_floor(searched_pixels(W, H, D, BLOCK) * frames_per_launch, D, BLOCK, clock_ghz, avg_ms) \
         if m.search_variant.startswith("fast") else None
     variant = m.search_variant
-    cpu_frames = [(dL[i].cpu().numpy(), dR[i].cpu().numpy()) for i in range(min(B, 32))] if rank == 0 else None
+    cpu_frames = [(dL[i].cpu().numpy(), dR[i].cpu().numpy()) for i in range(min(B, 32))] if rank == 0 and not args.no_cpu_baseline else None
     filtered = m.filtered
 
     # the other BASELINE configurations (rank 0; at world > 1 the other ranks wait at the final barrier)
@@ -738,7 +753,7 @@ def main():
                    "pairs_per_step_per_gpu": B, "search_kernel": variant,
                    "parallelism": "whole-frame sharding, %d rank(s), no data-path collective" % world,
                    "valid_fraction": round(valid_frac, 4)},
-        "parity_checked_frames": len(idx) * world, "parity_ok": bool(parity_ok),
+        "parity_checked_frames": checked, "parity_ok": None if parity_ok is None else bool(parity_ok),
         "timed_region_s": round(elapsed, 4), "sustained": sustained,
         "roofline": {"bound": "hbm", "kernel": "SAD search (%s)" % variant,
                      "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
@@ -765,7 +780,7 @@ def main():
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
-    if not parity_ok:
+    if parity_ok is False:
         sys.stderr.write("bench.py: PARITY MISMATCH against the oracle on %s of rank %d\n" % (bad, rank))
         sys.exit(4)
     del filtered

@@ -91,7 +91,7 @@ def test_bench_gpus2_launches_two_ranks_itself():
     env = {"RTDM_DIST_BACKEND": "gloo"}
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         os.environ.pop(k, None)
-    out = _bench(["--gpus", "2", "--steps", "2", "--warmup", "2", "--batch", "16", "--no-cpu-baseline", "--no-configs"], env=env)
+    out = _bench(["--full", "--gpus", "2", "--steps", "2", "--warmup", "2", "--batch", "16", "--no-cpu-baseline", "--no-configs"], env=env)
     assert out["n_gpus"] == 2 and out["parity_ok"] is True and out["parity_checked_frames"] == 6
     # config 4 through the same launcher, two ranks
     out = _bench(["--gpus", "2", "--rccl-stream", "10", "--chunk", "2", "--steps", "1", "--warmup", "1"], env=env)

@@ -223,7 +223,7 @@ def _bench(args, env=None, timeout=900):
 
 
 def test_bench_line_carries_every_north_star_size_with_parity():
-    out = _bench(["--steps", "3", "--warmup", "2", "--batch", "64"])
+    out = _bench(["--full", "--steps", "3", "--warmup", "2", "--batch", "64"])
     assert out["n_gpus"] == 1 and out["ranks_seen"] == 1 and out["steps"] == 3 and out["parity_ok"] is True
     keys = [c["key"] for c in out["configs"]]
     assert keys == ["config1", "config2", "config3", "reference_default", "config5"]
@@ -246,7 +246,7 @@ def test_bench_line_carries_every_north_star_size_with_parity():
 
 def test_bench_two_ranks_keep_cpu_baseline_and_roofline():
     # gloo: both ranks share this GPU; the N > 1 line must be as complete as the N = 1 line
-    out = _bench(["--gpus", "2", "--steps", "2", "--warmup", "2", "--batch", "16", "--no-configs"], env={"RTDM_DIST_BACKEND": "gloo"})
+    out = _bench(["--full", "--gpus", "2", "--steps", "2", "--warmup", "2", "--batch", "16", "--no-configs"], env={"RTDM_DIST_BACKEND": "gloo"})
     assert out["n_gpus"] == 2 and out["ranks_seen"] == 2 and out["parity_ok"] is True and out["parity_checked_frames"] == 6
     assert out["cpu_baseline"] is not None and out["cpu_baseline"]["value"] > 0
     assert out["roofline"]["achieved"] > 0
@@ -254,7 +254,7 @@ def test_bench_two_ranks_keep_cpu_baseline_and_roofline():
 
 def test_bench_dump_outputs_repeat_and_are_what_the_timed_path_computed(oracle, synth, tmp_path):
     # 32 frames of 720p as float32 are over the 64 MB budget: a fixed seeded sample of whole frames, the same in every run
-    args = ["--headline-only", "--steps", "2", "--warmup", "1", "--batch", "32"]
+    args = ["--full", "--headline-only", "--steps", "2", "--warmup", "1", "--batch", "32"]
     dumps = []
     for name in ("a", "b"):
         d = tmp_path / name
@@ -273,6 +273,23 @@ def test_bench_dump_outputs_repeat_and_are_what_the_timed_path_computed(oracle, 
         assert_same(disp[k].astype(np.int16), oracle.bm_compute(L, R, nthreads=8, numDisparities=64, blockSize=9))
 
 
+def test_plain_bench_run_is_the_headline_alone(oracle, synth, tmp_path):
+    # no --full: set-up, warm-up, the timed steps, the dump and the line; nothing compared with the oracle, nothing else timed
+    out = _bench(["--steps", "2", "--warmup", "1", "--batch", "16", "--dump-outputs", str(tmp_path)])
+    assert out["metric"] == "stereo-pairs/sec, 1280x720 d=64 9x9 SAD" and out["unit"] == "stereo-pairs/s"
+    assert out["higher_is_better"] is True and out["dtype"] == "u8" and out["steps"] == 2 and out["warmup"] == 1
+    assert out["value"] > 0 and abs(out["value"] - 16 * 1e3 / out["ms_per_step"]) <= 0.01 * out["value"]
+    assert out["parity_ok"] is None and out["parity_checked_frames"] == 0
+    for k in ("sustained", "configs", "single_frame", "cpu_baseline"):
+        assert out[k] is None, k
+    assert out["roofline"]["achieved"] > 0
+    disp, idx = np.load(tmp_path / "disparity.npy"), np.load(tmp_path / "frame_index.npy")
+    assert np.array_equal(idx, np.arange(16)) and disp.shape == (16, 720, 1280)
+    for k in (0, 15):
+        L, R = synth.make_pair(synth.STREAM_SEED + k, 1280, 720, 64)
+        assert_same(disp[k].astype(np.int16), oracle.bm_compute(L, R, nthreads=8, numDisparities=64, blockSize=9))
+
+
 def test_two_gpus_over_rccl_when_the_box_has_them():
     """Multi-rank RCCL execution: runs only where torch sees >= 2 GPUs (the driver's 8-GPU node); a one-GPU box skips.  No
     scaling curve is produced or simulated here."""
@@ -280,7 +297,7 @@ def test_two_gpus_over_rccl_when_the_box_has_them():
     if torch.cuda.device_count() < 2:
         pytest.skip("needs >= 2 GPUs: multi-rank RCCL is unmeasured on a one-GPU box")
     env = {"RTDM_DIST_BACKEND": "nccl"}
-    out = _bench(["--gpus", "2", "--steps", "3", "--warmup", "2", "--batch", "64", "--no-configs"], env=env)
+    out = _bench(["--full", "--gpus", "2", "--steps", "3", "--warmup", "2", "--batch", "64", "--no-configs"], env=env)
     assert out["n_gpus"] == 2 and out["ranks_seen"] == 2 and out["parity_ok"] is True
     assert out["cpu_baseline"] is not None
     out = _bench(["--gpus", "2", "--rccl-stream", "64", "--chunk", "8", "--steps", "2", "--warmup", "1"], env=env)
