@@ -120,10 +120,9 @@ const char* rtdm_bm_search_variant(const rtdm_bm* bm);
 /* Diagnostic counters of the strip-count tuner inside rtdm_bm_compute_device (it times a few search launches the second
  * time a batch shape is seen): shapes measured so far and the extra search launches that took.  Either pointer may be NULL. */
 int rtdm_bm_get_tuner_stats(const rtdm_bm* bm, long* shapes_measured, long* timing_launches);
-/* Diagnostic A/B switch, process wide: which of the hand-written search kernels may be chosen for configurations that
+/* Diagnostic switch, process wide: which of the hand-written search kernels may be chosen for configurations that
  * several cover.  0: k_search_fast only; 1: k_search_ring where it is instantiated; 2 / 4 / 8: as 1, with two / four / eight
- * lanes per pixel where that form of the ring kernel exists; -1 (default): the library's choice (environment RTDM_RING=0/1 and
- * RTDM_RING_LPP=2/4 override it).  Results never depend on it. */
+ * lanes per pixel where that form of the ring kernel exists; -1 (default): the library's choice.  Results never depend on it. */
 void rtdm_debug_search_kernel(int mode);
 /* Diagnostic switch, process wide: 0 (default): the library picks the SAD-search kernel and, for the disparity-sliced one
  * ("generic_dslice_*": configurations whose column sums do not fit the generic kernel's LDS, numDisparities > 256 among
@@ -198,9 +197,9 @@ int rtdm_sgm_compute_device(rtdm_sgm* sg, int n, const uint8_t* d_left, const ui
  * each: k_sgm_sweep), *gave_up = 1 once such a pass has given up waiting for a neighbouring strip (the call that finds this
  * returns RTDM_ERR_HIP once; from then on the handle runs one pass per direction).  Either pointer may be NULL. */
 int rtdm_sgm_get_pass_stats(const rtdm_sgm* sg, long* sweeps, int* gave_up);
-/* Name of the path-pass form this handle's last call ran: "sweep" (row-synchronous sweeps), "half" (half-wave lines), "wave",
- * "block" (the A/B forms), "wide_w1" / "wide_w4" (the wide-line pass, one wave / four waves per line: numDisparities > 256 or
- * forced); "" before the first call. */
+/* Name of the path-pass form this handle's last call ran: "sweep" (row-synchronous sweeps), "half" (half-wave lines),
+ * "wide_w1" / "wide_w4" (the wide-line pass, one wave / four waves per line: numDisparities > 256 or forced); "" before the
+ * first call. */
 const char* rtdm_sgm_path_variant(const rtdm_sgm* sg);
 /* Diagnostic switch, process wide: 0 (default): the library's choice (numDisparities > 256 runs the wide-line pass, one wave
  * per line up to 1024 disparities, four above).  1: EVERY numDisparities runs the wide-line pass, one wave per line where that

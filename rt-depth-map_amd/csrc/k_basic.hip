@@ -232,13 +232,13 @@ void launch_prefilter(Plane8 L, Plane8 R, Plane8W Lp, Plane8W Rp, int W, int H, 
 {
     const auto al16 = [](const Plane8& p) { return (((size_t)p.base | p.pitch | p.frame) & 15) == 0; };
     const size_t w16 = (size_t)((W + 15) & ~15);
-    static const int strip16 = env_int("RTDM_PREFILTER_STRIP", 1);
-    if (strip16 && al16(L) && al16(R) && L.pitch >= w16 && R.pitch >= w16 && ((size_t)Lp.base & 15) == 0 && ((size_t)Rp.base & 15) == 0) {
+    if (al16(L) && al16(R) && L.pitch >= w16 && R.pitch >= w16 && ((size_t)Lp.base & 15) == 0 && ((size_t)Rp.base & 15) == 0) {
         constexpr int RY = 8;
         const int nxb = (W + 15) / 16;
         const int pblocks = (nxb * ((H + RY - 1) / RY) + 255) / 256;
         FillArgs fa{};
-        static const int fuse_fill = env_int("RTDM_FILL_IN_PREFILTER", 1);      // A/B: 0 = k_fill_frame as a launch of its own
+        // RTDM_FILL_IN_PREFILTER=0 (test hook): k_fill_frame as a launch of its own, as for frames the strip form cannot take
+        static const int fuse_fill = env_int("RTDM_FILL_IN_PREFILTER", 1);
         if (fill && fuse_fill) {
             const int nw = (W + 15) / 16, nl = (fill->cx0 + 15) / 16, nr = (W - fill->cx1 + 15) / 16, nv = fill->vy1 - fill->vy0;
             const int units = nw * fill->vy0 + nw * (H - fill->vy1) + (nl + nr) * nv + (fill->rowcnt ? H : 0);
@@ -318,15 +318,8 @@ void launch_fill16(Plane16W disp, int x0, int x1, int y0, int y1, int n, int val
 // the same pass.  With SPK the final row is handed straight to the speckle filter's init step.
 // ---------------------------------------------------------------------------------------------
 // KT = key type: 32-bit keys (cost << 16 | x) when the cost plane is 16-bit, else 64-bit (cost << 32 | x).
-// R = rows per workgroup.  With the speckle filter on (SPK) the R checked rows stay in LDS together with their
-// head maps, so the R-1 row pairs inside the block are merged right here (one union per vertical contact
-// segment) and only every R-th pair is left to k_spk_merge.
-static int lr_rows()   // rows per workgroup when the speckle init is fused (RTDM_LR_ROWS = 1 | 2 | 4)
-{
-    static const int r = [] { const int v = env_int("RTDM_LR_ROWS", 1); return (v == 1 || v == 2 || v == 4) ? v : 1; }();
-    return r;
-}
-
+// R = rows per workgroup; only R = 1 is launched (the multi-row form, which merged the R-1 row pairs inside a block from
+// the head maps it kept in LDS, was measured and retired: DESIGN.md section 6).
 template <bool SPK, typename CT, typename KT, int R>
 __global__ __launch_bounds__(256) void k_lrcheck(Plane16W disp, const CT* cost, BMGeom g, int maxDiff16,
                                                  int32_t* label, int32_t* size, uint32_t* runs, int32_t* rowcnt,
@@ -674,7 +667,7 @@ __global__ __launch_bounds__(256) void k_spk_merge_rec(int32_t* label, const uin
 // validity of the final row, the connected-to-the-left flags) is extracted -- eight flags at a time with two v_perm and two
 // v_dot4_u32_u8.  Measured: 354 instead of 509 VALU instructions on the always-taken path, but packed ops and v_perm issue at
 // 4.4 cycles where most of k_lrcheck_vec's v_and / v_or / v_add / v_sub issue at 2.6: 1.39 -> 1.32 ms per 1024 720p pairs,
-// 0.527 -> 0.487 at 640x480.  NIT > 1 (thread constants formed once for NIT row pairs; RTDM_LR_PK_PAIRS) is SLOWER, with or
+// 0.527 -> 0.487 at 640x480.  NIT > 1 (thread constants formed once for NIT row pairs; measured and retired, only NIT = 1 is launched) is SLOWER, with or
 // without the next trip's rows requested a trip ahead (1.51-1.77 ms): 74+ VGPRs instead of 44, and what bounds the kernel is
 // how many short barrier-chained workgroups a CU holds, not its instruction count (also with barriers that do not wait
 // for global memory: 1.79 ms).  Timing-only ablations (LRPK_ABL, profiles/r03_lrcheck_ablation.txt): loading the two planes and
@@ -920,17 +913,15 @@ int launch_lrcheck(Plane16W disp, const void* cost, const BMGeom& g, int disp12M
     dim3 block(256);
     const bool k32 = g.cost16 && g.W < 65536;
     const size_t kb = k32 ? 4 : 8;
-#define RTDM_LR(SPK, CT, KT, RR)                                                                                     \
-    hipLaunchKernelGGL((k_lrcheck<SPK, CT, KT, RR>), dim3(1, (nrows + RR - 1) / RR, n), block,                        \
-                       (size_t)g.W * (kb + 2 + (SPK ? 4 * RR : 2 * RR)), stream, disp, (const CT*)cost, g, md, label, size, runs, \
-                       rowcnt, headmap, spkDiff)
+#define RTDM_LR(SPK, CT, KT)                                                                                          \
+    hipLaunchKernelGGL((k_lrcheck<SPK, CT, KT, 1>), dim3(1, nrows, n), block, (size_t)g.W * (kb + 2 + (SPK ? 4 : 2)), stream, \
+                       disp, (const CT*)cost, g, md, label, size, runs, rowcnt, headmap, spkDiff)
     const int Wp = (g.W + 7) & ~7;                      // a ragged last chunk is masked in registers; it needs padding columns
-    const bool vec = k32 && (g.Ws & 7) == 0 && g.W <= 4096 && lr_rows() == 1 && disp.pitch_e >= (size_t)Wp &&   // that belong to the plane
+    const bool vec = k32 && (g.Ws & 7) == 0 && g.W <= 4096 && disp.pitch_e >= (size_t)Wp &&   // that belong to the plane
                      (((size_t)disp.base | (disp.pitch_e * 2) | (disp.frame_e * 2) | (size_t)cost | (size_t)headmap) & 15) == 0;
     if (vec) {
         const int chunks = Wp >> 3;
         const auto per_half = [&](int nb) { return (size_t)Wp * 4 + 16 + (size_t)nb * Wp * 2; };
-        static const int two_env = env_int("RTDM_LR_TWO_ROWS", 1);   // A/B: 0 = one row per workgroup (round 2)
         // row pairs a workgroup walks and merges (1: none -- every pair is left to k_spk_merge_strip, round 3's first form)
         // Two row pairs per workgroup with the vertical contacts inside the block found right here (k_lrcheck_vec<.., NIT = 2> +
         // k_spk_merge_rec): a frame's contacts are chains of dependent L2 round trips, and with half of them settled from the head
@@ -938,40 +929,31 @@ int launch_lrcheck(Plane16W disp, const void* cost, const BMGeom& g, int disp12M
         // the packed one-pair form (k_lrcheck_pk + k_spk_merge_strip<4>) over batch sizes (profiles/r03_lr_pairs_ab.txt): frames
         // up to 1024 wide -- faster or level at every batch size (640x480: -32 % at 12 pairs, -5 % at 128, level at 512); 1280
         // wide -- faster up to ~16 pairs per call (-9 % for one frame, -23 % at 4), 2-5 % slower beyond, where k_lrcheck_pk
-        // streams and the merge is HBM bound.  RTDM_LR_PAIRS=1 / 2 / 4 / 8 fixes the choice (A/B).
+        // streams and the merge is HBM bound.  RTDM_LR_PAIRS=1 / 2 (test hook) fixes the choice.
         static const int pairs_raw = env_int("RTDM_LR_PAIRS", 0);
-        static const long pairs_rows = env_int("RTDM_LR_PAIRS_ROWS", 11520);
-        const int pairs_env = (pairs_raw == 1 || pairs_raw == 2 || pairs_raw == 4 || pairs_raw == 8) ? pairs_raw
-                              : ((g.W <= 1024 || (long)n * nrows <= pairs_rows) ? 2 : 1);
-        // two rows per workgroup where the half-wave form wastes fewer lanes than the whole-wave form and fits 512 threads
+        const int pairs = (pairs_raw == 1 || pairs_raw == 2) ? pairs_raw : ((g.W <= 1024 || (long)n * nrows <= 11520) ? 2 : 1);
+        // two rows per workgroup (one per half-wave) where that fits 512 threads: it never takes more lanes than the whole-wave form
         const int waves1 = (chunks + 63) / 64, waves2 = (chunks + 31) / 32;
-        static const int two_eq = env_int("RTDM_LR_TWO_EQ", 1);      // A/B: 1 = the half-wave form also where it only ties on lanes (W = 320)
-        const bool two = two_env && waves2 <= 8 && nrows >= 2 && (waves2 < 2 * waves1 || (two_eq && waves2 == 2 * waves1));
+        const bool two = waves2 <= 8 && nrows >= 2;
         // packed form (k_lrcheck_pk): costs below 32768, every quantity of the consistency / closeness tests inside int16,
-        // LDS byte addresses inside 16 bits
-        static const int pk_env = env_int("RTDM_LR_PACKED", 1);      // A/B: 0 = k_lrcheck_vec; NIT from RTDM_LR_PK_PAIRS
-        static const int pk_pairs = [] { const int v = env_int("RTDM_LR_PK_PAIRS", 1); return (v == 2 || v == 4 || v == 8) ? v : 1; }();
+        // LDS byte addresses inside 16 bits.  RTDM_LR_PACKED=0 (test hook): k_lrcheck_vec, the form wherever these fail.
+        static const int pk_env = env_int("RTDM_LR_PACKED", 1);
         const bool pk_ok = pk_env && two_ok_for_pk(g, md, spkDiff) && 2 * per_half(1) + 1024 < 65536;
-        const bool contacts_here = two && label && nrows >= 4 && pairs_env > 1;   // k_lrcheck_vec<.., NIT > 1> below
+        const bool contacts_here = two && label && nrows >= 4 && pairs > 1;   // k_lrcheck_vec<.., NIT = 2> below
         if (two && pk_ok && !contacts_here) {
             const dim3 vblock((unsigned)(waves2 * 64));
-            const int nit = nrows >= 16 ? pk_pairs : 1;
-#define RTDM_LRP(SPK, NIT) hipLaunchKernelGGL((k_lrcheck_pk<SPK, NIT>), dim3(1, (nrows + 2 * NIT - 1) / (2 * NIT), n), vblock, 2 * per_half(1), stream, disp, \
-                               (const uint16_t*)cost, g, md, label, size, runs, rowcnt, headmap, spkDiff)
-#define RTDM_LRP2(NIT) do { if (label) RTDM_LRP(true, NIT); else RTDM_LRP(false, NIT); } while (0)
-            if (nit == 8) RTDM_LRP2(8); else if (nit == 4) RTDM_LRP2(4); else if (nit == 2) RTDM_LRP2(2); else RTDM_LRP2(1);
-#undef RTDM_LRP2
+#define RTDM_LRP(SPK) hipLaunchKernelGGL((k_lrcheck_pk<SPK, 1>), dim3(1, (nrows + 1) / 2, n), vblock, 2 * per_half(1), stream, disp, \
+                                 (const uint16_t*)cost, g, md, label, size, runs, rowcnt, headmap, spkDiff)
+            if (label) RTDM_LRP(true); else RTDM_LRP(false);
 #undef RTDM_LRP
             return label ? 1 : 0;
         }
         if (two) {
             const dim3 vblock((unsigned)(waves2 * 64));
-            const int nit = (label && nrows >= 4) ? pairs_env : 1;
+            const int nit = (label && nrows >= 4) ? pairs : 1;
 #define RTDM_LRV(SPK, NIT) hipLaunchKernelGGL((k_lrcheck_vec<SPK, true, NIT>), dim3(1, (nrows + 2 * NIT - 1) / (2 * NIT), n), vblock, \
                                2 * per_half(NIT > 1 ? 2 : 1), stream, disp, (const uint16_t*)cost, g, md, label, size, runs, rowcnt, headmap, spkDiff)
             if (!label) RTDM_LRV(false, 1);
-            else if (nit == 8) RTDM_LRV(true, 8);
-            else if (nit == 4) RTDM_LRV(true, 4);
             else if (nit == 2) RTDM_LRV(true, 2);
             else RTDM_LRV(true, 1);
 #undef RTDM_LRV
@@ -983,20 +965,17 @@ int launch_lrcheck(Plane16W disp, const void* cost, const BMGeom& g, int disp12M
         else       hipLaunchKernelGGL((k_lrcheck_vec<false, false, 1>), dim3(1, nrows, n), vblock, lds, stream, disp, (const uint16_t*)cost, g, md, label, size, runs, rowcnt, headmap, spkDiff);
         return label ? 1 : 0;
     } else if (label) {
-        const int rr = lr_rows();
-        if (k32) { if (rr == 4) RTDM_LR(true, uint16_t, uint32_t, 4); else if (rr == 2) RTDM_LR(true, uint16_t, uint32_t, 2); else RTDM_LR(true, uint16_t, uint32_t, 1); }
-        else if (g.cost16) { if (rr == 4) RTDM_LR(true, uint16_t, unsigned long long, 4); else if (rr == 2) RTDM_LR(true, uint16_t, unsigned long long, 2); else RTDM_LR(true, uint16_t, unsigned long long, 1); }
-        else { if (rr == 4) RTDM_LR(true, int32_t, unsigned long long, 4); else if (rr == 2) RTDM_LR(true, int32_t, unsigned long long, 2); else RTDM_LR(true, int32_t, unsigned long long, 1); }
+        if (k32) RTDM_LR(true, uint16_t, uint32_t);
+        else if (g.cost16) RTDM_LR(true, uint16_t, unsigned long long);
+        else RTDM_LR(true, int32_t, unsigned long long);
     } else {
-        if (k32) RTDM_LR(false, uint16_t, uint32_t, 1);
-        else if (g.cost16) RTDM_LR(false, uint16_t, unsigned long long, 1);
-        else RTDM_LR(false, int32_t, unsigned long long, 1);
+        if (k32) RTDM_LR(false, uint16_t, uint32_t);
+        else if (g.cost16) RTDM_LR(false, uint16_t, unsigned long long);
+        else RTDM_LR(false, int32_t, unsigned long long);
     }
 #undef RTDM_LR
     return 0;
 }
-
-int lrcheck_rows_per_block() { return lr_rows(); }
 
 // ---------------------------------------------------------------------------------------------
 // K4 speckle filter (cv::filterSpeckles as called by cv::StereoBM::compute, SURVEY.md Appendix
@@ -1031,9 +1010,8 @@ __global__ __launch_bounds__(256) void k_spk_init(Plane16W disp, int32_t* label,
 
 // merge: one thread = 8 consecutive pixels of a row pair (y, y+1); no LDS, no scans: the heads come
 // from the head map.  A pixel is skipped when its left neighbour already linked the same two runs.
-// VEC: rows are 16-byte aligned, so the 8 pixels of each row come in as one 128-bit load.
-
-template <bool VEC>
+// For rows that are not 16-byte aligned (aligned rows go to k_spk_merge_strip).  (ystep is always 1 since the multi-row
+// left-right check was retired.)
 __global__ __launch_bounds__(256) void k_spk_merge(Plane16W disp, int32_t* label, const int16_t* headmap, int W, int Ws, int H,
                                                    int y_lo, int npairs, int ystep, int newVal, int maxDiff)
 {
@@ -1052,24 +1030,15 @@ __global__ __launch_bounds__(256) void k_spk_merge(Plane16W disp, int32_t* label
     const int16_t* h0 = headmap + base0;
     const int16_t* h1 = headmap + base1;
     Short8 a8, b8, ha8, hb8;
-    const bool full = VEC && x0 + 8 <= W;
     unsigned cm = 0;
     if (inb) {
-        if (full) {
-            a8 = *(const Short8*)(d0 + x0); b8 = *(const Short8*)(d1 + x0);
-        } else {
-            for (int k = 0; k < 8; ++k) { const int x = min(x0 + k, W - 1); a8.v[k] = d0[x]; b8.v[k] = d1[x]; }
-        }
+        for (int k = 0; k < 8; ++k) { const int x = min(x0 + k, W - 1); a8.v[k] = d0[x]; b8.v[k] = d1[x]; }
 #pragma unroll
         for (int k = 0; k < 8; ++k) cm |= (unsigned)((x0 + k < W) && conn(a8.v[k], b8.v[k], newVal, maxDiff)) << k;
     }
     ha8.v[7] = hb8.v[7] = 0;
     if (cm) {
-        if (full) {
-            ha8 = *(const Short8*)(h0 + x0); hb8 = *(const Short8*)(h1 + x0);
-        } else {
-            for (int k = 0; k < 8; ++k) { const int x = min(x0 + k, W - 1); ha8.v[k] = h0[x]; hb8.v[k] = h1[x]; }
-        }
+        for (int k = 0; k < 8; ++k) { const int x = min(x0 + k, W - 1); ha8.v[k] = h0[x]; hb8.v[k] = h1[x]; }
     }
     // state of the pixel left of x0: lane-1 holds it in element 7 (same row whenever x0 > 0)
     const int packed = (int)(cm >> 7) | ((int)(uint16_t)ha8.v[7] << 1) | ((int)(uint16_t)hb8.v[7] << 17);
@@ -1096,7 +1065,7 @@ __global__ __launch_bounds__(256) void k_spk_merge(Plane16W disp, int32_t* label
 
 // Strip form of the merge for aligned rows: one thread walks RS consecutive row pairs of its 8 columns, so every
 // row of disparities / heads is loaded once instead of twice (as the lower row of one pair and the upper row of the
-// next).  Same unions as k_spk_merge<true> with ystep = 1.
+// next).  Same unions as k_spk_merge with ystep = 1.
 // size / maxSize: a contact between two runs that are EACH longer than maxSize needs no union -- both components are
 // "large" whatever else they touch, and only "size <= maxSize" is ever asked (exact; it removes most unions: disparity
 // maps are made of long runs).  size[] still holds the run lengths here (k_spk_count runs afterwards).
@@ -1313,13 +1282,14 @@ void launch_speckle(Plane16W disp, int32_t* label, int32_t* size, uint32_t* runs
                            W, Ws, H, newVal, maxDiff);
     }
     // row pairs still to merge: (y, y+1), y = first + k*step.  The init pass may already have merged the pairs
-    // inside blocks of premerged_rows rows (k_lrcheck<SPK>); then only the pairs across blocks remain.
+    // inside blocks of premerged_rows rows (k_lrcheck_vec<.., NIT = 2>, compact heads); then only the pairs across blocks remain.
     const int step = premerged_rows > 1 ? premerged_rows : 1;
     const int first = y_lo + step - 1;
     const int last = min(y_hi, H) - 2;               // last y with y+1 initialised
     const int npairs = last >= first ? (last - first) / step + 1 : 0;
     MergeRecArgs rec{};
-    static const int fuse_rec = env_int("RTDM_MERGE_REC_FUSED", 1);      // A/B: 0 = k_spk_merge_rec as a launch of its own
+    // RTDM_MERGE_REC_FUSED=0 (test hook): k_spk_merge_rec as a launch of its own, as where no pair is left across blocks
+    static const int fuse_rec = env_int("RTDM_MERGE_REC_FUSED", 1);
     if (compact_heads && step > 1) {               // the contacts inside blocks of `step` rows are in the head records (k_lrcheck_vec<.., NIT > 1>)
         const int nr = min(y_hi, H) - y_lo, inside = (nr / step) * (step - 1) + max(nr % step - 1, 0), nxb = (W + 7) / 8;
         if (inside > 0) {
@@ -1332,8 +1302,6 @@ void launch_speckle(Plane16W disp, int32_t* label, int32_t* size, uint32_t* runs
         const int nxb = (W + 7) / 8;
         const bool vec = (((size_t)disp.base | (disp.pitch_e * 2) | (disp.frame_e * 2)) & 15) == 0 && (Ws & 7) == 0 &&
                          disp.pitch_e >= (size_t)((W + 7) & ~7);   // a ragged last chunk reads (never writes) padding columns
-        dim3 grid((nxb * npairs + 255) / 256, n);
-        static const int rs = env_int("RTDM_MERGE_STRIP", 4);
         if (compact_heads && step > 1) {           // k_lrcheck_vec<.., NIT > 1> has found the contacts inside blocks of `step` rows
             dim3 sgrid((nxb * npairs + 255) / 256 + rec.blocks, n);
             if (rec.blocks) hipLaunchKernelGGL((k_spk_merge_strip<1, true, true>), sgrid, block, 0, stream, disp, label, headmap, W, Ws, H, first, npairs, newVal, maxDiff, size, maxSize, step, rec);
@@ -1344,23 +1312,18 @@ void launch_speckle(Plane16W disp, int32_t* label, int32_t* size, uint32_t* runs
             // plane) -- but a single frame is 111 workgroups whose threads each work through up to four queued unions, chains of
             // dependent L2 round trips: 32 us, more than the frame's search.  Small launches take shorter strips: more workgroups,
             // one union per thread.
-            static const int rs_env = env_int("RTDM_MERGE_RS", 0);    // A/B: 1 / 2 / 4 fixes the strip length
             int rsc = 4;
             while (rsc > 1 && (long)((nxb * ((npairs + rsc - 1) / rsc) + 255) / 256) * n < 1024) rsc >>= 1;
-            if (rs_env == 1 || rs_env == 2 || rs_env == 4) rsc = rs_env;
             dim3 sgrid((nxb * ((npairs + rsc - 1) / rsc) + 255) / 256, n);
             if (rsc == 4)      hipLaunchKernelGGL((k_spk_merge_strip<4, true>), sgrid, block, 0, stream, disp, label, headmap, W, Ws, H, first, npairs, newVal, maxDiff, size, maxSize, 1, MergeRecArgs{});
             else if (rsc == 2) hipLaunchKernelGGL((k_spk_merge_strip<2, true>), sgrid, block, 0, stream, disp, label, headmap, W, Ws, H, first, npairs, newVal, maxDiff, size, maxSize, 1, MergeRecArgs{});
             else               hipLaunchKernelGGL((k_spk_merge_strip<1, true>), sgrid, block, 0, stream, disp, label, headmap, W, Ws, H, first, npairs, newVal, maxDiff, size, maxSize, 1, MergeRecArgs{});
-        } else
-        if (vec && step == 1 && rs > 1) {
-            const int RSV = rs >= 8 ? 8 : 4;
-            dim3 sgrid((nxb * ((npairs + RSV - 1) / RSV) + 255) / 256, n);
-            if (RSV == 8) hipLaunchKernelGGL((k_spk_merge_strip<8, false>), sgrid, block, 0, stream, disp, label, headmap, W, Ws, H, first, npairs, newVal, maxDiff, size, maxSize, 1, MergeRecArgs{});
-            else          hipLaunchKernelGGL((k_spk_merge_strip<4, false>), sgrid, block, 0, stream, disp, label, headmap, W, Ws, H, first, npairs, newVal, maxDiff, size, maxSize, 1, MergeRecArgs{});
-        } else
-        if (vec) hipLaunchKernelGGL(k_spk_merge<true>, grid, block, 0, stream, disp, label, headmap, W, Ws, H, first, npairs, step, newVal, maxDiff);
-        else     hipLaunchKernelGGL(k_spk_merge<false>, grid, block, 0, stream, disp, label, headmap, W, Ws, H, first, npairs, step, newVal, maxDiff);
+        } else if (vec) {                          // (step == 1: without compact heads nothing was merged in blocks)
+            dim3 sgrid((nxb * ((npairs + 3) / 4) + 255) / 256, n);
+            hipLaunchKernelGGL((k_spk_merge_strip<4, false>), sgrid, block, 0, stream, disp, label, headmap, W, Ws, H, first, npairs, newVal, maxDiff, size, maxSize, 1, MergeRecArgs{});
+        } else {
+            hipLaunchKernelGGL(k_spk_merge, dim3((nxb * npairs + 255) / 256, n), block, 0, stream, disp, label, headmap, W, Ws, H, first, npairs, step, newVal, maxDiff);
+        }
     }
     const int nrows = n * H;
     if (compact_heads) {                          // k_lrcheck_vec: nodes are run indices

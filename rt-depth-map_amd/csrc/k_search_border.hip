@@ -25,17 +25,25 @@ bool border_search_supported(const BMGeom& g)
     return g.w <= 21 && g.D <= 256 && 2L * g.cap * g.w * g.w <= 65535;
 }
 
-// Geometry + LDS bytes of the border work; returns the grid (x = column groups, y = strips), 0 columns -> false.
 // Rows per border workgroup: 128 for batches (the w-1 halo rows are then 6 % of the visits), shorter when the whole launch
 // would otherwise consist of a handful of long, latency-bound walks (single frames: the reference's real-time case).
 static int border_rows(int nrows, int ncols, int n)
 {
-    static const int rs_env = env_int("RTDM_BORDER_RS", 0);
-    if (rs_env >= 8) return rs_env;
     const long want = (long)nrows * ((ncols + 3) / 4) * n / 256;     // rows per workgroup that still leave >= 256 workgroups
     return (int)std::min(128L, std::max(16L, want));
 }
 
+static int border_rsp(int D, int w) { return (D + w + 3 + 63 + 64) & ~3; }   // + one chunk of slack for lanes with e >= D
+
+// dynamic LDS of a border workgroup (four waves): it depends on (D, w) alone
+size_t border_lds_bytes(int D, int w)
+{
+    const int nch = (D + 63) / 64;
+    const size_t per_wave = ((size_t)RB * border_rsp(D, w) + (size_t)RB * 32 + (size_t)w * (nch * 64) * 2 + (size_t)w * 4 + 15) & ~(size_t)15;
+    return per_wave * 4;
+}
+
+// Geometry + LDS bytes of the border work; returns the grid (x = column groups, y = strips), 0 columns -> false.
 bool border_geometry(const BMGeom& g, int lx0, int lx1, int rx0, int rx1, int n, BorderGeom* out, int* gx, int* gy, size_t* lds_bytes)
 {
     const int ncols = max(0, lx1 - lx0) + max(0, rx1 - rx0);
@@ -44,10 +52,8 @@ bool border_geometry(const BMGeom& g, int lx0, int lx1, int rx0, int rx1, int n,
     bg.lx0 = lx0; bg.lx1 = max(lx1, lx0); bg.rx0 = rx0; bg.rx1 = max(rx1, rx0);
     const int nrows = g.vy1 - g.vy0;
     bg.rs = border_rows(nrows, ncols, n);
-    bg.rsp = (g.D + g.w + 3 + 63 + 64) & ~3;       // + one chunk of slack for lanes with e >= D
-    const int nch = (g.D + 63) / 64;
-    const size_t per_wave = ((size_t)RB * bg.rsp + (size_t)RB * 32 + (size_t)g.w * (nch * 64) * 2 + (size_t)g.w * 4 + 15) & ~(size_t)15;
-    *out = bg; *gx = (ncols + 3) / 4; *gy = (nrows + bg.rs - 1) / bg.rs; *lds_bytes = per_wave * 4;
+    bg.rsp = border_rsp(g.D, g.w);
+    *out = bg; *gx = (ncols + 3) / 4; *gy = (nrows + bg.rs - 1) / bg.rs; *lds_bytes = border_lds_bytes(g.D, g.w);
     return true;
 }
 
@@ -58,14 +64,11 @@ void launch_search_border(Plane8 Lp, Plane8 Rp, Plane16W disp, void* cost, const
     if (ncols <= 0) return;
     if (launch_search_border2(Lp, Rp, disp, cost, g, n, stream, lx0, lx1, rx0, rx1)) return;   // rows in the lanes: far fewer instructions
     BorderGeom bg;
-    bg.lx0 = lx0; bg.lx1 = max(lx1, lx0); bg.rx0 = rx0; bg.rx1 = max(rx1, rx0);
-    const int nrows = g.vy1 - g.vy0;
-    bg.rs = border_rows(nrows, ncols, n);
-    bg.rsp = (g.D + g.w + 3 + 63 + 64) & ~3;       // + one chunk of slack for lanes with e >= D
+    int gx = 0, gy = 0;
+    size_t lds = 0;
+    border_geometry(g, lx0, lx1, rx0, rx1, n, &bg, &gx, &gy, &lds);
     const int nch = (g.D + 63) / 64;
-    const size_t per_wave = ((size_t)RB * bg.rsp + (size_t)RB * 32 + (size_t)g.w * (nch * 64) * 2 + (size_t)g.w * 4 + 15) & ~(size_t)15;
-    const size_t lds = per_wave * 4;
-    dim3 grid((ncols + 3) / 4, (nrows + bg.rs - 1) / bg.rs, n), block(256);
+    dim3 grid(gx, gy, n), block(256);
     const auto go = [&](auto nc, auto lg) {
         hipLaunchKernelGGL((k_search_border<decltype(nc)::value, decltype(lg)::value>), grid, block, lds, stream, Lp, Rp, disp, (uint16_t*)cost, g, bg);
     };

@@ -56,7 +56,8 @@ static bool border2_columns_ok(const BMGeom& g, int lx0, int lx1, int rx0, int r
 // per frame; gx = 0: no border columns at all).  Also used by k_search_ring to put these workgroups in front of its own.
 bool border2_plan(const BMGeom& g, int lx0, int lx1, int rx0, int rx1, Border2Geom* bg, int* gx, int* gy)
 {
-    static const int enabled = env_int("RTDM_BORDER2", 1);            // A/B switch: 0 = k_search_border for everything
+    // RTDM_BORDER2=0 (test hook): k_search_border for everything -- what serves legacy clamp, w > 16 and D outside the table
+    static const int enabled = env_int("RTDM_BORDER2", 1);
     if (!enabled || g.legacy || g.w > 16 || g.w < 5) return false;
     if (64L * g.w * 2 * g.cap > 65535) return false;                  // packed u16 prefix sums over 64 rows
     if (2L * g.cap * g.w * g.w > 32766) return false;                 // select_disparity's T + 1 <= 32767

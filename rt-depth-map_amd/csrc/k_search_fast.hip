@@ -310,8 +310,7 @@ static void launch_one(Plane8 Lp, Plane8 Rp, Plane16W disp, void* cost, const BM
     }
     fg.nfast = (unsigned)tiles * strips * n; fg.nborder = (unsigned)(fg.bgx * fg.bgy) * n;
     fg.gfast = (fg.nfast + 7) / 8; fg.gborder = (fg.nborder + 7) / 8;
-    static const int xcd_local = [] { const char* e = getenv("RTDM_FAST_XCD"); return e ? atoi(e) : 1; }();
-    fg.xcd_local = xcd_local;
+    fg.xcd_local = 1;                                 // XCD-local order (the kernel still accepts 0: plain order)
     if (ldsb > 48 * 1024) (void)hipFuncSetAttribute((const void*)k_search_fast<D, NP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsb);
     hipLaunchKernelGGL((k_search_fast<D, NP>), dim3((fg.gfast + fg.gborder) * 8), dim3(256), ldsb, stream, Lp, Rp, disp, (uint16_t*)cost, g, fg, bg);
 }

@@ -628,9 +628,8 @@ static int ring_lpp(const BMGeom& g);
 // trips of the row loop between two rebases of the ring (0: one trip is longer than the cap -- no rebasing, short strips)
 static int ring_rebase_trips(const BMGeom& g)
 {
-    static const int enabled = env_int("RTDM_RING_REBASE", 1);        // A/B switch: 0 = short strips (round 2)
     const int lpp = ring_lpp(g);
-    if (!enabled || !lpp) return 0;
+    if (!lpp) return 0;
     const int W1 = g.w + 1, rpg = ring_rpg(g.D, lpp);
     const int trip = (W1 % rpg == 0) ? W1 : (2 * W1 % rpg == 0) ? 2 * W1 : 4 * W1;   // RingCfg::TRIP
     return ring_rows_cap(g) / trip;
@@ -653,7 +652,7 @@ static int ring_min_strips(const BMGeom& g, int nrows)
                            X(192, 9, 8) X(192, 11, 8) X(192, 13, 8) X(192, 15, 8) X(256, 9, 16) X(256, 11, 16) X(256, 13, 16) X(256, 15, 16)
 #endif
 
-// rtdm_debug_search_kernel (a process-wide A/B switch; one atomic word so that a launch on another thread sees a consistent
+// rtdm_debug_search_kernel (a process-wide diagnostic switch; one atomic word so that a launch on another thread sees a consistent
 // pair): low byte = mode + 1 (0 never, 1 wherever instantiated, -1 default), next byte = lanes per pixel to force (0: none)
 static std::atomic<int> g_ring_switch{0};
 void ring_set_mode(int mode)
@@ -664,15 +663,14 @@ void ring_set_mode(int mode)
 static int ring_mode() { return (g_ring_switch.load(std::memory_order_relaxed) & 0xff) - 1; }
 static int ring_forced_lpp() { return g_ring_switch.load(std::memory_order_relaxed) >> 8; }
 
-// lanes per pixel for a configuration (0: not instantiated).  RTDM_RING_LPP = 2 / 4 forces one form where it exists (A/B).
+// lanes per pixel for a configuration (0: not instantiated).  rtdm_debug_search_kernel may force one form where it exists.
 static int ring_lpp(const BMGeom& g)
 {
-    static const int env = [] { const char* e = getenv("RTDM_RING_LPP"); return e ? atoi(e) : 0; }();
     int have = 0;                          // bit mask of the forms instantiated for (D, w)
 #define X(DD, WW, LL) if (g.D == DD && g.w == WW) have |= LL;
     RTDM_RING_TABLE(X)
 #undef X
-    const int forced = ring_forced_lpp(), want = forced ? forced : env;
+    const int want = ring_forced_lpp();
     if (want && (have & want) == want) return want;
     // measured (tools/ab_ring.py): more lanes per pixel win where the ring holds the two-lane form at two waves per SIMD
     return (have & 16) ? 16 : (have & 8) ? 8 : (have & 4) ? 4 : (have & 2) ? 2 : 0;
@@ -738,9 +736,8 @@ static bool ring_launch_one(Plane8 Lp, Plane8 Rp, Plane16W disp, void* cost, con
     strips = (nrows + rg.rs - 1) / rg.rs;
     rg.tiles = tiles; rg.strips = strips;
     rg.nitems = (unsigned)tiles * strips * n;
-    static const bool xcd_local = [] { const char* e = getenv("RTDM_RING_XCD"); return !e || atoi(e) != 0; }();   // A/B switch
-    rg.chunk = xcd_local ? (rg.nitems + 7) / 8 : 0;
-    const unsigned grid = rg.chunk ? rg.chunk * 8 : rg.nitems;
+    rg.chunk = (rg.nitems + 7) / 8;                   // XCD-local order (the kernel still accepts chunk == 0: plain order)
+    const unsigned grid = rg.chunk * 8;
     BorderGeom bg{};
     Border2Geom b2g{};
     size_t blds = 0;
@@ -749,28 +746,31 @@ static bool ring_launch_one(Plane8 Lp, Plane8 Rp, Plane16W disp, void* cost, con
     if (fuse_border) {
         int lx0, lx1, rx0, rx1;
         fast_border_ranges(g, &lx0, &lx1, &rx0, &rx1);
-        static const int fuse2 = env_int("RTDM_RING_FUSE_BORDER2", 1);   // A/B: 0 = border2 never rides in this grid (round 3's first form)
-        if (fuse2 && C::FUSE_BORDER2 && border2_plan(g, lx0, lx1, rx0, rx1, &b2g, &rg.bgx, &rg.bgy)) {
+        if (C::FUSE_BORDER2 && border2_plan(g, lx0, lx1, rx0, rx1, &b2g, &rg.bgx, &rg.bgy)) {
             rg.b2 = 1; fused = true;
             rg.nborder = (unsigned)(rg.bgx * rg.bgy) * (unsigned)n;
         } else if constexpr (C::FUSE_BORDER) {
             if (border_geometry(g, lx0, lx1, rx0, rx1, n, &bg, &rg.bgx, &rg.bgy, &blds)) { rg.nborder = (unsigned)(rg.bgx * rg.bgy) * (unsigned)n; fused = true; }
         }
     }
-    static const size_t ldspad = [] { const char* e = getenv("RTDM_RING_LDSPAD"); return e ? (size_t)atol(e) : (size_t)0; }();
-    const size_t ldsb = max((size_t)4 * C::WAVE_LDS * sizeof(uint32_t), blds) + ldspad;   // (padding: occupancy experiments)
+    const size_t ldsb = max((size_t)4 * C::WAVE_LDS * sizeof(uint32_t), blds);
     const auto launch = [&](auto Fc) {
         constexpr bool F = decltype(Fc)::value;
-        if (ldsb > 48 * 1024) {                     // once per device of this process (a handle lives on one device)
-            // (one flag per instantiation; a second thread that races the first caller on the same device sets the same value)
-            static OncePerDevice once;
-            static std::atomic<size_t> granted{0};
-            const size_t want = max(ldsb, (size_t)64 * 1024);
-            if (once.first() || granted.load(std::memory_order_acquire) < want) {
-                (void)hipFuncSetAttribute((const void*)k_search_ring<D, WS, LPP, F>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)want);
-                size_t g0 = granted.load(std::memory_order_relaxed);
-                while (g0 < want && !granted.compare_exchange_weak(g0, want, std::memory_order_release)) {}
-            }
+        // The most this instantiation ever asks for depends on (D, w, LPP) alone: its ring records, or the border workgroups'
+        // LDS where they ride in its grid.  Above 48 KB it is granted once per device of this process (a handle lives on one
+        // device; a second thread that races the first caller on the same device sets the same value), never beyond the
+        // device's LDS.
+        constexpr size_t ring_lds = (size_t)4 * C::WAVE_LDS * sizeof(uint32_t);
+        const size_t most = C::FUSE_BORDER ? max(ring_lds, border_lds_bytes(D, WS)) : ring_lds;
+        static OncePerDevice once;
+        if (most > 48 * 1024 && once.first()) {
+            int dev = 0, lds_max = 0;
+            size_t want = max(most, (size_t)64 * 1024);
+            if (hipGetDevice(&dev) == hipSuccess &&
+                hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, dev) == hipSuccess && lds_max > 0)
+                want = min(want, (size_t)lds_max);
+            (void)hipGetLastError();
+            (void)hipFuncSetAttribute((const void*)k_search_ring<D, WS, LPP, F>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)want);
         }
         hipLaunchKernelGGL((k_search_ring<D, WS, LPP, F>), dim3(grid + rg.nborder), dim3(256), ldsb, stream, Lp, Rp, disp, (uint16_t*)cost, g, rg, bg, b2g);
     };
@@ -781,9 +781,7 @@ static bool ring_launch_one(Plane8 Lp, Plane8 Rp, Plane16W disp, void* cost, con
 
 bool ring_search_supported(const BMGeom& g)
 {
-    static const int env = [] { const char* e = getenv("RTDM_RING"); return e ? atoi(e) : -1; }();   // A/B switch
-    const int sw = ring_mode(), mode = sw >= 0 ? sw : env;
-    if (mode == 0) return false;
+    if (ring_mode() == 0) return false;
     if (2L * g.cap * g.w * g.w > 32766) return false;       // packed u16 sums + the T+1 <= 32767 argument of the selection
     if (2L * g.cap * g.w * g.w >= 0x7C00) return false;     // ... and positive finite f16 for the group minima (sel_pk_min3_h; cap <= 63
                                                             //     keeps every ring form below: 2 * 63 * 15^2 = 28350)

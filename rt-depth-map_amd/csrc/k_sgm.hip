@@ -17,7 +17,6 @@
 //   k_sgm_lrfinal one workgroup per row: the votes of the integer winners (LDS, right-most voter wins ties: R7) and the
 //                always-on left-right check (R9)
 //   k_sgm_median 3x3 median with clamped coordinates (R10) + the speckle filter's per-row init
-//   (round-2 forms kept for A/B: k_sgm_path / k_sgm_path_w, one workgroup / one wave per line and direction; k_sgm_select)
 #include "rtdm_kernels.h"
 #include "rtdm_device.h"
 
@@ -411,201 +410,6 @@ __global__ __launch_bounds__(256) void k_sgm_pixbox16(const uint2* bl, const uin
     if (cost_limit > 0 && over) *ovf = 1;
 }
 
-// wave-wide minimum (DPP), uniform result
-__device__ __forceinline__ int wave_min_i32(int v)
-{
-#define RTDM_DPP_MIN(ctrl, rmask) v = min(v, __builtin_amdgcn_update_dpp(0x7fffffff, v, ctrl, rmask, 0xf, false))
-    RTDM_DPP_MIN(0xB1, 0xf); RTDM_DPP_MIN(0x4E, 0xf); RTDM_DPP_MIN(0x141, 0xf); RTDM_DPP_MIN(0x140, 0xf);
-    RTDM_DPP_MIN(0x142, 0xa); RTDM_DPP_MIN(0x143, 0xc);
-#undef RTDM_DPP_MIN
-    return __builtin_amdgcn_readlane(v, 63);
-}
-
-// One workgroup per path line of direction (dx, dy); thread t = disparity t (blockDim = D rounded
-// up to a multiple of 64).  S (+)= L_r.
-__global__ __launch_bounds__(256) void k_sgm_path(const uint16_t* C, uint16_t* S, SGMGeom g, int dx, int dy, int P1, int P2,
-                                                  int first_dir)
-{
-    __shared__ int lbuf[2][256 + 2];      // L_r of the previous pixel, padded at d = -1 and d = D
-    __shared__ int wmin[2][4];
-    const int d = threadIdx.x, D = g.D, W1 = g.W1, H = g.H;
-    const int nw = (blockDim.x + 63) >> 6, wv = threadIdx.x >> 6;
-    const int f = blockIdx.y;
-    // start pixel of this line
-    int sx, sy;
-    const int line = blockIdx.x;
-    if (dy == 0) { sy = line; sx = dx > 0 ? 0 : W1 - 1; }
-    else if (dx == 0) { sx = line; sy = dy > 0 ? 0 : H - 1; }
-    else if (line < W1) { sx = line; sy = dy > 0 ? 0 : H - 1; }
-    else { const int k = line - W1 + 1; sx = dx > 0 ? 0 : W1 - 1; sy = dy > 0 ? k : H - 1 - k; }
-    const size_t fbase = (size_t)f * H * W1 * D;
-    const bool live = d < D;
-    const int BIG = 1 << 28;
-    int x = sx, y = sy, step = 0;
-    int cnext = (live && x >= 0 && x < W1 && y >= 0 && y < H) ? C[fbase + ((size_t)y * W1 + x) * D + d] : 0;
-    while (x >= 0 && x < W1 && y >= 0 && y < H) {
-        const size_t off = fbase + ((size_t)y * W1 + x) * D + d;
-        const int c = cnext;
-        const int nx = x + dx, ny = y + dy;
-        if (live && nx >= 0 && nx < W1 && ny >= 0 && ny < H) cnext = C[fbase + ((size_t)ny * W1 + nx) * D + d];   // prefetch
-        int l;
-        if (step == 0) {
-            l = c;
-        } else {
-            const int* pb = lbuf[(step - 1) & 1];
-            int mprev = wmin[(step - 1) & 1][0];
-            for (int q = 1; q < nw; ++q) mprev = min(mprev, wmin[(step - 1) & 1][q]);
-            const int best = min(min(pb[d + 1], mprev + P2), min(pb[d], pb[d + 2]) + P1);
-            l = c + best - mprev;
-        }
-        if (live) {
-            if (first_dir) S[off] = (uint16_t)l; else S[off] = (uint16_t)min((int)S[off] + l, 32767);   // R5
-        }
-        int* cb = lbuf[step & 1];
-        cb[d + 1] = live ? l : BIG;
-        if (d == 0) { cb[0] = BIG; cb[D + 1] = BIG; }
-        const int m = wave_min_i32(live ? l : BIG);
-        if ((threadIdx.x & 63) == 0) wmin[step & 1][wv] = m;
-        __syncthreads();
-        x = nx; y = ny; ++step;
-    }
-}
-
-// Wave-per-line form of k_sgm_path: one WAVE walks one path line, lane l holds the NPL consecutive disparities
-// l*NPL .. l*NPL+NPL-1 (NPL divides D), so the recurrence needs no LDS and no barrier: d-1 / d+1 of the lane's end
-// elements come from the neighbouring lanes by DPP wave shifts, the line minimum by a DPP reduction.  The walk is a
-// serial chain of W1 (or H) steps whose loads would each cost a full memory round trip, so C and S are fetched PF
-// steps ahead through a register ring.  S (+)= L_r, same values as k_sgm_path.
-template <int NPL> struct PackU16 { uint16_t v[NPL]; };
-
-template <int NPL>
-__device__ __forceinline__ PackU16<NPL> ld_pack(const uint16_t* p)
-{
-    PackU16<NPL> r;
-    if constexpr (NPL == 2) { const uint32_t w = *(const uint32_t*)p; r.v[0] = (uint16_t)w; r.v[1] = (uint16_t)(w >> 16); }
-    else if constexpr (NPL == 4) { const uint2 w = *(const uint2*)p; r.v[0] = (uint16_t)w.x; r.v[1] = (uint16_t)(w.x >> 16); r.v[2] = (uint16_t)w.y; r.v[3] = (uint16_t)(w.y >> 16); }
-    else { for (int j = 0; j < NPL; ++j) r.v[j] = p[j]; }
-    return r;
-}
-template <int NPL>
-__device__ __forceinline__ void st_pack(uint16_t* p, const int* l)
-{
-    if constexpr (NPL == 2) { *(uint32_t*)p = (uint32_t)(l[0] & 0xffff) | ((uint32_t)l[1] << 16); }
-    else if constexpr (NPL == 4) { *(uint2*)p = make_uint2((uint32_t)(l[0] & 0xffff) | ((uint32_t)l[1] << 16), (uint32_t)(l[2] & 0xffff) | ((uint32_t)l[3] << 16)); }
-    else { for (int j = 0; j < NPL; ++j) p[j] = (uint16_t)l[j]; }
-}
-
-// LAST (the last direction of a frame): the aggregated costs min(S + L_r, 32767) of a pixel are complete the moment this
-// wave has them in its lanes, so the winner-take-all step of k_sgm_select runs right here -- wave minimum of S << 8 | d,
-// uniqueness vote, S[d* +- 1] by v_readlane, quadratic sub-pixel in lane 0 -- and S is neither written back nor read again
-// (424 MB of HBM traffic per 720p D = 128 pair, and the select kernel's launch).  What leaves is 8 bytes per pixel:
-// {x16 disparity or INV, integer winner + minD or minD - 1, minimum cost, 0} for k_sgm_lrfinal.
-// (SgmWin: rtdm_kernels.h)
-
-template <int NPL, int PF, bool LAST>
-__global__ __launch_bounds__(256) void k_sgm_path_w(const uint16_t* C, uint16_t* S, SGMGeom g, int dx, int dy, int P1, int P2,
-                                                    int first_dir, int nlines, SgmWin* win, int uniq)
-{
-    const int lane = threadIdx.x & 63;
-    const int line = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (line >= nlines) return;                                   // whole waves only
-    const int D = g.D, W1 = g.W1, H = g.H;
-    int sx, sy;
-    if (dy == 0) { sy = line; sx = dx > 0 ? 0 : W1 - 1; }
-    else if (dx == 0) { sx = line; sy = dy > 0 ? 0 : H - 1; }
-    else if (line < W1) { sx = line; sy = dy > 0 ? 0 : H - 1; }
-    else { const int k = line - W1 + 1; sx = dx > 0 ? 0 : W1 - 1; sy = dy > 0 ? k : H - 1 - k; }
-    const int nx = dx > 0 ? W1 - sx : (dx < 0 ? sx + 1 : 0x7fffffff);
-    const int ny = dy > 0 ? H - sy : (dy < 0 ? sy + 1 : 0x7fffffff);
-    const int nsteps = min(nx, ny);
-    const int d0 = lane * NPL;
-    const bool live = d0 < D;
-    const int BIG = 1 << 28;
-    const long stride = ((long)dy * W1 + dx) * D;
-    const size_t off0 = (size_t)blockIdx.y * H * W1 * D + ((size_t)sy * W1 + sx) * D + (live ? d0 : 0);
-    const uint16_t* cp = C + off0;
-    uint16_t* sp = S + off0;
-    PackU16<NPL> cr[PF], sr[PF];
-#pragma unroll
-    for (int k = 0; k < PF; ++k) {
-        if (k < nsteps) {
-            cr[k] = ld_pack<NPL>(cp + (long)k * stride);
-            if (!first_dir) sr[k] = ld_pack<NPL>(sp + (long)k * stride);
-        }
-    }
-    int l[NPL];
-    int mprev = 0;
-    for (int base = 0; base < nsteps; base += PF) {
-#pragma unroll
-        for (int k = 0; k < PF; ++k) {
-            const int step = base + k;
-            if (step >= nsteps) break;
-            const PackU16<NPL> c = cr[k], sv = sr[k];
-            if (step + PF < nsteps) {
-                cr[k] = ld_pack<NPL>(cp + (long)(step + PF) * stride);
-                if (!first_dir) sr[k] = ld_pack<NPL>(sp + (long)(step + PF) * stride);
-            }
-            if (step == 0) {
-#pragma unroll
-                for (int j = 0; j < NPL; ++j) l[j] = live ? (int)c.v[j] : BIG;
-            } else {
-                // neighbours of the lane's end elements: lane-1's last, lane+1's first (BIG outside the wave)
-                const int lo = __builtin_amdgcn_update_dpp(BIG, l[NPL - 1], 0x138, 0xf, 0xf, false);   // wave_shr:1
-                const int hi = __builtin_amdgcn_update_dpp(BIG, l[0], 0x130, 0xf, 0xf, false);         // wave_shl:1
-                int nl[NPL];
-#pragma unroll
-                for (int j = 0; j < NPL; ++j) {
-                    const int dn = j ? l[j - 1] : lo, up = j + 1 < NPL ? l[j + 1] : hi;
-                    const int best = min(min(l[j], mprev + P2), min(dn, up) + P1);
-                    nl[j] = live ? (int)c.v[j] + best - mprev : BIG;
-                }
-#pragma unroll
-                for (int j = 0; j < NPL; ++j) l[j] = nl[j];
-            }
-            int o[NPL];
-#pragma unroll
-            for (int j = 0; j < NPL; ++j) o[j] = first_dir ? l[j] : min((int)sv.v[j] + l[j], 32767);   // R5: saturating sum
-            if constexpr (!LAST) {
-                if (live) st_pack<NPL>(sp + (long)step * stride, o);
-            } else {
-                // winner-take-all on the finished pixel (k_sgm_select's first half, lanes = NPL consecutive disparities each)
-                unsigned key = 0x7fffffffu;
-#pragma unroll
-                for (int j = 0; j < NPL; ++j) if (live) key = min(key, ((unsigned)o[j] << 8) | (unsigned)(d0 + j));
-                key = (unsigned)wave_min_i32((int)key);              // keys are < 2^24: the signed minimum is fine
-                const int mins = (int)(key >> 8), bd = (int)(key & 0xffu);
-                bool hit = false;
-                const int lim = mins * 100;
-#pragma unroll
-                for (int j = 0; j < NPL; ++j) hit |= live && abs(d0 + j - bd) > 1 && o[j] * (100 - uniq) < lim;
-                const int xi = sx + step * dx, yy = sy + step * dy;
-                SgmWin wv;
-                wv.d16 = (int16_t)((g.minD - 1) * 16); wv.bd = (int16_t)(g.minD - 1); wv.mins = 0; wv.pad = 0;
-                if (!__any(hit) && mins < 32767) {                    // wave-uniform (mins = 32767: every cost saturated, the library finds no winner)
-                    const int ip = min(bd + 1, D - 1), in = max(bd - 1, 0);
-                    int s_p = 0, s_n = 0;
-#pragma unroll
-                    for (int j = 0; j < NPL; ++j) {
-                        if (ip % NPL == j) s_p = __builtin_amdgcn_readlane(o[j], ip / NPL);
-                        if (in % NPL == j) s_n = __builtin_amdgcn_readlane(o[j], in / NPL);
-                    }
-                    int d16 = bd * 16;
-                    if (bd > 0 && bd < D - 1) {
-                        const int den = max(s_n + s_p - 2 * mins, 1);
-                        d16 += div_trunc_rcp((s_n - s_p) * 16 + den, den * 2);        // |numerator| < 2^21
-                    }
-                    wv.d16 = (int16_t)(d16 + g.minD * 16); wv.bd = (int16_t)(bd + g.minD); wv.mins = (uint16_t)mins;
-                }
-                if (lane == 0) win[((size_t)blockIdx.y * H + yy) * W1 + xi] = wv;
-            }
-            int m = l[0];
-#pragma unroll
-            for (int j = 1; j < NPL; ++j) m = min(m, l[j]);
-            mprev = wave_min_i32(m);
-        }
-    }
-}
-
 // Half-wave form of the path pass (round 3, second half): one HALF-WAVE per path line, two neighbouring lines per wave, and
 // the whole recurrence in packed 16-bit arithmetic.  A lane holds 2 * NP2 consecutive disparities as NP2 u16 pairs
 // (D = 64 * NP2 fills the 32 lanes; a smaller D leaves the upper lanes dead), so
@@ -617,7 +421,10 @@ __global__ __launch_bounds__(256) void k_sgm_path_w(const uint16_t* C, uint16_t*
 //     both lines at once;
 //   * the two lines of a wave are neighbours in memory for every direction but the horizontal ones (columns x and x + 1 of
 //     one row: 2 * 2 D bytes in one piece), which halves the number of separate pieces the pass asks HBM for.
-// Same values as k_sgm_path_w / k_sgm_path (tests: every D, both modes, against the oracle).
+// LAST (the last direction of a frame): the aggregated costs min(S + L_r, 32767) of a pixel are complete the moment this
+// wave has them in its lanes, so the winner-take-all step runs right here (sgm_wta_half) and S is neither written back nor
+// read again.  What leaves is 8 bytes per pixel (SgmWin, rtdm_kernels.h) for k_sgm_lrfinal.
+// (Tests: every D, both modes, against the oracle.)
 template <int NP2> struct PackW { uint32_t w[NP2]; };
 template <int NP2>
 __device__ __forceinline__ PackW<NP2> ld_w(const uint16_t* p)
@@ -646,8 +453,8 @@ __device__ __forceinline__ int half_min_i32(int v)
     return min((int)s[0], (int)s[1]);
 }
 
-// Winner-take-all on the finished pixels of a wave's two half-waves (k_sgm_select's first half; as in k_sgm_path_w<.., true>,
-// but every quantity is a per-half VECTOR value: both pixels are decided by the same instructions).  o = the aggregated
+// Winner-take-all on the finished pixels of a wave's two half-waves: wave minimum of S << 8 | d, uniqueness vote, S[d* +- 1],
+// quadratic sub-pixel -- every quantity a per-half VECTOR value: both pixels are decided by the same instructions.  o = the aggregated
 // costs of the lane's 2 * NP2 disparities d0 .. as u16 pairs.  Every lane of a half returns that half's record.
 template <int NP2>
 __device__ __forceinline__ SgmWin sgm_wta_half(const uint32_t* o, bool live, int lane, int d0, int D, int uniq, int minD)
@@ -1003,112 +810,7 @@ __global__ __launch_bounds__(256) void k_sgm_sweep(const uint16_t* C, uint16_t* 
     }
 }
 
-// winner-take-all + uniqueness + sub-pixel + left-right check; one workgroup per row.  Each WAVE takes
-// every 4th pixel of the row with its LANES on the disparities (coalesced 2*D-byte reads of S): wave-min of
-// the key S << 8 | d (first minimum), __any() for the uniqueness test, readlane for S[d* +- 1].
-template <bool SPK, int NCH>
-__global__ __launch_bounds__(256) void k_sgm_select(const uint16_t* S, Plane16W disp, SGMGeom g, int uniq, int disp12MaxDiff,
-                                                    int32_t* label, int32_t* size, uint32_t* runs, int32_t* rowcnt,
-                                                    int16_t* headmap, int spkDiff)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    unsigned long long* key = (unsigned long long*)smem;     // W : (minS << 32 | x) votes per right column
-    int16_t* bdv = (int16_t*)(key + g.W);                    // W : integer winner + minD of column x (or minD-1)
-    int16_t* row = bdv + g.W;                                // W : disparity row
-    __shared__ int wsum[4];
-    const int y = blockIdx.y, f = blockIdx.z;
-    const int W = g.W, D = g.D, minD = g.minD, INV = (minD - 1) * 16;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    for (int x = threadIdx.x; x < W; x += 256) { key[x] = ~0ull; bdv[x] = (int16_t)(minD - 1); row[x] = (int16_t)INV; }
-    __syncthreads();
-    const uint16_t* srow = S + (((size_t)f * g.H + y) * g.W1) * D;
-    // the wave's pixels are a serial chain (reduce, test, vote): their S values are fetched PF pixels ahead, otherwise every
-    // pixel would cost a full memory round trip
-    constexpr int PF = 6;
-    uint16_t pre[PF][NCH];
-#pragma unroll
-    for (int p = 0; p < PF; ++p) {
-        const int xp = wv + 4 * p;
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) { const int d = lane + 64 * c; pre[p][c] = (xp < g.W1 && d < D) ? srow[(size_t)xp * D + d] : (uint16_t)0x7fff; }
-    }
-    for (int xb = wv; xb < g.W1; xb += 4 * PF) {
-#pragma unroll
-      for (int p = 0; p < PF; ++p) {
-        const int xi = xb + 4 * p;
-        if (xi >= g.W1) break;
-        int v[NCH];
-        unsigned k = 0x7fffffffu;                            // (reduced as signed: keep the sentinel positive)
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) {
-            const int d = lane + 64 * c;
-            v[c] = d < D ? (int)pre[p][c] : 0x7fff;
-            if (d < D) k = min(k, ((unsigned)v[c] << 8) | (unsigned)d);
-        }
-        {
-            const int xn = xi + 4 * PF;                      // refill this ring slot
-#pragma unroll
-            for (int c = 0; c < NCH; ++c) { const int d = lane + 64 * c; if (xn < g.W1 && d < D) pre[p][c] = srow[(size_t)xn * D + d]; }
-        }
-        k = (unsigned)wave_min_i32((int)k);                  // keys are < 2^24: signed min is fine
-        const int mins = (int)(k >> 8), bd = (int)(k & 0xffu);
-        bool hit = false;
-        const int lim = mins * 100;
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) {
-            const int d = lane + 64 * c;
-            hit |= d < D && abs(d - bd) > 1 && v[c] * (100 - uniq) < lim;
-        }
-        if (__any(hit) || mins >= 32767) continue;            // wave-uniform (mins = 32767: every cost saturated, the library finds no winner)
-        const int ip = min(bd + 1, D - 1), in = max(bd - 1, 0);
-        int sp = 0, sn = 0;
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) {
-            if ((ip >> 6) == c) sp = __builtin_amdgcn_readlane(v[c], ip & 63);
-            if ((in >> 6) == c) sn = __builtin_amdgcn_readlane(v[c], in & 63);
-        }
-        if (lane == 0) {
-            const int x = g.x0 + xi;
-            const int x2 = x - (bd + minD);
-            // R7: the library walks the row from right to left and replaces a vote only by a strictly smaller cost, so among
-            // equal costs the right-most voter stays: the key's low word grows to the left
-            if (x2 >= 0 && x2 < W) atomicMin(&key[x2], ((unsigned long long)(unsigned)mins << 32) | (unsigned)(0xffff - x));
-            bdv[x] = (int16_t)(bd + minD);
-            int d16 = bd * 16;
-            if (bd > 0 && bd < D - 1) {
-                const int den = max(sn + sp - 2 * mins, 1);
-                d16 += div_trunc_rcp((sn - sp) * 16 + den, den * 2);        // |numerator| < 2^21
-            }
-            row[x] = (int16_t)(d16 + minD * 16);
-        }
-      }
-    }
-    __syncthreads();
-    int16_t* out = disp.base + (size_t)f * disp.frame_e + (size_t)y * disp.pitch_e;
-    int16_t* fin = (int16_t*)(row + W);                      // W : final row (for the speckle init)
-    for (int x = threadIdx.x; x < W; x += 256) {
-        int d1 = row[x];
-        if (d1 != INV) {                                      // R9: always on (the host passes disp12MaxDiff > 0 ? it : 1)
-            const int da = d1 >> 4, db = (d1 + 15) >> 4;
-            const int xa = x - da, xb = x - db;
-            // a column nobody voted for holds the library's initial value, the SCALED invalid disparity, which passes its
-            // ">= minD" test for minD >= 2 (restated, not repaired)
-            const auto vote = [&](int xv) -> int { return key[xv] != ~0ull ? (int)bdv[0xffff - (unsigned)(key[xv] & 0xffffu)] : INV; };
-            bool ba = false, bb = false;
-            if (xa >= 0 && xa < W) { const int v = vote(xa); ba = v >= minD && abs(v - da) > disp12MaxDiff; }
-            if (xb >= 0 && xb < W) { const int v = vote(xb); bb = v >= minD && abs(v - db) > disp12MaxDiff; }
-            if (ba && bb) d1 = INV;
-        }
-        out[x] = (int16_t)d1;
-        if (SPK) fin[x] = (int16_t)d1;
-    }
-    if (SPK) {
-        __syncthreads();
-        spk_row_init(fin, (int*)key, wsum, W, (f * g.H + y) * W, label, size, runs, rowcnt + (f * g.H + y), headmap, INV, spkDiff);
-    }
-}
-
-// The second half of k_sgm_select for winners that were found inside the last path pass (k_sgm_path_w<.., LAST>): the votes
+// The winners that were found inside the last path pass (k_sgm_path_h / k_sgm_sweep / k_sgm_wide, LAST): the votes
 // of a row (R7), the always-on left-right check (R9) and the row's x16 disparities.  One workgroup per row.
 __global__ __launch_bounds__(256) void k_sgm_lrfinal(const SgmWin* win, Plane16W disp, SGMGeom g, int disp12MaxDiff)
 {
@@ -1179,16 +881,6 @@ __global__ __launch_bounds__(256) void k_sgm_median(const int16_t* src, Plane16W
     }
 }
 
-template <bool SPK>
-static void launch_select(int nch, dim3 grid, size_t lds, hipStream_t stream, const uint16_t* S, Plane16W disp, const SGMGeom& g,
-                          int uniq, int md, const SGMBuffers& b, int spkDiff)
-{
-    dim3 blk(256);
-#define RTDM_SEL(N) hipLaunchKernelGGL((k_sgm_select<SPK, N>), grid, blk, lds, stream, S, disp, g, uniq, md, b.label, b.size, b.runs, b.rowcnt, b.headmap, spkDiff)
-    switch (nch) { case 1: RTDM_SEL(1); break; case 2: RTDM_SEL(2); break; case 3: RTDM_SEL(3); break; default: RTDM_SEL(4); break; }
-#undef RTDM_SEL
-}
-
 // S = min(S + S2, 32767) (R5), two elements per thread: only where the two horizontal directions ran side by side into S and S2
 // and the sweep that was to add them up could not be launched after all
 __global__ __launch_bounds__(256) void k_sgm_add_s2(uint32_t* S, const uint32_t* S2, size_t npairs)
@@ -1257,7 +949,7 @@ static bool launch_sweep_t(const SGMGeom& g, const SGMBuffers& b, int dy, int P1
     // the narrowest strips whose workgroups all fit the device at once: 8 columns (one per half-wave), 16, 32 -- a frame's rows
     // are a serial chain, so the pass is latency bound until every SIMD holds several waves, and the fewer lines a wave carries
     // the shorter its row; wider strips pay the per-row overhead (barrier, edges, addresses) less often
-    // (RTDM_SGM_SWEEP_COLS=1 / 2 / 4 fixes the choice: A/B)
+    // (RTDM_SGM_SWEEP_COLS=1 / 2 / 4, test hook: fixes the choice, as a capacity miss does)
     static const int cols_env = env_int("RTDM_SGM_SWEEP_COLS", 0);
     // (the instantiation that also adds S2 -- the first sweep after the side-by-side horizontal directions -- holds one more
     // volume's row in registers: a template parameter, so that the other sweep keeps its occupancy)
@@ -1286,7 +978,7 @@ static bool launch_sweep(bool last, const SGMGeom& g, const SGMBuffers& b, int d
 }
 
 static void sgm_finish(Plane16W disp, const SGMGeom& g, const SGMBuffers& b, int disp12MaxDiff, int speckleWindowSize,
-                       int speckleRange, int n, hipStream_t stream, const SgmWin* win, bool fused, int uniq);
+                       int speckleRange, int n, hipStream_t stream, const SgmWin* win);
 
 // rtdm_debug_sgm_cost16: the u16 cost forms for gray frames as well (they must give what the u8 forms give)
 static std::atomic<int> g_cost16{0};
@@ -1339,13 +1031,13 @@ const char* launch_sgm(Plane8 L, Plane8 R, Plane16W disp, const SGMGeom& g, cons
     if (cn == 3) hipLaunchKernelGGL(k_sgm_bounds<3>, bnd, blk, 0, stream, L, R, (uint2*)b.cl, (uint2*)b.cr, g.W, g.H, n, ftz);
     else hipLaunchKernelGGL(k_sgm_bounds<1>, bnd, blk, 0, stream, L, R, (uint2*)b.gl, (uint2*)b.gr, g.W, g.H, n, ftz);
     const unsigned nxd = (unsigned)(((size_t)g.W1 * (g.D / 4) + 255) / 256);       // D is a multiple of 16
-    // RTDM_SGM_PIXBOX=0 (A/B): pixel cost and block sum as two kernels with the u8 volume between them, for every window
-    static const int pixbox_env = env_int("RTDM_SGM_PIXBOX", 1);
+    // pixel cost and block sum fused for windows <= 7 and D in {16, 32, 64, 128, 256}; otherwise two kernels with the u8
+    // volume between them
     const int Rw = blockSize / 2, dq = g.D / 4;
     const bool dq_ok = dq == 4 || dq == 8 || dq == 16 || dq == 32 || dq == 64;
-    const bool pixbox = pixbox_env && Rw <= 3 && dq_ok && !cost_limit;
+    const bool pixbox = Rw <= 3 && dq_ok && !cost_limit;
     if (sgm_cost16_needed(cn, ftz)) {
-        launch_cost16(g, b, blockSize, cn, pixbox_env && Rw <= 3 && dq_ok, cost_limit, n, stream);
+        launch_cost16(g, b, blockSize, cn, Rw <= 3 && dq_ok, cost_limit, n, stream);
     } else if (pixbox) {
         const int rps = 48, strips = (g.H + rps - 1) / rps, tx = 4 * (256 / dq);
         const dim3 pgrid((g.W1 + tx - 1) / tx, strips, n);
@@ -1372,46 +1064,36 @@ const char* launch_sgm(Plane8 L, Plane8 R, Plane16W disp, const SGMGeom& g, cons
     const int last_dir = paths == 5 ? 5 : 7;
     SgmWin* win = (SgmWin*)b.gr;                     // the right image's bounds are dead once the pixel costs exist: 8 bytes per pixel
     // D > 256 (or rtdm_debug_sgm_wide_paths): one wide pass per direction (k_sgm_wide.hip), the last one deciding the winners;
-    // none of the forms below, whatever the A/B switches say -- they hold at most 256 disparities per line
+    // none of the forms below -- they hold at most 256 disparities per line
     if (g.D > 256 || sgm_wide_mode()) {
         for (int k = 0; k < 8; ++k) {
             if (paths == 5 && dirs[k][1] < 0) continue;
             launch_sgm_wide(g, b.C, b.S, dirs[k][0], dirs[k][1], P1, P2, k == 0 ? 1 : 0, k == last_dir, n, win, uniq, stream);
         }
-        sgm_finish(disp, g, b, disp12MaxDiff, speckleWindowSize, speckleRange, n, stream, win, true, uniq);
+        sgm_finish(disp, g, b, disp12MaxDiff, speckleWindowSize, speckleRange, n, stream, win);
         return sgm_wide_waves(g.D) == 1 ? "wide_w1" : "wide_w4";
     }
-    const char* variant = "block";
-    const int threads = (g.D + 63) & ~63;
-    int npl = (g.D + 63) / 64;                       // disparities per lane of the wave-per-line kernel: must divide D
-    if (g.D % npl) npl = 4;
-    static const int wave_paths = env_int("RTDM_SGM_WAVE_PATHS", 1);
-    const bool aligned = (((size_t)b.C | (size_t)b.S) & 7) == 0;
-    const bool aligned16 = (((size_t)b.C | (size_t)b.S) & 15) == 0;
-    // RTDM_SGM_HALF=0 (A/B): every path pass on k_sgm_path_w (one wave per line, 32-bit arithmetic)
-    static const int half_paths = env_int("RTDM_SGM_HALF", 2);
-    // RTDM_SGM_FUSE_SELECT=0 (A/B): the last direction writes S like the others and k_sgm_select reads it back
-    static const int fuse_env = env_int("RTDM_SGM_FUSE_SELECT", 1);
-    const bool fuse_select = fuse_env && wave_paths && aligned && g.D <= 256;
-    // RTDM_SGM_SWEEP=0 (A/B): one pass per direction for the six that advance a row per step as well
+    // (C, S and S2 are whole allocations: 16-byte aligned, as the packed loads and stores of the path passes need)
+    // RTDM_SGM_SWEEP=0 (test hook): one pass per direction for the six that advance a row per step as well -- what runs after
+    // a sweep gave up or did not fit
     static const int sweep_env = env_int("RTDM_SGM_SWEEP", 1);
-    bool sweep = sweep_env && half_paths && wave_paths && aligned16 && fuse_select && b.ring && b.abortf && *b.abortf == 0;
+    bool sweep = sweep_env && b.ring && b.abortf && *b.abortf == 0;
     bool swept_down = false, swept_up = false;
-    // RTDM_SGM_DUAL=0 (A/B): the two horizontal directions one after the other (the second adds to S) instead of side by side
+    // RTDM_SGM_DUAL=0 (test hook): the two horizontal directions one after the other (the second adds to S) instead of side by
+    // side -- what runs without S2
     static const int dual_env = env_int("RTDM_SGM_DUAL", 1);
     bool s2_pending = false;                         // S2 holds the (-1, 0) direction's L_r and has not been added to S yet
     bool swept = false;                              // a row-synchronous sweep ran (the variant this call reports)
     for (int k = 0; k < 8; ++k) {
         const int dx = dirs[k][0], dy = dirs[k][1];
         if (paths == 5 && dy < 0) continue;          // MODE_SGBM's five directions: nothing runs upwards
-        if (k == 0 && sweep && dual_env && b.S2 && (((size_t)b.S2) & 15) == 0 &&
+        if (k == 0 && sweep && dual_env && b.S2 &&
             launch_sweep(paths == 5, g, b, 1, P1, P2, n, win, uniq, stream, nullptr, true)) {
             // both horizontal directions in one launch: (1, 0) -> S, (-1, 0) -> S2; the downward sweep adds the two up
             const dim3 hgrid((2 * g.H + 7) / 8, n);
 #define RTDM_PATHD(N) hipLaunchKernelGGL((k_sgm_path_h<N, 8, false>), hgrid, blk, 0, stream, b.C, b.S, g, 1, 0, P1, P2, 1, g.H, win, uniq, b.S2)
             if (g.D <= 64) RTDM_PATHD(1); else if (g.D <= 128) RTDM_PATHD(2); else RTDM_PATHD(4);
 #undef RTDM_PATHD
-            variant = "half";
             s2_pending = true;
             continue;
         }
@@ -1432,40 +1114,22 @@ const char* launch_sgm(Plane8 L, Plane8 R, Plane16W disp, const SGMGeom& g, cons
             }
         }
         const int lines = dy == 0 ? g.H : (dx == 0 ? g.W1 : g.W1 + g.H - 1);
-        const bool last = fuse_select && k == last_dir;
-        if (half_paths && wave_paths && aligned16 && g.D <= 256 && (!last || half_paths > 1)) {
-            // half-wave lines, packed arithmetic: eight lines per workgroup (RTDM_SGM_HALF=1: all passes but the last)
-            const dim3 hgrid((lines + 7) / 8, n);
-            const int first = k == 0 ? 1 : 0;
+        const bool last = k == last_dir;
+        // half-wave lines, packed arithmetic: eight lines per workgroup
+        const dim3 hgrid((lines + 7) / 8, n);
+        const int first = k == 0 ? 1 : 0;
 #define RTDM_PATHH(N, P) do { if (last) hipLaunchKernelGGL((k_sgm_path_h<N, P, true>), hgrid, blk, 0, stream, b.C, b.S, g, dx, dy, P1, P2, first, lines, win, uniq, (uint16_t*)nullptr); \
                               else hipLaunchKernelGGL((k_sgm_path_h<N, P, false>), hgrid, blk, 0, stream, b.C, b.S, g, dx, dy, P1, P2, first, lines, win, uniq, (uint16_t*)nullptr); } while (0)
-            if (g.D <= 64) RTDM_PATHH(1, 8); else if (g.D <= 128) RTDM_PATHH(2, 8); else RTDM_PATHH(4, 8);
+        if (g.D <= 64) RTDM_PATHH(1, 8); else if (g.D <= 128) RTDM_PATHH(2, 8); else RTDM_PATHH(4, 8);
 #undef RTDM_PATHH
-            variant = "half";
-        } else if (wave_paths && aligned && g.D <= 256) {
-            const dim3 wgrid((lines + 3) / 4, n);
-            const int first = k == 0 ? 1 : 0;
-#define RTDM_PATHW(N, P) do { if (last) hipLaunchKernelGGL((k_sgm_path_w<N, P, true>), wgrid, blk, 0, stream, b.C, b.S, g, dx, dy, P1, P2, first, lines, win, uniq); \
-                              else hipLaunchKernelGGL((k_sgm_path_w<N, P, false>), wgrid, blk, 0, stream, b.C, b.S, g, dx, dy, P1, P2, first, lines, win, uniq); } while (0)
-            switch (npl) {
-                case 1: RTDM_PATHW(1, 8); break;
-                case 2: RTDM_PATHW(2, 8); break;
-                case 3: RTDM_PATHW(3, 8); break;
-                default: RTDM_PATHW(4, 8); break;
-            }
-#undef RTDM_PATHW
-            if (variant[0] == 'b') variant = "wave";
-        } else {
-            hipLaunchKernelGGL(k_sgm_path, dim3(lines, n), dim3(threads), 0, stream, b.C, b.S, g, dx, dy, P1, P2, k == 0 ? 1 : 0);
-        }
     }
-    sgm_finish(disp, g, b, disp12MaxDiff, speckleWindowSize, speckleRange, n, stream, win, fuse_select, uniq);
-    return swept ? "sweep" : variant;
+    sgm_finish(disp, g, b, disp12MaxDiff, speckleWindowSize, speckleRange, n, stream, win);
+    return swept ? "sweep" : "half";
 }
 
-// the winners (k_sgm_lrfinal where the last path pass decided them, else k_sgm_select), the median and the speckle filter
+// the winners' votes and left-right check (k_sgm_lrfinal: the last path pass decided them), the median and the speckle filter
 static void sgm_finish(Plane16W disp, const SGMGeom& g, const SGMBuffers& b, int disp12MaxDiff, int speckleWindowSize,
-                       int speckleRange, int n, hipStream_t stream, const SgmWin* win, bool fused, int uniq)
+                       int speckleRange, int n, hipStream_t stream, const SgmWin* win)
 {
     dim3 blk(256);
     const bool speckle = speckleWindowSize > 0;                           // R11
@@ -1473,8 +1137,7 @@ static void sgm_finish(Plane16W disp, const SGMGeom& g, const SGMBuffers& b, int
     // select -> a temporary plane (the bounds buffer of the left image is free again), median -> the caller's plane
     int16_t* tmp = (int16_t*)b.gl;
     const Plane16W tplane{tmp, (size_t)g.W, (size_t)g.W * g.H};
-    if (fused) hipLaunchKernelGGL(k_sgm_lrfinal, dim3(1, g.H, n), blk, lds, stream, win, tplane, g, disp12MaxDiff);
-    else launch_select<false>((g.D + 63) / 64, dim3(1, g.H, n), lds, stream, b.S, tplane, g, uniq, disp12MaxDiff, b, 0);
+    hipLaunchKernelGGL(k_sgm_lrfinal, dim3(1, g.H, n), blk, lds, stream, win, tplane, g, disp12MaxDiff);
     const size_t mlds = (size_t)g.W * 6;
     const int INV = (g.minD - 1) * 16;
     if (speckle) {

@@ -49,38 +49,21 @@ struct TuneKey {
 };
 struct TuneEntry { TuneKey key; int strips; };   // strips: 0 = seen once, not measured yet; -1 = measuring failed
 
-// A lane = one HIP stream plus its slice of the per-handle workspace.  A batch is cut into pieces that
-// alternate between two lanes, so that the latency-bound row kernels (left-right check, speckle
-// filter) of one piece run beside the VALU-bound SAD search of the other.
-struct Lane {
-    hipStream_t stream;
-    hipEvent_t done;
-    hipStream_t side;              // the border-column search runs here, next to the tile search (RTDM_BORDER_ASYNC)
-    hipEvent_t fork, join;
-    hipStream_t back;              // two-lane mode: left-right check and speckle filter of the lane's piece run here
-    hipEvent_t mid;                // ... after this event (the piece's search is complete)
-    uint8_t *dLp, *dRp;
-    int32_t *dCost, *dLabel, *dSize, *dRowCnt;
-    uint32_t* dRuns;
-    int16_t* dHead;
-    int16_t* dOut;                 // internal disparity plane of the lane (rows of Ws elements)
-};
-
 struct rtdm_bm {
     rtdm_bm_params p;
     int maxW, maxH, maxB, device;
     int roi1[4], roi2[4];
     hipStream_t stream;
-    Lane lane[2];
-    int nlanes, laneB;             // frames per lane piece
-    hipEvent_t evIn;
-    hipEvent_t evBand[4];          // rtdm_bm_compute: one per band of the result on its way back
+    hipStream_t sBorder;           // batches: the border-column search runs here, next to the tile search
+    hipStream_t sSpare[2];         // idle: they keep the runtime's stream-to-queue layout (rtdm_bm_create)
+    hipEvent_t evFork, evJoin;     // ... behind this event of the compute stream, which then waits for that one
+    hipEvent_t evBand[2];          // rtdm_bm_compute: one per band of the result on its way back
     hipStream_t sIn, sOut;         // rtdm_bm_compute_batch: copies in / out beside the compute stream
     hipEvent_t evH2D[2], evComp[2], evD2H[2];   // ... one set per half of the staging planes
     size_t ppitch;                 // pitch of the internal 8-bit planes
     uint8_t *dLp, *dRp;            // prefiltered planes   [maxB][maxH][ppitch]
     uint8_t *dInL, *dInR;          // staging for the host entry points
-    int16_t* dOut;                 //                      [maxB][maxH][maxW]
+    int16_t* dOut;                 // internal disparity plane [maxB][maxH][Ws] (Ws = maxW rounded up to 8)
     std::vector<TuneEntry> tuned;  // measured strip counts per work shape, least recently used first (<= 16 entries)
     long tune_shapes, tune_launches;   // rtdm_bm_get_tuner_stats
     int32_t *dCost, *dLabel, *dSize, *dRowCnt;
@@ -210,40 +193,22 @@ int rtdm_bm_create(const rtdm_bm_params* params, int max_width, int max_height, 
         rtdm_bm_destroy(bm);
         return e == hipErrorOutOfMemory ? RTDM_ERR_NOMEM : RTDM_ERR_HIP;
     }
-    {   // lanes: slices of the workspace (lane 1 starts laneB frames in)
-        const char* env = getenv("RTDM_LANES");
-        // opt-in.  Measured in round 2 with the ring kernel (profiles/r02_two_lane_pipeline_ab.txt): the row kernels of piece k
-        // under the search of piece k+1 give 51.8 k pairs/s with 2 pieces and 51.2 k with 4 against 52.1 k on one lane -- a
-        // search wave loses as many issue slots to a co-resident row-kernel wave as the overlap hides; with the front stream at
-        // high and the back streams at low priority the row kernels starve (left-right check 1.7 -> 4.5 ms) and the search
-        // still slows by 8 %: 47.7 k.
-        bm->nlanes = (max_batch >= 2 && env && atoi(env) == 2) ? 2 : 1;
-        bm->laneB = bm->nlanes == 2 ? (max_batch + 1) / 2 : max_batch;
-        HIPC(hipEventCreateWithFlags(&bm->evIn, hipEventDisableTiming));
-        for (auto& e : bm->evBand) HIPC(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        HIPC(hipStreamCreateWithFlags(&bm->sIn, hipStreamNonBlocking));
-        HIPC(hipStreamCreateWithFlags(&bm->sOut, hipStreamNonBlocking));
-        for (int k = 0; k < 2; ++k) {
-            HIPC(hipEventCreateWithFlags(&bm->evH2D[k], hipEventDisableTiming));
-            HIPC(hipEventCreateWithFlags(&bm->evComp[k], hipEventDisableTiming));
-            HIPC(hipEventCreateWithFlags(&bm->evD2H[k], hipEventDisableTiming));
-        }
-        for (int k = 0; k < bm->nlanes; ++k) {
-            Lane& ln = bm->lane[k];
-            const size_t fo = (size_t)k * bm->laneB;                       // first frame of the slice
-            const size_t po = fo * ((max_width + 7) & ~7) * max_height;     // in workspace pixels
-            HIPC(hipStreamCreateWithFlags(&ln.stream, hipStreamNonBlocking));
-            HIPC(hipEventCreateWithFlags(&ln.done, hipEventDisableTiming));
-            HIPC(hipStreamCreateWithFlags(&ln.side, hipStreamNonBlocking));
-            HIPC(hipEventCreateWithFlags(&ln.fork, hipEventDisableTiming));
-            HIPC(hipEventCreateWithFlags(&ln.join, hipEventDisableTiming));
-            HIPC(hipStreamCreateWithFlags(&ln.back, hipStreamNonBlocking));
-            HIPC(hipEventCreateWithFlags(&ln.mid, hipEventDisableTiming));
-            ln.dLp = bm->dLp + fo * bm->ppitch * max_height; ln.dRp = bm->dRp + fo * bm->ppitch * max_height;
-            ln.dCost = bm->dCost + po; ln.dLabel = bm->dLabel + po; ln.dSize = bm->dSize + po;
-            ln.dRuns = bm->dRuns + po; ln.dHead = bm->dHead + po; ln.dOut = bm->dOut + po; ln.dRowCnt = bm->dRowCnt + fo * max_height;
-        }
+    for (auto& e : bm->evBand) HIPC(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    HIPC(hipStreamCreateWithFlags(&bm->sIn, hipStreamNonBlocking));
+    HIPC(hipStreamCreateWithFlags(&bm->sOut, hipStreamNonBlocking));
+    for (int k = 0; k < 2; ++k) {
+        HIPC(hipEventCreateWithFlags(&bm->evH2D[k], hipEventDisableTiming));
+        HIPC(hipEventCreateWithFlags(&bm->evComp[k], hipEventDisableTiming));
+        HIPC(hipEventCreateWithFlags(&bm->evD2H[k], hipEventDisableTiming));
     }
+    // The runtime maps streams onto its few hardware queues in creation order, and which queue the border side stream shares
+    // shows in the search stage (~1 % at the headline).  The streams are therefore created in the order the handle has always
+    // created them: sSpare are the two idle streams of the retired two-lane layout.
+    HIPC(hipStreamCreateWithFlags(&bm->sSpare[0], hipStreamNonBlocking));
+    HIPC(hipStreamCreateWithFlags(&bm->sBorder, hipStreamNonBlocking));
+    HIPC(hipStreamCreateWithFlags(&bm->sSpare[1], hipStreamNonBlocking));
+    HIPC(hipEventCreateWithFlags(&bm->evFork, hipEventDisableTiming));
+    HIPC(hipEventCreateWithFlags(&bm->evJoin, hipEventDisableTiming));
     *out = bm;
     return RTDM_OK;
 }
@@ -253,16 +218,10 @@ void rtdm_bm_destroy(rtdm_bm* bm)
     if (!bm) return;
     (void)hipSetDevice(bm->device);
     if (bm->stream) (void)hipStreamSynchronize(bm->stream);
-    for (int k = 0; k < bm->nlanes; ++k) {
-        if (bm->lane[k].stream) { (void)hipStreamSynchronize(bm->lane[k].stream); (void)hipStreamDestroy(bm->lane[k].stream); }
-        if (bm->lane[k].done) (void)hipEventDestroy(bm->lane[k].done);
-        if (bm->lane[k].side) { (void)hipStreamSynchronize(bm->lane[k].side); (void)hipStreamDestroy(bm->lane[k].side); }
-        if (bm->lane[k].fork) (void)hipEventDestroy(bm->lane[k].fork);
-        if (bm->lane[k].join) (void)hipEventDestroy(bm->lane[k].join);
-        if (bm->lane[k].back) { (void)hipStreamSynchronize(bm->lane[k].back); (void)hipStreamDestroy(bm->lane[k].back); }
-        if (bm->lane[k].mid) (void)hipEventDestroy(bm->lane[k].mid);
-    }
-    if (bm->evIn) (void)hipEventDestroy(bm->evIn);
+    if (bm->sBorder) { (void)hipStreamSynchronize(bm->sBorder); (void)hipStreamDestroy(bm->sBorder); }
+    for (auto& q : bm->sSpare) if (q) (void)hipStreamDestroy(q);
+    if (bm->evFork) (void)hipEventDestroy(bm->evFork);
+    if (bm->evJoin) (void)hipEventDestroy(bm->evJoin);
     for (auto& e : bm->evBand) if (e) (void)hipEventDestroy(e);
     if (bm->sIn) { (void)hipStreamSynchronize(bm->sIn); (void)hipStreamDestroy(bm->sIn); }
     if (bm->sOut) { (void)hipStreamSynchronize(bm->sOut); (void)hipStreamDestroy(bm->sOut); }
@@ -347,9 +306,9 @@ static void stage_end(rtdm_bm* bm, hipStream_t s, StageEvent* ev)
     bm->pending.push_back(*ev);
 }
 
-static int chunk_front(rtdm_bm* bm, const Lane& ln, int n, Plane8 L, Plane8 R, int W, int H, Plane16W disp, hipStream_t s,
-                       BMGeom* gout, bool* anyout);
-static int chunk_back(rtdm_bm* bm, const Lane& ln, int n, int W, int H, Plane16W disp, const BMGeom& g, hipStream_t s);
+static int chunk_front(rtdm_bm* bm, int n, Plane8 L, Plane8 R, int W, int H, Plane16W disp, hipStream_t s, BMGeom* gout,
+                       bool* anyout);
+static int chunk_back(rtdm_bm* bm, int n, int W, int H, Plane16W disp, const BMGeom& g, hipStream_t s);
 
 // Row strips per frame for the fast search of a batch, chosen by measurement and remembered in the handle: the model
 // (fast_strips_model) is right on average, but neighbouring strip counts differ by up to 5 % through scheduling effects it
@@ -358,11 +317,11 @@ static int chunk_back(rtdm_bm* bm, const Lane& ln, int n, int W, int H, Plane16W
 // counts, not positions): a caller that moves a same-sized ROI around (estimator.cpp:53-54) keeps its entry.  A shape is
 // measured the SECOND time it is seen -- a caller whose ROI changes size every call never pays the ~30 extra launches and
 // the stream synchronisation -- and the table is a 16-entry LRU.  Small batches keep the model.  RTDM_AUTOTUNE=0: off.
-static int tune_strips(rtdm_bm* bm, const Lane& ln, Plane8 Lpr, Plane8 Rpr, Plane16W disp, const BMGeom& g, int n, hipStream_t s, bool fuse, bool ring)
+static int tune_strips(rtdm_bm* bm, Plane8 Lpr, Plane8 Rpr, Plane16W disp, const BMGeom& g, int n, hipStream_t s, bool fuse, bool ring)
 {
     const auto launch = [&](int c) {
-        if (ring) launch_search_ring(Lpr, Rpr, disp, ln.dCost, g, n, s, c, fuse);
-        else launch_search_fast(Lpr, Rpr, disp, ln.dCost, g, n, s, fuse, c);
+        if (ring) launch_search_ring(Lpr, Rpr, disp, bm->dCost, g, n, s, c, fuse);
+        else launch_search_fast(Lpr, Rpr, disp, bm->dCost, g, n, s, fuse, c);
     };
     static const bool enabled = env_int("RTDM_AUTOTUNE", 1) != 0 && getenv("RTDM_FAST_WGS") == nullptr;
     if (!enabled || n < 16) return 0;
@@ -417,38 +376,29 @@ static int tune_strips(rtdm_bm* bm, const Lane& ln, Plane8 Lpr, Plane8 Rpr, Plan
 // One chunk (n <= maxB) of device-resident frames, enqueued on `s`.  The row kernels move 8 columns per 128-bit
 // access and let a ragged last chunk spill into the row padding, so they need 16-byte aligned rows of at least
 // W rounded up to 8 elements whose padding is ours to write.  A caller's plane qualifies only if W % 8 == 0 and it
-// is aligned; anything else (the reference's own crops are 233, 534 and 934 columns wide) runs on the lane's
+// is aligned; anything else (the reference's own crops are 233, 534 and 934 columns wide) runs on the handle's
 // internal plane and is copied out at the end.
-// `back` (two-lane mode): the stream the chunk's row kernels run on, behind the event ln.mid recorded after the search;
-// nullptr = everything on `s`.
-static int run_chunk(rtdm_bm* bm, const Lane& ln, int n, Plane8 L, Plane8 R, int W, int H, Plane16W out, hipStream_t s,
-                     hipStream_t back = nullptr)
+static int run_chunk(rtdm_bm* bm, int n, Plane8 L, Plane8 R, int W, int H, Plane16W out, hipStream_t s)
 {
     const size_t Ws = (size_t)((W + 7) & ~7);
-    // (the lane's own plane, or a frame-aligned part of it: rows of Ws elements whose padding is ours)
-    const bool internal = out.pitch_e == Ws && out.base >= ln.dOut && out.base < ln.dOut + (size_t)bm->laneB * Ws * (size_t)H &&
-                          (size_t)(out.base - ln.dOut) % (Ws * (size_t)H) == 0;
+    // (the handle's own plane, or a frame-aligned part of it: rows of Ws elements whose padding is ours)
+    const bool internal = out.pitch_e == Ws && out.base >= bm->dOut && out.base < bm->dOut + (size_t)bm->maxB * Ws * (size_t)H &&
+                          (size_t)(out.base - bm->dOut) % (Ws * (size_t)H) == 0;
     const bool direct = internal || ((W & 7) == 0 && (((size_t)out.base | (out.pitch_e * 2) | (out.frame_e * 2)) & 15) == 0);
-    const Plane16W disp = direct ? out : Plane16W{ln.dOut, Ws, Ws * (size_t)H};
+    const Plane16W disp = direct ? out : Plane16W{bm->dOut, Ws, Ws * (size_t)H};
     BMGeom g;
     bool any = false;
-    int rc = chunk_front(bm, ln, n, L, R, W, H, disp, s, &g, &any);
+    int rc = chunk_front(bm, n, L, R, W, H, disp, s, &g, &any);
     if (rc) return rc;
-    hipStream_t b = s;
-    if (back) {
-        HIPC(hipEventRecord(ln.mid, s));
-        HIPC(hipStreamWaitEvent(back, ln.mid, 0));
-        b = back;
-    }
-    if (any) { rc = chunk_back(bm, ln, n, W, H, disp, g, b); if (rc) return rc; }
-    if (!direct) launch_copy16(disp, out, W, H, n, b);
+    if (any) { rc = chunk_back(bm, n, W, H, disp, g, s); if (rc) return rc; }
+    if (!direct) launch_copy16(disp, out, W, H, n, s);
     HIPC(hipGetLastError());
     return RTDM_OK;
 }
 
 // Fill + prefilter + SAD search of a chunk (VALU bound); *any = false: the whole frame is FILTERED, nothing follows.
-static int chunk_front(rtdm_bm* bm, const Lane& ln, int n, Plane8 L, Plane8 R, int W, int H, Plane16W disp, hipStream_t s,
-                       BMGeom* gout, bool* anyout)
+static int chunk_front(rtdm_bm* bm, int n, Plane8 L, Plane8 R, int W, int H, Plane16W disp, hipStream_t s, BMGeom* gout,
+                       bool* anyout)
 {
     const rtdm_bm_params& p = bm->p;
     BMGeom& g = *gout;
@@ -457,7 +407,7 @@ static int chunk_front(rtdm_bm* bm, const Lane& ln, int n, Plane8 L, Plane8 R, i
     if (!any) { launch_fill16(disp, 0, W, 0, H, n, g.filtered, s); return RTDM_OK; }
     // the search kernels write columns [cx0, cx1) of the valid rows; everything else is FILTERED
     // (+ the speckle filter's run counts = 0); the fill rides in the prefilter's launch
-    const FillJob fill{disp, g.cx0, g.cx1, g.vy0, g.vy1, g.filtered, (p.speckleRange >= 0 && p.speckleWindowSize > 0) ? ln.dRowCnt : nullptr};
+    const FillJob fill{disp, g.cx0, g.cx1, g.vy0, g.vy1, g.filtered, (p.speckleRange >= 0 && p.speckleWindowSize > 0) ? bm->dRowCnt : nullptr};
     StageEvent ev;
     bool u16 = false;
     // what k_search_generic cannot hold in LDS (D > 256, large windows at large D) -- or everything, when
@@ -469,51 +419,48 @@ static int chunk_front(rtdm_bm* bm, const Lane& ln, int n, Plane8 L, Plane8 R, i
         const int lpp = ring ? ring_lanes_per_pixel(g) : 0;
         bm->variant = dslice ? (u16 ? "generic_dslice_u16" : "generic_dslice_u32")
                     : ring ? (lpp == 16 ? "fast_ring16_qsad" : lpp == 8 ? "fast_ring8_qsad" : lpp == 4 ? "fast_ring4_qsad" : "fast_ring_qsad") : fast ? "fast_qsad" : (u16 ? "generic_u16" : "generic_u32");
-        Plane8W Lp{ln.dLp, bm->ppitch, bm->ppitch * (size_t)H}, Rp{ln.dRp, bm->ppitch, bm->ppitch * (size_t)H};
+        Plane8W Lp{bm->dLp, bm->ppitch, bm->ppitch * (size_t)H}, Rp{bm->dRp, bm->ppitch, bm->ppitch * (size_t)H};
         stage_begin(bm, RTDM_STAGE_PREFILTER, n, s, &ev);
         launch_prefilter(L, R, Lp, Rp, W, H, p.preFilterCap, n, s, &fill);
         stage_end(bm, s, &ev);
-        Plane8 Lpr{ln.dLp, Lp.pitch, Lp.frame}, Rpr{ln.dRp, Rp.pitch, Rp.frame};
+        Plane8 Lpr{bm->dLp, Lp.pitch, Lp.frame}, Rpr{bm->dRp, Rp.pitch, Rp.frame};
         stage_begin(bm, RTDM_STAGE_SEARCH, n, s, &ev);
         if (fast) {
             int lx0, lx1, rx0, rx1;
             fast_border_ranges(g, &lx0, &lx1, &rx0, &rx1);
-            static const bool separate = getenv("RTDM_SEPARATE_BORDER") != nullptr;   // A/B switch
-            // Batches: the border columns run as a kernel of their own on a side stream, concurrently with the tile kernel.
-            // Its waves need 37-72 VGPRs and fit NEXT to the four tile waves of a SIMD, whereas inside the tile kernel's
-            // grid a border workgroup takes a tile workgroup's slot for the length of its latency-bound walk
-            // (search -2 %).  Single frames keep the fused launch (one kernel less).  RTDM_BORDER_ASYNC=0: always fused.
-            static const bool async_border = [] { const char* e = getenv("RTDM_BORDER_ASYNC"); return !e || atoi(e) != 0; }();
-            static const int side_min = env_int("RTDM_BORDER_SIDE_MIN", 16);   // (A/B: smallest batch whose border columns get the side stream)
-            const bool side = async_border && border_search_supported(g) && n >= side_min;
+            // Batches of 16 or more: the border columns run as a kernel of their own on a side stream, concurrently with the
+            // tile kernel.  Its waves need 37-72 VGPRs and fit NEXT to the four tile waves of a SIMD, whereas inside the tile
+            // kernel's grid a border workgroup takes a tile workgroup's slot for the length of its latency-bound walk
+            // (search -2 %).  Smaller batches keep the fused launch (one kernel less).
+            const bool side = border_search_supported(g) && n >= 16;
             // (the 3.x clamp exists in the stand-alone border kernel only: the fused forms keep their register budget)
-            const bool fuse = border_search_supported(g) && !separate && !side && !g.legacy;   // border workgroups inside the tile kernel's grid
+            const bool fuse = border_search_supported(g) && !side && !g.legacy;   // border workgroups inside the tile kernel's grid
             // (measured, if at all, before the side stream forks: nothing else runs beside the timed launches)
-            const int strips = tune_strips(bm, ln, Lpr, Rpr, disp, g, n, s, fuse, ring);
+            const int strips = tune_strips(bm, Lpr, Rpr, disp, g, n, s, fuse, ring);
             if (side) {
-                HIPC(hipEventRecord(ln.fork, s));
-                HIPC(hipStreamWaitEvent(ln.side, ln.fork, 0));
+                HIPC(hipEventRecord(bm->evFork, s));
+                HIPC(hipStreamWaitEvent(bm->sBorder, bm->evFork, 0));
 #ifndef RTDM_DEBUG_SKIP_BORDER   // (timing-only variant build: what the border columns cost the search stage; outputs are wrong)
-                launch_search_border(Lpr, Rpr, disp, ln.dCost, g, n, ln.side, lx0, lx1, rx0, rx1);
+                launch_search_border(Lpr, Rpr, disp, bm->dCost, g, n, bm->sBorder, lx0, lx1, rx0, rx1);
 #endif
-                HIPC(hipEventRecord(ln.join, ln.side));
+                HIPC(hipEventRecord(bm->evJoin, bm->sBorder));
             }
             bool fused = fuse;
-            if (ring) fused = launch_search_ring(Lpr, Rpr, disp, ln.dCost, g, n, s, strips, fuse);
-            else launch_search_fast(Lpr, Rpr, disp, ln.dCost, g, n, s, fuse, strips);
+            if (ring) fused = launch_search_ring(Lpr, Rpr, disp, bm->dCost, g, n, s, strips, fuse);
+            else launch_search_fast(Lpr, Rpr, disp, bm->dCost, g, n, s, fuse, strips);
             if (side) {
-                HIPC(hipStreamWaitEvent(s, ln.join, 0));
+                HIPC(hipStreamWaitEvent(s, bm->evJoin, 0));
             } else if (fused) {
             } else if (border_search_supported(g)) {
-                launch_search_border(Lpr, Rpr, disp, ln.dCost, g, n, s, lx0, lx1, rx0, rx1);
+                launch_search_border(Lpr, Rpr, disp, bm->dCost, g, n, s, lx0, lx1, rx0, rx1);
             } else {
-                launch_search_generic(Lpr, Rpr, disp, ln.dCost, g, n, s, lx0, lx1);
-                launch_search_generic(Lpr, Rpr, disp, ln.dCost, g, n, s, rx0, rx1);
+                launch_search_generic(Lpr, Rpr, disp, bm->dCost, g, n, s, lx0, lx1);
+                launch_search_generic(Lpr, Rpr, disp, bm->dCost, g, n, s, rx0, rx1);
             }
         } else if (dslice) {
-            launch_search_dslice(Lpr, Rpr, disp, ln.dCost, g, n, s, g.cx0 - g.lofs, g.cx1 - g.lofs);
+            launch_search_dslice(Lpr, Rpr, disp, bm->dCost, g, n, s, g.cx0 - g.lofs, g.cx1 - g.lofs);
         } else {
-            launch_search_generic(Lpr, Rpr, disp, ln.dCost, g, n, s, g.cx0 - g.lofs, g.cx1 - g.lofs);
+            launch_search_generic(Lpr, Rpr, disp, bm->dCost, g, n, s, g.cx0 - g.lofs, g.cx1 - g.lofs);
         }
         stage_end(bm, s, &ev);
     }
@@ -522,7 +469,7 @@ static int chunk_front(rtdm_bm* bm, const Lane& ln, int n, Plane8 L, Plane8 R, i
 }
 
 // Left-right check + speckle filter of a chunk, in place on `disp` (latency bound).
-static int chunk_back(rtdm_bm* bm, const Lane& ln, int n, int W, int H, Plane16W disp, const BMGeom& g, hipStream_t s)
+static int chunk_back(rtdm_bm* bm, int n, int W, int H, Plane16W disp, const BMGeom& g, hipStream_t s)
 {
     const rtdm_bm_params& p = bm->p;
     StageEvent ev;
@@ -531,15 +478,15 @@ static int chunk_back(rtdm_bm* bm, const Lane& ln, int n, int W, int H, Plane16W
     int compact_rows = 0;                // > 0: k_lrcheck_vec wrote per-chunk head records and merged blocks of that many rows
     if (lr) {
         stage_begin(bm, RTDM_STAGE_LRCHECK, n, s, &ev);
-        if (speckle) compact_rows = launch_lrcheck(disp, ln.dCost, g, p.disp12MaxDiff, n, s, ln.dLabel, ln.dSize, ln.dRuns, ln.dRowCnt, ln.dHead,
+        if (speckle) compact_rows = launch_lrcheck(disp, bm->dCost, g, p.disp12MaxDiff, n, s, bm->dLabel, bm->dSize, bm->dRuns, bm->dRowCnt, bm->dHead,
                                                    p.speckleRange);
-        else         launch_lrcheck(disp, ln.dCost, g, p.disp12MaxDiff, n, s);
+        else         launch_lrcheck(disp, bm->dCost, g, p.disp12MaxDiff, n, s);
         stage_end(bm, s, &ev);
     }
     if (speckle) {
         stage_begin(bm, RTDM_STAGE_SPECKLE, n, s, &ev);
-        launch_speckle(disp, ln.dLabel, ln.dSize, ln.dRuns, ln.dRowCnt, ln.dHead, W, g.Ws, H, n, g.filtered, p.speckleWindowSize,
-                       p.speckleRange, lr, !lr ? 1 : compact_rows > 0 ? compact_rows : lrcheck_rows_per_block(), g.vy0, g.vy1, s, compact_rows > 0);
+        launch_speckle(disp, bm->dLabel, bm->dSize, bm->dRuns, bm->dRowCnt, bm->dHead, W, g.Ws, H, n, g.filtered, p.speckleWindowSize,
+                       p.speckleRange, lr, std::max(compact_rows, 1), g.vy0, g.vy1, s, compact_rows > 0);
         stage_end(bm, s, &ev);
     }
     HIPC(hipGetLastError());
@@ -573,44 +520,14 @@ int rtdm_bm_compute_device(rtdm_bm* bm, int n, const uint8_t* d_left, const uint
         return RTDM_ERR_BAD_SIZE;
     HIPC(hipSetDevice(bm->device));
     hipStream_t s = (hipStream_t)hip_stream;          // NULL = the HIP null stream (what torch's default stream is)
-    const bool split = bm->nlanes == 2 && n >= 2;
-    if (!split) {
-        for (int i0 = 0; i0 < n; i0 += bm->laneB) {
-            const int m = std::min(bm->laneB, n - i0);
-            Plane8 L{d_left + (size_t)i0 * frame_stride, pitch, frame_stride};
-            Plane8 R{d_right + (size_t)i0 * frame_stride, pitch, frame_stride};
-            Plane16W O{d_disp + (size_t)i0 * (disp_frame_stride / 2), disp_pitch / 2, disp_frame_stride / 2};
-            rc = run_chunk(bm, bm->lane[0], m, L, R, width, height, O, s);
-            if (rc) return rc;
-        }
-        return RTDM_OK;
-    }
-    // Two lanes: the batch is cut into pieces whose searches run back to back on ONE front stream (two searches side by
-    // side would only share the VALUs), while the row kernels of piece k (latency bound, <= 40 VGPRs: their waves fit beside
-    // the two 232-VGPR search waves of a SIMD) run on the lane's back stream under the search of piece k+1.  The pieces
-    // alternate between the two workspace slices; a slice is reused once its previous piece's row kernels are done.
-    // RTDM_PIECES = pieces per call.
-    hipStream_t front = bm->lane[0].stream;
-    HIPC(hipEventRecord(bm->evIn, s));
-    HIPC(hipStreamWaitEvent(front, bm->evIn, 0));
-    static const int npieces = std::max(2, env_int("RTDM_PIECES", 4));
-    const int piece = std::max(1, std::min(bm->laneB, (n + npieces - 1) / npieces));
-    bool used[2] = {false, false};
-    int k = 0;
-    for (int i0 = 0; i0 < n; i0 += piece, k ^= 1) {
-        const int m = std::min(piece, n - i0);
-        Lane& ln = bm->lane[k];
-        if (used[k]) HIPC(hipStreamWaitEvent(front, ln.done, 0));
+    for (int i0 = 0; i0 < n; i0 += bm->maxB) {
+        const int m = std::min(bm->maxB, n - i0);
         Plane8 L{d_left + (size_t)i0 * frame_stride, pitch, frame_stride};
         Plane8 R{d_right + (size_t)i0 * frame_stride, pitch, frame_stride};
         Plane16W O{d_disp + (size_t)i0 * (disp_frame_stride / 2), disp_pitch / 2, disp_frame_stride / 2};
-        rc = run_chunk(bm, ln, m, L, R, width, height, O, front, ln.back);
+        rc = run_chunk(bm, m, L, R, width, height, O, s);
         if (rc) return rc;
-        HIPC(hipEventRecord(ln.done, ln.back));
-        used[k] = true;
     }
-    for (int q = 0; q < 2; ++q)
-        if (used[q]) HIPC(hipStreamWaitEvent(s, bm->lane[q].done, 0));
     return RTDM_OK;
 }
 
@@ -644,17 +561,16 @@ static int compute_batch_enqueue(rtdm_bm* bm, int n, const uint8_t* left, const 
     int rc = RTDM_OK;
     hipStream_t s = bm->stream;
     const size_t dpitch = bm->ppitch, dframe = bm->ppitch * (size_t)height;
-    const size_t Ws = (size_t)((width + 7) & ~7);                      // the lane's internal plane (see run_chunk)
+    const size_t Ws = (size_t)((width + 7) & ~7);                      // the handle's internal plane (see run_chunk)
     const size_t opitch = Ws * 2, oframe = opitch * (size_t)height;
     // Three streams, two halves of the staging planes: while chunk k is computed, chunk k+1 comes in over PCIe and chunk
     // k-1 goes out (both directions of the bus at once).  It pays for page-locked caller memory (hipHostMalloc /
     // hipHostRegister: the copies are true DMA); pageable frames are staged by the runtime inside the copy call.
     // Measured (tools/host_batch_rate.py, 256 x 720p): page-locked 11.6 k -> 21.1 k pairs/s (78 GB/s over PCIe, both ways),
-    // pageable 11.2 k -> 10.5 k: so only for page-locked callers.  RTDM_BATCH_PIPELINE = 0 never, 2 always.
-    const int half = std::max(1, bm->laneB / 2);
-    static const int pipe_mode = [] { const char* e = getenv("RTDM_BATCH_PIPELINE"); return e ? atoi(e) : 1; }();
-    const bool two = bm->laneB >= 2 && (pipe_mode == 2 || (pipe_mode == 1 && page_locked(left) && page_locked(right) && page_locked(disp)));
-    const int chunk = two ? half : bm->laneB;
+    // pageable 11.2 k -> 10.5 k: so only for page-locked callers.
+    const int half = std::max(1, bm->maxB / 2);
+    const bool two = bm->maxB >= 2 && page_locked(left) && page_locked(right) && page_locked(disp);
+    const int chunk = two ? half : bm->maxB;
     int k = 0;
     for (int i0 = 0; i0 < n; i0 += chunk, ++k) {
         const int m = std::min(chunk, n - i0), b = two ? (k & 1) : 0;
@@ -681,7 +597,7 @@ static int compute_batch_enqueue(rtdm_bm* bm, int n, const uint8_t* left, const 
         Plane8 L{dl, dpitch, dframe}, R{dr, dpitch, dframe};
         int16_t* dout = bm->dOut + fo * Ws * (size_t)height;
         Plane16W O{dout, Ws, Ws * (size_t)height};
-        rc = run_chunk(bm, bm->lane[0], m, L, R, width, height, O, s);
+        rc = run_chunk(bm, m, L, R, width, height, O, s);
         if (rc) return rc;
         if (two) { HIPC(hipEventRecord(bm->evComp[b], s)); HIPC(hipStreamWaitEvent(so, bm->evComp[b], 0)); }
         // one linear copy only when the internal rows carry no padding: with width < Ws it would write the pad columns
@@ -716,8 +632,8 @@ int rtdm_bm_compute(rtdm_bm* bm, const uint8_t* left, size_t left_pitch, const u
     // area on the host and go over in linear async copies -- in two BANDS of rows per direction, so that the host gathers
     // band 1 while band 0 is on the bus, and scatters band 0 of the result while band 1 arrives.  720p pair, host to host:
     // 0.363 ms with one copy per plane and row-by-row gathers, 0.347 with one band, 0.325 with two, 0.375 with four (every
-    // further async copy costs more in the runtime than its overlap hides; RTDM_HOST_BANDS=1..4).  Rows that are contiguous
-    // in the caller's plane move as one memcpy.
+    // further async copy costs more in the runtime than its overlap hides).  Rows that are contiguous in the caller's plane
+    // move as one memcpy.
     const size_t Wsd = (size_t)((width + 7) & ~7);
     if (page_locked(left) && page_locked(right) && page_locked(disp)) {
         // the caller's planes are page-locked: DMA straight from and to them, no gathers on the host
@@ -725,7 +641,7 @@ int rtdm_bm_compute(rtdm_bm* bm, const uint8_t* left, size_t left_pitch, const u
         HIPC(hipMemcpy2DAsync(bm->dInR, dpitch, right, right_pitch, (size_t)width, height, hipMemcpyHostToDevice, s));
         Plane8 Ld{bm->dInL, dpitch, dframe}, Rd{bm->dInR, dpitch, dframe};
         Plane16W Od{bm->dOut, Wsd, Wsd * (size_t)height};
-        rc = run_chunk(bm, bm->lane[0], 1, Ld, Rd, width, height, Od, s);
+        rc = run_chunk(bm, 1, Ld, Rd, width, height, Od, s);
         if (rc) return rc;
         HIPC(hipMemcpy2DAsync(disp, disp_pitch, bm->dOut, Wsd * sizeof(int16_t), (size_t)width * sizeof(int16_t), height, hipMemcpyDeviceToHost, s));
         HIPC(hipStreamSynchronize(s));
@@ -735,8 +651,7 @@ int rtdm_bm_compute(rtdm_bm* bm, const uint8_t* left, size_t left_pitch, const u
     uint8_t* hL = bm->hStage;
     uint8_t* hR = hL + dframe;
     int16_t* hD = (int16_t*)(bm->hStage + 2 * bm->ppitch * (size_t)bm->maxH);
-    static const int bands = [] { const char* e = getenv("RTDM_HOST_BANDS"); return e ? std::max(1, std::min(4, atoi(e))) : 2; }();
-    const int nb = height >= 256 ? bands : 1, bh = (height + nb - 1) / nb;
+    const int nb = height >= 256 ? 2 : 1, bh = (height + nb - 1) / nb;
     const auto gather = [&](uint8_t* dst, const uint8_t* src, size_t spitch, int y0, int y1) {
         if (spitch == dpitch) { memcpy(dst + (size_t)y0 * dpitch, src + (size_t)y0 * spitch, (size_t)(y1 - y0 - 1) * dpitch + (size_t)width); return; }
         for (int y = y0; y < y1; ++y) memcpy(dst + (size_t)y * dpitch, src + (size_t)y * spitch, (size_t)width);
@@ -750,9 +665,9 @@ int rtdm_bm_compute(rtdm_bm* bm, const uint8_t* left, size_t left_pitch, const u
         HIPC(hipMemcpyAsync(bm->dInR + (size_t)y0 * dpitch, hR + (size_t)y0 * dpitch, (size_t)(y1 - y0) * dpitch, hipMemcpyHostToDevice, s));
     }
     Plane8 L{bm->dInL, dpitch, dframe}, R{bm->dInR, dpitch, dframe};
-    const size_t Ws = (size_t)((width + 7) & ~7);                      // the lane's internal plane (see run_chunk)
+    const size_t Ws = (size_t)((width + 7) & ~7);                      // the handle's internal plane (see run_chunk)
     Plane16W O{bm->dOut, Ws, Ws * (size_t)height};
-    rc = run_chunk(bm, bm->lane[0], 1, L, R, width, height, O, s);
+    rc = run_chunk(bm, 1, L, R, width, height, O, s);
     if (rc) return rc;
     int nbo = 0;
     for (int b = 0; b < nb; ++b, ++nbo) {
@@ -986,9 +901,9 @@ int rtdm_bm_compute_depth(rtdm_bm* bm, const uint8_t* left, size_t left_pitch, c
     HIPC(hipMemcpyAsync(bm->dInR, hR, dframe, hipMemcpyHostToDevice, s));
     HIPC(hipMemcpyAsync(bm->dMask, hM, (size_t)width * height, hipMemcpyHostToDevice, s));
     Plane8 L{bm->dInL, dpitch, dframe}, R{bm->dInR, dpitch, dframe};
-    const size_t Ws = (size_t)((width + 7) & ~7);                      // the lane's internal plane (see run_chunk)
+    const size_t Ws = (size_t)((width + 7) & ~7);                      // the handle's internal plane (see run_chunk)
     Plane16W O{bm->dOut, Ws, Ws * (size_t)height};
-    rc = run_chunk(bm, bm->lane[0], 1, L, R, width, height, O, s);
+    rc = run_chunk(bm, 1, L, R, width, height, O, s);
     if (rc) return rc;
     DepthQ q; std::copy(Q, Q + 16, q.q);
     launch_depth_stats(bm->dOut, Ws, width, height, q, bm->dMask, (size_t)width, flat, nregions, bm->maxH,
@@ -1130,6 +1045,7 @@ int rtdm_sgm_create(const rtdm_sgm_params* params, int max_width, int max_height
     if (e == hipSuccess) e = hipMalloc((void**)&sg->b.ring, sg->b.ring_words * sizeof(unsigned long long));
     if (e == hipSuccess) e = hipMemset(sg->b.ring, 0, sg->b.ring_words * sizeof(unsigned long long));
     if (e == hipSuccess) e = hipHostMalloc((void**)&sg->b.abortf, sizeof(int32_t), hipHostMallocMapped);
+    // (C, S and S2 are whole allocations, so at least 256-byte aligned: the path passes' packed loads and stores need 16 bytes)
     if (e == hipSuccess && !wide && hipMalloc((void**)&sg->b.S2, vol * 2) != hipSuccess) { (void)hipGetLastError(); sg->b.S2 = nullptr; }   // (optional: without it the horizontal passes run one after the other)
     if (e == hipSuccess) *sg->b.abortf = 0;
     sg->b.epoch = &sg->sweep_epoch; sg->b.sweep_cap = sg->sweep_cap;
@@ -1421,13 +1337,13 @@ int rtdm_rectify_gray_device(rtdm_rectify* rc, int n, const uint8_t* d_rgb_left,
 static int rgb_chunks(rtdm_bm* bm, rtdm_rectify* rc, int n, const uint8_t* dl, const uint8_t* dr, Plane16W out, hipStream_t s)
 {
     const size_t fbytes = (size_t)rc->W * rc->H * 3, gframe = rc->gpitch * rc->rh;
-    const int chunk = std::min(bm->laneB, rc->maxB);
+    const int chunk = std::min(bm->maxB, rc->maxB);
     for (int i0 = 0; i0 < n; i0 += chunk) {
         const int m = std::min(chunk, n - i0);
         rectify_gray_launch(rc, dl + (size_t)i0 * fbytes, dr + (size_t)i0 * fbytes, m,
                             Plane8W{rc->dGray[0], rc->gpitch, gframe}, Plane8W{rc->dGray[1], rc->gpitch, gframe}, s);
         HIPC(hipGetLastError());
-        const int st = run_chunk(bm, bm->lane[0], m, Plane8{rc->dGray[0], rc->gpitch, gframe}, Plane8{rc->dGray[1], rc->gpitch, gframe},
+        const int st = run_chunk(bm, m, Plane8{rc->dGray[0], rc->gpitch, gframe}, Plane8{rc->dGray[1], rc->gpitch, gframe},
                                  rc->rw, rc->rh, Plane16W{out.base + (size_t)i0 * out.frame_e, out.pitch_e, out.frame_e}, s);
         if (st) return st;
     }
@@ -1460,7 +1376,7 @@ int rtdm_bm_compute_rgb(rtdm_bm* bm, rtdm_rectify* rc, const uint8_t* rgb_left, 
     hipStream_t s = bm->stream;
     st = rectify_upload(rc, rgb_left, left_pitch, rgb_right, right_pitch, s);
     if (st) return st;
-    const size_t Ws = (size_t)((rc->rw + 7) & ~7);                     // the lane's internal plane (see run_chunk)
+    const size_t Ws = (size_t)((rc->rw + 7) & ~7);                     // the handle's internal plane (see run_chunk)
     st = rgb_chunks(bm, rc, 1, rc->dRgb[0], rc->dRgb[1], Plane16W{bm->dOut, Ws, Ws * (size_t)rc->rh}, s);
     if (st) return st;
     int16_t* hD = (int16_t*)(bm->hStage + 2 * bm->ppitch * (size_t)bm->maxH);
@@ -1618,7 +1534,7 @@ int rtdm_estimate_frame(rtdm_bm* bm, rtdm_rectify* rc, rtdm_objects* ob, const u
     st = rtdm_bm_set_roi(bm, 1, roi.x, roi.y, roi.width, roi.height);
     if (st) return st;
     const size_t Ws = (size_t)((W + 7) & ~7);
-    st = run_chunk(bm, bm->lane[0], 1, Plane8{rc->dGray[0], rc->gpitch, gframe}, Plane8{rc->dGray[1], rc->gpitch, gframe}, W, H,
+    st = run_chunk(bm, 1, Plane8{rc->dGray[0], rc->gpitch, gframe}, Plane8{rc->dGray[1], rc->gpitch, gframe}, W, H,
                    Plane16W{bm->dOut, Ws, Ws * (size_t)H}, s);
     if (st) return st;
     // estimator.cpp:75-77

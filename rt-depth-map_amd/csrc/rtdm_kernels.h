@@ -10,9 +10,10 @@
 
 namespace rtdm {
 
-// Process-wide state shared BETWEEN handles (two handles may be driven from two host threads): environment switches are
-// read through env_int() into a function-local `static const` (C++11 initialises those exactly once, thread-safely), and
-// "once per device" actions go through OncePerDevice.  Nothing else in the launch paths is static and mutable.
+// Process-wide state shared BETWEEN handles (two handles may be driven from two host threads): environment switches (test
+// hooks that force a form the library also runs on its own, and measurement knobs) are read through
+// env_int() into a function-local `static const` (C++11 initialises those exactly once, thread-safely), and "once per
+// device" actions go through OncePerDevice.  Nothing else in the launch paths is static and mutable.
 inline int env_int(const char* name, int dflt)
 {
     const char* e = getenv(name);
@@ -136,15 +137,14 @@ int launch_lrcheck(Plane16W disp, const void* cost, const BMGeom& g, int disp12M
 // K4: speckle filter (connected components under |a-b| <= maxDiff, size <= maxSize removed).
 // label/size/runs/headmap: n*W*H elements each, rowcnt: n*H.  init_done: rows [y_lo,y_hi) were
 // initialised by the caller's row kernel (rowcnt zeroed beforehand) and every other row is entirely
-// `newVal`; premerged_rows > 1: that kernel also merged the row pairs inside blocks of that many rows
-// (lrcheck_rows_per_block() for launch_lrcheck).
+// `newVal`; premerged_rows > 1 (compact_heads only): that kernel also merged the row pairs inside blocks of that many rows
+// (launch_lrcheck's return value).
 void launch_speckle(Plane16W disp, int32_t* label, int32_t* size, uint32_t* runs, int32_t* rowcnt, int16_t* headmap,
                     int W, int Ws, int H, int n, int newVal, int maxSize, int maxDiff, bool init_done, int premerged_rows,
                     int y_lo, int y_hi, hipStream_t stream, bool compact_heads = false);
 // Ws = row stride of label/size/runs/headmap (>= W)
 // n frames of W x H int16: src -> dst (any pitches)
 void launch_copy16(Plane16W src, Plane16W dst, int W, int H, int n, hipStream_t stream);
-int lrcheck_rows_per_block();
 
 // K5: erode / dilate / dilate / erode with the 10x10 ellipse; tmp = n*W*H bytes scratch.
 void launch_morph_open_close(Plane8 in, Plane8W out, uint8_t* tmp0, uint8_t* tmp1, int W, int H,
@@ -182,8 +182,8 @@ int sgm_wide_mode();
 // cost_limit > 0: block costs above it set *b.ovf (the caller reads it back: rtdm_api.hip).  cn: 1 (gray) or 3 (interleaved
 // colour, reads b.cl / b.cr); ftz: R1's ftzero = max(preFilterCap, 15) | 1, at most 127.  Where a pixel cost can pass 255
 // (sgm_cost16_needed: colour, ftz >= 97, or rtdm_debug_sgm_cost16) the cost stage runs on u16 pixel costs.
-// Returns the name of the path-pass form the call ran ("sweep", "half", "wave", "block", "wide_w1", "wide_w4").  D > 256 (or a
-// forced wide mode) runs the wide pass for every direction, whatever the A/B environment switches say.
+// Returns the name of the path-pass form the call ran ("sweep", "half", "wide_w1", "wide_w4").  D > 256 (or a forced wide
+// mode) runs the wide pass for every direction.
 const char* launch_sgm(Plane8 L, Plane8 R, Plane16W disp, const SGMGeom& g, const SGMBuffers& b, int blockSize, int P1, int P2,
                        int uniq, int disp12MaxDiff, int speckleWindowSize, int speckleRange, int paths, int n, hipStream_t stream,
                        int cost_limit = 0, int cn = 1, int ftz = 15);

@@ -217,7 +217,7 @@ class HIPSemiGlobalMatcher:
 
     @property
     def path_variant(self):
-        """the path-pass form of the last call: "sweep", "half", "wave", "block", "wide_w1", "wide_w4" -- rtdm_sgm_path_variant"""
+        """the path-pass form of the last call: "sweep", "half", "wide_w1", "wide_w4" -- rtdm_sgm_path_variant"""
         return B.lib().rtdm_sgm_path_variant(self._h).decode()
 
     def compute_device(self, d_left, d_right, d_disp, stream=None):

@@ -247,7 +247,7 @@ print("ok")
 '''
 
 
-@pytest.mark.parametrize("var", ["RTDM_SGM_WAVE_PATHS", "RTDM_SGM_HALF", "RTDM_SGM_FUSE_SELECT", "RTDM_SGM_SWEEP", "RTDM_SGM_DUAL"])
+@pytest.mark.parametrize("var", ["RTDM_SGM_SWEEP", "RTDM_SGM_DUAL"])
 def test_ab_switches_leave_wide_lines_alone(var):
     env = dict(os.environ, **{var: "0"})
     p = subprocess.run(["timeout", "-k", "10", "600", sys.executable, "-c", _AB_CASE % (ROOT, os.path.join(ROOT, "tests"))],
