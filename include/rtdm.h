@@ -297,6 +297,65 @@ int rtdm_estimate_frame(rtdm_bm* bm, rtdm_rectify* rc, rtdm_objects* ob, const u
                         int min_area, int zero_border, double calibration_unit, rtdm_region* boxes, double* mean_cm,
                         int* counts, int max_boxes, int* nboxes, int16_t* disp, size_t disp_pitch);
 
+/* ---- the step after the matcher that the reference keeps switched off: the disparity WLS post-filter -------------------
+ * ENABLE_POST_FILTER (estimator.cpp:57-70, 106-109; include/estimator.h:32,116) -- cv::ximgproc's createRightMatcher,
+ * createDisparityWLSFilter, setLambda(8000), setSigmaColor(1.5) and filter(left_disp, left_rect, filtered, right_disp).
+ * The rules W1-W8 it follows are restated in DESIGN.md section 4.9 (from memory: parity with the library is unpinned).
+ * The result is FGS(C dL) / FGS(C): C is a confidence in {0, 255} from a left-right check and two discontinuity maps, FGS
+ * a fast global smoother guided by the left view (three horizontal + vertical passes of tridiagonal solves, fp32). */
+typedef struct rtdm_wls_params {
+    double lambda;              /* >= 0; 8000 (setLambda) */
+    double sigma_color;         /* > 0; 1.5 (setSigmaColor) */
+    int lrc_thresh;             /* T >= 0, x16 units; 24 */
+    int depth_discontinuity_radius;   /* r >= 0; ceil(0.33 w) from a StereoBM, ceil(0.5 w) from a StereoSGBM */
+    int min_disparity;          /* of the LEFT matcher: its invalid value is (min_disparity - 1) * 16 */
+    int num_disparities;        /* of the left matcher: the right matcher's minD is -(min_disparity + num_disparities) + 1 */
+    int roi_left, roi_right, roi_top, roi_bottom;   /* >= 0: the valid ROI is the frame minus these (W2) */
+    int num_iter;               /* 1 .. 16; 3 */
+    double attenuation;         /* (0, 1]; 0.25: lambda of pass t + 1 = lambda of pass t * attenuation */
+    int use_confidence;         /* 1: the filter above; 0: ximgproc's generic filter, FGS(dL) alone (no right map) */
+} rtdm_wls_params;
+typedef struct rtdm_wls rtdm_wls;
+/* W2: the parameters createDisparityWLSFilter derives from a left StereoBM / StereoSGBM (common: lambda 8000, sigma 1.5,
+ * T 24, 3 iterations, attenuation 0.25, use_confidence 1).  RTDM_ERR_NULL / RTDM_OK; nothing is validated here. */
+int rtdm_wls_params_for_bm(const rtdm_bm_params* left, rtdm_wls_params* out);
+int rtdm_wls_params_for_sgm(const rtdm_sgm_params* left, rtdm_wls_params* out);
+/* W1: the parameters of createRightMatcher: the same matcher with minDisparity -(minD + numD) + 1, no texture / uniqueness /
+ * speckle filtering and disp12MaxDiff 1000000; it is called as compute(right, left).  The StereoSGBM's preFilterCap is not part
+ * of rtdm_sgm_params (rtdm_sgm_set_prefilter_cap sets it): the caller copies it to the right handle (the adapters do). */
+int rtdm_bm_right_params(const rtdm_bm_params* left, rtdm_bm_params* right);
+int rtdm_sgm_right_params(const rtdm_sgm_params* left, rtdm_sgm_params* right);
+/* Parameters are validated before any device use: RTDM_ERR_BAD_PARAM for lambda < 0, sigma <= 0, T < 0, r < 0, a negative
+ * offset, num_iter outside 1..16 or attenuation outside (0, 1].  max_width > 4096 or max_height > 4096: RTDM_ERR_UNSUPPORTED
+ * (a row or column segment is solved by one wave).  set_params synchronises the device when sigma changes (the weight table
+ * is rebuilt). */
+int rtdm_wls_create(const rtdm_wls_params* params, int max_width, int max_height, int max_batch, int device, rtdm_wls** out);
+void rtdm_wls_destroy(rtdm_wls* wls);
+int rtdm_wls_set_params(rtdm_wls* wls, const rtdm_wls_params* params);
+int rtdm_wls_get_params(const rtdm_wls* wls, rtdm_wls_params* out);
+/* Host planes, pitches in bytes.  disp_left / disp_right: the x16 maps of the left and the right matcher (disp_right may be
+ * NULL when use_confidence is 0); guide: the left view, 8-bit, channels 1 or 3 (interleaved).  out: int16 x16 map, invalid
+ * value (min_disparity - 1) * 16 outside the valid ROI and where FGS(C) is 0.  conf (optional): the confidence C as float
+ * (0 outside the ROI, and everywhere when use_confidence is 0).  filtered (optional): FGS(C dL) / FGS(C) as float before
+ * rounding (the invalid value where out has it).  Synchronous. */
+int rtdm_wls_filter(rtdm_wls* wls, const int16_t* disp_left, size_t left_pitch, const int16_t* disp_right, size_t right_pitch,
+                    const uint8_t* guide, size_t guide_pitch, int channels, int width, int height, int16_t* out,
+                    size_t out_pitch, float* conf, size_t conf_pitch, float* filtered, size_t filtered_pitch);
+/* n device frames (frame i of a plane at base + i * frame_stride bytes), enqueued on hip_stream, NOT synchronised; n may
+ * exceed max_batch (chunks). */
+int rtdm_wls_filter_device(rtdm_wls* wls, int n, const int16_t* d_left, size_t left_pitch, size_t left_frame_stride,
+                           const int16_t* d_right, size_t right_pitch, size_t right_frame_stride, const uint8_t* d_guide,
+                           size_t guide_pitch, size_t guide_frame_stride, int channels, int width, int height,
+                           int16_t* d_out, size_t out_pitch, size_t out_frame_stride, float* d_conf, size_t conf_pitch,
+                           size_t conf_frame_stride, float* d_filtered, size_t filtered_pitch, size_t filtered_frame_stride,
+                           void* hip_stream);
+/* estimator.cpp:56-61 in one call: left_bm->compute(left, right), right_bm->compute(right, left) and the filter guided by the
+ * left view.  The raw maps and the confidence stay in HBM; raw_left (optional) receives the left matcher's map.  right_bm is
+ * a handle made with rtdm_bm_right_params; all three handles live on the same device.  Synchronous. */
+int rtdm_bm_compute_filtered(rtdm_bm* left_bm, rtdm_bm* right_bm, rtdm_wls* wls, const uint8_t* left, size_t left_pitch,
+                             const uint8_t* right, size_t right_pitch, int width, int height, int16_t* out, size_t out_pitch,
+                             int16_t* raw_left, size_t raw_left_pitch);
+
 /* ---- synthetic rectified-pair stream (stands in for stream/ + decoder/, which are out of
  * scope): frame f of the stream uses seed + f; bit-identical to rt-depth-map_amd/synth.py. */
 int rtdm_synth_pairs_device(uint64_t seed, int first_frame, int n, int width, int height,

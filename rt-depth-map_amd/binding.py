@@ -45,6 +45,12 @@ class BMParams(C.Structure):
         "uniquenessRatio", "speckleWindowSize", "speckleRange", "disp12MaxDiff", "legacy_right_clamp")]
 
 
+class WLSParams(C.Structure):
+    _fields_ = [("lambda_", C.c_double), ("sigma_color", C.c_double)] + [(n, C.c_int) for n in (
+        "lrc_thresh", "depth_discontinuity_radius", "min_disparity", "num_disparities", "roi_left", "roi_right", "roi_top",
+        "roi_bottom", "num_iter")] + [("attenuation", C.c_double), ("use_confidence", C.c_int)]
+
+
 _lib = None
 
 
@@ -115,6 +121,18 @@ def lib():
         "rtdm_estimate_frame": (C.c_int, [vp, vp, vp, u8p, sz, u8p, sz, C.POINTER(C.c_double), C.POINTER(HsvRange), C.c_int, C.c_int,
                                           C.c_double, C.POINTER(Region), C.POINTER(C.c_double), C.POINTER(C.c_int), C.c_int,
                                           C.POINTER(C.c_int), i16p, sz]),
+        "rtdm_wls_params_for_bm": (C.c_int, [C.POINTER(BMParams), C.POINTER(WLSParams)]),
+        "rtdm_wls_params_for_sgm": (C.c_int, [C.POINTER(SGMParams), C.POINTER(WLSParams)]),
+        "rtdm_bm_right_params": (C.c_int, [C.POINTER(BMParams), C.POINTER(BMParams)]),
+        "rtdm_sgm_right_params": (C.c_int, [C.POINTER(SGMParams), C.POINTER(SGMParams)]),
+        "rtdm_wls_create": (C.c_int, [C.POINTER(WLSParams), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]),
+        "rtdm_wls_destroy": (None, [vp]),
+        "rtdm_wls_set_params": (C.c_int, [vp, C.POINTER(WLSParams)]),
+        "rtdm_wls_get_params": (C.c_int, [vp, C.POINTER(WLSParams)]),
+        "rtdm_wls_filter": (C.c_int, [vp, i16p, sz, i16p, sz, u8p, sz, C.c_int, C.c_int, C.c_int, i16p, sz, vp, sz, vp, sz]),
+        "rtdm_wls_filter_device": (C.c_int, [vp, C.c_int, i16p, sz, sz, i16p, sz, sz, u8p, sz, sz, C.c_int, C.c_int, C.c_int,
+                                             i16p, sz, sz, vp, sz, sz, vp, sz, sz, vp]),
+        "rtdm_bm_compute_filtered": (C.c_int, [vp, vp, vp, u8p, sz, u8p, sz, C.c_int, C.c_int, i16p, sz, i16p, sz]),
         "rtdm_synth_pairs_device": (C.c_int, [C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, u8p, u8p,
                                               sz, sz, C.c_int, vp]),
     }
@@ -135,7 +153,9 @@ EXPORTS = ("rtdm_strerror rtdm_last_hip_error rtdm_abi_version rtdm_device_count
            "rtdm_sgm_set_prefilter_cap rtdm_sgm_compute_cn rtdm_sgm_compute_device_cn rtdm_debug_sgm_cost16 rtdm_bm_compute_depth rtdm_depth_stats_device "
            "rtdm_rectify_create rtdm_rectify_destroy rtdm_rectify_gray rtdm_rectify_rgb rtdm_rectify_gray_device "
            "rtdm_bm_compute_rgb rtdm_bm_compute_rgb_device rtdm_objects_create rtdm_objects_destroy rtdm_objects_detect "
-           "rtdm_estimate_frame").split()
+           "rtdm_estimate_frame rtdm_wls_params_for_bm rtdm_wls_params_for_sgm rtdm_bm_right_params rtdm_sgm_right_params "
+           "rtdm_wls_create rtdm_wls_destroy rtdm_wls_set_params rtdm_wls_get_params rtdm_wls_filter rtdm_wls_filter_device "
+           "rtdm_bm_compute_filtered").split()
 
 
 def check(status, where):

@@ -215,6 +215,31 @@ size_t cc_scratch_bytes(int W, int H, int max_records);
 void launch_cc_boxes(const uint8_t* mask, size_t mpitch, int W, int H, int zero_border, void* scratch, int max_records,
                      int** d_count, int** d_records, hipStream_t stream);
 
+// Disparity WLS post-filter (k_wls.hip, rules W1-W8 in DESIGN.md section 4.9).  Internal planes (F, weights, confidence,
+// window statistics) share one layout: element (f, y, x) at f * frame + y * pitch + x.
+struct WlsDisp { const int16_t* base; size_t pitch_e, frame_e; };
+struct WlsGuide { const uint8_t* base; size_t pitch, frame; int cn; };     // bytes
+struct WlsGeom { int x0, x1, y0, y1; };                                      // valid ROI [x0,x1) x [y0,y1)
+struct __align__(8) WlsMM { int16_t mn, mx, cnt, pad; };                     // W3 row window: min, max, valid count
+struct WlsOut {                                                              // strides in elements; filt / conf may be null
+    int16_t* out; size_t out_pitch, out_frame;
+    float* filt; size_t filt_pitch, filt_frame;
+    float* conf; size_t conf_pitch, conf_frame;
+};
+#define RTDM_WLS_MAX_ITER 16
+struct WlsLaunch {
+    WlsDisp dl, dr;                // dr unused when use_conf == 0
+    WlsGuide guide;
+    WlsOut out;
+    WlsGeom g;
+    int W, H, r, T, invL, invR, use_conf, num_iter;
+    float lambda[RTDM_WLS_MAX_ITER];
+    const float* lut;
+    size_t pitch, frame;
+    float2* F; float *wh, *wv; uint8_t* conf; WlsMM *mmL, *mmR;
+};
+void launch_wls(const WlsLaunch& L, int n, hipStream_t stream);
+
 // Synthetic stream generator (bit-identical to synth.py).
 void launch_synth(uint64_t seed, int first_frame, int n, int W, int H, int D, Plane8W L, Plane8W R,
                   void* param_scratch, hipStream_t stream);

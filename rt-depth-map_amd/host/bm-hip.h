@@ -23,6 +23,9 @@ public:
 	void setROI1(cv::Rect roi1);
 	void setROI2(cv::Rect roi2);
 	int compute(cv::InputArray left, cv::InputArray right, cv::OutputArray out);
+	/* takes ownership of a core (createRightMatcher, wls-hip.cpp) */
+	explicit HIPMatcher(rtdm::HIPMatcherCore* core) : core(core) {}
+	rtdm::HIPMatcherCore* getCore() { return core; }
 private:
 	rtdm::HIPMatcherCore* core;
 };

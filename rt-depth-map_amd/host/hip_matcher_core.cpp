@@ -20,6 +20,7 @@ HIPMatcherCore::HIPMatcherCore(const Rect& roi1, const Rect& roi2, int preFilter
     params_.speckleRange = speckleRange;
     params_.disp12MaxDiff = disp12MaxDiff;
     params_.legacy_right_clamp = legacyRightClamp ? 1 : 0;
+    maxWidth_ = maxWidth; maxHeight_ = maxHeight; device_ = device;
     status_ = rtdm_bm_create(&params_, maxWidth, maxHeight, maxBatch, device, &bm_);
     if (status_ != RTDM_OK)
         std::fprintf(stderr, "HIPMatcher: %s%s%s\n", rtdm_strerror(status_),
@@ -127,6 +128,7 @@ HIPSGMCore::HIPSGMCore(int blockSize, int minDisparity, int numOfDisparities, in
     rtdm_sgm_default_params(&p, numOfDisparities, blockSize);     // P1 = 8*3*5*5, P2 = 32*3*5*5 (sgbm-sw.cpp:17-18)
     p.minDisparity = minDisparity; p.uniquenessRatio = uniquenessRatio; p.speckleWindowSize = speckleWindowSize;
     p.speckleRange = speckleRange; p.disp12MaxDiff = disp12MaxDiff; p.paths = paths;
+    params_ = p; maxWidth_ = maxWidth; maxHeight_ = maxHeight; device_ = device;
     status_ = rtdm_sgm_create(&p, maxWidth, maxHeight, 1, device, &sg_);
     if (status_ != RTDM_OK) std::fprintf(stderr, "HIPSemiGlobalMatcher: %s\n", rtdm_strerror(status_));
 }
@@ -148,7 +150,86 @@ int HIPSGMCore::compute(int channels, const uint8_t* left, size_t leftStep, cons
 int HIPSGMCore::setPreFilterCap(int preFilterCap)
 {
     if (!sg_) return status_ != RTDM_OK ? status_ : RTDM_ERR_NO_DEVICE;
-    return rtdm_sgm_set_prefilter_cap(sg_, preFilterCap);
+    const int rc = rtdm_sgm_set_prefilter_cap(sg_, preFilterCap);
+    if (rc == RTDM_OK) preFilterCap_ = preFilterCap;
+    return rc;
+}
+
+HIPWLSCore::HIPWLSCore(const rtdm_wls_params& params, int maxWidth, int maxHeight, int device) : params_(params)
+{
+    create(maxWidth, maxHeight, device);
+}
+HIPWLSCore::HIPWLSCore(const HIPMatcherCore& m)
+{
+    rtdm_wls_params_for_bm(&m.params(), &params_);
+    create(m.maxWidth(), m.maxHeight(), m.device());
+}
+HIPWLSCore::HIPWLSCore(const HIPSGMCore& m)
+{
+    rtdm_wls_params_for_sgm(&m.params(), &params_);
+    create(m.maxWidth(), m.maxHeight(), m.device());
+}
+void HIPWLSCore::create(int maxWidth, int maxHeight, int device)
+{
+    status_ = rtdm_wls_create(&params_, maxWidth, maxHeight, 1, device, &wls_);
+    if (status_ == RTDM_OK) conf_ = new float[(size_t)maxWidth * maxHeight]();
+    else std::fprintf(stderr, "HIPDisparityWLSFilter: %s\n", rtdm_strerror(status_));
+}
+HIPWLSCore::~HIPWLSCore() { rtdm_wls_destroy(wls_); delete[] conf_; }
+int HIPWLSCore::set(const rtdm_wls_params& p)
+{
+    if (!wls_) return status_ != RTDM_OK ? status_ : RTDM_ERR_NO_DEVICE;
+    status_ = rtdm_wls_set_params(wls_, &p);
+    if (status_ == RTDM_OK) params_ = p;
+    return status_;
+}
+int HIPWLSCore::setLambda(double v) { rtdm_wls_params p = params_; p.lambda = v; return set(p); }
+int HIPWLSCore::setSigmaColor(double v) { rtdm_wls_params p = params_; p.sigma_color = v; return set(p); }
+int HIPWLSCore::setLRCthresh(int v) { rtdm_wls_params p = params_; p.lrc_thresh = v; return set(p); }
+int HIPWLSCore::setDepthDiscontinuityRadius(int v) { rtdm_wls_params p = params_; p.depth_discontinuity_radius = v; return set(p); }
+int HIPWLSCore::filter(const int16_t* left, size_t leftStep, const uint8_t* guide, size_t guideStep, int channels, int rows,
+                       int cols, int16_t* out, size_t outStep, const int16_t* right, size_t rightStep, float* filtered,
+                       size_t filteredStep)
+{
+    if (!wls_) return status_ != RTDM_OK ? status_ : RTDM_ERR_NO_DEVICE;
+    status_ = rtdm_wls_filter(wls_, left, leftStep, right, rightStep, guide, guideStep, channels, cols, rows, out, outStep,
+                              conf_, (size_t)cols * sizeof(float), filtered, filteredStep);
+    return status_;
+}
+Rect HIPWLSCore::roi(int rows, int cols) const
+{
+    Rect r;
+    const int w = cols - params_.roi_left - params_.roi_right, h = rows - params_.roi_top - params_.roi_bottom;
+    if (w > 0 && h > 0) { r.x = params_.roi_left; r.y = params_.roi_top; r.width = w; r.height = h; }
+    return r;
+}
+int HIPWLSCore::computeFiltered(HIPMatcherCore& left, HIPMatcherCore& right, const uint8_t* l, size_t lStep, const uint8_t* r,
+                                size_t rStep, int rows, int cols, int16_t* out, size_t outStep, int16_t* rawLeft,
+                                size_t rawLeftStep)
+{
+    if (!wls_) return status_ != RTDM_OK ? status_ : RTDM_ERR_NO_DEVICE;
+    status_ = rtdm_bm_compute_filtered(left.handle(), right.handle(), wls_, l, lStep, r, rStep, cols, rows, out, outStep,
+                                       rawLeft, rawLeftStep);
+    return status_;
+}
+
+HIPMatcherCore* createRightMatcher(const HIPMatcherCore& left)
+{
+    rtdm_bm_params p;
+    rtdm_bm_right_params(&left.params(), &p);
+    Rect none;
+    return new HIPMatcherCore(none, none, p.preFilterCap, p.blockSize, p.minDisparity, p.textureThreshold, p.numDisparities,
+                              p.numDisparities, p.uniquenessRatio, p.speckleWindowSize, p.speckleRange, p.disp12MaxDiff,
+                              left.maxWidth(), left.maxHeight(), 1, left.device(), p.legacy_right_clamp != 0);
+}
+HIPSGMCore* createRightMatcher(const HIPSGMCore& left)
+{
+    rtdm_sgm_params p;
+    rtdm_sgm_right_params(&left.params(), &p);
+    HIPSGMCore* m = new HIPSGMCore(p.blockSize, p.minDisparity, p.numDisparities, p.uniquenessRatio, p.speckleWindowSize,
+                                   p.speckleRange, p.disp12MaxDiff, left.maxWidth(), left.maxHeight(), left.device(), p.paths);
+    if (left.preFilterCap()) m->setPreFilterCap(left.preFilterCap());     // not part of rtdm_sgm_params (W1)
+    return m;
 }
 
 HIPMorphCore::HIPMorphCore(int w, int h, int bpp, int device) : width_(w), height_(h), bpp_(bpp)

@@ -53,12 +53,17 @@ public:
     int status() const { return status_; }           // result of construction / last call
     const char* statusText() const { return rtdm_strerror(status_); }
     int filteredValue() const { return (params_.minDisparity - 1) * 16; }
+    const rtdm_bm_params& params() const { return params_; }
+    int maxWidth() const { return maxWidth_; }
+    int maxHeight() const { return maxHeight_; }
+    int device() const { return device_; }
     rtdm_bm* handle() { return bm_; }
 
 private:
     rtdm_bm_params params_;
     rtdm_bm* bm_ = nullptr;
     int status_ = RTDM_OK;
+    int maxWidth_ = 0, maxHeight_ = 0, device_ = 0;
 };
 
 // SWSemiGlobalMatcher counterpart (/root/reference/include/stereo-matcher/sgbm-sw.h:24-37): the same seven
@@ -80,11 +85,65 @@ public:
     // cv::StereoSGBM::setPreFilterCap (0 .. 127), from the next compute on
     int setPreFilterCap(int preFilterCap);
     int status() const { return status_; }
+    const rtdm_sgm_params& params() const { return params_; }
+    int preFilterCap() const { return preFilterCap_; }
+    int maxWidth() const { return maxWidth_; }
+    int maxHeight() const { return maxHeight_; }
+    int device() const { return device_; }
 
 private:
     rtdm_sgm* sg_ = nullptr;
     int status_ = RTDM_OK;
+    rtdm_sgm_params params_;
+    int preFilterCap_ = 0, maxWidth_ = 0, maxHeight_ = 0, device_ = 0;
 };
+
+// The disparity WLS post-filter (cv::ximgproc::DisparityWLSFilter, the reference's ENABLE_POST_FILTER block,
+// /root/reference/estimator.cpp:57-70): rules W1-W8 of DESIGN.md section 4.9.  Constructed from the left matcher's
+// parameters (createDisparityWLSFilter, W2) or from explicit ones.  filter() has ximgproc's argument order: left map,
+// left view (the guide, 1 or 3 interleaved channels), filtered output, right map (may be null without confidence).
+class HIPWLSCore {
+public:
+    HIPWLSCore(const rtdm_wls_params& params, int maxWidth, int maxHeight, int device = 0);
+    HIPWLSCore(const HIPMatcherCore& leftMatcher);
+    HIPWLSCore(const HIPSGMCore& leftMatcher);
+    ~HIPWLSCore();
+    HIPWLSCore(const HIPWLSCore&) = delete;
+    HIPWLSCore& operator=(const HIPWLSCore&) = delete;
+    int setLambda(double lambda);
+    double getLambda() const { return params_.lambda; }
+    int setSigmaColor(double sigma);
+    double getSigmaColor() const { return params_.sigma_color; }
+    int setLRCthresh(int thresh);
+    int getLRCthresh() const { return params_.lrc_thresh; }
+    int setDepthDiscontinuityRadius(int radius);
+    int getDepthDiscontinuityRadius() const { return params_.depth_discontinuity_radius; }
+    // steps in bytes; filtered (optional) receives the float map before rounding.  The confidence of the call stays
+    // readable through confidenceMap() (rows x cols floats, 0 / 255) until the next call.
+    int filter(const int16_t* left, size_t leftStep, const uint8_t* guide, size_t guideStep, int channels, int rows, int cols,
+               int16_t* out, size_t outStep, const int16_t* right, size_t rightStep, float* filtered = nullptr,
+               size_t filteredStep = 0);
+    const float* confidenceMap() const { return conf_; }
+    Rect roi(int rows, int cols) const;     // the valid ROI (W2); empty: all zero
+    // estimator.cpp:56-61 in one call (rtdm_bm_compute_filtered); right = the core createRightMatcher made
+    int computeFiltered(HIPMatcherCore& left, HIPMatcherCore& right, const uint8_t* l, size_t lStep, const uint8_t* r,
+                        size_t rStep, int rows, int cols, int16_t* out, size_t outStep, int16_t* rawLeft = nullptr,
+                        size_t rawLeftStep = 0);
+    int status() const { return status_; }
+    rtdm_wls* handle() { return wls_; }
+
+private:
+    void create(int maxWidth, int maxHeight, int device);
+    int set(const rtdm_wls_params& p);
+    rtdm_wls_params params_;
+    rtdm_wls* wls_ = nullptr;
+    float* conf_ = nullptr;
+    int status_ = RTDM_OK;
+};
+
+// createRightMatcher (W1): new cores that match right against left (compute(right, left)); the caller deletes them
+HIPMatcherCore* createRightMatcher(const HIPMatcherCore& left);
+HIPSGMCore* createRightMatcher(const HIPSGMCore& left);
 
 // The caller's lines in front of the matcher (/root/reference/estimator.cpp:29-39): cvtColor(RGB2GRAY) + remap with
 // the CV_16SC2 maps of main.cpp:95-96 + crop to roif, for both cameras, on the device.  Not behind an interface in

@@ -24,6 +24,9 @@ public:
 	int setPreFilterCap(int preFilterCap) { return core->setPreFilterCap(preFilterCap); }
 	void setROI1(cv::Rect roi1) {}
 	void setROI2(cv::Rect roi2) {}
+	/* takes ownership of a core (createRightMatcher, wls-hip.cpp) */
+	explicit HIPSemiGlobalMatcher(rtdm::HIPSGMCore* core) : core(core) {}
+	rtdm::HIPSGMCore* getCore() { return core; }
 private:
 	rtdm::HIPSGMCore* core;
 };
