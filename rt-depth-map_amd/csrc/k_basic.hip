@@ -670,7 +670,7 @@ __global__ __launch_bounds__(256) void k_spk_merge_rec(int32_t* label, const uin
 // 0.527 -> 0.487 at 640x480.  NIT > 1 (thread constants formed once for NIT row pairs; measured and retired, only NIT = 1 is launched) is SLOWER, with or
 // without the next trip's rows requested a trip ahead (1.51-1.77 ms): 74+ VGPRs instead of 44, and what bounds the kernel is
 // how many short barrier-chained workgroups a CU holds, not its instruction count (also with barriers that do not wait
-// for global memory: 1.79 ms).  Timing-only ablations (LRPK_ABL, profiles/r03_lrcheck_ablation.txt): loading the two planes and
+// for global memory: 1.79 ms).  Timing-only ablations (profiles/r03_lrcheck_ablation.txt): loading the two planes and
 // resetting the keys alone takes 0.59 ms -- 3.8 GB at 6.4 TB/s, the HBM floor; the speckle init costs 0.25 ms, the votes 0.09.  Key slots: key[W] takes the votes nobody may see, key[W + 1] is never written
 // ("no vote").  Needs: costs < 32768 (a slot's cost half is negative only in the empty slot), minD .. minD + D inside
 // int16 / 16, the workgroup's LDS below 64 KB.  Same bytes as k_lrcheck_vec.
@@ -708,9 +708,6 @@ __device__ __forceinline__ unsigned lr_bits8(const uint32_t (&h)[4])
     return __builtin_amdgcn_udot4(g1, 0x80402010u, __builtin_amdgcn_udot4(g0, 0x08040201u, 0u, false), false);
 }
 
-#ifndef LRPK_ABL          // timing-only ablations of k_lrcheck_pk (variant builds, wrong results): 1 no votes, 2 no look-ups, 3 no speckle
-#define LRPK_ABL 0        // init, 4 no run records, 5 no row loads, 6 nothing behind the loads
-#endif
 template <bool SPK, int NIT>
 __global__ __launch_bounds__(512) void k_lrcheck_pk(Plane16W disp, const uint16_t* cost, BMGeom g, int maxDiff16,
                                                     int32_t* label, int32_t* size, uint32_t* runs, int32_t* rowcnt,
@@ -761,11 +758,7 @@ __global__ __launch_bounds__(512) void k_lrcheck_pk(Plane16W disp, const uint16_
         [[maybe_unused]] const uint16_t* crow = cost + ((size_t)f * g.H + y0) * g.Ws + (half ? (uint32_t)g.Ws : 0u);
         uint32_t D[4] = {INVpk, INVpk, INVpk, INVpk}, C[4] = {0, 0, 0, 0};
         if (active) {
-#if LRPK_ABL == 5
-            const uint4 dq = make_uint4(0x00200020u + lane, 0x00300030u, 0x00400040u + it, 0x00200020u), cq = make_uint4(lane, 5, 6, 7);
-#else
             const uint4 dq = *(const uint4*)(row + x0), cq = *(const uint4*)(crow + x0);
-#endif
             D[0] = dq.x; D[1] = dq.y; D[2] = dq.z; D[3] = dq.w; C[0] = cq.x; C[1] = cq.y; C[2] = cq.z; C[3] = cq.w;
             if (x0 + 8 > W) {                                         // ragged last chunk: padding columns do not exist
 #pragma unroll
@@ -778,11 +771,7 @@ __global__ __launch_bounds__(512) void k_lrcheck_pk(Plane16W disp, const uint16_
             ((uint4*)(key + x0))[0] = none; ((uint4*)(key + x0))[1] = none;
         }
         lr_lds_barrier();
-#if LRPK_ABL == 6
-        if (active && (D[0] ^ C[1]) == 0x12345678u) row[x0] = 1;
-        continue;
-#endif
-        uint32_t V[4], Dx[4];                                         // halves: is a disparity (0xffff / 0); d + 0x8000
+        uint32_t V[4], Dx[4];                                        // halves: is a disparity (0xffff / 0); d + 0x8000
         if (active) {
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
@@ -793,12 +782,8 @@ __global__ __launch_bounds__(512) void k_lrcheck_pk(Plane16W disp, const uint16_
                 // (negative cost half) -- no address select; targets outside the row (none inside the vote range) go to key[W]
                 const uint32_t cv = C[k] | ~(V[k] & VOTEM[k]);
                 const uint32_t a = slot_addr(pk_sub(X[k], pk_ashr<4>(pk_add(D[k], 0x00080008u))), TRASH);
-#if LRPK_ABL == 1
-                if ((a ^ cv) == 0x12345678u) key[0] = a;
-#else
                 lr_lds_min(a & 0xffffu, __builtin_amdgcn_perm(cv, Dx[k], 0x05040100u));
                 lr_lds_min(a >> 16, __builtin_amdgcn_perm(cv, Dx[k], 0x07060302u));
-#endif
             }
         }
         lr_lds_barrier();
@@ -809,11 +794,7 @@ __global__ __launch_bounds__(512) void k_lrcheck_pk(Plane16W disp, const uint16_
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const uint32_t a = slot_addr(pk_sub(X[k], pk_ashr<4>(D[k])), NONE);
-#if LRPK_ABL == 2
-                const uint32_t qe = a, qo = ~a;
-#else
                 const uint32_t qe = lr_lds_ld(a & 0xffffu), qo = lr_lds_ld(a >> 16);
-#endif
                 const uint32_t df = pk_sub(__builtin_amdgcn_perm(qo, qe, 0x05040100u), Dx[k]);
                 const uint32_t r = pk_sub(Mpk, pk_max_i(df, pk_sub(0u, df)));
                 bad0[k] = r & ~__builtin_amdgcn_perm(qo, qe, 0x07060302u) & V[k] & VOTEM[k] & KEEPM[k];
@@ -845,7 +826,7 @@ __global__ __launch_bounds__(512) void k_lrcheck_pk(Plane16W disp, const uint16_
         lr_lds_barrier();
         // ---- speckle init of the finished row (as in k_lrcheck_vec) ----
         unsigned im = 0, cb = 0;
-        if (active && LRPK_ABL != 3) {
+        if (active) {
             const int left = x0 > 0 ? (int)fin[x0 - 1] : INV, right = x0 + 8 < W ? (int)fin[x0 + 8] : INV;
             uint32_t iz[4], cl[4];
 #pragma unroll
@@ -877,7 +858,7 @@ __global__ __launch_bounds__(512) void k_lrcheck_pk(Plane16W disp, const uint16_
             const int base = (f * g.H + y) * g.Ws;
             const int hin = (run & 0xffff) - 1, cin = run >> 16;     // head and run count carried in from the left
             ((uint32_t*)headmap)[(size_t)(f * g.H + y) * (g.Ws >> 3) + chunk] = (uint32_t)cin | (hm << 16);
-            while (lm && LRPK_ABL != 4) {                             // one trip per run that ends in this chunk
+            while (lm) {                                              // one trip per run that ends in this chunk
                 const int k = __builtin_ctz(lm);
                 lm &= lm - 1;
                 const unsigned hb = hm & ((2u << k) - 1u);            // heads at or left of the end
@@ -1216,13 +1197,9 @@ __global__ __launch_bounds__(256) void k_spk_merge_strip(Plane16W disp, int32_t*
         d += disp.pitch_e; h += Ws; base += Ws;
     }
     __syncthreads();
-#ifndef MERGE_ABL          // timing-only ablations (variant builds): 1 no unions at all, 2 marks but no unions, 3 no queue either
-#define MERGE_ABL 0
-#endif
-    const int total = MERGE_ABL == 1 || MERGE_ABL == 3 ? 0 : min(qn, QCAP);
+    const int total = min(qn, QCAP);
     for (int i = threadIdx.x; i < total; i += 256) {
         const int a = queue[i].x, b = queue[i].y;
-        if (MERGE_ABL == 2) { spk_large_contact(size, a, b, maxSize); continue; }
         uf_union_contact(label, size, a, b, maxSize);
     }
 }

@@ -20,9 +20,9 @@
 // Selection wants all D values of a pixel in one place.  Two forms (rtdm_select.h):
 //   * transposing (LPP = 2, D <= 32): one v_permlane32_swap per register hands the lower lane both halves of row t and the
 //     upper lane both halves of row t+1; each lane runs the single-lane selection select_disparity_lds;
-//   * GroupSelect (everything else): nothing is transposed.  Each lane writes its slice of a row into the owner's LDS
-//     record and folds it into per-group minima as soon as the row's step is over (the SADs are dead after that), and per
-//     row only three words cross between the lanes: partial key minima, thresholds, partial counts.
+//   * GroupSelectRec (everything else): nothing is transposed.  As soon as a row's step is over (the SADs are dead after
+//     that) each lane writes its slice of the row and the minima of the slice's groups of eight into the owner's LDS record;
+//     nothing crosses between the lanes, and the owner selects from its record alone.
 //
 // Mapping: workgroup = 4 * 64/LPP output columns x `rs` rows of one frame; wave = byte phase phi, lane (p, h) = column
 // x_tile + phi + 4 p.  The four waves never synchronise: each stages ITS byte-shifted copy of the entering rows (64 or 128
@@ -43,47 +43,6 @@
 #include <type_traits>
 #include <utility>
 
-#ifndef RING_ABL          // timing-only ablations (tools/ring_ablate.sh): 1 no selection, 2 no stores, 3 no global loads,
-#define RING_ABL 0        // 4 no quad-SADs, 5 no swaps, 6 no swaps + no selection.  Outputs are wrong for n != 0.
-#endif
-#ifndef RING_LDS_SELECT   // 1: select_disparity_lds (fetches through LDS), 0: select_disparity (v_cndmask tree)
-#define RING_LDS_SELECT 1
-#endif
-#ifndef RING_MINREC       // 0: GroupSelect (lane reductions) also where GroupSelectRec (minima in the owner's record) applies: A/B
-#define RING_MINREC 1
-#endif
-#ifndef RING_W3_LIMIT      // two-lane forms: most ring registers a three-wave form may hold.  (32, 13) sits AT 112 and spills ten dwords
-#define RING_W3_LIMIT 112  // at 168 VGPRs -- and is still 9 % faster than as a two-wave form without (111): profiles/r03_ring_spills.txt
-#endif
-#ifndef RING_STATIC_SLOTS // 1: four staging slots where a trip of the row loop is a multiple of four rows: the slot of every unrolled row step
-#define RING_STATIC_SLOTS 1 // is a compile-time constant and all LDS addresses are base + immediate (3-4 VALU per row less)
-#endif
-#ifndef RING_DIRECT_LOADS // 1: a staged dword is ONE (unaligned) global load at uniform row base + lane offset, stored as it is; 0: two
-#define RING_DIRECT_LOADS 1 // aligned dwords per lane and row, shifted into place by v_alignbyte
-#endif
-#ifndef RING_B64REC       // 1: D = 64 writes / reads its selection records in 8-byte pieces (34-dword stride: four workgroups per CU at (64, 9, 4))
-#define RING_B64REC 1
-#endif
-#ifndef RING_MINREC96     // 1: GroupSelectRec at D = 96 too (records of 240 instead of 208 bytes)
-#define RING_MINREC96 1
-#endif
-#ifndef RING_SPLIT_SELECT // 1: GroupSelect also for the two-lane configurations that default to the transposing selection
-#define RING_SPLIT_SELECT 0 // (D = 16, D = 32 except w = 9: measured 0-8 % slower there, profiles/r02_ring_split_select_ab.txt;
-#endif                      //  tools/ring_split_ab.sh)
-
-#ifdef RING_STAMPS        // diagnostic build only (tools/ring_stamps.sh): where a row pair spends its cycles
-__device__ unsigned long long ring_stamps[8];
-#define RING_STAMP(i) do { unsigned long long t_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) :: "memory"); \
-                           stamp_sum[i] += t_ - stamp_last; stamp_last = t_; } while (0)
-extern "C" void rtdm_debug_ring_stamps(unsigned long long* out, int reset)
-{
-    (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(ring_stamps), sizeof(unsigned long long) * 8);
-    if (reset) { unsigned long long z[8] = {0}; (void)hipMemcpyToSymbol(HIP_SYMBOL(ring_stamps), z, sizeof z); }
-}
-#else
-#define RING_STAMP(i) do { } while (0)
-#endif
-
 namespace rtdm {
 
 struct RingGeom {
@@ -103,36 +62,23 @@ struct RingGeom {
 
 // LPP = lanes per pixel: the D disparities of a pixel are split over LPP lanes of a wave (p + h * 64/LPP, h = 0..LPP-1), and
 // rows are processed in groups of LPP, one owner lane per row for the selection.
-// RPG = rows per group: the lanes with h < RPG own the group's rows; RPG < LPP (GroupSelectRec only: its lanes exchange
-// nothing) halves / quarters the number of selection records a wave needs -- what lets D = 192 and D = 256 (records of 432 /
-// 592 bytes) keep two workgroups per CU -- at the price of a selection that runs with RPG / LPP of its lanes.
-#ifndef RING_RPG96        // A/B (tools/ring_dev.py with `make variant`): rows per group at D = 96, 128, 256
-#define RING_RPG96 4
-#endif
-#ifndef RING_RPG128       // (measured: four rows per group + GroupSelectRec 6-8 % faster than eight + GroupSelect; D = 96 with two
-#define RING_RPG128 4     //  rows and D = 256 with eight are slower than four: profiles/r03_ring_rows_per_group_ab.txt)
-#endif
-#ifndef RING_RPG256
-#define RING_RPG256 4
-#endif
-__host__ __device__ constexpr int ring_rpg(int D, int LPP)
-{ return D == 256 ? RING_RPG256 : D >= 192 ? 4 : D == 128 ? RING_RPG128 : D == 96 ? RING_RPG96 : LPP; }
+// RPG = rows per group: the lanes with h < RPG own the group's rows; RPG < LPP (GroupSelectRec's lanes exchange nothing)
+// halves / quarters the number of selection records a wave needs -- what lets D = 192 and D = 256 (records of 432 / 592
+// bytes) keep two workgroups per CU -- at the price of a selection that runs with RPG / LPP of its lanes.  Four rows per group
+// from D = 96 up: 6-8 % faster at D = 128 than eight rows with a lane-exchange selection, and D = 96 with two rows and D = 256
+// with eight are slower too (profiles/r03_ring_rows_per_group_ab.txt).
+__host__ __device__ constexpr int ring_rpg(int D, int LPP) { return D >= 96 ? 4 : LPP; }
 
 template <int D, int WS, int LPP = 2>
 struct RingCfg {
     static constexpr int RPG = ring_rpg(D, LPP);
-    // selection without transposing the lanes' slices (GroupSelect / GroupSelectRec): always for four and more lanes per pixel;
-    // with two lanes where it measured faster than transposing (tools/ring_split_ab.sh, profiles/r02_ring_split_select_ab.txt)
-    // (round 3 re-measured with GroupSelectRec: D = 32, w = 5 joins (+10 %); the other D = 16 / 32 forms stay within +-1-5 %
-    //  of transposing, profiles/r03_ring_split_select_ab.txt)
-    static constexpr bool SPLIT = LPP != 2 || D >= 48 || (D == 32 && (WS == 9 || WS == 5)) || (RING_SPLIT_SELECT && RING_LDS_SELECT);
-    // the group minima live in the owner's record too and nothing crosses between the lanes (GroupSelectRec).  Not at D = 128
-    // with eight rows per group: 64 records of 304 bytes would leave one workgroup per CU.
-    static constexpr bool MINREC = SPLIT && RING_MINREC && !(D == 128 && RPG == 8) && !(D == 96 && !RING_MINREC96);
-    static_assert(RPG == LPP || MINREC, "GroupSelect's lane reductions need one owner per lane of a pixel");
-    // D = 64: records in 8-byte pieces at a 34-dword stride (rtdm_select.h)
-    static constexpr bool B64 = MINREC && D == 64 && RING_B64REC;
-    using Rec = SelRecord<D, MINREC || !SPLIT, B64>;
+    // selection without transposing the lanes' slices (GroupSelectRec): always for four and more lanes per pixel; with two
+    // lanes where it measured faster than transposing (profiles/r02_ring_split_select_ab.txt; round 3 re-measured: D = 32,
+    // w = 5 joins (+10 %); the other D = 16 / 32 forms stay within +-1-5 % of transposing, profiles/r03_ring_split_select_ab.txt)
+    static constexpr bool SPLIT = LPP != 2 || D >= 48 || (D == 32 && (WS == 9 || WS == 5));
+    // D = 64: records in 8-byte pieces at a 34-dword stride (rtdm_select.h: four workgroups per CU at (64, 9, 4))
+    static constexpr bool B64 = SPLIT && D == 64;
+    using Rec = SelRecord<D, B64>;
     static constexpr int NP = (WS + 3) / 4;        // 4-byte pieces of a window row
     static constexpr int W1 = WS + 1;              // ring slots
     static constexpr int PPW = 64 / LPP;           // pixels (columns) per wave
@@ -148,16 +94,20 @@ struct RingCfg {
     static constexpr int TRIP = (W1 % RPG == 0) ? W1 : (2 * W1 % RPG == 0) ? 2 * W1 : 4 * W1;
     static_assert(W1 % 2 == 0 && TRIP % RPG == 0 && TRIP % W1 == 0, "block sizes are odd");
     // staged rows in flight per wave: three (row t is read while t+1 waits and t+2 arrives), or four where that makes the
-    // slot of every unrolled step a constant (one item per row only: ds_read2's 8-bit dword offsets must reach the slots)
-    static constexpr bool STATIC_SLOTS = RING_STATIC_SLOTS && ITEMS == 1 && TRIP % 4 == 0;
+    // slot of every unrolled step a constant and every LDS address base + immediate, 3-4 VALU per row less (one item per row
+    // only: ds_read2's 8-bit dword offsets must reach the slots)
+    static constexpr bool STATIC_SLOTS = ITEMS == 1 && TRIP % 4 == 0;
     static constexpr int NSLOT = STATIC_SLOTS ? 4 : 3;
     // dwords per wave: staged rows + the texture prefix ring [W1][PPW] + the window texture sums of a group's rows [RPG][PPW] (u16)
     static constexpr int STG = (NSLOT * SLOT + (W1 + RPG) * PPW / 2 + 3) & ~3;
     static constexpr int WAVE_LDS = STG + PPW * RPG * Rec::DWORDS;   // + the selection's records, one per owner lane (rtdm_select.h)
     // waves per SIMD the register budget is set for: the ring takes W1 * NRL registers, the rest of the kernel about 50
     static constexpr int RING_REGS = W1 * NRL;
+    // two-lane forms: most ring registers a three-wave form may hold.  (32, 13) sits AT 112 and spills ten dwords at 168 VGPRs
+    // -- and is still 9 % faster than as a two-wave form without (111): profiles/r03_ring_spills.txt
+    static constexpr int W3_LIMIT = 112;
     // (tighter bounds spill; eight lanes per pixel = D = 128: the selection records, 17 KB per wave, allow two workgroups per CU)
-    static constexpr int WAVES = LPP >= 8 ? 2 : LPP == 4 ? (RING_REGS <= (MINREC ? 80 : 64) ? 4 : (RING_REGS <= 96 && NRL <= 8) ? 3 : 2) : (RING_REGS <= 72 && NRL <= 8) ? 4 : RING_REGS <= RING_W3_LIMIT ? 3 : 2;
+    static constexpr int WAVES = LPP >= 8 ? 2 : LPP == 4 ? (RING_REGS <= 80 ? 4 : (RING_REGS <= 96 && NRL <= 8) ? 3 : 2) : (RING_REGS <= 72 && NRL <= 8) ? 4 : RING_REGS <= W3_LIMIT ? 3 : 2;
     static constexpr int TILE = 4 * PPW;           // four byte phases
     // border-column workgroups may ride in this kernel's grid (small launches): border2_body in every form (it needs no LDS
     // and 52-120 VGPRs for D <= 64); border_body (configurations border2 does not cover) not in the four-wave forms, whose
@@ -173,10 +123,7 @@ struct RingCfg {
 // where the occupancy bound buys nothing) is compiled for one wave per SIMD less: border2_body on top of a form that sits at
 // its register limit spilled two dwords ((64, 9, 4) at 128 VGPRs, (192, 15, 8) at 256).
 template <int D, int WS, int LPP, bool BORDER>
-#ifndef RING_BORDER_RELAX   // A/B: 0 = the same bound for both forms (round 3 until then)
-#define RING_BORDER_RELAX 1
-#endif
-struct RingBounds { static constexpr int WAVES = RING_BORDER_RELAX && BORDER && RingCfg<D, WS, LPP>::WAVES > 1 ? RingCfg<D, WS, LPP>::WAVES - 1 : RingCfg<D, WS, LPP>::WAVES; };
+struct RingBounds { static constexpr int WAVES = BORDER && RingCfg<D, WS, LPP>::WAVES > 1 ? RingCfg<D, WS, LPP>::WAVES - 1 : RingCfg<D, WS, LPP>::WAVES; };
 
 template <int D, int WS, int LPP = 2>
 struct RingState { uint64_t P[RingCfg<D, WS, LPP>::W1][RingCfg<D, WS, LPP>::NGL]; };   // only ever indexed with constants: registers
@@ -230,12 +177,8 @@ __device__ __forceinline__ void ring_step(RingState<D, WS, LPP>& st, const RowRe
             const int gi = j - k;
             if (gi >= 0 && gi < NGL) {
                 const uint64_t acc = k == 0 ? P[KP][gi] : P[K][gi];
-#if RING_ABL == 4
-                P[K][gi] = acc + (rw.win[j] ^ l[k]);
-#else
                 if (k == NP - 1) P[K][gi] = __builtin_amdgcn_mqsad_pk_u16_u8(rw.win[j], l[k], acc);
                 else             P[K][gi] = __builtin_amdgcn_qsad_pk_u16_u8(rw.win[j], l[k], acc);
-#endif
             }
         }
     }
@@ -273,7 +216,7 @@ __global__ __launch_bounds__(256, (RingBounds<D, WS, LPP, FUSE>::WAVES)) void k_
 {
     using C = RingCfg<D, WS, LPP>;
     constexpr int NGL = C::NGL, NRL = C::NRL, W1 = C::W1, LWD = C::LWD, SLOT = C::SLOT, ITEMS = C::ITEMS, PPW = C::PPW, RPG = C::RPG;
-    constexpr bool SPLIT = C::SPLIT, MINREC = C::MINREC;
+    constexpr bool SPLIT = C::SPLIT;
     constexpr int RECD = C::Rec::DWORDS;
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
 
@@ -310,9 +253,6 @@ __global__ __launch_bounds__(256, (RingBounds<D, WS, LPP, FUSE>::WAVES)) void k_
     if (ys0 >= ys1) return;
     const int r = g.r;
     const uint8_t* Lb = Lp.base + (size_t)f * Lp.frame;
-#if !RING_DIRECT_LOADS
-    const uint8_t* Rb = Rp.base + (size_t)f * Rp.frame;
-#endif
     const int Lbase = g.lofs + x_tile - r + phi;   // image column of byte 0 of this wave's copy (left)
     const int Rbase = g.rofs + x_tile - r + phi;   //                                            (right)
     const uint32_t capb = (uint32_t)(g.cap + PREFILTER_BIAS) * 0x01010101u;
@@ -328,16 +268,15 @@ __global__ __launch_bounds__(256, (RingBounds<D, WS, LPP, FUSE>::WAVES)) void k_
     const unsigned short* ptw_own = ptw + (owner ? h : 0) * PPW + p;
     uint32_t* scr = stg + C::STG + (owner ? lane : 0) * RECD;        // this lane's selection record (lanes that own nothing: never used)
     uint32_t* scr_w = stg + C::STG + p * RECD + h * NRL;             // SPLIT: where this lane's slice of the group's first row goes
-    using GSel = std::conditional_t<MINREC, GroupSelectRec<D, LPP, C::B64>, GroupSelect<D, LPP>>;
+    using GSel = GroupSelectRec<D, LPP, C::B64>;
     unsigned short* scr_m = (unsigned short*)(stg + C::STG + p * RECD + D / 2) + h * (NRL / 4);   // ... and the minima of its groups
-    if constexpr (MINREC) GSel::init(scr);
+    if constexpr (SPLIT) GSel::init(scr);
 
     // --- staging: item idx = one dword of the wave's copy; dword m holds copy bytes [4m, 4m+4) (biased planes) ---------
     // Unconditional loads: bytes past a row's end only ever reach lanes that are not `active`, and the prefiltered planes
     // are allocated with 1 KB of slack behind the last row (rtdm_api.hip).  Two rows of loads are in flight (pre[0/1]).
     const int row0 = ys0 - r;
     const int Hm1 = g.H - 1;
-#if RING_DIRECT_LOADS
     // One load per staged dword: address = the left plane's row (wave-uniform: lives in SGPRs and advances on the scalar
     // unit) + a 32-bit lane offset -- the right plane lies rg.rdelta bytes behind the left one (one allocation, rtdm_api.hip).
     // The byte phase makes the address unaligned; the memory pipeline takes unaligned dwords, and what arrives is what gets
@@ -357,14 +296,10 @@ __global__ __launch_bounds__(256, (RingBounds<D, WS, LPP, FUSE>::WAVES)) void k_
         constexpr int SET = decltype(Sc)::value;
 #pragma unroll
         for (int it = 0; it < ITEMS; ++it) {
-#if RING_ABL == 3
-            pre[SET][it] = (uint32_t)next_row * 0x01020304u + lane;
-#else
             // (the empty asm keeps the zero-extension of the offset next to the load: hoisted out of the loop as a 64-bit
             //  value it hides the "SGPR base + 32-bit VGPR offset" addressing mode and costs a 64-bit VALU add per load)
             asm volatile("" : "+v"(loff[it]));
             pre[SET][it] = *(const uint32_t*)(rowp + loff[it]);
-#endif
         }
         rowp += next_row < Hm1 ? Lp.pitch : 0;
         ++next_row;
@@ -375,46 +310,6 @@ __global__ __launch_bounds__(256, (RingBounds<D, WS, LPP, FUSE>::WAVES)) void k_
         for (int it = 0; it < ITEMS; ++it) stg[slot * SLOT + lane + it * 64] = pre[SET][it];   // (the planes carry the +1 bias themselves)
         __builtin_amdgcn_wave_barrier();           // the wave's later reads stay behind these writes (LDS is in order per wave)
     };
-#else
-    const uint8_t* src[ITEMS];                      // where the next row to be issued starts, per item
-    int it_sh[ITEMS];
-#pragma unroll
-    for (int it = 0; it < ITEMS; ++it) {
-        const int idx = lane + it * 64;
-        const bool isr = idx >= LWD;
-        const int m = isr ? idx - LWD : idx;
-        const int col = (isr ? Rbase : Lbase) + 4 * m;
-        src[it] = (isr ? Rb : Lb) + (size_t)row0 * Lp.pitch + (col & ~3);
-        it_sh[it] = col & 3;
-    }
-    int next_row = row0;
-    uint32_t pre[2][ITEMS][2];
-    auto issue = [&](auto Sc) {                     // loads of the next row into register set Sc; rows past H-1 repeat H-1
-        constexpr int SET = decltype(Sc)::value;
-#pragma unroll
-        for (int it = 0; it < ITEMS; ++it) {
-#if RING_ABL == 3
-            pre[SET][it][0] = (uint32_t)next_row * 0x01020304u + lane; pre[SET][it][1] = (uint32_t)next_row * 0x04030201u ^ lane;
-#else
-            pre[SET][it][0] = *(const uint32_t*)(src[it]);
-            pre[SET][it][1] = *(const uint32_t*)(src[it] + 4);
-#endif
-        }
-        const size_t adv = next_row < Hm1 ? Lp.pitch : 0;
-#pragma unroll
-        for (int it = 0; it < ITEMS; ++it) src[it] += adv;
-        ++next_row;
-    };
-    auto commit = [&](auto Sc, auto slot) {        // slot: an int, or an integral_constant where the slots are static
-        constexpr int SET = decltype(Sc)::value;
-#pragma unroll
-        for (int it = 0; it < ITEMS; ++it) {
-            const uint32_t v = __builtin_amdgcn_alignbyte(pre[SET][it][1], pre[SET][it][0], (uint32_t)it_sh[it]);
-            stg[slot * SLOT + lane + it * 64] = v;                          // (the planes carry the +1 bias themselves)
-        }
-        __builtin_amdgcn_wave_barrier();           // the wave's later reads stay behind these writes (LDS is in order per wave)
-    };
-#endif
     using Set0 = std::integral_constant<int, 0>;
     using Set1 = std::integral_constant<int, 1>;
 
@@ -445,10 +340,6 @@ __global__ __launch_bounds__(256, (RingBounds<D, WS, LPP, FUSE>::WAVES)) void k_
     const bool masked_col = g.mask_cols && (col < g.vx0 || col >= g.vx1);
 
     uint32_t S[RPG][NRL];
-#ifdef RING_STAMPS
-    unsigned long long stamp_sum[8] = {0, 0, 0, 0, 0, 0, 0, 0}, stamp_last;
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(stamp_last) :: "memory");
-#endif
     // Row t is read from LDS slot t mod 3, where it was put two steps earlier.  Step t issues the global loads of row
     // t+3 at its start and, at its end, writes row t+2 (issued one step earlier) to LDS -- BEHIND the step's quad-SADs
     // (the empty asm on S pins that order: left alone the compiler sinks the SADs below the commit and every step then
@@ -524,22 +415,16 @@ __global__ __launch_bounds__(256, (RingBounds<D, WS, LPP, FUSE>::WAVES)) void k_
             constexpr int U = RPG * decltype(Uc)::value;
             const int t = t0 + U;
             if (t >= nstepsg) return false;
-            RING_STAMP(0);                                          // (loop overhead + whatever precedes the group)
             GSel gsel;
             ring_for_rows(std::make_integer_sequence<int, RPG>{}, [&](auto Rc) {
                 constexpr int R = decltype(Rc)::value;
                 RowRegs<D, WS, LPP> rw;
                 using SL = std::integral_constant<int, (U + R) % 4>;    // (static slots: TRIP % 4 == 0, so t % 4 == (U + R) % 4)
                 lds_row(SL{}, rw);
-                RING_STAMP(1);                                      // LDS reads of the row (the stamp waits for them)
                 step(std::integral_constant<int, (U + R) % W1>{}, SL{}, Rc, rw, S[R]);
-                RING_STAMP(2);
-                if constexpr (SPLIT && RING_ABL == 0) {
-                    // the row's slice goes to its owner's record and into the group minima at once: S[R] is dead after this
-                    // (also while the window fills: a branch around it turns into selects on all of gsel's state)
-                    if constexpr (MINREC) gsel.template row<R>(S[R], scr_w + R * (PPW * RECD), scr_m + R * (PPW * RECD * 2));
-                    else gsel.template row<R>(S[R], scr_w + R * (PPW * RECD), (uint32_t)(h * (NRL / 4)));
-                }
+                // the row's slice and the minima of its groups go to its owner's record at once: S[R] is dead after this
+                // (also while the window fills: no branch around it)
+                if constexpr (SPLIT) gsel.template row<R>(S[R], scr_w + R * (PPW * RECD), scr_m + R * (PPW * RECD * 2));
             });
             if (t + RPG - 1 < WS - 1) return true;                  // the window is still filling
             // the lanes p + h PPW hold the LPP slices of a pixel for the rows t .. t+RPG-1; the lane with h = k < RPG owns row t+k
@@ -557,55 +442,29 @@ __global__ __launch_bounds__(256, (RingBounds<D, WS, LPP, FUSE>::WAVES)) void k_
             } else {
                 int m1; bool fail;
                 int out;
-                if constexpr (SPLIT && MINREC && RING_ABL == 0) {
+                if constexpr (SPLIT) {
                     int uq = g.uniq;
                     asm volatile("" : "+s"(uq));                     // (tested here, on the scalar unit, not hoisted as a lane mask)
                     out = gsel.finish(tsum, g, uq > 0, scr, &m1, &fail);
-                    RING_STAMP(5);
-                } else if constexpr (SPLIT && RING_ABL == 0) {
-                    out = gsel.finish(tsum, g, scr, &m1, &fail);
-                    RING_STAMP(5);
                 } else {
                     // two lanes per pixel: after the swap the lower lane has both halves of row t and the upper lane both
                     // halves of row t+1
                     uint32_t rr[D / 2];
 #pragma unroll
                     for (int i = 0; i < NRL; ++i) {
-#if RING_ABL == 5 || RING_ABL == 6
-                        rr[i] = S[0][i]; rr[NRL + i] = S[RPG - 1][i];
-#else
                         const auto sw = __builtin_amdgcn_permlane32_swap(S[0][i], S[RPG - 1][i], false, false);
                         rr[i] = sw[0]; rr[NRL + i] = sw[1];
-#endif
                     }
-                    RING_STAMP(5);                                  // swaps
-#if RING_ABL == 1 || RING_ABL == 6
-                    uint32_t xo = 0;
-#pragma unroll
-                    for (int i = 0; i < D / 2; ++i) xo ^= rr[i];
-                    out = (int)xo; m1 = (int)(xo >> 3); fail = (xo & 1) != 0;
-#elif RING_LDS_SELECT
                     out = select_disparity_lds<D>(rr, tsum, g, scr, &m1, &fail);
-#else
-                    out = select_disparity<D>(rr, tsum, g, &m1, &fail);
-#endif
                 }
-#if RING_ABL == 2
-                if (active && row_ok && out == 0x12345678) {
-#else
                 if (active && row_ok) {
-#endif
                     if (!fail && g.want_cost) *(uint16_t*)(cb + cof) = (uint16_t)m1;
                     *(int16_t*)(db + dof) = (int16_t)(masked_col ? g.filtered : out);
                 }
             }
-            RING_STAMP(6);                                          // selection + stores
             return true;
         });
     }
-#ifdef RING_STAMPS
-    if (lane == 0) for (int i = 0; i < 8; ++i) atomicAdd(&ring_stamps[i], stamp_sum[i]);
-#endif
 }
 
 // ---- host side ----------------------------------------------------------------------------
@@ -797,7 +656,7 @@ bool launch_search_ring(Plane8 Lp, Plane8 Rp, Plane16W disp, void* cost, const B
     const int lpp = ring_lpp(g);
     // the kernel addresses both planes from the left plane's rows with 32-bit lane offsets: they must be one allocation, the
     // right plane behind the left one, with the same strides (rtdm_api.hip allocates them that way)
-    if (RING_DIRECT_LOADS && !(Rp.base > Lp.base && (size_t)(Rp.base - Lp.base) < ((size_t)1 << 32) - ((size_t)1 << 20) && Rp.pitch == Lp.pitch && Rp.frame == Lp.frame)) {
+    if (!(Rp.base > Lp.base && (size_t)(Rp.base - Lp.base) < ((size_t)1 << 32) - ((size_t)1 << 20) && Rp.pitch == Lp.pitch && Rp.frame == Lp.frame)) {
         launch_search_fast(Lp, Rp, disp, cost, g, n, stream, fuse_border, 0);
         return fuse_border;
     }

@@ -442,9 +442,7 @@ static int chunk_front(rtdm_bm* bm, int n, Plane8 L, Plane8 R, int W, int H, Pla
             if (side) {
                 HIPC(hipEventRecord(bm->evFork, s));
                 HIPC(hipStreamWaitEvent(bm->sBorder, bm->evFork, 0));
-#ifndef RTDM_DEBUG_SKIP_BORDER   // (timing-only variant build: what the border columns cost the search stage; outputs are wrong)
                 launch_search_border(Lpr, Rpr, disp, bm->dCost, g, n, bm->sBorder, lx0, lx1, rx0, rx1);
-#endif
                 HIPC(hipEventRecord(bm->evJoin, bm->sBorder));
             }
             bool fused = fuse;

@@ -165,11 +165,10 @@ __device__ __forceinline__ int select_disparity(const uint32_t (&rr)[D / 2], int
 // D/2 SAD dwords + D/16 dwords of packed group minima (GroupSelectRec), rounded up to an ODD number of 16-byte quads so that
 // eight consecutive lanes' 16-byte stores start in eight different bank quads: 12, 20, 28, 36 dwords for D = 16 .. 64 (the
 // minima fill what used to be padding), 60 / 76 / 108 / 148 for D = 96 / 128 / 192 / 256
-// (MINIMA = false, GroupSelect at D = 96 / 128: D/2 + 4 = 52 / 68 dwords)
 // B64: the record is written and read in 8-byte pieces instead (GroupSelectRec): the stride only has to be an odd number of
 // 8-byte pairs -- 34 dwords at D = 64, which is what lets four workgroups of k_search_ring<64, 9, 4> share a CU's 160 KB.
-template <int D, bool MINIMA = true, bool B64 = false> struct SelRecord {
-    static constexpr int QUADS = MINIMA ? (D / 2 + D / 16 + 3) / 4 : D / 8 + 1;
+template <int D, bool B64 = false> struct SelRecord {
+    static constexpr int QUADS = (D / 2 + D / 16 + 3) / 4;
     static constexpr int PAIRS = (D / 2 + D / 16 + 1) / 2;
     static constexpr int DWORDS = B64 ? 2 * (PAIRS | 1) : 4 * (QUADS | 1);
 };
@@ -250,191 +249,28 @@ __device__ __forceinline__ int select_disparity_lds(const uint32_t (&rr)[D / 2],
 
 // ---- selection for pixels whose D values are spread over LPP lanes (k_search_ring), without transposing them --------
 // The LPP lanes {p + h * 64/LPP, h = 0..LPP-1} of a wave each hold one SLICE of the D values -- indices [h D/LPP, (h+1) D/LPP)
-// -- of LPP pixel rows: S[r] belongs to the row owned by the lane with h = r.  Each lane writes its slices into the owners'
-// LDS records, runs level one (group minima and keys) and the uniqueness sums on what it holds -- in total the work of one
-// whole row -- and only three values per row cross between the lanes (v_permlane32_swap / v_permlane16_swap): the partial
-// key minima (reduced towards the owner), the owners' thresholds T+1 (broadcast back) and the partial sums (reduced).
-// Everything after that is the owner's: winning group back from its record, argmin inside it, sad[a-1], sad[a+1], the
-// tests, the sub-pixel step.  Results are those of select_disparity_lds on the gathered values.  (A first version kept the
-// slices in registers and evaluated the sum identity of select_disparity_lds on them: 13 % more instructions and 10 more
-// VGPRs at D = 64, four lanes, 0.968 vs 1.018 ms per 64 pairs.)
-
-// xr_reduce: v[r] = this lane's partial value for row r; returns op over the pixel's LPP lanes of v[h] -- the full value of
-// the row this lane owns.  xr_bcast: t = the owner's value; out[r] = the value of the owner of row r, in every lane.
-template <int LPP, class Op>
-__device__ __forceinline__ uint32_t xr_reduce(const uint32_t (&v)[LPP], Op op)
-{
-    static_assert(LPP == 2 || LPP == 4 || LPP == 8, "lane bits 5, 4 and 3");
-    if constexpr (LPP == 2) {
-        // lower lane: {own v0, partner's v0}; upper lane: {partner's v1, own v1}
-        const auto s = __builtin_amdgcn_permlane32_swap(v[0], v[1], false, false);
-        return op(s[0], s[1]);
-    } else if constexpr (LPP == 4) {
-        const auto s0 = __builtin_amdgcn_permlane32_swap(v[0], v[2], false, false);   // h < 2: row 0 over {h, h+2}; h >= 2: row 2
-        const auto s1 = __builtin_amdgcn_permlane32_swap(v[1], v[3], false, false);   //        row 1                       row 3
-        const uint32_t a = op(s0[0], s0[1]), b = op(s1[0], s1[1]);
-        const auto s2 = __builtin_amdgcn_permlane16_swap(a, b, false, false);         // even h: {own a, partner's a}; odd h: {partner's b, own b}
-        return op(s2[0], s2[1]);
-    } else {
-        // h = lane >> 3: bit 2 = lane bit 5, bit 1 = lane bit 4, bit 0 = lane bit 3
-        uint32_t w[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {                                                 // keeps rows (h & 4) + k, over {h, h ^ 4}
-            const auto sk = __builtin_amdgcn_permlane32_swap(v[k], v[k + 4], false, false);
-            w[k] = op(sk[0], sk[1]);
-        }
-        const auto t0 = __builtin_amdgcn_permlane16_swap(w[0], w[2], false, false);   // keeps rows (h & 6) + 0 and + 1, over four lanes
-        const auto t1 = __builtin_amdgcn_permlane16_swap(w[1], w[3], false, false);
-        const uint32_t x0 = op(t0[0], t0[1]), x1 = op(t1[0], t1[1]);
-        const bool odd = (__lane_id() & 8) != 0;
-        const uint32_t send = odd ? x0 : x1, own = odd ? x1 : x0;                     // the partner (lane ^ 8) owns the other row
-        const uint32_t recv = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)send, 0x128, 0xf, 0xf, false);   // row_ror:8
-        return op(own, recv);
-    }
-}
-template <int LPP>
-__device__ __forceinline__ void xr_bcast(uint32_t t, uint32_t (&out)[LPP])
-{
-    if constexpr (LPP == 2) {
-        const auto s = __builtin_amdgcn_permlane32_swap(t, t, false, false);
-        out[0] = s[0]; out[1] = s[1];
-    } else if constexpr (LPP == 4) {
-        const auto s = __builtin_amdgcn_permlane16_swap(t, t, false, false);          // {value of the even h of the pair, of the odd h}
-        const auto se = __builtin_amdgcn_permlane32_swap(s[0], s[0], false, false);   // {h = 0, h = 2}
-        const auto so = __builtin_amdgcn_permlane32_swap(s[1], s[1], false, false);   // {h = 1, h = 3}
-        out[0] = se[0]; out[2] = se[1]; out[1] = so[0]; out[3] = so[1];
-    } else {
-        const bool odd = (__lane_id() & 8) != 0;
-        const uint32_t other = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)t, 0x128, 0xf, 0xf, false);     // row_ror:8: lane ^ 8
-        const uint32_t e = odd ? other : t, o = odd ? t : other;                      // rows (h & 6) + 0 and + 1
-        const auto se = __builtin_amdgcn_permlane16_swap(e, e, false, false);         // rows (h & 4) + {0, 2}
-        const auto so = __builtin_amdgcn_permlane16_swap(o, o, false, false);         //               {1, 3}
-        const uint32_t q[4] = {se[0], so[0], se[1], so[1]};
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const auto sk = __builtin_amdgcn_permlane32_swap(q[k], q[k], false, false);
-            out[k] = sk[0]; out[k + 4] = sk[1];
-        }
-    }
-}
-
-// GroupSelect is fed row by row (k_search_ring: the SADs of a row are dead as soon as its step is over, so a group of LPP
-// rows holds LPP * NGH + LPP registers of state instead of LPP * D / (2 LPP)), with the uniqueness test split in two so that
-// it needs no SAD value a second time:
-//   (A) no group of eight other than the winner's and the one its neighbour a-1 / a+1 may lie in has a minimum <= T:
-//       every lane counts the groups of its slices whose minimum is <= T, the counts are reduced to the owner, and the owner
-//       expects 1 (+ 1 if the neighbour group's minimum is <= T);
+// -- of up to LPP pixel rows: S[r] belongs to the row owned by the lane with h = r.  Results are those of select_disparity_lds
+// on the gathered values.  (A first version kept the slices in registers and evaluated the sum identity of
+// select_disparity_lds on them: 13 % more instructions and 10 more VGPRs at D = 64, four lanes, 0.968 vs 1.018 ms per 64 pairs.)
+//
+// GroupSelectRec is fed row by row (k_search_ring: the SADs of a row are dead as soon as its step is over).  Each lane writes
+// its slice of the row into the LDS record of the row's owner, and behind the D/2 SAD dwords the packed u16 minima of the
+// slice's groups of eight (v_pk_minimum3_f16 + v_pk_min + one SDWA minimum per group, written with ds_write_b16; D <= 64: the
+// D/16 <= 4 dwords of minima fill the record's padding).  NOTHING crosses between the lanes: the owner reads the minima of
+// all D/8 groups back with one 16-byte read, builds the keys (v_perm, v_min3), reads the winning group back and finds the
+// first argmin inside it.  The uniqueness test is split in two, so that besides the minima it reads back no more than one or
+// two groups of SADs:
+//   (A) no group of eight other than the winner's and the one its neighbour a-1 / a+1 may lie in has a minimum <= T;
 //   (B) inside those one or two groups -- read back from the owner's record -- the identity
 //       sum_e max(T+1 - sad[e], 0) == the same sum over {a-1, a, a+1}.
 // Exact: {a-1, a, a+1} lies inside the two groups, so an index outside it with sad <= T is either in another group (A) or
-// one of the up to sixteen values of (B).
-template <int D, int LPP>
-struct GroupSelect {
-    static constexpr int NRL = D / (2 * LPP), NGH = NRL / 4;
-    static_assert(D == 16 || D == 32 || D == 48 || D == 64 || D == 96 || D == 128, "record stride checked for these sizes only");
-    static_assert(NRL % 4 == 0, "a lane's slice must be whole groups of eight disparities");
-    typedef uint32_t u4 __attribute__((ext_vector_type(4)));
-    uint32_t mm[LPP][NGH];      // minimum of each group of this lane's slice, per row
-    uint32_t kpart[LPP];        // min over the slice of (minimum << 8 | group), per row
-
-    // row R of the group: sv = this lane's slice of its window sums; wr = where the slice goes in the record of the row's
-    // owner; hofs = h * NGH, the number of the slice's first group
-    template <int R>
-    __device__ __forceinline__ void row(const uint32_t (&sv)[NRL], uint32_t* wr, uint32_t hofs)
-    {
-#pragma unroll
-        for (int i = 0; i < NRL; i += 4) *(u4*)(wr + i) = u4{sv[i], sv[i + 1], sv[i + 2], sv[i + 3]};
-        uint32_t k = 0xffffffffu;
-#pragma unroll
-        for (int gq = 0; gq < NGH; ++gq) {
-            const uint32_t m = sel_pk_min(sel_pk_min(sv[4 * gq], sv[4 * gq + 1]), sel_pk_min(sv[4 * gq + 2], sv[4 * gq + 3]));
-            const uint32_t m1 = min(m & 0xffffu, m >> 16);
-            mm[R][gq] = m1;
-            k = min(k, (m1 << 8) | (uint32_t)gq);
-        }
-        kpart[R] = k + hofs;
-    }
-
-    // after the LPP rows: the result for the row this lane owns (rec_own = its record)
-    __device__ __forceinline__ int finish(int tsum, const BMGeom& g, const uint32_t* rec_own, int* minsad, bool* rejected)
-    {
-        const uint32_t kmin = xr_reduce<LPP>(kpart, [](uint32_t a, uint32_t b) { return min(a, b); });
-        const int m1 = (int)(kmin >> 8);
-        const int gs = (int)(kmin & 0xffu);
-        const u4 grp = *(const u4*)(rec_own + 4 * gs);               // the four registers of the winning group
-        uint32_t T1 = 0, cnt = 0;
-        if (g.uniq > 0) {
-            uint32_t T = (uint32_t)m1 + ((uint32_t)m1 * (uint32_t)g.uniq) / 100u;
-            T = min(T, 32766u);
-            T1 = T + 1u;
-            uint32_t t1r[LPP], cpart[LPP];
-            xr_bcast<LPP>(T1, t1r);
-#pragma unroll
-            for (int r = 0; r < LPP; ++r) {
-                uint32_t c = 0;
-#pragma unroll
-                for (int gq = 0; gq < NGH; ++gq) c += (uint32_t)(mm[r][gq] < t1r[r]);
-                cpart[r] = c;
-            }
-            cnt = xr_reduce<LPP>(cpart, [](uint32_t a, uint32_t b) { return a + b; });
-        }
-        uint32_t k3[2] = {0xffffffffu, 0xffffffffu};
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const uint32_t ec = (uint32_t)(2 * q) | ((uint32_t)(2 * q + 1) << 8);
-            const uint32_t klo = __builtin_amdgcn_perm(grp[q], ec, 0x0C050400u);
-            const uint32_t khi = __builtin_amdgcn_perm(grp[q], ec, 0x0C070601u);
-            k3[q & 1] = min(min(k3[q & 1], klo), khi);
-        }
-        const int e = (int)(min(k3[0], k3[1]) & 0xffu);
-        const int a = 8 * gs + e;
-        const bool has_n = a > 0, has_p = a + 1 < D;
-        const unsigned short* sv = (const unsigned short*)rec_own;
-        const int n_real = sv[has_n ? a - 1 : a];
-        const int p_real = sv[has_p ? a + 1 : a];
-        bool fail = tsum < g.tex;
-        if (g.uniq > 0) {
-            // the group a-1 or a+1 falls into, if that is not the winner's
-            const int nbq = (e == 0 && has_n) ? gs - 1 : (e == 7 && has_p) ? gs + 1 : gs;
-            const bool has_nb = nbq != gs;
-            const u4 nbg = *(const u4*)(rec_own + 4 * nbq);
-            const uint32_t nbm = sel_pk_min(sel_pk_min(nbg[0], nbg[1]), sel_pk_min(nbg[2], nbg[3]));
-            const uint32_t nbmin = min(nbm & 0xffffu, nbm >> 16);
-            const uint32_t expect = 1u + (uint32_t)(has_nb && nbmin < T1);
-            const uint32_t T1pk = T1 * 0x00010001u, nbmask = has_nb ? 0xffffffffu : 0u;
-            uint32_t zz[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-                zz[q] = sel_pk_add_sat(sel_pk_sub_sat(T1pk, grp[q]), sel_pk_sub_sat(T1pk, nbg[q]) & nbmask);
-            const uint32_t zp = sel_pk_add_sat(sel_pk_add_sat(zz[0], zz[1]), sel_pk_add_sat(zz[2], zz[3]));
-            // a 16-bit half saturates at 65535, more than the (at most two) terms of {a-1, a, a+1} it can hold add up to:
-            // the total stays >= the expected total, with equality only if nothing saturated and nothing else contributed
-            const uint32_t z = (zp & 0xffffu) + (zp >> 16);
-            const auto term = [&](int v) -> uint32_t { return T1 > (uint32_t)v ? T1 - (uint32_t)v : 0u; };
-            const uint32_t want = term(m1) + (has_n ? term(n_real) : 0u) + (has_p ? term(p_real) : 0u);
-            fail |= (z != want) | (cnt != expect);
-        }
-        const int pp = has_p ? p_real : n_real;
-        const int nn = has_n ? n_real : p_real;
-        const int out = ((D - a - 1 + g.minD) * 256 + sel_subpixel(pp, nn, m1) + 15) >> 4;
-        *minsad = m1;
-        *rejected = fail;
-        return fail ? g.filtered : out;
-    }
-};
-
-// GroupSelectRec: GroupSelect with the group minima kept in the OWNER's record as well (D <= 64: the D/8 packed u16 minima
-// are D/16 <= 4 dwords and live in the four padding dwords behind the D/2 SAD dwords).  A lane's part of a row shrinks to
-// the packed minima of its groups (v_pk_minimum3_f16 + v_pk_min + one SDWA minimum per group, written with ds_write_b16)
-// and NOTHING crosses between the lanes any more: the owner reads the minima of all D/8 groups back with one 16-byte read and builds the keys
-// (v_perm, v_min3: 12 instructions at D = 64 against 16 per-row key instructions + an 8-instruction lane reduction), and
-// evaluates test (A) itself as a second sum identity over those minima (8 packed instructions against a 9-instruction
-// broadcast of T+1, 16 compares in the other lanes and a 10-instruction reduction).  Per 64 pixel-rows at D = 64, four lanes per pixel: about 45 VALU instructions
-// and 12 registers of per-group state (mm, kpart) less.  Same results: the tests (A) and (B) of GroupSelect, same values.
+// one of the up to sixteen values of (B).  (A) is evaluated as a second sum identity, over the group minima.  Against the
+// lane-exchange form it replaced (partial key minima, thresholds and counts reduced across the lanes): per 64 pixel-rows at
+// D = 64, four lanes per pixel, about 45 VALU instructions and 12 registers of per-group state less.
 template <int D, int LPP, bool B64 = false>
 struct GroupSelectRec {
     static constexpr int NRL = D / (2 * LPP), NGH = NRL / 4, NG = D / 8, NGD = NG / 2, NGQ = (NGD + 3) / 4;
-    static_assert(D % 16 == 0 && D / 2 + (B64 ? 2 * ((NGD + 1) / 2) : 4 * NGQ) <= SelRecord<D, true, B64>::DWORDS, "the minima live behind the SADs of the record");
+    static_assert(D % 16 == 0 && D / 2 + (B64 ? 2 * ((NGD + 1) / 2) : 4 * NGQ) <= SelRecord<D, B64>::DWORDS, "the minima live behind the SADs of the record");
     static_assert(NRL % 4 == 0, "a lane's slice must be whole groups of eight disparities");
     typedef uint32_t u4 __attribute__((ext_vector_type(4)));
     typedef uint32_t u2 __attribute__((ext_vector_type(2)));

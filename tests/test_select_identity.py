@@ -4,8 +4,9 @@ outside [a-1, a+1] has sad <= T = minsad + minsad * ratio / 100.
 
   * the sum identity (select_disparity, select_disparity_lds): sum_e max(T+1 - sad[e], 0) over ALL e equals the same sum over
     {a-1, a, a+1} iff no other index has sad <= T -- with saturating 16-bit halves (even / odd indices);
-  * the split test of GroupSelect: (A) the number of groups of eight whose minimum is <= T equals 1 (+1 if the group the
-    neighbour a-1 / a+1 falls into has a minimum <= T), (B) the sum identity restricted to those one or two groups;
+  * the split test (A) + (B) of GroupSelectRec, in its count form: (A) the number of groups of eight whose minimum is <= T
+    equals 1 (+1 if the group the neighbour a-1 / a+1 falls into has a minimum <= T), (B) the sum identity restricted to
+    those one or two groups;
   * the one-correction truncating division of the sub-pixel step.
 """
 import numpy as np
