@@ -35,8 +35,8 @@ typedef enum rtdm_status {
 } rtdm_status;
 
 /* Same nine knobs SWMatcherKonolige's constructor forwards to cv::StereoBM
- * (stereo-matcher/bm-sw.cpp:16-25; literals at main.cpp:134-135).  preFilterType is XSOBEL,
- * the cv::StereoBM default the reference never changes. */
+ * (stereo-matcher/bm-sw.cpp:16-25; literals at main.cpp:134-135).  preFilterType and preFilterSize,
+ * which the reference leaves at cv::StereoBM's defaults (XSOBEL, 9), are set with rtdm_bm_set_prefilter. */
 typedef struct rtdm_bm_params {
     int preFilterCap;      /* 1..63 */
     int blockSize;         /* odd, 5..255, smaller than min(width,height) */
@@ -85,6 +85,16 @@ int rtdm_bm_create(const rtdm_bm_params* params, int max_width, int max_height, 
 void rtdm_bm_destroy(rtdm_bm* bm);
 int rtdm_bm_set_roi(rtdm_bm* bm, int which, int x, int y, int width, int height);
 int rtdm_bm_get_params(const rtdm_bm* bm, rtdm_bm_params* out);
+/* cv::StereoBM::setPreFilterType / setPreFilterSize, from the next compute call on (every entry point that runs the matcher).
+ * A new handle reports (RTDM_PREFILTER_XSOBEL, 9), the library's defaults.  NORMALIZED_RESPONSE is the Konolige prefilter:
+ * (4 c + l + r + u + d) * scale_g - (box sum over preFilterSize^2) * scale_s, >> 10, clipped to +-preFilterCap (rules N1-N6,
+ * DESIGN.md section 4.10; restated from memory, parity with the library unpinned).  preFilterSize is read by that type only,
+ * but checked for both, as cv::StereoBM::compute does: RTDM_ERR_BAD_PARAM for a type other than 0 / 1 and for a size that is
+ * even or outside 5 .. 255.  No device synchronisation, no reallocation. */
+#define RTDM_PREFILTER_NORMALIZED_RESPONSE 0   /* cv::StereoBM::PREFILTER_NORMALIZED_RESPONSE */
+#define RTDM_PREFILTER_XSOBEL 1                /* cv::StereoBM::PREFILTER_XSOBEL, the default */
+int rtdm_bm_set_prefilter(rtdm_bm* bm, int preFilterType, int preFilterSize);
+int rtdm_bm_get_prefilter(const rtdm_bm* bm, int* preFilterType, int* preFilterSize);
 int rtdm_bm_compute(rtdm_bm* bm, const uint8_t* left, size_t left_pitch, const uint8_t* right,
                     size_t right_pitch, int width, int height, int16_t* disp, size_t disp_pitch);
 
@@ -322,7 +332,8 @@ int rtdm_wls_params_for_bm(const rtdm_bm_params* left, rtdm_wls_params* out);
 int rtdm_wls_params_for_sgm(const rtdm_sgm_params* left, rtdm_wls_params* out);
 /* W1: the parameters of createRightMatcher: the same matcher with minDisparity -(minD + numD) + 1, no texture / uniqueness /
  * speckle filtering and disp12MaxDiff 1000000; it is called as compute(right, left).  The StereoSGBM's preFilterCap is not part
- * of rtdm_sgm_params (rtdm_sgm_set_prefilter_cap sets it): the caller copies it to the right handle (the adapters do). */
+ * of rtdm_sgm_params (rtdm_sgm_set_prefilter_cap sets it): the caller copies it to the right handle (the adapters do).
+ * Likewise the StereoBM's preFilterType and preFilterSize (rtdm_bm_set_prefilter), which createRightMatcher copies too. */
 int rtdm_bm_right_params(const rtdm_bm_params* left, rtdm_bm_params* right);
 int rtdm_sgm_right_params(const rtdm_sgm_params* left, rtdm_sgm_params* right);
 /* Parameters are validated before any device use: RTDM_ERR_BAD_PARAM for lambda < 0, sigma <= 0, T < 0, r < 0, a negative

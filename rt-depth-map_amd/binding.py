@@ -14,6 +14,7 @@ RTDM_OK = 0
 STATUS = {0: "RTDM_OK", -1: "RTDM_ERR_BAD_PARAM", -2: "RTDM_ERR_BAD_SIZE", -3: "RTDM_ERR_NO_DEVICE",
           -4: "RTDM_ERR_HIP", -5: "RTDM_ERR_NOMEM", -6: "RTDM_ERR_UNSUPPORTED", -7: "RTDM_ERR_NULL"}
 STAGES = ("prefilter", "search", "lrcheck", "speckle")
+PREFILTER_NORMALIZED_RESPONSE, PREFILTER_XSOBEL = 0, 1   # cv::StereoBM's values (RTDM_PREFILTER_* in rtdm.h)
 
 
 class RtdmError(RuntimeError):
@@ -69,6 +70,8 @@ def lib():
         "rtdm_bm_destroy": (None, [vp]),
         "rtdm_bm_set_roi": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
         "rtdm_bm_get_params": (C.c_int, [vp, C.POINTER(BMParams)]),
+        "rtdm_bm_set_prefilter": (C.c_int, [vp, C.c_int, C.c_int]),
+        "rtdm_bm_get_prefilter": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
         "rtdm_bm_compute": (C.c_int, [vp, u8p, sz, u8p, sz, C.c_int, C.c_int, i16p, sz]),
         "rtdm_bm_compute_device": (C.c_int, [vp, C.c_int, u8p, u8p, sz, sz, C.c_int, C.c_int, i16p, sz, sz, vp]),
         "rtdm_bm_compute_batch": (C.c_int, [vp, C.c_int, u8p, u8p, sz, sz, C.c_int, C.c_int, i16p, sz, sz]),
@@ -140,7 +143,7 @@ def lib():
 
 
 EXPORTS = ("rtdm_strerror rtdm_last_hip_error rtdm_abi_version rtdm_device_count rtdm_bm_default_params "
-           "rtdm_bm_create rtdm_bm_destroy rtdm_bm_set_roi rtdm_bm_get_params rtdm_bm_compute "
+           "rtdm_bm_create rtdm_bm_destroy rtdm_bm_set_roi rtdm_bm_get_params rtdm_bm_set_prefilter rtdm_bm_get_prefilter rtdm_bm_compute "
            "rtdm_bm_compute_device rtdm_bm_compute_batch rtdm_bm_synchronize rtdm_bm_set_profiling "
            "rtdm_bm_get_stage_time rtdm_bm_reset_stage_times rtdm_bm_search_variant rtdm_bm_get_tuner_stats rtdm_debug_search_kernel rtdm_debug_disparity_slice rtdm_morph_create "
            "rtdm_morph_destroy rtdm_morph_in_buffer rtdm_morph_out_buffer rtdm_morph_run "

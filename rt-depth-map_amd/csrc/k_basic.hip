@@ -226,10 +226,15 @@ __global__ __launch_bounds__(256) void k_prefilter1(Plane8 L, Plane8 R, Plane8W 
 }
 
 // fill != null: the frame fill (launch_fill_frame's arguments) rides in the prefilter's grid where the strip kernel runs, and is a
-// launch of its own before the other forms
+// launch of its own before the other forms (and before the normalised-response prefilter, k_prefilter_norm.hip)
 void launch_prefilter(Plane8 L, Plane8 R, Plane8W Lp, Plane8W Rp, int W, int H, int cap, int n,
-                      hipStream_t stream, const FillJob* fill)
+                      hipStream_t stream, const FillJob* fill, int type, int ws)
 {
+    if (type == 0) {                                        // RTDM_PREFILTER_NORMALIZED_RESPONSE
+        if (fill) launch_fill_frame(fill->disp, W, H, fill->cx0, fill->cx1, fill->vy0, fill->vy1, n, fill->value, fill->rowcnt, stream);
+        launch_prefilter_norm(L, R, Lp, Rp, W, H, cap, ws, n, stream);
+        return;
+    }
     const auto al16 = [](const Plane8& p) { return (((size_t)p.base | p.pitch | p.frame) & 15) == 0; };
     const size_t w16 = (size_t)((W + 15) & ~15);
     if (al16(L) && al16(R) && L.pitch >= w16 && R.pitch >= w16 && ((size_t)Lp.base & 15) == 0 && ((size_t)Rp.base & 15) == 0) {

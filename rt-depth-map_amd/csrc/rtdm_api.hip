@@ -53,6 +53,7 @@ struct TuneEntry { TuneKey key; int strips; };   // strips: 0 = seen once, not m
 
 struct rtdm_bm {
     rtdm_bm_params p;
+    int prefilter_type, prefilter_size;   // rtdm_bm_set_prefilter: cv::StereoBM's preFilterType / preFilterSize (XSOBEL, 9)
     int maxW, maxH, maxB, device;
     int roi1[4], roi2[4];
     hipStream_t stream;
@@ -162,7 +163,8 @@ int rtdm_bm_create(const rtdm_bm_params* params, int max_width, int max_height, 
     if (rc) return rc;
     rtdm_bm* bm = new (std::nothrow) rtdm_bm();
     if (!bm) return RTDM_ERR_NOMEM;
-    bm->p = *params; bm->maxW = max_width; bm->maxH = max_height; bm->maxB = max_batch; bm->device = device;
+    bm->p = *params; bm->prefilter_type = RTDM_PREFILTER_XSOBEL; bm->prefilter_size = 9;
+    bm->maxW = max_width; bm->maxH = max_height; bm->maxB = max_batch; bm->device = device;
     for (int i = 0; i < 4; ++i) bm->roi1[i] = bm->roi2[i] = 0;
     bm->profiling = false;
     bm->tune_shapes = bm->tune_launches = 0;
@@ -253,6 +255,23 @@ int rtdm_bm_get_params(const rtdm_bm* bm, rtdm_bm_params* out)
 {
     if (!bm || !out) return RTDM_ERR_NULL;
     *out = bm->p;
+    return RTDM_OK;
+}
+
+int rtdm_bm_set_prefilter(rtdm_bm* bm, int preFilterType, int preFilterSize)
+{
+    if (!bm) return RTDM_ERR_NULL;
+    if (preFilterType != RTDM_PREFILTER_NORMALIZED_RESPONSE && preFilterType != RTDM_PREFILTER_XSOBEL) return RTDM_ERR_BAD_PARAM;
+    // (cv::StereoBM::compute checks the size whatever the type)
+    if (preFilterSize < 5 || preFilterSize > 255 || (preFilterSize & 1) == 0) return RTDM_ERR_BAD_PARAM;
+    bm->prefilter_type = preFilterType; bm->prefilter_size = preFilterSize;
+    return RTDM_OK;
+}
+
+int rtdm_bm_get_prefilter(const rtdm_bm* bm, int* preFilterType, int* preFilterSize)
+{
+    if (!bm || !preFilterType || !preFilterSize) return RTDM_ERR_NULL;
+    *preFilterType = bm->prefilter_type; *preFilterSize = bm->prefilter_size;
     return RTDM_OK;
 }
 
@@ -423,7 +442,7 @@ static int chunk_front(rtdm_bm* bm, int n, Plane8 L, Plane8 R, int W, int H, Pla
                     : ring ? (lpp == 16 ? "fast_ring16_qsad" : lpp == 8 ? "fast_ring8_qsad" : lpp == 4 ? "fast_ring4_qsad" : "fast_ring_qsad") : fast ? "fast_qsad" : (u16 ? "generic_u16" : "generic_u32");
         Plane8W Lp{bm->dLp, bm->ppitch, bm->ppitch * (size_t)H}, Rp{bm->dRp, bm->ppitch, bm->ppitch * (size_t)H};
         stage_begin(bm, RTDM_STAGE_PREFILTER, n, s, &ev);
-        launch_prefilter(L, R, Lp, Rp, W, H, p.preFilterCap, n, s, &fill);
+        launch_prefilter(L, R, Lp, Rp, W, H, p.preFilterCap, n, s, &fill, bm->prefilter_type, bm->prefilter_size);
         stage_end(bm, s, &ev);
         Plane8 Lpr{bm->dLp, Lp.pitch, Lp.frame}, Rpr{bm->dRp, Rp.pitch, Rp.frame};
         stage_begin(bm, RTDM_STAGE_SEARCH, n, s, &ev);

@@ -65,12 +65,15 @@ struct Plane16W { int16_t* base; size_t pitch_e, frame_e; };  // strides in elem
 // search wave added the bias to each staged dword itself.)  cap <= 63: the bytes stay <= 127.
 static constexpr int PREFILTER_BIAS = 1;
 
-// K1: x-Sobel prefilter of n left and n right frames in one launch (writes biased values, see above).
+// K1: prefilter of n left and n right frames in one launch (writes biased values, see above).  type: RTDM_PREFILTER_XSOBEL
+// (k_basic.hip; ws is not read) or RTDM_PREFILTER_NORMALIZED_RESPONSE with window ws (k_prefilter_norm.hip).
 // fill != null: launch_fill_frame's job (below) for the same n frames rides in the same launch where the strip form runs
 // (a single frame is bound by the number of its launches), and is launched by itself before the other forms.
 struct FillJob { Plane16W disp; int cx0, cx1, vy0, vy1, value; int32_t* rowcnt; };
 void launch_prefilter(Plane8 L, Plane8 R, Plane8W Lp, Plane8W Rp, int W, int H, int cap, int n,
-                      hipStream_t stream, const FillJob* fill = nullptr);
+                      hipStream_t stream, const FillJob* fill = nullptr, int type = 1, int ws = 9);
+// The NORMALIZED_RESPONSE form by itself (rules N1-N5); every alignment class of L / R, the planes Lp / Rp 16-byte aligned.
+void launch_prefilter_norm(Plane8 L, Plane8 R, Plane8W Lp, Plane8W Rp, int W, int H, int cap, int ws, int n, hipStream_t stream);
 
 // Fill the rectangle [x0,x1) x [y0,y1) of every disparity frame with `value`.
 void launch_fill16(Plane16W disp, int x0, int x1, int y0, int y1, int n, int value, hipStream_t stream);

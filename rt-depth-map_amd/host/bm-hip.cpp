@@ -37,6 +37,9 @@ int HIPMatcher::compute(cv::InputArray left, cv::InputArray right, cv::OutputArr
 	return core->compute(l.data, l.step, r.data, r.step, l.rows, l.cols, (int16_t*) d.data, d.step);
 }
 
+int HIPMatcher::setPreFilterType(int preFilterType) { return core->setPreFilterType(preFilterType); }
+int HIPMatcher::setPreFilterSize(int preFilterSize) { return core->setPreFilterSize(preFilterSize); }
+
 void HIPMatcher::setROI1(cv::Rect roi1)
 {
 	core->setROI1(to_rect(roi1));

@@ -22,6 +22,10 @@ public:
 	~HIPMatcher();
 	void setROI1(cv::Rect roi1);
 	void setROI2(cv::Rect roi2);
+	/* cv::StereoBM::setPreFilterType (cv::StereoBM::PREFILTER_XSOBEL = 1, the default, PREFILTER_NORMALIZED_RESPONSE = 0) and
+	 * setPreFilterSize (odd, 5 .. 255), from the next compute on; they return the module's status (0 on success) */
+	int setPreFilterType(int preFilterType);
+	int setPreFilterSize(int preFilterSize);
 	int compute(cv::InputArray left, cv::InputArray right, cv::OutputArray out);
 	/* takes ownership of a core (createRightMatcher, wls-hip.cpp) */
 	explicit HIPMatcher(rtdm::HIPMatcherCore* core) : core(core) {}

@@ -32,6 +32,16 @@ HIPMatcherCore::~HIPMatcherCore() { rtdm_bm_destroy(bm_); }
 void HIPMatcherCore::setROI1(const Rect& r) { if (bm_) status_ = rtdm_bm_set_roi(bm_, 1, r.x, r.y, r.width, r.height); }
 void HIPMatcherCore::setROI2(const Rect& r) { if (bm_) status_ = rtdm_bm_set_roi(bm_, 2, r.x, r.y, r.width, r.height); }
 
+int HIPMatcherCore::setPrefilter(int type, int size)
+{
+    if (!bm_) return status_ != RTDM_OK ? status_ : RTDM_ERR_NO_DEVICE;
+    const int rc = rtdm_bm_set_prefilter(bm_, type, size);
+    if (rc == RTDM_OK) { preFilterType_ = type; preFilterSize_ = size; }
+    return rc;
+}
+int HIPMatcherCore::setPreFilterType(int preFilterType) { return setPrefilter(preFilterType, preFilterSize_); }
+int HIPMatcherCore::setPreFilterSize(int preFilterSize) { return setPrefilter(preFilterType_, preFilterSize); }
+
 int HIPMatcherCore::compute(const uint8_t* left, size_t leftStep, const uint8_t* right, size_t rightStep,
                             int rows, int cols, int16_t* out, size_t outStep)
 {
@@ -218,9 +228,16 @@ HIPMatcherCore* createRightMatcher(const HIPMatcherCore& left)
     rtdm_bm_params p;
     rtdm_bm_right_params(&left.params(), &p);
     Rect none;
-    return new HIPMatcherCore(none, none, p.preFilterCap, p.blockSize, p.minDisparity, p.textureThreshold, p.numDisparities,
-                              p.numDisparities, p.uniquenessRatio, p.speckleWindowSize, p.speckleRange, p.disp12MaxDiff,
-                              left.maxWidth(), left.maxHeight(), 1, left.device(), p.legacy_right_clamp != 0);
+    HIPMatcherCore* m = new HIPMatcherCore(none, none, p.preFilterCap, p.blockSize, p.minDisparity, p.textureThreshold,
+                                           p.numDisparities, p.numDisparities, p.uniquenessRatio, p.speckleWindowSize,
+                                           p.speckleRange, p.disp12MaxDiff, left.maxWidth(), left.maxHeight(), 1, left.device(),
+                                           p.legacy_right_clamp != 0);
+    // not part of rtdm_bm_params (W1: createRightMatcher copies preFilterType and preFilterSize)
+    if (left.preFilterType() != RTDM_PREFILTER_XSOBEL || left.preFilterSize() != 9) {
+        m->setPreFilterSize(left.preFilterSize());
+        m->setPreFilterType(left.preFilterType());
+    }
+    return m;
 }
 HIPSGMCore* createRightMatcher(const HIPSGMCore& left)
 {

@@ -34,6 +34,12 @@ public:
 
     void setROI1(const Rect& roi1);
     void setROI2(const Rect& roi2);
+    // cv::StereoBM::setPreFilterType (RTDM_PREFILTER_XSOBEL, the default, or RTDM_PREFILTER_NORMALIZED_RESPONSE) and
+    // setPreFilterSize (odd, 5 .. 255; read by the normalised response only), from the next compute on.  Return the status.
+    int setPreFilterType(int preFilterType);
+    int setPreFilterSize(int preFilterSize);
+    int preFilterType() const { return preFilterType_; }
+    int preFilterSize() const { return preFilterSize_; }
     // 8-bit single-channel inputs with free row pitch, 16-bit signed fixed-point (x16) output.
     // Returns 0 on success, a negative rtdm_status otherwise (the reference's compute() returns
     // int and its caller ignores it, estimator.cpp:56; nothing here throws).
@@ -64,6 +70,8 @@ private:
     rtdm_bm* bm_ = nullptr;
     int status_ = RTDM_OK;
     int maxWidth_ = 0, maxHeight_ = 0, device_ = 0;
+    int preFilterType_ = RTDM_PREFILTER_XSOBEL, preFilterSize_ = 9;
+    int setPrefilter(int type, int size);
 };
 
 // SWSemiGlobalMatcher counterpart (/root/reference/include/stereo-matcher/sgbm-sw.h:24-37): the same seven

@@ -13,13 +13,18 @@ import numpy as np
 
 from . import binding as B
 
+PREFILTER_NORMALIZED_RESPONSE, PREFILTER_XSOBEL = B.PREFILTER_NORMALIZED_RESPONSE, B.PREFILTER_XSOBEL
+
 
 class HIPMatcher:
     """numOfDisparities: any multiple of 16 with minDisparity + numOfDisparities <= 2047 (up to 4080), any odd blockSize
-    5..255 -- the parameters go to rtdm_bm_create unchanged; only frames wider than 4096 are refused."""
+    5..255 -- the parameters go to rtdm_bm_create unchanged; only frames wider than 4096 are refused.
+    preFilterType (PREFILTER_XSOBEL, PREFILTER_NORMALIZED_RESPONSE) and preFilterSize (odd, 5..255) are cv::StereoBM's;
+    they go through rtdm_bm_set_prefilter, at construction and by setPreFilterType / setPreFilterSize."""
     def __init__(self, roi1=None, roi2=None, preFilterCap=31, blockSize=13, minDisparity=0, textureThreshold=10,
                  numOfDisparities=64, maxDisparity=None, uniquenessRatio=10, speckleWindowSize=100,
-                 speckleRange=32, disp12MaxDiff=1, width=1280, height=720, max_batch=1, device=0, legacy_right_clamp=0):
+                 speckleRange=32, disp12MaxDiff=1, width=1280, height=720, max_batch=1, device=0, legacy_right_clamp=0,
+                 preFilterType=PREFILTER_XSOBEL, preFilterSize=9):
         # roi1/roi2/maxDisparity are accepted and ignored, exactly like bm-sw.cpp:12-26
         self._h = C.c_void_p()
         self.params = B.make_params(preFilterCap, blockSize, minDisparity, numOfDisparities, textureThreshold,
@@ -27,6 +32,34 @@ class HIPMatcher:
         self.width, self.height, self.max_batch, self.device = width, height, max_batch, device
         B.check(B.lib().rtdm_bm_create(C.byref(self.params), width, height, max_batch, device, C.byref(self._h)),
                 "rtdm_bm_create")
+        if (preFilterType, preFilterSize) != (PREFILTER_XSOBEL, 9):
+            try:
+                self._set_prefilter(preFilterType, preFilterSize)
+            except B.RtdmError:
+                self.close()
+                raise
+
+    def _set_prefilter(self, preFilterType, preFilterSize):
+        B.check(B.lib().rtdm_bm_set_prefilter(self._h, int(preFilterType), int(preFilterSize)), "rtdm_bm_set_prefilter")
+
+    def _get_prefilter(self):
+        t, s = C.c_int(), C.c_int()
+        B.check(B.lib().rtdm_bm_get_prefilter(self._h, C.byref(t), C.byref(s)), "rtdm_bm_get_prefilter")
+        return t.value, s.value
+
+    def setPreFilterType(self, preFilterType):
+        """cv::StereoBM::setPreFilterType: applies from the next compute call."""
+        self._set_prefilter(preFilterType, self._get_prefilter()[1])
+
+    def setPreFilterSize(self, preFilterSize):
+        """cv::StereoBM::setPreFilterSize (odd, 5..255; only NORMALIZED_RESPONSE reads it): applies from the next compute call."""
+        self._set_prefilter(self._get_prefilter()[0], preFilterSize)
+
+    def getPreFilterType(self):
+        return self._get_prefilter()[0]
+
+    def getPreFilterSize(self):
+        return self._get_prefilter()[1]
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
@@ -253,7 +286,8 @@ def create_right_matcher(m):
                           textureThreshold=rp.textureThreshold, numOfDisparities=rp.numDisparities,
                           uniquenessRatio=rp.uniquenessRatio, speckleWindowSize=rp.speckleWindowSize,
                           speckleRange=rp.speckleRange, disp12MaxDiff=rp.disp12MaxDiff, width=m.width, height=m.height,
-                          max_batch=m.max_batch, device=m.device, legacy_right_clamp=rp.legacy_right_clamp)
+                          max_batch=m.max_batch, device=m.device, legacy_right_clamp=rp.legacy_right_clamp,
+                          preFilterType=m.getPreFilterType(), preFilterSize=m.getPreFilterSize())
     if isinstance(m, HIPSemiGlobalMatcher):
         rp = B.SGMParams()
         B.check(B.lib().rtdm_sgm_right_params(C.byref(m.params), C.byref(rp)), "rtdm_sgm_right_params")
