@@ -188,8 +188,12 @@ typedef struct rtdm_sgm_params {
     int speckleWindowSize; /* <= 0 disables the speckle filter */
     int speckleRange;      /* multiplied by 16, as cv::StereoSGBM does */
     int disp12MaxDiff;     /* <= 0 -> 1: the library's left-right check cannot be switched off */
-    int paths;             /* 5: MODE_SGBM, the mode sgbm-sw.cpp:15 creates (left, right, down, down-right, down-left);
-                            * 8: MODE_HH, all eight neighbours (BASELINE config 5) */
+    int paths;             /* cv::StereoSGBM::setMode by its direction count.  5: MODE_SGBM, the mode sgbm-sw.cpp:15 creates (left,
+                            * right, down, down-right, down-left); 8: MODE_HH, all eight neighbours (BASELINE config 5);
+                            * 4: MODE_HH4 (OpenCV 3.4 / 4.x), left, right, down, up and no others (rule R4', DESIGN.md section 4
+                            * "K6 for MODE_HH4"; restated from memory, parity with the library unpinned like R1-R12).
+                            * 3 (MODE_SGBM_3WAY): RTDM_ERR_UNSUPPORTED, valid for the library but not implemented.  Any other
+                            * value: RTDM_ERR_BAD_PARAM */
 } rtdm_sgm_params;
 typedef struct rtdm_sgm rtdm_sgm;
 /* blockSize as given, minD 0, P1 600, P2 2400 (sgbm-sw.cpp:17-18), uniqueness 10, speckle 100/32,
@@ -205,9 +209,11 @@ int rtdm_sgm_compute_device(rtdm_sgm* sg, int n, const uint8_t* d_left, const ui
                             int16_t* d_disp, size_t disp_pitch, size_t disp_frame_stride, void* hip_stream);
 /* How the path directions of this handle's calls have run so far: *sweeps = row-synchronous passes launched (three directions
  * each: k_sgm_sweep), *gave_up = 1 once such a pass has given up waiting for a neighbouring strip (the call that finds this
- * returns RTDM_ERR_HIP once; from then on the handle runs one pass per direction).  Either pointer may be NULL. */
+ * returns RTDM_ERR_HIP once; from then on the handle runs one pass per direction).  Either pointer may be NULL.  A MODE_HH4
+ * handle (paths = 4) never runs such a pass -- its vertical directions wait for no other workgroup -- and stays at 0 / 0. */
 int rtdm_sgm_get_pass_stats(const rtdm_sgm* sg, long* sweeps, int* gave_up);
-/* Name of the path-pass form this handle's last call ran: "sweep" (row-synchronous sweeps), "half" (half-wave lines),
+/* Name of the path-pass form this handle's last call ran: "sweep" (row-synchronous sweeps), "vert" (MODE_HH4: the two
+ * horizontal directions and the column-parallel vertical pass, k_sgm_vert), "half" (half-wave lines, one pass per direction),
  * "wide_w1" / "wide_w4" (the wide-line pass, one wave / four waves per line: numDisparities > 256 or forced); "" before the
  * first call. */
 const char* rtdm_sgm_path_variant(const rtdm_sgm* sg);

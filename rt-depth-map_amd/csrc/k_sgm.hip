@@ -1,6 +1,6 @@
 // k_sgm.hip -- the device counterpart of the reference's SWSemiGlobalMatcher (/root/reference/stereo-matcher/
 // sgbm-sw.cpp:12-37 -> cv::StereoSGBM, P1 = 600, P2 = 2400): paths = 5 is the library's MODE_SGBM (what sgbm-sw.cpp:15
-// creates), paths = 8 its MODE_HH (BASELINE config 5, "8-path").  The algorithm is the restatement in
+// creates), paths = 8 its MODE_HH (BASELINE config 5, "8-path"), paths = 4 its MODE_HH4 (left, right, down, up).  The algorithm is the restatement in
 // oracle/sgm_oracle.c (rules R1-R12 there; integer arithmetic, tolerance 0 against that oracle; parity against a real
 // cv::StereoSGBM is unpinned).  Cost volumes live on the column domain [x0, x1) = [minD+D, W+min(minD,0)) and are laid
 // out [frame][y][x - x0][d] with d fastest, so a wavefront's lanes = consecutive disparities = one coalesced line per pixel.
@@ -14,6 +14,8 @@
 //                directions in one launch (-> S, <- S2)
 //   k_sgm_sweep  the three directions that advance a row per step in one row-synchronous pass (adds S2; the last sweep decides
 //                the winners: wave minimum, uniqueness, quadratic sub-pixel) -> 8 bytes per pixel
+//   k_sgm_vert   MODE_HH4's two vertical directions, one pass each: a line per half-wave, neighbouring columns in neighbouring
+//                half-waves, no LDS, no barrier, no wait on another workgroup (the upward pass decides the winners)
 //   k_sgm_lrfinal one workgroup per row: the votes of the integer winners (LDS, right-most voter wins ties: R7) and the
 //                always-on left-right check (R9)
 //   k_sgm_median 3x3 median with clamped coordinates (R10) + the speckle filter's per-row init
@@ -810,7 +812,75 @@ __global__ __launch_bounds__(256) void k_sgm_sweep(const uint16_t* C, uint16_t* 
     }
 }
 
-// The winners that were found inside the last path pass (k_sgm_path_h / k_sgm_sweep / k_sgm_wide, LAST): the votes
+// Column-parallel vertical pass (MODE_HH4, rule R4'): the direction (0, dy) alone.  A vertical line never changes column, so
+// nothing crosses a half-wave: no LDS edge, no barrier, no ring, no wait on another workgroup in any form -- the grid may be of
+// any size and run in any order.  One line per half-wave (k_sgm_path_h's layout, sgm_line_step's recurrence with the previous
+// row's L_r in registers); neighbouring half-waves take neighbouring columns, so a workgroup's row step is one contiguous piece
+// of C and of S (columns per workgroup = blockDim.x / 32).  A lone line is a serial chain of H steps: C and S (and S2) are
+// requested PF rows ahead.  ADD2 (the downward pass after the side-by-side horizontal directions): S2, the (-1, 0) direction's
+// L_r, is added as it is loaded.  LAST (the upward pass): the winners are decided in the lanes (sgm_wta_half), S is not written.
+template <int NP2, bool LAST, bool ADD2, int PF>
+__global__ __launch_bounds__(256) void k_sgm_vert(const uint16_t* C, uint16_t* S, const uint16_t* S2, SGMGeom g, int dy, int P1, int P2,
+                                                  SgmWin* win, int uniq)
+{
+    const int lane = threadIdx.x & 63, hl = lane & 31;
+    const int D = g.D, W1 = g.W1, H = g.H;
+    const int col = blockIdx.x * (blockDim.x >> 5) + (threadIdx.x >> 5);
+    if ((col & ~1) >= W1) return;                                 // whole waves only
+    const bool ok = col < W1;                                     // (an odd W1's last wave: its second half repeats the last column)
+    const int xc = min(col, W1 - 1), f = blockIdx.y;
+    const int d0 = hl * 2 * NP2;
+    const bool live = d0 < D;                                     // D is a multiple of 16 = of 2 * NP2
+    const uint32_t P1s = (uint32_t)P1 * 0x10001u, P2s = (uint32_t)P2 * 0x10001u;
+    const long stride = (long)dy * W1 * D;                        // one row, elements
+    const size_t off0 = ((size_t)f * H + (dy > 0 ? 0 : H - 1)) * W1 * D + (size_t)xc * D + (live ? d0 : 0);
+    const uint16_t* cp = C + off0;
+    uint16_t* sp = S + off0;
+    const uint16_t* tp = ADD2 ? S2 + off0 : nullptr;
+    PackW<NP2> cr[PF], sr[PF], tr[ADD2 ? PF : 1];
+#pragma unroll
+    for (int k = 0; k < PF; ++k) {
+        if (k < H) {
+            cr[k] = ld_w<NP2>(cp + (long)k * stride);
+            sr[k] = ld_w<NP2>(sp + (long)k * stride);
+            if constexpr (ADD2) tr[k] = ld_w<NP2>(tp + (long)k * stride);
+        }
+    }
+    uint32_t l[NP2], mps = 0;
+#pragma unroll
+    for (int r = 0; r < NP2; ++r) l[r] = 0xffffffffu;
+    for (int base = 0; base < H; base += PF) {
+#pragma unroll
+        for (int k = 0; k < PF; ++k) {
+            const int step = base + k;
+            if (step >= H) break;
+            const PackW<NP2> c = cr[k];
+            uint32_t o[NP2];
+#pragma unroll
+            for (int r = 0; r < NP2; ++r) o[r] = sr[k].w[r];
+            if constexpr (ADD2) {
+#pragma unroll
+                for (int r = 0; r < NP2; ++r) o[r] = sgm_min2(sgm_add2(o[r], tr[k].w[r]), 0x7fff7fffu);       // R5
+            }
+            if (step + PF < H) {
+                cr[k] = ld_w<NP2>(cp + (long)(step + PF) * stride);
+                sr[k] = ld_w<NP2>(sp + (long)(step + PF) * stride);
+                if constexpr (ADD2) tr[k] = ld_w<NP2>(tp + (long)(step + PF) * stride);
+            }
+            sgm_line_step<NP2, true>(l, mps, l, mps, c.w, step == 0, live, hl, P1s, P2s);
+#pragma unroll
+            for (int r = 0; r < NP2; ++r) o[r] = sgm_min2(sgm_add2(o[r], l[r]), 0x7fff7fffu);                  // R5
+            if constexpr (!LAST) {
+                if (live && ok) st_w<NP2>(sp + (long)step * stride, o);
+            } else {
+                const SgmWin wv = sgm_wta_half<NP2>(o, live, lane, d0, D, uniq, g.minD);
+                if (hl == 0 && ok) win[((size_t)f * H + (dy > 0 ? step : H - 1 - step)) * W1 + xc] = wv;
+            }
+        }
+    }
+}
+
+// The winners that were found inside the last path pass (k_sgm_path_h / k_sgm_sweep / k_sgm_vert / k_sgm_wide, LAST): the votes
 // of a row (R7), the always-on left-right check (R9) and the row's x16 disparities.  One workgroup per row.
 __global__ __launch_bounds__(256) void k_sgm_lrfinal(const SgmWin* win, Plane16W disp, SGMGeom g, int disp12MaxDiff)
 {
@@ -980,6 +1050,36 @@ static bool launch_sweep(bool last, const SGMGeom& g, const SGMBuffers& b, int d
 static void sgm_finish(Plane16W disp, const SGMGeom& g, const SGMBuffers& b, int disp12MaxDiff, int speckleWindowSize,
                        int speckleRange, int n, hipStream_t stream, const SgmWin* win);
 
+// One k_sgm_path_h launch: half-wave lines, packed arithmetic, eight lines per workgroup.  S2 != null: the two horizontal
+// directions side by side, (dx, 0) -> S and (-dx, 0) -> S2 (first = 1).
+static void launch_path_h(const SGMGeom& g, const SGMBuffers& b, int dx, int dy, int P1, int P2, int first, bool last, int n, SgmWin* win,
+                          int uniq, hipStream_t stream, uint16_t* S2 = nullptr)
+{
+    const int lines = dy == 0 ? g.H : (dx == 0 ? g.W1 : g.W1 + g.H - 1);
+    const dim3 hgrid(((S2 ? 2 : 1) * lines + 7) / 8, n), blk(256);
+#define RTDM_PATHH(N) do { if (last) hipLaunchKernelGGL((k_sgm_path_h<N, 8, true>), hgrid, blk, 0, stream, b.C, b.S, g, dx, dy, P1, P2, first, lines, win, uniq, S2); \
+                           else hipLaunchKernelGGL((k_sgm_path_h<N, 8, false>), hgrid, blk, 0, stream, b.C, b.S, g, dx, dy, P1, P2, first, lines, win, uniq, S2); } while (0)
+    if (g.D <= 64) RTDM_PATHH(1); else if (g.D <= 128) RTDM_PATHH(2); else RTDM_PATHH(4);
+#undef RTDM_PATHH
+}
+
+// One k_sgm_vert launch over (0, dy).  last: the winners instead of S; S2 != null (never with last): S2 is added to S on the way.
+static void launch_vert(const SGMGeom& g, const SGMBuffers& b, int dy, int P1, int P2, bool last, int n, SgmWin* win, int uniq,
+                        hipStream_t stream, const uint16_t* S2)
+{
+    // columns per workgroup and rows of prefetch, by measurement (profiles/sgm_hh4_time.txt: 720p, D = 128, 1 / 4 / 16 pairs per
+    // call): 2 columns -- one wave per workgroup, so that a lone pair's 576 waves spread over all compute units -- and 8 rows
+    // (2 / 4 / 16 rows: 14 % / 6 % / 3 % slower at one pair per call; 4 or 8 columns: 2 % to 15 % slower there; all within 4 %
+    // of each other at 16 pairs); D = 64 and D = 256 agree
+    constexpr int cols = 2, PF = 8;
+    const dim3 vgrid((g.W1 + cols - 1) / cols, n), blk(32 * cols);
+#define RTDM_VERT(N) do { if (last) hipLaunchKernelGGL((k_sgm_vert<N, true, false, PF>), vgrid, blk, 0, stream, b.C, b.S, S2, g, dy, P1, P2, win, uniq); \
+                          else if (S2) hipLaunchKernelGGL((k_sgm_vert<N, false, true, PF>), vgrid, blk, 0, stream, b.C, b.S, S2, g, dy, P1, P2, win, uniq); \
+                          else hipLaunchKernelGGL((k_sgm_vert<N, false, false, PF>), vgrid, blk, 0, stream, b.C, b.S, S2, g, dy, P1, P2, win, uniq); } while (0)
+    if (g.D <= 64) RTDM_VERT(1); else if (g.D <= 128) RTDM_VERT(2); else RTDM_VERT(4);
+#undef RTDM_VERT
+}
+
 // rtdm_debug_sgm_cost16: the u16 cost forms for gray frames as well (they must give what the u8 forms give)
 static std::atomic<int> g_cost16{0};
 void sgm_cost16_set(int on) { g_cost16.store(on ? 1 : 0, std::memory_order_relaxed); }
@@ -1061,12 +1161,12 @@ const char* launch_sgm(Plane8 L, Plane8 R, Plane16W disp, const SGMGeom& g, cons
     }
     }
     static const int dirs[8][2] = {{1, 0}, {-1, 0}, {0, 1}, {0, -1}, {1, 1}, {-1, 1}, {1, -1}, {-1, -1}};
-    const int last_dir = paths == 5 ? 5 : 7;
+    const int last_dir = paths == 4 ? 3 : (paths == 5 ? 5 : 7);   // MODE_HH4 (R4'): the first four directions and no others
     SgmWin* win = (SgmWin*)b.gr;                     // the right image's bounds are dead once the pixel costs exist: 8 bytes per pixel
     // D > 256 (or rtdm_debug_sgm_wide_paths): one wide pass per direction (k_sgm_wide.hip), the last one deciding the winners;
     // none of the forms below -- they hold at most 256 disparities per line
     if (g.D > 256 || sgm_wide_mode()) {
-        for (int k = 0; k < 8; ++k) {
+        for (int k = 0; k <= last_dir; ++k) {
             if (paths == 5 && dirs[k][1] < 0) continue;
             launch_sgm_wide(g, b.C, b.S, dirs[k][0], dirs[k][1], P1, P2, k == 0 ? 1 : 0, k == last_dir, n, win, uniq, stream);
         }
@@ -1082,6 +1182,23 @@ const char* launch_sgm(Plane8 L, Plane8 R, Plane16W disp, const SGMGeom& g, cons
     // RTDM_SGM_DUAL=0 (test hook): the two horizontal directions one after the other (the second adds to S) instead of side by
     // side -- what runs without S2
     static const int dual_env = env_int("RTDM_SGM_DUAL", 1);
+    if (paths == 4) {
+        // MODE_HH4: -> and <- (side by side into S and S2 where there is an S2), then the two vertical directions on the
+        // column-parallel pass, the upward one deciding the winners -- no sweep, no ring, no epoch, no sweep stream.
+        // RTDM_SGM_SWEEP=0: one k_sgm_path_h pass per direction instead (what k_sgm_vert is timed against)
+        if (!sweep_env) {
+            for (int k = 0; k < 4; ++k) launch_path_h(g, b, dirs[k][0], dirs[k][1], P1, P2, k == 0, k == 3, n, win, uniq, stream);
+            sgm_finish(disp, g, b, disp12MaxDiff, speckleWindowSize, speckleRange, n, stream, win);
+            return "half";
+        }
+        const bool dual = dual_env && b.S2;
+        launch_path_h(g, b, 1, 0, P1, P2, 1, false, n, win, uniq, stream, dual ? b.S2 : nullptr);
+        if (!dual) launch_path_h(g, b, -1, 0, P1, P2, 0, false, n, win, uniq, stream);
+        launch_vert(g, b, 1, P1, P2, false, n, win, uniq, stream, dual ? b.S2 : nullptr);
+        launch_vert(g, b, -1, P1, P2, true, n, win, uniq, stream, nullptr);
+        sgm_finish(disp, g, b, disp12MaxDiff, speckleWindowSize, speckleRange, n, stream, win);
+        return "vert";
+    }
     bool s2_pending = false;                         // S2 holds the (-1, 0) direction's L_r and has not been added to S yet
     bool swept = false;                              // a row-synchronous sweep ran (the variant this call reports)
     for (int k = 0; k < 8; ++k) {
@@ -1090,10 +1207,7 @@ const char* launch_sgm(Plane8 L, Plane8 R, Plane16W disp, const SGMGeom& g, cons
         if (k == 0 && sweep && dual_env && b.S2 &&
             launch_sweep(paths == 5, g, b, 1, P1, P2, n, win, uniq, stream, nullptr, true)) {
             // both horizontal directions in one launch: (1, 0) -> S, (-1, 0) -> S2; the downward sweep adds the two up
-            const dim3 hgrid((2 * g.H + 7) / 8, n);
-#define RTDM_PATHD(N) hipLaunchKernelGGL((k_sgm_path_h<N, 8, false>), hgrid, blk, 0, stream, b.C, b.S, g, 1, 0, P1, P2, 1, g.H, win, uniq, b.S2)
-            if (g.D <= 64) RTDM_PATHD(1); else if (g.D <= 128) RTDM_PATHD(2); else RTDM_PATHD(4);
-#undef RTDM_PATHD
+            launch_path_h(g, b, 1, 0, P1, P2, 1, false, n, win, uniq, stream, b.S2);
             s2_pending = true;
             continue;
         }
@@ -1113,15 +1227,7 @@ const char* launch_sgm(Plane8 L, Plane8 R, Plane16W disp, const SGMGeom& g, cons
                 s2_pending = false;
             }
         }
-        const int lines = dy == 0 ? g.H : (dx == 0 ? g.W1 : g.W1 + g.H - 1);
-        const bool last = k == last_dir;
-        // half-wave lines, packed arithmetic: eight lines per workgroup
-        const dim3 hgrid((lines + 7) / 8, n);
-        const int first = k == 0 ? 1 : 0;
-#define RTDM_PATHH(N, P) do { if (last) hipLaunchKernelGGL((k_sgm_path_h<N, P, true>), hgrid, blk, 0, stream, b.C, b.S, g, dx, dy, P1, P2, first, lines, win, uniq, (uint16_t*)nullptr); \
-                              else hipLaunchKernelGGL((k_sgm_path_h<N, P, false>), hgrid, blk, 0, stream, b.C, b.S, g, dx, dy, P1, P2, first, lines, win, uniq, (uint16_t*)nullptr); } while (0)
-        if (g.D <= 64) RTDM_PATHH(1, 8); else if (g.D <= 128) RTDM_PATHH(2, 8); else RTDM_PATHH(4, 8);
-#undef RTDM_PATHH
+        launch_path_h(g, b, dx, dy, P1, P2, k == 0, k == last_dir, n, win, uniq, stream);
     }
     sgm_finish(disp, g, b, disp12MaxDiff, speckleWindowSize, speckleRange, n, stream, win);
     return swept ? "sweep" : "half";

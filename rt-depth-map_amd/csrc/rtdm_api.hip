@@ -1020,7 +1020,10 @@ int rtdm_sgm_create(const rtdm_sgm_params* params, int max_width, int max_height
     rtdm_sgm_params p = *params;
     if (p.numDisparities <= 0 || p.numDisparities % 16 != 0 || p.blockSize < 1) return RTDM_ERR_BAD_PARAM;
     if (p.uniquenessRatio > 100) return RTDM_ERR_BAD_PARAM;
-    if (p.paths != 5 && p.paths != 8) return RTDM_ERR_BAD_PARAM;
+    // cv::StereoSGBM's modes by their direction count: 5 MODE_SGBM, 8 MODE_HH, 4 MODE_HH4 (R4'); 3 is MODE_SGBM_3WAY, which the
+    // library serves and this build does not
+    if (p.paths == 3) return RTDM_ERR_UNSUPPORTED;
+    if (p.paths != 4 && p.paths != 5 && p.paths != 8) return RTDM_ERR_BAD_PARAM;
     // cv::StereoSGBM never checks the parity of blockSize: its window is SADWindowSize / 2 either side, an even size runs as
     // the next odd one (sgbm-sw.cpp:15 hands the caller's blockSize straight through)
     p.blockSize = p.blockSize / 2 * 2 + 1;
@@ -1060,9 +1063,10 @@ int rtdm_sgm_create(const rtdm_sgm_params* params, int max_width, int max_height
     if (e == hipSuccess) e = hipMalloc((void**)&sg->b.ovf, sizeof(int32_t));
     if (e == hipSuccess) e = hipMemset(sg->b.ovf, 0, sizeof(int32_t));
     if (e == hipSuccess) e = hipHostMalloc((void**)&sg->hOvf, sizeof(int32_t), hipHostMallocDefault);
-    sg->b.ring_words = sgm_ring_words(max_width, p.numDisparities, max_batch);
-    if (e == hipSuccess) e = hipMalloc((void**)&sg->b.ring, sg->b.ring_words * sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMemset(sg->b.ring, 0, sg->b.ring_words * sizeof(unsigned long long));
+    // (MODE_HH4 never runs a row-synchronous sweep: no edge ring)
+    sg->b.ring_words = p.paths == 4 ? 0 : sgm_ring_words(max_width, p.numDisparities, max_batch);
+    if (e == hipSuccess && sg->b.ring_words) e = hipMalloc((void**)&sg->b.ring, sg->b.ring_words * sizeof(unsigned long long));
+    if (e == hipSuccess && sg->b.ring_words) e = hipMemset(sg->b.ring, 0, sg->b.ring_words * sizeof(unsigned long long));
     if (e == hipSuccess) e = hipHostMalloc((void**)&sg->b.abortf, sizeof(int32_t), hipHostMallocMapped);
     // (C, S and S2 are whole allocations, so at least 256-byte aligned: the path passes' packed loads and stores need 16 bytes)
     if (e == hipSuccess && !wide && hipMalloc((void**)&sg->b.S2, vol * 2) != hipSuccess) { (void)hipGetLastError(); sg->b.S2 = nullptr; }   // (optional: without it the horizontal passes run one after the other)

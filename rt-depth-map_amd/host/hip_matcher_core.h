@@ -77,9 +77,14 @@ private:
 // SWSemiGlobalMatcher counterpart (/root/reference/include/stereo-matcher/sgbm-sw.h:24-37): the same seven
 // constructor arguments in the same order plus the frame size; P1 = 600 and P2 = 2400 as sgbm-sw.cpp:17-18
 // hard-codes them; setROI1/2 are no-ops there too.  paths = 8 (BASELINE config 5) or 5: the directions of
-// cv::StereoSGBM's default MODE_SGBM, which is what sgbm-sw.cpp:15 creates -- the adapter sgbm-hip.cpp passes 5.
+// cv::StereoSGBM's default MODE_SGBM, which is what sgbm-sw.cpp:15 creates -- the adapter sgbm-hip.cpp passes 5 unless told
+// another mode; 4: MODE_HH4 (left, right, down, up).  pathsForMode maps cv::StereoSGBM::setMode's values to the direction
+// count; MODE_SGBM_3WAY maps to 3, which rtdm_sgm_create refuses (RTDM_ERR_UNSUPPORTED), anything else to 0 (RTDM_ERR_BAD_PARAM).
+enum SGMMode { MODE_SGBM = 0, MODE_HH = 1, MODE_SGBM_3WAY = 2, MODE_HH4 = 3 };   // cv::StereoSGBM's values
 class HIPSGMCore {
 public:
+    static int pathsForMode(int mode)
+    { return mode == MODE_SGBM ? 5 : (mode == MODE_HH ? 8 : (mode == MODE_SGBM_3WAY ? 3 : (mode == MODE_HH4 ? 4 : 0))); }
     HIPSGMCore(int blockSize, int minDisparity, int numOfDisparities, int uniquenessRatio, int speckleWindowSize,
                int speckleRange, int disp12MaxDiff, int maxWidth, int maxHeight, int device = 0, int paths = 8);
     ~HIPSGMCore();

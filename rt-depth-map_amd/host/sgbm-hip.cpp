@@ -6,10 +6,11 @@
 #include "stereo-matcher/sgbm-hip.h"
 
 HIPSemiGlobalMatcher::HIPSemiGlobalMatcher(int blockSize, int minDisparity, int numOfDisparities, int uniquenessRatio,
-		int speckleWindowSize, int speckleRange, int disp12MaxDiff, int width, int height)
+		int speckleWindowSize, int speckleRange, int disp12MaxDiff, int width, int height, int mode)
 {
+	/* the default mode, MODE_SGBM, is the five directions StereoSGBM::create gives sgbm-sw.cpp:15 */
 	core = new rtdm::HIPSGMCore(blockSize, minDisparity, numOfDisparities, uniquenessRatio, speckleWindowSize,
-			speckleRange, disp12MaxDiff, width, height, 0, 5 /* the five directions of StereoSGBM's default mode */);
+			speckleRange, disp12MaxDiff, width, height, 0, rtdm::HIPSGMCore::pathsForMode(mode));
 }
 
 HIPSemiGlobalMatcher::~HIPSemiGlobalMatcher()

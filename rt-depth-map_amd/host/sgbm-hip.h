@@ -2,7 +2,7 @@
  * sgbm-hip.h -- install as include/stereo-matcher/sgbm-hip.h.  HIPSemiGlobalMatcher derives from the reference's
  * BlockMatcher with SWSemiGlobalMatcher's constructor (include/stereo-matcher/sgbm-sw.h:27-28) plus the frame size.
  * Like SWSemiGlobalMatcher it is not selected by main.cpp unless the maintainer does so.  The device module runs
- * cv::StereoSGBM's MODE_SGBM as restated in oracle/sgm_oracle.c (bit-exact against that restatement; against the
+ * cv::StereoSGBM's MODE_SGBM (or, by the trailing mode argument, MODE_HH or MODE_HH4; MODE_SGBM_3WAY is refused) as restated in oracle/sgm_oracle.c (bit-exact against that restatement; against the
  * library itself parity is unpinned); numOfDisparities is any multiple of 16, as in the library (checked by the device module,
  * not here; above 256 the path passes run on its wide-line kernel); an even blockSize runs as the next odd one (as in the library); where a window is large enough, a frame whose block cost + P2 would pass 32767 (where the library's 16-bit costs wrap) makes compute return an error.
  * compute takes CV_8UC1 or CV_8UC3 pairs and setPreFilterCap takes 0 .. 127, as cv::StereoSGBM does (the colour pixel cost
@@ -18,7 +18,8 @@ class HIPSemiGlobalMatcher: public BlockMatcher
 {
 public:
 	HIPSemiGlobalMatcher(int blockSize, int minDisparity, int numOfDisparities, int uniquenessRatio,
-			int speckleWindowSize, int speckleRange, int disp12MaxDiff, int width, int height);
+			int speckleWindowSize, int speckleRange, int disp12MaxDiff, int width, int height,
+			int mode = rtdm::MODE_SGBM /* cv::StereoSGBM::setMode: MODE_SGBM, MODE_HH, MODE_HH4 */);
 	~HIPSemiGlobalMatcher();
 	int compute(cv::InputArray left, cv::InputArray right, cv::OutputArray out);
 	int setPreFilterCap(int preFilterCap) { return core->setPreFilterCap(preFilterCap); }

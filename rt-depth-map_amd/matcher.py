@@ -171,12 +171,26 @@ class HIPSemiGlobalMatcher:
     speckleWindowSize, speckleRange, disp12MaxDiff; P1/P2 are the literals of sgbm-sw.cpp:17-18.  numOfDisparities is
     any multiple of 16, as in cv::StereoSGBM (above 256 the path passes run on the wide-line kernel); the library checks it.
     preFilterCap is cv::StereoSGBM's (0 .. 127, setPreFilterCap); compute / compute_device take gray (H x W) or
-    interleaved colour (H x W x 3) uint8 frames, as cv::StereoSGBM::compute takes CV_8UC1 and CV_8UC3."""
+    interleaved colour (H x W x 3) uint8 frames, as cv::StereoSGBM::compute takes CV_8UC1 and CV_8UC3.
+    mode is cv::StereoSGBM::setMode's value (MODE_SGBM, MODE_HH, MODE_HH4; MODE_SGBM_3WAY is refused by the library with
+    RTDM_ERR_UNSUPPORTED); paths names the same thing by its direction count (5, 8, 4) and defaults to 8."""
+
+    MODE_SGBM, MODE_HH, MODE_SGBM_3WAY, MODE_HH4 = 0, 1, 2, 3          # cv::StereoSGBM's values
+    _MODE_PATHS = {MODE_SGBM: 5, MODE_HH: 8, MODE_SGBM_3WAY: 3, MODE_HH4: 4}
 
     def __init__(self, blockSize=5, minDisparity=0, numOfDisparities=128, uniquenessRatio=10, speckleWindowSize=100,
-                 speckleRange=32, disp12MaxDiff=1, P1=600, P2=2400, width=1280, height=720, max_batch=1, device=0, paths=8,
-                 preFilterCap=0):
-        # paths: 5 = cv::StereoSGBM's default MODE_SGBM (what sgbm-sw.cpp:15 creates), 8 = MODE_HH (BASELINE config 5)
+                 speckleRange=32, disp12MaxDiff=1, P1=600, P2=2400, width=1280, height=720, max_batch=1, device=0, paths=None,
+                 preFilterCap=0, mode=None):
+        # paths: 5 = cv::StereoSGBM's default MODE_SGBM (what sgbm-sw.cpp:15 creates), 8 = MODE_HH (BASELINE config 5),
+        # 4 = MODE_HH4 (the two horizontal and the two vertical directions)
+        if mode is not None:
+            if mode not in self._MODE_PATHS:
+                raise ValueError("mode must be MODE_SGBM (0), MODE_HH (1), MODE_SGBM_3WAY (2) or MODE_HH4 (3); got %r" % (mode,))
+            if paths is not None and paths != self._MODE_PATHS[mode]:
+                raise ValueError("mode=%d means paths=%d; got paths=%d" % (mode, self._MODE_PATHS[mode], paths))
+            paths = self._MODE_PATHS[mode]
+        elif paths is None:
+            paths = 8
         self._h = C.c_void_p()
         self.params = B.SGMParams(blockSize, minDisparity, numOfDisparities, P1, P2, uniquenessRatio, speckleWindowSize,
                                   speckleRange, disp12MaxDiff, paths)
@@ -216,6 +230,11 @@ class HIPSemiGlobalMatcher:
     def filtered(self):
         return (self.params.minDisparity - 1) * 16
 
+    @property
+    def mode(self):
+        """cv::StereoSGBM::getMode of this matcher's direction set"""
+        return {v: k for k, v in self._MODE_PATHS.items()}[self.params.paths]
+
     @staticmethod
     def _channels(shape, lead):
         """channel count of a gray (lead + (H, W)) or colour (lead + (H, W, 3)) frame shape"""
@@ -251,7 +270,7 @@ class HIPSemiGlobalMatcher:
 
     @property
     def path_variant(self):
-        """the path-pass form of the last call: "sweep", "half", "wide_w1", "wide_w4" -- rtdm_sgm_path_variant"""
+        """the path-pass form of the last call: "sweep", "vert", "half", "wide_w1", "wide_w4" -- rtdm_sgm_path_variant"""
         return B.lib().rtdm_sgm_path_variant(self._h).decode()
 
     def compute_device(self, d_left, d_right, d_disp, stream=None):
