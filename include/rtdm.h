@@ -373,6 +373,68 @@ int rtdm_bm_compute_filtered(rtdm_bm* left_bm, rtdm_bm* right_bm, rtdm_wls* wls,
                              const uint8_t* right, size_t right_pitch, int width, int height, int16_t* out, size_t out_pitch,
                              int16_t* raw_left, size_t raw_left_pitch);
 
+/* ---- the depth map and the point cloud: reprojectImageTo3D on the device ----------------------------------------------------
+ * rtdm_xyz_map    <- estimator.cpp:75-77: left_disp /= 16.; reprojectImageTo3D(left_disp, xyz, Q, true, CV_32F): the xyz image
+ *                    (height x width x 3 interleaved floats, CV_32FC3) that the reference hands to calc_depth, and / or its Z
+ *                    plane (height x width floats), from an x16 disparity map.
+ * rtdm_xyz_cloud  <- the pixels calc_depth keeps (estimator.cpp:235), compacted in row-major order into 16-byte records with
+ *                    the colour of an optional guide image (the rectified colour crop rtdm_rectify_rgb gives, or a gray view).
+ * The rules X1-X8 are restated in DESIGN.md section 4.11 (from memory of OpenCV: parity with the library is unpinned).  The
+ * homogeneous point is computed in double without fused multiply-adds, h_r = ((Q[4r] x + Q[4r+1] y) + Q[4r+2] d) + Q[4r+3], a
+ * component is (float)(h_r / h_3); where h_3 is 0, inf and NaN are stored as the library stores them.  A pixel is kept iff its
+ * disparity is not (min_disparity - 1) * 16, fabs((double)Z - 10000.0) >= FLT_EPSILON, fabs((double)Z) <= max_z (so NaN is
+ * dropped) and its mask byte, where a mask is given, is non-zero.  Results are bit-identical run to run. */
+#define RTDM_XYZ_FIXED16 0   /* d = disp / 16.0, exact: the sub-pixel value convertTo(CV_32F, 1/16.) gives */
+#define RTDM_XYZ_ROUNDED 1   /* d = disp / 16 rounded half to even: the reference's `left_disp /= 16.` on CV_16S, and the rule of
+                              * rtdm_depth_stats_device */
+typedef struct rtdm_xyz_params {
+    double Q[16];               /* 4x4 row major (stereoRectify's Q, main.cpp:92); every entry finite */
+    int disparity_mode;         /* RTDM_XYZ_FIXED16 | RTDM_XYZ_ROUNDED */
+    int handle_missing_values;  /* 0 | 1: a pixel whose d equals the minimum of d over its own frame gets Z = 10000.0f (X, Y stay) */
+    int min_disparity;          /* of the matcher: the cloud drops its invalid value (min_disparity - 1) * 16 */
+    double max_z;               /* > 0; 10000.0: calc_depth's bound */
+} rtdm_xyz_params;
+typedef struct rtdm_point { float x, y, z; uint8_t r, g, b, a; } rtdm_point;   /* 16 bytes; a = 255; r = g = b = 0 without a guide */
+typedef struct rtdm_xyz rtdm_xyz;
+/* The reference's call: ROUNDED, handle_missing_values 1, max_z 10000.  Q NULL: the identity. */
+void rtdm_xyz_default_params(rtdm_xyz_params* p, const double* Q, int min_disparity);
+/* Parameters are validated before any device use: RTDM_ERR_BAD_PARAM for a mode or a flag other than 0 / 1, a non-finite Q
+ * entry or max_z that is not > 0.  There is no row limit (no 4096 cap): RTDM_ERR_UNSUPPORTED only where max_width *
+ * max_height does not fit an int.  The handle owns its scratch -- frame minima, tile counts, counts, and the single-frame
+ * staging of the host entries (40 bytes per pixel of max_width x max_height) -- so no entry allocates anything per call. */
+int rtdm_xyz_create(const rtdm_xyz_params* params, int max_width, int max_height, int max_batch, int device, rtdm_xyz** out);
+void rtdm_xyz_destroy(rtdm_xyz* xyz);
+int rtdm_xyz_set_params(rtdm_xyz* xyz, const rtdm_xyz_params* params);   /* from the next call on; no synchronisation */
+int rtdm_xyz_get_params(const rtdm_xyz* xyz, rtdm_xyz_params* out);
+/* Host planes, pitches in bytes.  disp: the x16 map; xyz (optional): 3 floats per pixel; z (optional): the Z plane.
+ * RTDM_ERR_BAD_SIZE when both outputs are absent.  Synchronous. */
+int rtdm_xyz_map(rtdm_xyz* xyz, const int16_t* disp, size_t disp_pitch, int width, int height, float* xyz_out, size_t xyz_pitch,
+                 float* z, size_t z_pitch);
+/* n device frames (frame i of a plane at base + i * frame_stride bytes), enqueued on hip_stream, NOT synchronised; n may
+ * exceed max_batch (chunks).  Calls that share a handle must be ordered on one stream: they share its scratch. */
+int rtdm_xyz_map_device(rtdm_xyz* xyz, int n, const int16_t* d_disp, size_t disp_pitch, size_t disp_frame_stride, int width,
+                        int height, float* d_xyz, size_t xyz_pitch, size_t xyz_frame_stride, float* d_z, size_t z_pitch,
+                        size_t z_frame_stride, void* hip_stream);
+/* Host planes.  guide: channels 0 (none; guide may be NULL), 1 (copied to r, g and b) or 3 (interleaved, R first); other
+ * counts: RTDM_ERR_BAD_PARAM, as is a negative capacity.  mask (optional): 8-bit.  *count = the number of kept pixels, even
+ * when it exceeds capacity; only the first min(*count, capacity) records are written and nothing beyond them is touched
+ * (points may be NULL when capacity is 0).  Synchronous. */
+int rtdm_xyz_cloud(rtdm_xyz* xyz, const int16_t* disp, size_t disp_pitch, const uint8_t* guide, size_t guide_pitch, int channels,
+                   const uint8_t* mask, size_t mask_pitch, int width, int height, rtdm_point* points, int capacity, int* count);
+/* n device frames: the records of frame i start at d_points + i * points_frame_stride bytes (4-byte aligned, at least
+ * capacity records apart), capacity holds per frame, d_counts receives n ints.  Enqueued on hip_stream, NOT synchronised. */
+int rtdm_xyz_cloud_device(rtdm_xyz* xyz, int n, const int16_t* d_disp, size_t disp_pitch, size_t disp_frame_stride,
+                          const uint8_t* d_guide, size_t guide_pitch, size_t guide_frame_stride, int channels,
+                          const uint8_t* d_mask, size_t mask_pitch, size_t mask_frame_stride, int width, int height,
+                          rtdm_point* d_points, size_t points_frame_stride, int capacity, int* d_counts, void* hip_stream);
+/* estimator.cpp:56 + 75-77 in one call: bm->compute(left, right) and the cloud of its map, which stays in HBM (disp, optional,
+ * receives it).  The handles live on the same device and xyz's min_disparity equals the matcher's, otherwise
+ * RTDM_ERR_BAD_PARAM.  Synchronous. */
+int rtdm_bm_compute_cloud(rtdm_bm* bm, rtdm_xyz* xyz, const uint8_t* left, size_t left_pitch, const uint8_t* right,
+                          size_t right_pitch, int width, int height, const uint8_t* guide, size_t guide_pitch, int channels,
+                          const uint8_t* mask, size_t mask_pitch, rtdm_point* points, int capacity, int* count, int16_t* disp,
+                          size_t disp_pitch);
+
 /* ---- synthetic rectified-pair stream (stands in for stream/ + decoder/, which are out of
  * scope): frame f of the stream uses seed + f; bit-identical to rt-depth-map_amd/synth.py. */
 int rtdm_synth_pairs_device(uint64_t seed, int first_frame, int n, int width, int height,

@@ -48,6 +48,17 @@ class WLSParams(C.Structure):
         "roi_bottom", "num_iter")] + [("attenuation", C.c_double), ("use_confidence", C.c_int)]
 
 
+class XYZParams(C.Structure):
+    _fields_ = [("Q", C.c_double * 16), ("disparity_mode", C.c_int), ("handle_missing_values", C.c_int),
+                ("min_disparity", C.c_int), ("max_z", C.c_double)]
+
+
+class Point(C.Structure):               # rtdm_point, 16 bytes
+    _fields_ = [("x", C.c_float), ("y", C.c_float), ("z", C.c_float)] + [(n, C.c_uint8) for n in "rgba"]
+
+
+XYZ_FIXED16, XYZ_ROUNDED = 0, 1          # RTDM_XYZ_* in rtdm.h
+
 _lib = None
 
 
@@ -132,6 +143,18 @@ def lib():
         "rtdm_wls_filter_device": (C.c_int, [vp, C.c_int, i16p, sz, sz, i16p, sz, sz, u8p, sz, sz, C.c_int, C.c_int, C.c_int,
                                              i16p, sz, sz, vp, sz, sz, vp, sz, sz, vp]),
         "rtdm_bm_compute_filtered": (C.c_int, [vp, vp, vp, u8p, sz, u8p, sz, C.c_int, C.c_int, i16p, sz, i16p, sz]),
+        "rtdm_xyz_default_params": (None, [C.POINTER(XYZParams), C.POINTER(C.c_double), C.c_int]),
+        "rtdm_xyz_create": (C.c_int, [C.POINTER(XYZParams), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]),
+        "rtdm_xyz_destroy": (None, [vp]),
+        "rtdm_xyz_set_params": (C.c_int, [vp, C.POINTER(XYZParams)]),
+        "rtdm_xyz_get_params": (C.c_int, [vp, C.POINTER(XYZParams)]),
+        "rtdm_xyz_map": (C.c_int, [vp, i16p, sz, C.c_int, C.c_int, vp, sz, vp, sz]),
+        "rtdm_xyz_map_device": (C.c_int, [vp, C.c_int, i16p, sz, sz, C.c_int, C.c_int, vp, sz, sz, vp, sz, sz, vp]),
+        "rtdm_xyz_cloud": (C.c_int, [vp, i16p, sz, u8p, sz, C.c_int, u8p, sz, C.c_int, C.c_int, vp, C.c_int, C.POINTER(C.c_int)]),
+        "rtdm_xyz_cloud_device": (C.c_int, [vp, C.c_int, i16p, sz, sz, u8p, sz, sz, C.c_int, u8p, sz, sz, C.c_int, C.c_int,
+                                            vp, sz, C.c_int, vp, vp]),
+        "rtdm_bm_compute_cloud": (C.c_int, [vp, vp, u8p, sz, u8p, sz, C.c_int, C.c_int, u8p, sz, C.c_int, u8p, sz, vp, C.c_int,
+                                            C.POINTER(C.c_int), i16p, sz]),
         "rtdm_synth_pairs_device": (C.c_int, [C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, u8p, u8p,
                                               sz, sz, C.c_int, vp]),
     }
@@ -154,7 +177,8 @@ EXPORTS = ("rtdm_strerror rtdm_last_hip_error rtdm_abi_version rtdm_device_count
            "rtdm_bm_compute_rgb rtdm_bm_compute_rgb_device rtdm_objects_create rtdm_objects_destroy rtdm_objects_detect "
            "rtdm_estimate_frame rtdm_wls_params_for_bm rtdm_wls_params_for_sgm rtdm_bm_right_params rtdm_sgm_right_params "
            "rtdm_wls_create rtdm_wls_destroy rtdm_wls_set_params rtdm_wls_get_params rtdm_wls_filter rtdm_wls_filter_device "
-           "rtdm_bm_compute_filtered").split()
+           "rtdm_bm_compute_filtered rtdm_xyz_default_params rtdm_xyz_create rtdm_xyz_destroy rtdm_xyz_set_params "
+           "rtdm_xyz_get_params rtdm_xyz_map rtdm_xyz_map_device rtdm_xyz_cloud rtdm_xyz_cloud_device rtdm_bm_compute_cloud").split()
 
 
 def check(status, where):

@@ -243,6 +243,25 @@ struct WlsLaunch {
 };
 void launch_wls(const WlsLaunch& L, int n, hipStream_t stream);
 
+// reprojectImageTo3D and the point cloud (k_xyz.hip, rules X1-X8 in DESIGN.md section 4.11).  A frame is cut into tiles of
+// XYZ_TILE consecutive pixels of its row-major order; minkey holds one int per frame of the launch, tile_cnt
+// xyz_tiles(W, H) ints per frame.  Strides are in elements unless the name says bytes.
+#define XYZ_TILE 1024
+struct XyzParams { double q[16]; double max_z; int mode, hmv, invalid16; };  // invalid16 = (min_disparity - 1) * 16
+struct XyzDisp { const int16_t* base; size_t pitch_e, frame_e; };
+struct XyzMap { float* xyz; size_t xyz_pitch, xyz_frame; float* z; size_t z_pitch, z_frame; };   // either may be null
+struct XyzCloudIn {
+    XyzDisp disp;
+    const uint8_t* guide; size_t gpitch, gframe; int cn;                     // bytes; cn 0: no guide
+    const uint8_t* mask; size_t mpitch, mframe;                              // null: every pixel passes
+};
+struct XyzRec { float x, y, z; uint32_t rgba; };                             // rtdm_point: r in the lowest byte
+int xyz_tiles(int W, int H);
+void launch_xyz_map(XyzDisp D, int n, int W, int H, const XyzParams& P, int* minkey, XyzMap O, hipStream_t stream);
+// counts: n ints (device), the kept pixels of every frame; records at or beyond `capacity` are not written
+void launch_xyz_cloud(const XyzCloudIn& I, int n, int W, int H, const XyzParams& P, int* minkey, int* tile_cnt, XyzRec* points,
+                      size_t points_frame_b, int capacity, int* counts, hipStream_t stream);
+
 // Synthetic stream generator (bit-identical to synth.py).
 void launch_synth(uint64_t seed, int first_frame, int n, int W, int H, int D, Plane8W L, Plane8W R,
                   void* param_scratch, hipStream_t stream);

@@ -249,6 +249,56 @@ HIPSGMCore* createRightMatcher(const HIPSGMCore& left)
     return m;
 }
 
+HIPXYZCore::HIPXYZCore(const double Q[16], int maxWidth, int maxHeight, int minDisparity, int disparityMode,
+                       bool handleMissingValues, double maxZ, int device) : maxWidth_(maxWidth), maxHeight_(maxHeight)
+{
+    rtdm_xyz_default_params(&params_, Q, minDisparity);
+    params_.disparity_mode = disparityMode; params_.handle_missing_values = handleMissingValues ? 1 : 0; params_.max_z = maxZ;
+    status_ = rtdm_xyz_create(&params_, maxWidth, maxHeight, 1, device, &xyz_);
+    if (status_ != RTDM_OK) std::fprintf(stderr, "HIPXYZCore: %s\n", rtdm_strerror(status_));
+}
+HIPXYZCore::~HIPXYZCore() { rtdm_xyz_destroy(xyz_); }
+int HIPXYZCore::set(const rtdm_xyz_params& p)
+{
+    if (!xyz_) return status_ != RTDM_OK ? status_ : RTDM_ERR_NO_DEVICE;
+    status_ = rtdm_xyz_set_params(xyz_, &p);
+    if (status_ == RTDM_OK) params_ = p;
+    return status_;
+}
+int HIPXYZCore::setQ(const double Q[16])
+{
+    if (!Q) return status_ = RTDM_ERR_NULL;
+    rtdm_xyz_params p = params_;
+    for (int i = 0; i < 16; ++i) p.Q[i] = Q[i];
+    return set(p);
+}
+int HIPXYZCore::setDisparityMode(int v) { rtdm_xyz_params p = params_; p.disparity_mode = v; return set(p); }
+int HIPXYZCore::setHandleMissingValues(bool v) { rtdm_xyz_params p = params_; p.handle_missing_values = v ? 1 : 0; return set(p); }
+int HIPXYZCore::setMaxZ(double v) { rtdm_xyz_params p = params_; p.max_z = v; return set(p); }
+int HIPXYZCore::reprojectImageTo3D(const int16_t* disp, size_t dispStep, int rows, int cols, float* xyz, size_t xyzStep, float* z,
+                                   size_t zStep)
+{
+    if (!xyz_) return status_ != RTDM_OK ? status_ : RTDM_ERR_NO_DEVICE;
+    status_ = rtdm_xyz_map(xyz_, disp, dispStep, cols, rows, xyz, xyzStep, z, zStep);
+    return status_;
+}
+int HIPXYZCore::cloud(const int16_t* disp, size_t dispStep, const uint8_t* guide, size_t guideStep, int channels,
+                      const uint8_t* mask, size_t maskStep, int rows, int cols, rtdm_point* points, int capacity, int* count)
+{
+    if (!xyz_) return status_ != RTDM_OK ? status_ : RTDM_ERR_NO_DEVICE;
+    status_ = rtdm_xyz_cloud(xyz_, disp, dispStep, guide, guideStep, channels, mask, maskStep, cols, rows, points, capacity, count);
+    return status_;
+}
+int HIPXYZCore::computeCloud(HIPMatcherCore& matcher, const uint8_t* left, size_t leftStep, const uint8_t* right, size_t rightStep,
+                             int rows, int cols, const uint8_t* guide, size_t guideStep, int channels, const uint8_t* mask,
+                             size_t maskStep, rtdm_point* points, int capacity, int* count, int16_t* disp, size_t dispStep)
+{
+    if (!xyz_) return status_ != RTDM_OK ? status_ : RTDM_ERR_NO_DEVICE;
+    status_ = rtdm_bm_compute_cloud(matcher.handle(), xyz_, left, leftStep, right, rightStep, cols, rows, guide, guideStep,
+                                    channels, mask, maskStep, points, capacity, count, disp, dispStep);
+    return status_;
+}
+
 HIPMorphCore::HIPMorphCore(int w, int h, int bpp, int device) : width_(w), height_(h), bpp_(bpp)
 {
     status_ = (bpp == 8) ? rtdm_morph_create(w, h, 1, device, &mf_) : RTDM_ERR_UNSUPPORTED;

@@ -158,6 +158,43 @@ private:
 HIPMatcherCore* createRightMatcher(const HIPMatcherCore& left);
 HIPSGMCore* createRightMatcher(const HIPSGMCore& left);
 
+// The caller's two lines after the matcher (/root/reference/estimator.cpp:75-76): left_disp /= 16.; reprojectImageTo3D(left_disp,
+// xyz, Q, true, CV_32F) -- the xyz image calc_depth reads -- and the coloured point cloud of the pixels calc_depth keeps (:235).
+// Rules X1-X8 of DESIGN.md section 4.11.  Disparity maps are the matchers' 16-bit x16 maps; steps in bytes.
+class HIPXYZCore {
+public:
+    HIPXYZCore(const double Q[16], int maxWidth, int maxHeight, int minDisparity = 0, int disparityMode = RTDM_XYZ_ROUNDED,
+               bool handleMissingValues = true, double maxZ = 10000.0, int device = 0);
+    ~HIPXYZCore();
+    HIPXYZCore(const HIPXYZCore&) = delete;
+    HIPXYZCore& operator=(const HIPXYZCore&) = delete;
+    int setQ(const double Q[16]);
+    int setDisparityMode(int disparityMode);
+    int setHandleMissingValues(bool handleMissingValues);
+    int setMaxZ(double maxZ);
+    // xyz: rows x cols x 3 floats (CV_32FC3), z: rows x cols floats; either may be null, not both
+    int reprojectImageTo3D(const int16_t* disp, size_t dispStep, int rows, int cols, float* xyz, size_t xyzStep,
+                           float* z = nullptr, size_t zStep = 0);
+    // guide: channels 0 (none), 1 or 3 (R first); mask may be null.  *count = kept pixels; min(*count, capacity) are stored
+    int cloud(const int16_t* disp, size_t dispStep, const uint8_t* guide, size_t guideStep, int channels, const uint8_t* mask,
+              size_t maskStep, int rows, int cols, rtdm_point* points, int capacity, int* count);
+    // estimator.cpp:56 + 75-77 in one call (rtdm_bm_compute_cloud); disp (optional) receives the matcher's map
+    int computeCloud(HIPMatcherCore& matcher, const uint8_t* left, size_t leftStep, const uint8_t* right, size_t rightStep,
+                     int rows, int cols, const uint8_t* guide, size_t guideStep, int channels, const uint8_t* mask,
+                     size_t maskStep, rtdm_point* points, int capacity, int* count, int16_t* disp = nullptr, size_t dispStep = 0);
+    int status() const { return status_; }
+    const rtdm_xyz_params& params() const { return params_; }
+    int maxWidth() const { return maxWidth_; }
+    int maxHeight() const { return maxHeight_; }
+    rtdm_xyz* handle() { return xyz_; }
+
+private:
+    int set(const rtdm_xyz_params& p);
+    rtdm_xyz_params params_;
+    rtdm_xyz* xyz_ = nullptr;
+    int status_ = RTDM_OK, maxWidth_ = 0, maxHeight_ = 0;
+};
+
 // The caller's lines in front of the matcher (/root/reference/estimator.cpp:29-39): cvtColor(RGB2GRAY) + remap with
 // the CV_16SC2 maps of main.cpp:95-96 + crop to roif, for both cameras, on the device.  Not behind an interface in
 // the reference (OpenCV is called inline there), so using it means replacing those lines.
