@@ -7,6 +7,6 @@ nothing in this package falls back to the CPU.
 """
 from . import binding, synth  # noqa: F401
 from .matcher import (POINT_DTYPE, PREFILTER_NORMALIZED_RESPONSE, PREFILTER_XSOBEL, XYZ_FIXED16, XYZ_ROUNDED,  # noqa: F401
-                      HIPDisparityWLSFilter, HIPMatcher, HIPMorphologicalFilter, HIPObjectDetector,  # noqa: F401
+                      HIPDisparityWLSFilter, HIPMatcher, HIPMJPEGDecoder, HIPMorphologicalFilter, HIPObjectDetector,  # noqa: F401
                       HIPReprojector, HIPRectifier, HIPSemiGlobalMatcher, create_disparity_wls_filter, create_right_matcher,
-                      depth_stats_device, estimate_frame, synth_pairs_device, wls_params_for)
+                      depth_stats_device, estimate_frame, mjpeg_probe, synth_pairs_device, wls_params_for)

@@ -12,7 +12,7 @@ LIB_PATH = os.path.join(_HERE, "lib", "librtdm_hip.so")
 
 RTDM_OK = 0
 STATUS = {0: "RTDM_OK", -1: "RTDM_ERR_BAD_PARAM", -2: "RTDM_ERR_BAD_SIZE", -3: "RTDM_ERR_NO_DEVICE",
-          -4: "RTDM_ERR_HIP", -5: "RTDM_ERR_NOMEM", -6: "RTDM_ERR_UNSUPPORTED", -7: "RTDM_ERR_NULL"}
+          -4: "RTDM_ERR_HIP", -5: "RTDM_ERR_NOMEM", -6: "RTDM_ERR_UNSUPPORTED", -7: "RTDM_ERR_NULL", -8: "RTDM_ERR_BAD_STREAM"}
 STAGES = ("prefilter", "search", "lrcheck", "speckle")
 PREFILTER_NORMALIZED_RESPONSE, PREFILTER_XSOBEL = 0, 1   # cv::StereoBM's values (RTDM_PREFILTER_* in rtdm.h)
 
@@ -58,6 +58,12 @@ class Point(C.Structure):               # rtdm_point, 16 bytes
 
 
 XYZ_FIXED16, XYZ_ROUNDED = 0, 1          # RTDM_XYZ_* in rtdm.h
+
+
+class MJPEGInfo(C.Structure):           # rtdm_mjpeg_info
+    _fields_ = [(n, C.c_int) for n in ("width", "height", "components", "h_samp", "v_samp", "restart_interval", "segments",
+                                       "has_dht")]
+
 
 _lib = None
 
@@ -155,6 +161,13 @@ def lib():
                                             vp, sz, C.c_int, vp, vp]),
         "rtdm_bm_compute_cloud": (C.c_int, [vp, vp, u8p, sz, u8p, sz, C.c_int, C.c_int, u8p, sz, C.c_int, u8p, sz, vp, C.c_int,
                                             C.POINTER(C.c_int), i16p, sz]),
+        "rtdm_mjpeg_probe": (C.c_int, [u8p, sz, C.POINTER(MJPEGInfo)]),
+        "rtdm_mjpeg_create": (C.c_int, [C.c_int, C.c_int, C.c_int, sz, C.c_int, C.POINTER(vp)]),
+        "rtdm_mjpeg_destroy": (None, [vp]),
+        "rtdm_mjpeg_decode": (C.c_int, [vp, u8p, sz, C.c_int, C.c_int, u8p, sz]),
+        "rtdm_mjpeg_decode_batch_device": (C.c_int, [vp, C.c_int, C.POINTER(C.c_void_p), C.POINTER(sz), C.c_int, C.c_int, u8p,
+                                                     sz, sz, vp, vp]),
+        "rtdm_bm_compute_mjpeg": (C.c_int, [vp, vp, vp, u8p, sz, u8p, sz, C.c_int, C.c_int, i16p, sz]),
         "rtdm_synth_pairs_device": (C.c_int, [C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, u8p, u8p,
                                               sz, sz, C.c_int, vp]),
     }
@@ -178,7 +191,9 @@ EXPORTS = ("rtdm_strerror rtdm_last_hip_error rtdm_abi_version rtdm_device_count
            "rtdm_estimate_frame rtdm_wls_params_for_bm rtdm_wls_params_for_sgm rtdm_bm_right_params rtdm_sgm_right_params "
            "rtdm_wls_create rtdm_wls_destroy rtdm_wls_set_params rtdm_wls_get_params rtdm_wls_filter rtdm_wls_filter_device "
            "rtdm_bm_compute_filtered rtdm_xyz_default_params rtdm_xyz_create rtdm_xyz_destroy rtdm_xyz_set_params "
-           "rtdm_xyz_get_params rtdm_xyz_map rtdm_xyz_map_device rtdm_xyz_cloud rtdm_xyz_cloud_device rtdm_bm_compute_cloud").split()
+           "rtdm_xyz_get_params rtdm_xyz_map rtdm_xyz_map_device rtdm_xyz_cloud rtdm_xyz_cloud_device rtdm_bm_compute_cloud "
+           "rtdm_mjpeg_probe rtdm_mjpeg_create rtdm_mjpeg_destroy rtdm_mjpeg_decode rtdm_mjpeg_decode_batch_device "
+           "rtdm_bm_compute_mjpeg").split()
 
 
 def check(status, where):

@@ -4,6 +4,7 @@
 // There is no CPU fallback anywhere in this file: every entry point needs a HIP device.
 #include "../../include/rtdm.h"
 #include "rtdm_kernels.h"
+#include "rtdm_mjpeg.h"
 
 #include <algorithm>
 #include <cfloat>
@@ -103,6 +104,7 @@ const char* rtdm_strerror(int s)
         case RTDM_ERR_NOMEM: return "out of memory";
         case RTDM_ERR_UNSUPPORTED: return "configuration not supported by this build";
         case RTDM_ERR_NULL: return "null pointer";
+        case RTDM_ERR_BAD_STREAM: return "damaged or incomplete JPEG stream";
         default: return "unknown rtdm status";
     }
 }
@@ -2170,6 +2172,238 @@ int rtdm_bm_compute_cloud(rtdm_bm* bm, rtdm_xyz* h, const uint8_t* left, size_t 
         HIPC(hipStreamSynchronize(s));
     }
     drain.armed = false;
+    return RTDM_OK;
+}
+
+// ---- DecoderDevice: baseline MJPEG frames (estimator.cpp:24-27; rules J1-J5) ------------------------
+static_assert(sizeof(rtdm_mjpeg_info) == sizeof(MjpegInfo), "rtdm_mjpeg_info and MjpegInfo are one layout");
+static_assert(MJ_BAD_STREAM == RTDM_ERR_BAD_STREAM && MJ_UNSUPPORTED == RTDM_ERR_UNSUPPORTED && MJ_BAD_SIZE == RTDM_ERR_BAD_SIZE &&
+              MJ_NULL == RTDM_ERR_NULL, "rtdm_mjpeg.h restates the status values");
+
+struct rtdm_mjpeg {
+    int maxW, maxH, maxB, device;
+    size_t maxBytes, slot;         // longest stream served; its slot in the staging area (maxBytes rounded up to 16)
+    size_t maxSegs, maxBlocks;     // per frame: entropy segments (one MCU each at worst), 8 x 8 blocks of three full planes
+    hipStream_t stream;
+    hipEvent_t evStaged;           // the staging area is on its way to the device up to here ...
+    bool staged;                   // ... and must not be overwritten before
+    uint8_t* hStreams; MjpegDesc* hDesc; MjpegSeg* hSegs; int* hStatus;     // page-locked
+    uint8_t* dStreams; MjpegDesc* dDesc; MjpegSeg* dSegs;
+    int16_t* dCoef;                // [maxB][blocks][64] dequantised coefficients
+    uint8_t* dPlanes;              // [maxB] planar Y, Cb, Cr at their own (padded) resolutions
+    uint8_t* dRgb;                 // one frame for the host entry point
+    int* dStatus;                  // [maxB + 1]
+};
+
+int rtdm_mjpeg_probe(const uint8_t* stream, size_t len, rtdm_mjpeg_info* out)
+{
+    if (!stream || !out) return RTDM_ERR_NULL;
+    MjpegDesc d;
+    return mjpeg_parse(stream, len, &d, (MjpegInfo*)out, nullptr, 0);
+}
+
+void rtdm_mjpeg_destroy(rtdm_mjpeg* h)
+{
+    if (!h) return;
+    (void)hipSetDevice(h->device);
+    if (h->staged) (void)hipEventSynchronize(h->evStaged);
+    if (h->stream) (void)hipStreamSynchronize(h->stream);
+    void* dev[] = {h->dStreams, h->dDesc, h->dSegs, h->dCoef, h->dPlanes, h->dRgb, h->dStatus};
+    for (void* b : dev) if (b) (void)hipFree(b);
+    void* host[] = {h->hStreams, h->hDesc, h->hSegs, h->hStatus};
+    for (void* b : host) if (b) (void)hipHostFree(b);
+    if (h->evStaged) (void)hipEventDestroy(h->evStaged);
+    if (h->stream) (void)hipStreamDestroy(h->stream);
+    delete h;
+}
+
+int rtdm_mjpeg_create(int max_width, int max_height, int max_batch, size_t max_stream_bytes, int device, rtdm_mjpeg** out)
+{
+    if (!out) return RTDM_ERR_NULL;
+    *out = nullptr;
+    if (max_width <= 0 || max_height <= 0 || max_width > 65535 || max_height > 65535 || max_batch <= 0 || max_batch > 65535)
+        return RTDM_ERR_BAD_SIZE;
+    if (max_stream_bytes < 4 || max_stream_bytes > (size_t)1 << 30) return RTDM_ERR_BAD_SIZE;
+    const size_t slot = (max_stream_bytes + 15) & ~(size_t)15;
+    if (slot * (size_t)max_batch > 0xFFFFFFFFu) return RTDM_ERR_BAD_SIZE;     // stream offsets are 32 bits wide
+    int rc = use_device(device);
+    if (rc) return rc;
+    rtdm_mjpeg* h = new (std::nothrow) rtdm_mjpeg();
+    if (!h) return RTDM_ERR_NOMEM;
+    h->maxW = max_width; h->maxH = max_height; h->maxB = max_batch; h->device = device;
+    h->maxBytes = max_stream_bytes; h->slot = slot;
+    h->maxSegs = (size_t)((max_width + 7) / 8) * ((max_height + 7) / 8);
+    h->maxBlocks = 3 * (size_t)((max_width + 15) / 16 * 2) * ((max_height + 15) / 16 * 2);
+    const size_t B = (size_t)max_batch;
+    hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&h->evStaged, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipHostMalloc((void**)&h->hStreams, slot * B, hipHostMallocDefault);
+    if (e == hipSuccess) e = hipHostMalloc((void**)&h->hDesc, sizeof(MjpegDesc) * B, hipHostMallocDefault);
+    if (e == hipSuccess) e = hipHostMalloc((void**)&h->hSegs, sizeof(MjpegSeg) * h->maxSegs * B, hipHostMallocDefault);
+    if (e == hipSuccess) e = hipHostMalloc((void**)&h->hStatus, sizeof(int) * 2, hipHostMallocDefault);
+    if (e == hipSuccess) e = hipMalloc((void**)&h->dStreams, slot * B);
+    if (e == hipSuccess) e = hipMalloc((void**)&h->dDesc, sizeof(MjpegDesc) * B);
+    if (e == hipSuccess) e = hipMalloc((void**)&h->dSegs, sizeof(MjpegSeg) * h->maxSegs * B);
+    if (e == hipSuccess) e = hipMalloc((void**)&h->dCoef, h->maxBlocks * 128 * B);
+    if (e == hipSuccess) e = hipMalloc((void**)&h->dPlanes, h->maxBlocks * 64 * B);
+    if (e == hipSuccess) e = hipMalloc((void**)&h->dRgb, (size_t)max_width * max_height * 3);
+    if (e == hipSuccess) e = hipMalloc((void**)&h->dStatus, sizeof(int) * (B + 1));
+    if (e != hipSuccess) {
+        g_hip_err = std::string("rtdm_mjpeg_create: ") + hipGetErrorString(e);
+        (void)hipGetLastError();
+        rtdm_mjpeg_destroy(h);
+        return e == hipErrorOutOfMemory ? RTDM_ERR_NOMEM : RTDM_ERR_HIP;
+    }
+    *out = h;
+    return RTDM_OK;
+}
+
+// what a frame of a call must be besides parseable: the call's size, within the handle, the sampling of the call's first frame
+static int mjpeg_fits(const rtdm_mjpeg* h, const MjpegDesc& d, int W, int H, const MjpegDesc* first)
+{
+    if (d.W != W || d.H != H || W > h->maxW || H > h->maxH || d.stream_len > h->maxBytes) return RTDM_ERR_BAD_SIZE;
+    if (first && (first->ncomp != d.ncomp || first->hs != d.hs || first->vs != d.vs)) return RTDM_ERR_BAD_SIZE;
+    return RTDM_OK;
+}
+
+// m <= maxB frames: parse and stage on the host, then copies, the zeroing of coefficients and status words, and the three
+// kernels on s.  *shape: the first frame of the CALL (ncomp 0 before it); d_status: m ints on the device.
+static int mjpeg_chunk(rtdm_mjpeg* h, int m, const uint8_t* const* streams, const size_t* lens, int W, int H, uint8_t* d_rgb,
+                       size_t pitch, size_t frame_stride, int* d_status, hipStream_t s, MjpegDesc* shape)
+{
+    if (h->staged) { HIPC(hipEventSynchronize(h->evStaged)); h->staged = false; }
+    size_t nsegs = 0, bytes = 0;
+    unsigned max_nseg = 1;
+    for (int k = 0; k < m; ++k) {
+        if (!streams[k]) return RTDM_ERR_NULL;
+        MjpegDesc& d = h->hDesc[k];
+        MjpegInfo info;
+        int st = mjpeg_parse(streams[k], lens[k], &d, &info, h->hSegs + nsegs, h->maxSegs);
+        if (st) return st;
+        st = mjpeg_fits(h, d, W, H, shape->ncomp ? shape : nullptr);
+        if (st) return st;
+        if (!shape->ncomp) *shape = d;
+        d.stream_off = (uint32_t)bytes; d.seg_first = (uint32_t)nsegs;
+        memcpy(h->hStreams + bytes, streams[k], d.stream_len);
+        bytes += ((size_t)d.stream_len + 15) & ~(size_t)15;
+        nsegs += d.nseg;
+        max_nseg = std::max(max_nseg, (unsigned)d.nseg);
+    }
+    const size_t nb = mjpeg_frame_blocks(*shape);
+    HIPC(hipMemcpyAsync(h->dStreams, h->hStreams, bytes, hipMemcpyHostToDevice, s));
+    HIPC(hipMemcpyAsync(h->dDesc, h->hDesc, sizeof(MjpegDesc) * m, hipMemcpyHostToDevice, s));
+    HIPC(hipMemcpyAsync(h->dSegs, h->hSegs, sizeof(MjpegSeg) * nsegs, hipMemcpyHostToDevice, s));
+    HIPC(hipEventRecord(h->evStaged, s));
+    h->staged = true;
+    HIPC(hipMemsetAsync(h->dCoef, 0, nb * 128 * m, s));
+    HIPC(hipMemsetAsync(d_status, 0, sizeof(int) * m, s));
+    launch_mjpeg(h->dStreams, h->dDesc, h->dSegs, m, *shape, max_nseg, h->dCoef, h->dPlanes, d_rgb, pitch, frame_stride, d_status, s);
+    HIPC(hipGetLastError());
+    return RTDM_OK;
+}
+
+int rtdm_mjpeg_decode_batch_device(rtdm_mjpeg* h, int n, const uint8_t* const* streams, const size_t* lens, int width, int height,
+                                   uint8_t* d_rgb, size_t pitch, size_t frame_stride, int* d_status, void* hip_stream)
+{
+    if (!h || !streams || !lens || !d_rgb) return RTDM_ERR_NULL;
+    if (n <= 0 || width <= 0 || height <= 0 || width > h->maxW || height > h->maxH) return RTDM_ERR_BAD_SIZE;
+    if (pitch < (size_t)width * 3 || (n > 1 && frame_stride < pitch * (size_t)height)) return RTDM_ERR_BAD_SIZE;
+    MjpegDesc shape;
+    shape.ncomp = 0;
+    if (n > h->maxB) {
+        // a call in chunks: every frame is checked before the first chunk reaches the device
+        MjpegDesc d, first;
+        MjpegInfo info;
+        first.ncomp = 0;
+        for (int k = 0; k < n; ++k) {
+            if (!streams[k]) return RTDM_ERR_NULL;
+            int st = mjpeg_parse(streams[k], lens[k], &d, &info, nullptr, 0);
+            if (st) return st;
+            if (d.nseg > h->maxSegs) return RTDM_ERR_BAD_SIZE;
+            st = mjpeg_fits(h, d, width, height, first.ncomp ? &first : nullptr);
+            if (st) return st;
+            if (!first.ncomp) first = d;
+        }
+    }
+    HIPC(hipSetDevice(h->device));
+    hipStream_t s = (hipStream_t)hip_stream;
+    for (int i0 = 0; i0 < n; i0 += h->maxB) {
+        const int m = std::min(h->maxB, n - i0);
+        const int st = mjpeg_chunk(h, m, streams + i0, lens + i0, width, height, d_rgb + (size_t)i0 * frame_stride, pitch,
+                                   frame_stride, d_status ? d_status + i0 : h->dStatus, s, &shape);
+        if (st) return st;
+    }
+    return RTDM_OK;
+}
+
+int rtdm_mjpeg_decode(rtdm_mjpeg* h, const uint8_t* stream, size_t len, int width, int height, uint8_t* rgb, size_t pitch)
+{
+    if (!h || !stream || !rgb) return RTDM_ERR_NULL;
+    if (width <= 0 || height <= 0 || width > h->maxW || height > h->maxH || pitch < (size_t)width * 3) return RTDM_ERR_BAD_SIZE;
+    MjpegDesc shape;
+    shape.ncomp = 0;
+    // refusals come first: the device is not touched for a frame that is not served
+    {
+        MjpegDesc d;
+        MjpegInfo info;
+        int st = mjpeg_parse(stream, len, &d, &info, nullptr, 0);
+        if (st) return st;
+        st = mjpeg_fits(h, d, width, height, nullptr);
+        if (st) return st;
+    }
+    HIPC(hipSetDevice(h->device));
+    hipStream_t s = h->stream;
+    DrainOnError drain{s};
+    const size_t row = (size_t)width * 3;
+    int st = mjpeg_chunk(h, 1, &stream, &len, width, height, h->dRgb, row, row * height, h->dStatus, s, &shape);
+    if (st) return st;
+    HIPC(hipMemcpy2DAsync(rgb, pitch, h->dRgb, row, row, height, hipMemcpyDeviceToHost, s));
+    HIPC(hipMemcpyAsync(h->hStatus, h->dStatus, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPC(hipStreamSynchronize(s));
+    drain.armed = false;
+    return h->hStatus[0] ? RTDM_ERR_BAD_STREAM : RTDM_OK;
+}
+
+int rtdm_bm_compute_mjpeg(rtdm_bm* bm, rtdm_rectify* rc, rtdm_mjpeg* dec, const uint8_t* left, size_t left_len,
+                          const uint8_t* right, size_t right_len, int width, int height, int16_t* disp, size_t disp_pitch)
+{
+    if (!bm || !rc || !dec || !left || !right || !disp) return RTDM_ERR_NULL;
+    if (bm->device != rc->device || bm->device != dec->device) return RTDM_ERR_BAD_PARAM;
+    if (width != rc->W || height != rc->H || width > dec->maxW || height > dec->maxH) return RTDM_ERR_BAD_SIZE;
+    int st = check_frame(bm, rc->rw, rc->rh);
+    if (st) return st;
+    if (disp_pitch < (size_t)rc->rw * 2) return RTDM_ERR_BAD_SIZE;
+    const uint8_t* src[2] = {left, right};
+    const size_t len[2] = {left_len, right_len};
+    for (int k = 0; k < 2; ++k) {                    // refusals before any device use
+        MjpegDesc d;
+        MjpegInfo info;
+        st = mjpeg_parse(src[k], len[k], &d, &info, nullptr, 0);
+        if (st) return st;
+        st = mjpeg_fits(dec, d, width, height, nullptr);
+        if (st) return st;
+    }
+    HIPC(hipSetDevice(bm->device));
+    hipStream_t s = bm->stream;
+    DrainOnError drain{s};
+    const size_t row = (size_t)width * 3;
+    for (int k = 0; k < 2; ++k) {                    // the two cameras may differ in sampling: one chunk each
+        MjpegDesc shape;
+        shape.ncomp = 0;
+        st = mjpeg_chunk(dec, 1, src + k, len + k, width, height, rc->dRgb[k], row, row * height, dec->dStatus + k, s, &shape);
+        if (st) return st;
+    }
+    HIPC(hipMemcpyAsync(dec->hStatus, dec->dStatus, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
+    const size_t Ws = (size_t)((rc->rw + 7) & ~7);                     // the handle's internal plane (see run_chunk)
+    st = rgb_chunks(bm, rc, 1, rc->dRgb[0], rc->dRgb[1], Plane16W{bm->dOut, Ws, Ws * (size_t)rc->rh}, s);
+    if (st) return st;
+    int16_t* hD = (int16_t*)(bm->hStage + 2 * bm->ppitch * (size_t)bm->maxH);
+    HIPC(hipMemcpyAsync(hD, bm->dOut, Ws * rc->rh * sizeof(int16_t), hipMemcpyDeviceToHost, s));
+    HIPC(hipStreamSynchronize(s));
+    drain.armed = false;
+    if (dec->hStatus[0] || dec->hStatus[1]) return RTDM_ERR_BAD_STREAM;
+    for (int y = 0; y < rc->rh; ++y)
+        memcpy((uint8_t*)disp + (size_t)y * disp_pitch, hD + (size_t)y * Ws, (size_t)rc->rw * sizeof(int16_t));
     return RTDM_OK;
 }
 

@@ -262,6 +262,16 @@ void launch_xyz_map(XyzDisp D, int n, int W, int H, const XyzParams& P, int* min
 void launch_xyz_cloud(const XyzCloudIn& I, int n, int W, int H, const XyzParams& P, int* minkey, int* tile_cnt, XyzRec* points,
                       size_t points_frame_b, int capacity, int* counts, hipStream_t stream);
 
+// Baseline MJPEG frames (k_mjpeg.hip, rules J1-J5 in DESIGN.md section 4.12): m frames of one geometry and sampling (`shape`:
+// any of their descriptors), descriptors, segment table and stream bytes on the device.  d_coef: m * blocks * 64 int16,
+// ZEROED by the caller; d_planes: m * blocks * 64 bytes; d_status: m ints, zeroed by the caller, MJ_BAD_STREAM where the
+// entropy data of a frame is damaged.  max_nseg: the largest segment count among the frames.  (Types: rtdm_mjpeg.h.)
+struct MjpegDesc;
+struct MjpegSeg;
+void launch_mjpeg(const uint8_t* d_streams, const MjpegDesc* d_desc, const MjpegSeg* d_segs, int m, const MjpegDesc& shape,
+                  unsigned max_nseg, int16_t* d_coef, uint8_t* d_planes, uint8_t* d_rgb, size_t pitch, size_t frame_stride,
+                  int* d_status, hipStream_t stream);
+
 // Synthetic stream generator (bit-identical to synth.py).
 void launch_synth(uint64_t seed, int first_frame, int n, int W, int H, int D, Plane8W L, Plane8W R,
                   void* param_scratch, hipStream_t stream);

@@ -299,6 +299,29 @@ int HIPXYZCore::computeCloud(HIPMatcherCore& matcher, const uint8_t* left, size_
     return status_;
 }
 
+HIPMJPEGCore::HIPMJPEGCore(int maxWidth, int maxHeight, size_t maxStreamBytes, int device)
+{
+    if (maxStreamBytes == 0 && maxWidth > 0 && maxHeight > 0) {
+        maxStreamBytes = (size_t)maxWidth * maxHeight * 3;
+        if (maxStreamBytes < 4096) maxStreamBytes = 4096;
+    }
+    status_ = rtdm_mjpeg_create(maxWidth, maxHeight, 1, maxStreamBytes, device, &dec_);
+    if (status_ != RTDM_OK) std::fprintf(stderr, "HIPMJPEGDecoder: %s\n", rtdm_strerror(status_));
+}
+HIPMJPEGCore::~HIPMJPEGCore() { rtdm_mjpeg_destroy(dec_); }
+int HIPMJPEGCore::decode(const uint8_t* in, size_t len, int width, int height, uint8_t* out, size_t outStep)
+{
+    if (!dec_) return status_ != RTDM_OK ? status_ : RTDM_ERR_NO_DEVICE;
+    return rtdm_mjpeg_decode(dec_, in, len, width, height, out, outStep ? outStep : (size_t)width * 3);
+}
+int HIPMJPEGCore::compute(HIPMatcherCore& matcher, HIPRectifierCore& rectifier, const uint8_t* left, size_t leftLen,
+                          const uint8_t* right, size_t rightLen, int width, int height, int16_t* out, size_t outStep)
+{
+    if (!dec_) return status_ != RTDM_OK ? status_ : RTDM_ERR_NO_DEVICE;
+    return rtdm_bm_compute_mjpeg(matcher.handle(), rectifier.handle(), dec_, left, leftLen, right, rightLen, width, height, out,
+                                 outStep);
+}
+
 HIPMorphCore::HIPMorphCore(int w, int h, int bpp, int device) : width_(w), height_(h), bpp_(bpp)
 {
     status_ = (bpp == 8) ? rtdm_morph_create(w, h, 1, device, &mf_) : RTDM_ERR_UNSUPPORTED;

@@ -250,6 +250,30 @@ private:
     int status_ = RTDM_OK;
 };
 
+// DecoderDevice counterpart (the reference's include/decoder/decoder.h:9-15, decoder/mjpeg-decoder-sw.cpp:95-142): one baseline
+// MJPEG frame -> interleaved RGB, decoded on the device with libjpeg's default methods (JDCT_ISLOW, fancy upsampling; rules
+// J1-J5 of DESIGN.md section 4.12 -- the reference asks libjpeg for JDCT_IFAST, which is not served).
+class HIPMJPEGCore {
+public:
+    // maxStreamBytes 0: width * height * 3 (no baseline frame of that size is longer in practice), at least 4096
+    HIPMJPEGCore(int maxWidth, int maxHeight, size_t maxStreamBytes = 0, int device = 0);
+    ~HIPMJPEGCore();
+    HIPMJPEGCore(const HIPMJPEGCore&) = delete;
+    HIPMJPEGCore& operator=(const HIPMJPEGCore&) = delete;
+    // out: height rows of width x 3 bytes (R first), outStep bytes apart (0: width * 3)
+    int decode(const uint8_t* in, size_t len, int width, int height, uint8_t* out, size_t outStep = 0);
+    // estimator.cpp:24-36 + 56 in one call (rtdm_bm_compute_mjpeg): both cameras' frames in, x16 disparity of the crop out
+    int compute(HIPMatcherCore& matcher, HIPRectifierCore& rectifier, const uint8_t* left, size_t leftLen, const uint8_t* right,
+                size_t rightLen, int width, int height, int16_t* out, size_t outStep);
+    static int probe(const uint8_t* in, size_t len, rtdm_mjpeg_info* info) { return rtdm_mjpeg_probe(in, len, info); }
+    int status() const { return status_; }
+    rtdm_mjpeg* handle() { return dec_; }
+
+private:
+    rtdm_mjpeg* dec_ = nullptr;
+    int status_ = RTDM_OK;
+};
+
 // VideoFilterDevice counterpart (/root/reference/include/filter/filter.h:13-37,
 // /root/reference/filter/mf-sw.cpp:10-28): owns the frame buffers it hands out.
 class HIPMorphCore {
