@@ -3,6 +3,7 @@ library decodes from them.  These pin the decoding rules J1-J5 (DESIGN.md sectio
 the files only and do not need Pillow.
 
     python tests/golden/make_mjpeg_golden.py                  # the fixtures
+    python tests/golden/make_mjpeg_golden.py --only NAME...   # some of them
     python tests/golden/make_mjpeg_golden.py --timing 32 DIR  # 32 + 32 1280x720 4:2:2 q85 streams (with / without restart
                                                               # intervals) for tools/time_mjpeg.py; DIR is not committed
 """
@@ -11,7 +12,11 @@ import os
 import sys
 
 import numpy as np
-from PIL import Image
+
+try:
+    from PIL import Image
+except ImportError:           # the image generators below serve tests that run without Pillow
+    Image = None
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
@@ -97,13 +102,20 @@ CASES = {
     "mjpeg_33x17_422_q90_corrupt": (33, 17, "422", 90, texture, 11, {}),
     # chroma planes of two columns: libjpeg replicates them instead of interpolating (J3)
     "mjpeg_4x5_420_q90_narrow": (4, 5, "420", 90, noise4, 12, {}),
+    # more than 256 blocks (k_mjpeg_idct runs a second workgroup), and 264 / 65 / 23 entropy segments (k_mjpeg_huff with 256 lanes
+    # and a second trip, with 128 lanes, with 64); in the 4:2:0 frame Cb starts inside the first workgroup, at block 180
+    "mjpeg_264x64_gray_q50_rst1": (264, 64, "gray", 50, texture, 13, dict(restart_marker_blocks=1)),
+    "mjpeg_200x40_422_q60_rst1": (200, 40, "422", 60, texture, 14, dict(restart_marker_blocks=1)),
+    "mjpeg_137x73_420_q75_rst2": (137, 73, "420", 75, texture, 15, dict(restart_marker_blocks=2)),
 }
 for _i in range(5):
     CASES["mjpeg_97x65_422_q75_batch%d" % _i] = (97, 65, "422", 75, texture, 20 + _i, dict(restart_marker_blocks=3))
 
 
-def fixtures():
+def fixtures(only=None):
     for name, (W, H, sampling, q, make, seed, opts) in CASES.items():
+        if only and name not in only:
+            continue
         stream = encode(make(W, H, seed), sampling, q, **opts)
         extra = {}
         if name.endswith("_nodht"):
@@ -128,6 +140,8 @@ def fixtures():
         np.savez_compressed(path, stream=np.frombuffer(stream, np.uint8), rgb=rgb, **extra)
         assert os.path.getsize(path) < 48 * 1024, name
         print(name, len(stream), "bytes of stream,", os.path.getsize(path), "bytes of file")
+    if only:
+        return
     # what the refusal tests and the default-table test need: a progressive stream, and the DHT payload of a plain stream
     img = texture(16, 8, 30)
     buf = io.BytesIO()
@@ -154,5 +168,7 @@ def timing(count, outdir):
 if __name__ == "__main__":
     if len(sys.argv) >= 4 and sys.argv[1] == "--timing":
         timing(int(sys.argv[2]), sys.argv[3])
+    elif len(sys.argv) >= 3 and sys.argv[1] == "--only":
+        fixtures(sys.argv[2:])
     else:
         fixtures()

@@ -293,9 +293,11 @@ import os  # noqa: E402
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 SINGLE = ["mjpeg_16x8_422_q75", "mjpeg_1x1_420_q75", "mjpeg_33x17_422_q90", "mjpeg_50x34_420_q75_rstrows",
           "mjpeg_97x65_422_q75_rst3", "mjpeg_40x24_444_q100_noise", "mjpeg_64x48_gray_q50_opt", "mjpeg_97x65_422_q30_opt",
-          "mjpeg_96x64_422_q75_nodht", "mjpeg_96x64_422_q75_gradient", "mjpeg_33x17_422_q90_corrupt", "mjpeg_4x5_420_q90_narrow"]
+          "mjpeg_96x64_422_q75_nodht", "mjpeg_96x64_422_q75_gradient", "mjpeg_33x17_422_q90_corrupt", "mjpeg_4x5_420_q90_narrow",
+          "mjpeg_264x64_gray_q50_rst1", "mjpeg_200x40_422_q60_rst1", "mjpeg_137x73_420_q75_rst2"]
 BATCH = ["mjpeg_97x65_422_q75_batch%d" % i for i in range(5)]
-FIXTURES = SINGLE + BATCH                          # sixteen, and the narrow frame that pins J3's replication rule
+FIXTURES = SINGLE + BATCH                          # sixteen, the narrow frame that pins J3's replication rule, and three
+                                                   # frames of more than 256 blocks with 264, 65 and 23 entropy segments
 CORRUPT_SEED, CORRUPT_COUNT = 20240607, 64         # make_mjpeg_golden.py stores eight of these corruptions
 
 
