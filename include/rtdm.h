@@ -21,7 +21,9 @@
 extern "C" {
 #endif
 
-#define RTDM_ABI_VERSION 3   /* 2: rtdm_bm_params.legacy_right_clamp, rtdm_bm_get_tuner_stats; 3: rtdm_sgm_get_pass_stats */
+#define RTDM_ABI_VERSION 3   /* 2: rtdm_bm_params.legacy_right_clamp, rtdm_bm_get_tuner_stats; 3: rtdm_sgm_get_pass_stats;
+                                * additions that only add entry points and types (rtdm_xyz_*, rtdm_mjpeg_*, rtdm_calib_load ..
+                                * rtdm_rectify_create_calib) change nothing for an existing caller and keep the number */
 
 typedef enum rtdm_status {
     RTDM_OK = 0,
@@ -32,7 +34,8 @@ typedef enum rtdm_status {
     RTDM_ERR_NOMEM = -5,
     RTDM_ERR_UNSUPPORTED = -6, /* valid for OpenCV but outside what this build implements */
     RTDM_ERR_NULL = -7,
-    RTDM_ERR_BAD_STREAM = -8   /* a JPEG stream that is damaged or incomplete (rtdm_mjpeg_*) */
+    RTDM_ERR_BAD_STREAM = -8   /* a JPEG stream that is damaged or incomplete (rtdm_mjpeg_*); a calibration file that
+                                * cannot be read or breaks the syntax (rtdm_calib_load) */
 } rtdm_status;
 
 /* Same nine knobs SWMatcherKonolige's constructor forwards to cv::StereoBM
@@ -289,6 +292,56 @@ int rtdm_bm_compute_rgb(rtdm_bm* bm, rtdm_rectify* rc, const uint8_t* rgb_left, 
                         const uint8_t* rgb_right, size_t right_pitch, int16_t* disp, size_t disp_pitch);
 int rtdm_bm_compute_rgb_device(rtdm_bm* bm, rtdm_rectify* rc, int n, const uint8_t* d_rgb_left,
                                const uint8_t* d_rgb_right, int16_t* d_disp, void* hip_stream);
+
+/* ---- rectification from the calibration files (main.cpp:53-98, get_rectified_remap_matrices) ---------------------------------
+ * rtdm_calib_load            <- FileStorage(intrinsics.yml / extrinsics.yml): the subset of OpenCV's YAML 1.0 those files use
+ *                               (`name: !!opencv-matrix` with rows / cols / dt: d / data, `name: [ a, b, c, d ]`, `name: scalar`;
+ *                               unknown keys are skipped).  Required: M1 D1 M2 D2 R T; a D of 4, 5, 8, 12 or 14 entries is
+ *                               zero-padded to 14.  Optional: Width Height ROI1 ROI2 R1 R2 P1 P2 Q -- what the calibration tool
+ *                               stored; *stored_mask says which were there (RTDM_CALIB_HAS_*; the others are zero; width /
+ *                               height are 0 when absent).  stored and stored_mask may be NULL.  RTDM_ERR_BAD_STREAM: a file
+ *                               that cannot be read, is longer than 1 MiB or breaks the syntax; RTDM_ERR_BAD_PARAM: a missing
+ *                               required key, a matrix of another shape or element type, rows * cols unlike the data count.
+ * rtdm_stereo_rectify        <- cv::stereoRectify(M1, D1, M2, D2, size, R, T, R1, R2, P1, P2, Q, flags, alpha, new_size, &roi1,
+ *                               &roi2), rules C1-C9 of DESIGN.md section 4.13.  With alpha = 1 and RTDM_CALIB_ZERO_DISPARITY the
+ *                               result is pinned to what the library itself returned for the reference's three calibrations
+ *                               (recorded in their extrinsics.yml: ROIs and P1 exact, the rest within 1e-12); every other alpha,
+ *                               the reference's own -1 (main.cpp:92) among them, rests on the same restated rules.  flags: 0 or
+ *                               RTDM_CALIB_ZERO_DISPARITY, otherwise RTDM_ERR_BAD_PARAM, as is an R that is no rotation
+ *                               (|R^T R - I| > 1e-6) and a zero baseline.  RTDM_ERR_UNSUPPORTED: a new size other than 0 x 0 or
+ *                               the image size, tilt coefficients (D[12], D[13]), a rotation by pi between the cameras.
+ * Both are host code: they work with no device present.
+ * rtdm_undistort_rectify_map <- initUndistortRectifyMap(M, D, R, P, size, CV_16SC2, map1, map2) on the device: map1 = height x
+ *                               width x 2 int16, map2 = height x width uint16, the maps rtdm_rectify_create takes; M, R: 3 x 3,
+ *                               D: 14, P: 3 x 4, row major.  The ray is accumulated along the row as the library's scalar loop
+ *                               does; bit-identical run to run.  Checked before any device use: RTDM_ERR_BAD_SIZE outside 1 ..
+ *                               32767, RTDM_ERR_BAD_PARAM for a singular P[:3,:3] R or a non-finite entry, RTDM_ERR_UNSUPPORTED
+ *                               for tilt.  The _device form writes device maps (d_map1 4-byte aligned) through hip_stream; both
+ *                               forms return when the maps are complete.
+ * rtdm_rectify_create_calib  <- main.cpp:95-96 + 80-85: both cameras' maps are built in device memory (only their roi part) and
+ *                               never exist on the host; the handle is what rtdm_rectify_create gives for the same maps. */
+typedef struct rtdm_calib { double M1[9], D1[14], M2[9], D2[14], R[9], T[3]; int width, height; } rtdm_calib;
+typedef struct rtdm_rectification { double R1[9], R2[9], P1[12], P2[12], Q[16]; rtdm_region roi1, roi2; } rtdm_rectification;
+#define RTDM_CALIB_ZERO_DISPARITY 1024   /* cv::CALIB_ZERO_DISPARITY */
+#define RTDM_CALIB_HAS_WIDTH 1
+#define RTDM_CALIB_HAS_HEIGHT 2
+#define RTDM_CALIB_HAS_ROI1 4
+#define RTDM_CALIB_HAS_ROI2 8
+#define RTDM_CALIB_HAS_R1 16
+#define RTDM_CALIB_HAS_R2 32
+#define RTDM_CALIB_HAS_P1 64
+#define RTDM_CALIB_HAS_P2 128
+#define RTDM_CALIB_HAS_Q 256
+int rtdm_calib_load(const char* intrinsics_path, const char* extrinsics_path, rtdm_calib* calib, rtdm_rectification* stored,
+                    unsigned* stored_mask);
+int rtdm_stereo_rectify(const rtdm_calib* calib, int flags, double alpha, int new_width, int new_height,
+                        rtdm_rectification* out);
+int rtdm_undistort_rectify_map(const double* M, const double* D, const double* R, const double* P, int width, int height,
+                               int device, int16_t* map1, uint16_t* map2);
+int rtdm_undistort_rectify_map_device(const double* M, const double* D, const double* R, const double* P, int width, int height,
+                                      int device, int16_t* d_map1, uint16_t* d_map2, void* hip_stream);
+int rtdm_rectify_create_calib(const rtdm_calib* calib, const rtdm_rectification* rect, int roi_x, int roi_y, int roi_width,
+                              int roi_height, int max_batch, int device, rtdm_rectify** out);
 
 /* ---- the object detection that yields the matcher's ROI ---------------
  * rtdm_objects_detect <- estimator.cpp:40-53: cvtColor(RGB2BGR) + cvtColor(BGR2HSV) + inRange(low, high) -> filter_in;

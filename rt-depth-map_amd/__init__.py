@@ -9,4 +9,5 @@ from . import binding, synth  # noqa: F401
 from .matcher import (POINT_DTYPE, PREFILTER_NORMALIZED_RESPONSE, PREFILTER_XSOBEL, XYZ_FIXED16, XYZ_ROUNDED,  # noqa: F401
                       HIPDisparityWLSFilter, HIPMatcher, HIPMJPEGDecoder, HIPMorphologicalFilter, HIPObjectDetector,  # noqa: F401
                       HIPReprojector, HIPRectifier, HIPSemiGlobalMatcher, create_disparity_wls_filter, create_right_matcher,
-                      depth_stats_device, estimate_frame, mjpeg_probe, synth_pairs_device, wls_params_for)
+                      depth_stats_device, estimate_frame, init_undistort_rectify_map, load_calibration, mjpeg_probe, stereo_rectify,
+                      synth_pairs_device, wls_params_for)

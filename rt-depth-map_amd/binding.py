@@ -65,6 +65,19 @@ class MJPEGInfo(C.Structure):           # rtdm_mjpeg_info
                                        "has_dht")]
 
 
+class Calib(C.Structure):               # rtdm_calib
+    _fields_ = [("M1", C.c_double * 9), ("D1", C.c_double * 14), ("M2", C.c_double * 9), ("D2", C.c_double * 14),
+                ("R", C.c_double * 9), ("T", C.c_double * 3), ("width", C.c_int), ("height", C.c_int)]
+
+
+class Rectification(C.Structure):       # rtdm_rectification
+    _fields_ = [("R1", C.c_double * 9), ("R2", C.c_double * 9), ("P1", C.c_double * 12), ("P2", C.c_double * 12),
+                ("Q", C.c_double * 16), ("roi1", Region), ("roi2", Region)]
+
+
+CALIB_ZERO_DISPARITY = 1024              # RTDM_CALIB_ZERO_DISPARITY
+CALIB_HAS = {"Width": 1, "Height": 2, "ROI1": 4, "ROI2": 8, "R1": 16, "R2": 32, "P1": 64, "P2": 128, "Q": 256}   # RTDM_CALIB_HAS_*
+
 _lib = None
 
 
@@ -130,6 +143,12 @@ def lib():
         "rtdm_rectify_gray_device": (C.c_int, [vp, C.c_int, u8p, u8p, u8p, u8p, vp]),
         "rtdm_bm_compute_rgb": (C.c_int, [vp, vp, u8p, sz, u8p, sz, i16p, sz]),
         "rtdm_bm_compute_rgb_device": (C.c_int, [vp, vp, C.c_int, u8p, u8p, i16p, vp]),
+        "rtdm_calib_load": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(Calib), C.POINTER(Rectification), C.POINTER(C.c_uint)]),
+        "rtdm_stereo_rectify": (C.c_int, [C.POINTER(Calib), C.c_int, C.c_double, C.c_int, C.c_int, C.POINTER(Rectification)]),
+        "rtdm_undistort_rectify_map": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, i16p, u16p]),
+        "rtdm_undistort_rectify_map_device": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, i16p, u16p, vp]),
+        "rtdm_rectify_create_calib": (C.c_int, [C.POINTER(Calib), C.POINTER(Rectification), C.c_int, C.c_int, C.c_int, C.c_int,
+                                                C.c_int, C.c_int, C.POINTER(vp)]),
         "rtdm_objects_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(vp)]),
         "rtdm_objects_destroy": (None, [vp]),
         "rtdm_objects_detect": (C.c_int, [vp, u8p, sz, C.POINTER(HsvRange), C.c_int, C.c_int, u8p, sz, C.POINTER(Region), C.c_int,
@@ -193,7 +212,8 @@ EXPORTS = ("rtdm_strerror rtdm_last_hip_error rtdm_abi_version rtdm_device_count
            "rtdm_bm_compute_filtered rtdm_xyz_default_params rtdm_xyz_create rtdm_xyz_destroy rtdm_xyz_set_params "
            "rtdm_xyz_get_params rtdm_xyz_map rtdm_xyz_map_device rtdm_xyz_cloud rtdm_xyz_cloud_device rtdm_bm_compute_cloud "
            "rtdm_mjpeg_probe rtdm_mjpeg_create rtdm_mjpeg_destroy rtdm_mjpeg_decode rtdm_mjpeg_decode_batch_device "
-           "rtdm_bm_compute_mjpeg").split()
+           "rtdm_bm_compute_mjpeg rtdm_calib_load rtdm_stereo_rectify rtdm_undistort_rectify_map "
+           "rtdm_undistort_rectify_map_device rtdm_rectify_create_calib").split()
 
 
 def check(status, where):

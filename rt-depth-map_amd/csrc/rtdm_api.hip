@@ -4,6 +4,7 @@
 // There is no CPU fallback anywhere in this file: every entry point needs a HIP device.
 #include "../../include/rtdm.h"
 #include "rtdm_kernels.h"
+#include "rtdm_calib.h"
 #include "rtdm_mjpeg.h"
 
 #include <algorithm>
@@ -1226,32 +1227,61 @@ void rtdm_rectify_destroy(rtdm_rectify* rc)
     delete rc;
 }
 
+// stream, device buffers and the pinned staging area of a handle whose geometry is set
+static hipError_t rectify_alloc(rtdm_rectify* rc)
+{
+    const size_t npx = (size_t)rc->rw * rc->rh, fbytes = (size_t)rc->W * rc->H * 3;
+    hipError_t e = hipStreamCreateWithFlags(&rc->stream, hipStreamNonBlocking);
+    for (int k = 0; k < 2 && e == hipSuccess; ++k) {
+        e = hipMalloc((void**)&rc->dMap1[k], npx * 4);
+        if (e == hipSuccess) e = hipMalloc((void**)&rc->dMap2[k], npx * 2);
+        if (e == hipSuccess) e = hipMalloc((void**)&rc->dRgb[k], fbytes + 16);
+        if (e == hipSuccess) e = hipMalloc((void**)&rc->dGray[k], rc->gpitch * rc->rh * (size_t)rc->maxB);
+    }
+    if (e == hipSuccess) e = hipMalloc((void**)&rc->dOut, npx * 3);
+    if (e == hipSuccess) e = hipHostMalloc((void**)&rc->hStage, 2 * fbytes + npx * 3 + 128 * (size_t)rc->rh, hipHostMallocDefault);
+    return e;
+}
+
+static int rectify_check_geometry(int width, int height, int roi_x, int roi_y, int roi_width, int roi_height, int max_batch)
+{
+    if (width <= 0 || height <= 0 || width > 32767 || height > 32767 || max_batch <= 0) return RTDM_ERR_BAD_SIZE;
+    if (roi_x < 0 || roi_y < 0 || roi_width <= 0 || roi_height <= 0 || roi_x + roi_width > width || roi_y + roi_height > height)
+        return RTDM_ERR_BAD_SIZE;
+    return RTDM_OK;
+}
+
+static rtdm_rectify* rectify_new(int width, int height, int roi_x, int roi_y, int roi_width, int roi_height, int max_batch, int device)
+{
+    rtdm_rectify* rc = new (std::nothrow) rtdm_rectify();
+    if (!rc) return nullptr;
+    rc->W = width; rc->H = height; rc->rx = roi_x; rc->ry = roi_y; rc->rw = roi_width; rc->rh = roi_height;
+    rc->maxB = max_batch; rc->device = device;
+    rc->gpitch = ((size_t)roi_width + 63) & ~(size_t)63;
+    return rc;
+}
+
+static int rectify_create_failed(rtdm_rectify* rc, const char* where, hipError_t e)
+{
+    g_hip_err = std::string(where) + ": " + hipGetErrorString(e);
+    rtdm_rectify_destroy(rc);
+    return e == hipErrorOutOfMemory ? RTDM_ERR_NOMEM : RTDM_ERR_HIP;
+}
+
 int rtdm_rectify_create(const int16_t* map1_left, const uint16_t* map2_left, const int16_t* map1_right,
                         const uint16_t* map2_right, int width, int height, int roi_x, int roi_y, int roi_width,
                         int roi_height, int max_batch, int device, rtdm_rectify** out)
 {
     if (!map1_left || !map2_left || !map1_right || !map2_right || !out) return RTDM_ERR_NULL;
     *out = nullptr;
-    if (width <= 0 || height <= 0 || width > 32767 || height > 32767 || max_batch <= 0) return RTDM_ERR_BAD_SIZE;
-    if (roi_x < 0 || roi_y < 0 || roi_width <= 0 || roi_height <= 0 || roi_x + roi_width > width || roi_y + roi_height > height)
-        return RTDM_ERR_BAD_SIZE;
-    int st = use_device(device);
+    int st = rectify_check_geometry(width, height, roi_x, roi_y, roi_width, roi_height, max_batch);
     if (st) return st;
-    rtdm_rectify* rc = new (std::nothrow) rtdm_rectify();
+    st = use_device(device);
+    if (st) return st;
+    rtdm_rectify* rc = rectify_new(width, height, roi_x, roi_y, roi_width, roi_height, max_batch, device);
     if (!rc) return RTDM_ERR_NOMEM;
-    rc->W = width; rc->H = height; rc->rx = roi_x; rc->ry = roi_y; rc->rw = roi_width; rc->rh = roi_height;
-    rc->maxB = max_batch; rc->device = device;
-    rc->gpitch = ((size_t)roi_width + 63) & ~(size_t)63;
-    const size_t npx = (size_t)roi_width * roi_height, fbytes = (size_t)width * height * 3;
-    hipError_t e = hipStreamCreateWithFlags(&rc->stream, hipStreamNonBlocking);
-    for (int k = 0; k < 2 && e == hipSuccess; ++k) {
-        e = hipMalloc((void**)&rc->dMap1[k], npx * 4);
-        if (e == hipSuccess) e = hipMalloc((void**)&rc->dMap2[k], npx * 2);
-        if (e == hipSuccess) e = hipMalloc((void**)&rc->dRgb[k], fbytes + 16);
-        if (e == hipSuccess) e = hipMalloc((void**)&rc->dGray[k], rc->gpitch * roi_height * (size_t)max_batch);
-    }
-    if (e == hipSuccess) e = hipMalloc((void**)&rc->dOut, npx * 3);
-    if (e == hipSuccess) e = hipHostMalloc((void**)&rc->hStage, 2 * fbytes + npx * 3 + 128 * (size_t)roi_height, hipHostMallocDefault);
+    const size_t npx = (size_t)roi_width * roi_height;
+    hipError_t e = rectify_alloc(rc);
     if (e == hipSuccess) {
         // crop the maps on the host (through the pinned area), one linear copy each
         for (int k = 0; k < 2 && e == hipSuccess; ++k) {
@@ -1267,11 +1297,135 @@ int rtdm_rectify_create(const int16_t* map1_left, const uint16_t* map2_left, con
             if (e == hipSuccess) e = hipMemcpy(rc->dMap2[k], h2, npx * 2, hipMemcpyHostToDevice);
         }
     }
+    if (e != hipSuccess) return rectify_create_failed(rc, "rtdm_rectify_create", e);
+    *out = rc;
+    return RTDM_OK;
+}
+
+// ---- rectification from the calibration files (main.cpp:53-98; rtdm_calib.h, k_rectmap.hip) -------------------------------------
+static_assert(sizeof(rtdm_calib) == sizeof(Calib) && sizeof(rtdm_rectification) == sizeof(Rectification) &&
+              sizeof(rtdm_region) == sizeof(CalibRegion), "rtdm_calib.h restates the layouts of rtdm.h");
+
+int rtdm_calib_load(const char* intrinsics_path, const char* extrinsics_path, rtdm_calib* calib, rtdm_rectification* stored,
+                    unsigned* stored_mask)
+{
+    if (!intrinsics_path || !extrinsics_path || !calib) return RTDM_ERR_NULL;
+    Calib c;
+    Rectification r;
+    unsigned mask = 0;
+    const int st = calib_load(intrinsics_path, extrinsics_path, &c, &r, &mask);
+    if (st) return st;
+    memcpy(calib, &c, sizeof c);
+    if (stored) memcpy(stored, &r, sizeof r);
+    if (stored_mask) *stored_mask = mask;
+    return RTDM_OK;
+}
+
+int rtdm_stereo_rectify(const rtdm_calib* calib, int flags, double alpha, int new_width, int new_height, rtdm_rectification* out)
+{
+    if (!calib || !out) return RTDM_ERR_NULL;
+    Calib c;
+    Rectification r;
+    memcpy(&c, calib, sizeof c);
+    const int st = calib_stereo_rectify(&c, flags, alpha, new_width, new_height, &r);
+    if (st) return st;
+    memcpy(out, &r, sizeof r);
+    return RTDM_OK;
+}
+
+static int rectmap_params(const double* M, const double* D, const double* R, const double* P, int width, int height, RectMapParams* o)
+{
+    const int st = calib_rectmap_check(M, D, R, P, width, height, o->ir);
+    if (st) return st;
+    o->fx = M[0]; o->fy = M[4]; o->u0 = M[2]; o->v0 = M[5];
+    for (int i = 0; i < 12; ++i) o->k[i] = D[i];
+    return RTDM_OK;
+}
+
+// the full maps of one camera into device memory; returns when they are complete
+static int rectmap_full(const RectMapParams& P, int width, int height, int16_t* d_map1, uint16_t* d_map2, hipStream_t s)
+{
+    double* ckpt = nullptr;
+    HIPC(hipMalloc((void**)&ckpt, rectmap_scratch_bytes(0, width, height)));
+    launch_rectmap(P, 0, 0, width, height, ckpt, d_map1, d_map2, s);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    (void)hipFree(ckpt);
     if (e != hipSuccess) {
-        g_hip_err = std::string("rtdm_rectify_create: ") + hipGetErrorString(e);
-        rtdm_rectify_destroy(rc);
-        return e == hipErrorOutOfMemory ? RTDM_ERR_NOMEM : RTDM_ERR_HIP;
+        g_hip_err = std::string("rtdm_undistort_rectify_map: ") + hipGetErrorString(e);
+        return RTDM_ERR_HIP;
     }
+    return RTDM_OK;
+}
+
+int rtdm_undistort_rectify_map_device(const double* M, const double* D, const double* R, const double* P, int width, int height,
+                                      int device, int16_t* d_map1, uint16_t* d_map2, void* hip_stream)
+{
+    if (!M || !D || !R || !P || !d_map1 || !d_map2) return RTDM_ERR_NULL;
+    RectMapParams prm;
+    int st = rectmap_params(M, D, R, P, width, height, &prm);
+    if (st) return st;
+    if (((uintptr_t)d_map1 & 3) || ((uintptr_t)d_map2 & 1)) return RTDM_ERR_BAD_SIZE;
+    st = use_device(device);
+    if (st) return st;
+    return rectmap_full(prm, width, height, d_map1, d_map2, (hipStream_t)hip_stream);
+}
+
+int rtdm_undistort_rectify_map(const double* M, const double* D, const double* R, const double* P, int width, int height,
+                               int device, int16_t* map1, uint16_t* map2)
+{
+    if (!M || !D || !R || !P || !map1 || !map2) return RTDM_ERR_NULL;
+    RectMapParams prm;
+    int st = rectmap_params(M, D, R, P, width, height, &prm);
+    if (st) return st;
+    st = use_device(device);
+    if (st) return st;
+    const size_t npx = (size_t)width * height;
+    int16_t* d1 = nullptr;
+    HIPC(hipMalloc((void**)&d1, npx * 6));                   // map1, then map2 behind it
+    uint16_t* d2 = (uint16_t*)(d1 + npx * 2);
+    st = rectmap_full(prm, width, height, d1, d2, nullptr);
+    hipError_t e = hipSuccess;
+    if (st == RTDM_OK) e = hipMemcpy(map1, d1, npx * 4, hipMemcpyDeviceToHost);
+    if (st == RTDM_OK && e == hipSuccess) e = hipMemcpy(map2, d2, npx * 2, hipMemcpyDeviceToHost);
+    (void)hipFree(d1);
+    if (st) return st;
+    if (e != hipSuccess) {
+        g_hip_err = std::string("rtdm_undistort_rectify_map: ") + hipGetErrorString(e);
+        return RTDM_ERR_HIP;
+    }
+    return RTDM_OK;
+}
+
+int rtdm_rectify_create_calib(const rtdm_calib* calib, const rtdm_rectification* rect, int roi_x, int roi_y, int roi_width,
+                              int roi_height, int max_batch, int device, rtdm_rectify** out)
+{
+    if (!calib || !rect || !out) return RTDM_ERR_NULL;
+    *out = nullptr;
+    const int width = calib->width, height = calib->height;
+    int st = rectify_check_geometry(width, height, roi_x, roi_y, roi_width, roi_height, max_batch);
+    if (st) return st;
+    RectMapParams prm[2];
+    st = rectmap_params(calib->M1, calib->D1, rect->R1, rect->P1, width, height, &prm[0]);
+    if (st == RTDM_OK) st = rectmap_params(calib->M2, calib->D2, rect->R2, rect->P2, width, height, &prm[1]);
+    if (st) return st;
+    st = use_device(device);
+    if (st) return st;
+    rtdm_rectify* rc = rectify_new(width, height, roi_x, roi_y, roi_width, roi_height, max_batch, device);
+    if (!rc) return RTDM_ERR_NOMEM;
+    hipError_t e = rectify_alloc(rc);
+    double* ckpt = nullptr;
+    const size_t cbytes = rectmap_scratch_bytes(roi_x, roi_width, roi_height);
+    if (e == hipSuccess) e = hipMalloc((void**)&ckpt, 2 * cbytes);
+    if (e == hipSuccess) {
+        for (int k = 0; k < 2; ++k)
+            launch_rectmap(prm[k], roi_x, roi_y, roi_width, roi_height, ckpt + k * (cbytes / sizeof(double)), rc->dMap1[k], rc->dMap2[k],
+                           rc->stream);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipStreamSynchronize(rc->stream);
+    }
+    if (ckpt) (void)hipFree(ckpt);
+    if (e != hipSuccess) return rectify_create_failed(rc, "rtdm_rectify_create_calib", e);
     *out = rc;
     return RTDM_OK;
 }

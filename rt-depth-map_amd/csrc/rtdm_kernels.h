@@ -210,6 +210,14 @@ void launch_rectify_gray(RectifySrc L, RectifySrc R, const int16_t* map1L, const
 void launch_rectify_rgb(RectifySrc S, const int16_t* map1, const uint16_t* map2, int sW, int sH, int rw, int rh, Plane8W out,
                         int n, hipStream_t stream);
 
+// initUndistortRectifyMap (k_rectmap.hip): the entries of the rectangle (rx, ry, rw, rh) of the maps of
+// a frame, rh x rw, map1 4-byte aligned.  ir: (P[:3,:3] R)^-1 (calib_rectmap_inverse); k: k1 k2 p1 p2 k3 k4 k5 k6 s1 s2 s3 s4.
+// ckpt: rectmap_scratch_bytes(rx, rw, rh) bytes, in use until the launch has finished.
+struct RectMapParams { double ir[9]; double fx, fy, u0, v0; double k[12]; };
+size_t rectmap_scratch_bytes(int rx, int rw, int rh);
+void launch_rectmap(const RectMapParams& P, int rx, int ry, int rw, int rh, double* ckpt, int16_t* map1, uint16_t* map2,
+                    hipStream_t stream);
+
 // Object detection that produces the matcher's ROI (estimator.cpp:40-53).  rgb: H x W x 3, R first.
 void launch_hsv_inrange(const uint8_t* rgb, size_t pitch, int W, int H, const int lo[3], const int hi[3], uint8_t* mask,
                         size_t mpitch, hipStream_t stream);
