@@ -1,0 +1,647 @@
+// api_bm.hip -- rtdm_bm, the StereoBM counterpart: parameter validation (cv::StereoBM::compute's checks, SURVEY.md Appendix
+// A.1), geometry, staging copies and the launches  K1 prefilter -> K2 search -> K3 left-right check -> K4 speckle filter.
+#include "rtdm_handles.h"
+
+using namespace rtdm;
+
+void rtdm_bm_default_params(rtdm_bm_params* p, int numDisparities)
+{
+    if (!p) return;
+    p->preFilterCap = 31; p->blockSize = 13; p->minDisparity = 0; p->numDisparities = numDisparities;
+    p->textureThreshold = 10; p->uniquenessRatio = 10; p->speckleWindowSize = 100; p->speckleRange = 32;
+    p->disp12MaxDiff = 1; p->legacy_right_clamp = 0;
+}
+
+static int validate_params(const rtdm_bm_params& p)
+{
+    if (p.preFilterCap < 1 || p.preFilterCap > 63) return RTDM_ERR_BAD_PARAM;
+    if (p.blockSize < 5 || p.blockSize > 255 || (p.blockSize & 1) == 0) return RTDM_ERR_BAD_PARAM;
+    if (p.numDisparities <= 0 || p.numDisparities % 16 != 0) return RTDM_ERR_BAD_PARAM;
+    if (p.textureThreshold < 0 || p.uniquenessRatio < 0) return RTDM_ERR_BAD_PARAM;
+    // the x16 fixed-point output is 16 bits wide: (minDisparity - 1) * 16 .. (minDisparity + numDisparities) * 16 must fit
+    if (p.minDisparity < -2047 || (long)p.minDisparity + p.numDisparities > 2047) return RTDM_ERR_BAD_PARAM;
+    if (p.legacy_right_clamp != 0 && p.legacy_right_clamp != 1) return RTDM_ERR_BAD_PARAM;
+    return RTDM_OK;
+}
+
+int rtdm_bm_create(const rtdm_bm_params* params, int max_width, int max_height, int max_batch,
+                   int device, rtdm_bm** out)
+{
+    if (!params || !out) return RTDM_ERR_NULL;
+    *out = nullptr;
+    int rc = validate_params(*params);
+    if (rc) return rc;
+    if (max_width <= 0 || max_height <= 0 || max_batch <= 0 || max_width > 32767 || max_height > 32767)
+        return RTDM_ERR_BAD_SIZE;
+    if ((long)max_batch * max_width * max_height >= (1L << 31)) return RTDM_ERR_BAD_SIZE;
+    if (max_width > 4096) return RTDM_ERR_UNSUPPORTED;   // row kernels keep whole rows in LDS
+    rc = use_device(device);
+    if (rc) return rc;
+    rtdm_bm* bm = new (std::nothrow) rtdm_bm();            // (value-initialised: ROIs, counters, streams and events start as zero)
+    if (!bm) return RTDM_ERR_NOMEM;
+    bm->p = *params; bm->prefilter_type = RTDM_PREFILTER_XSOBEL; bm->prefilter_size = 9;
+    bm->maxW = max_width; bm->maxH = max_height; bm->maxB = max_batch; bm->device = device;
+    bm->ppitch = ((size_t)max_width + 63) & ~(size_t)63;
+    const size_t plane = bm->ppitch * max_height * (size_t)max_batch;
+    // per-pixel workspace and the internal disparity plane use rows of Ws = max_width rounded up to 8 elements
+    const size_t px = bm_ws(max_width) * max_height * max_batch;
+    AllocList& m = bm->mem;
+    m.err = hipStreamCreateWithFlags(&bm->stream, hipStreamNonBlocking);
+    // + slack: the search kernels stage whole dwords of whole tiles and may read past the last row's end
+    // (one allocation, the right planes behind the left ones: k_search_ring addresses both from the left plane's rows)
+    const size_t plane_al = (plane + 1024 + 255) & ~(size_t)255;
+    if (m.dev(&bm->dLp, 2 * plane_al)) bm->dRp = bm->dLp + plane_al;
+    m.dev(&bm->dInL, plane); m.dev(&bm->dInR, plane); m.dev(&bm->dOut, px * sizeof(int16_t));
+    m.dev(&bm->dCost, px * sizeof(int32_t)); m.dev(&bm->dLabel, px * sizeof(int32_t)); m.dev(&bm->dSize, px * sizeof(int32_t));
+    m.dev(&bm->dRuns, px * sizeof(uint32_t)); m.dev(&bm->dHead, px * sizeof(int16_t));
+    m.dev(&bm->dMask, (size_t)max_width * max_height); m.dev(&bm->dDepth, depth_scratch_bytes(RTDM_MAX_REGIONS, max_height));
+    // the staging area: two input planes of ppitch x max_height | hD, the internal plane of one frame | hM, its mask | slack
+    const size_t hplanes = 2 * bm->ppitch * (size_t)max_height, hpx = bm_ws(max_width) * max_height;
+    m.host(&bm->hStage, hplanes + hpx * (sizeof(int16_t) + 1) + 1024);
+    if (bm->hStage) { bm->hD = (int16_t*)(bm->hStage + hplanes); bm->hM = (uint8_t*)(bm->hD + hpx); }
+    m.dev(&bm->dRowCnt, (size_t)max_batch * max_height * sizeof(int32_t));
+    // events and the side streams join the same chain: whatever fails, the handle goes through rtdm_bm_destroy
+    hipError_t e = m.err;
+    const auto new_event = [&e](hipEvent_t* ev) { if (e == hipSuccess) e = hipEventCreateWithFlags(ev, hipEventDisableTiming); };
+    const auto new_stream = [&e](hipStream_t* q) { if (e == hipSuccess) e = hipStreamCreateWithFlags(q, hipStreamNonBlocking); };
+    for (auto& ev : bm->evBand) new_event(&ev);
+    new_stream(&bm->sIn); new_stream(&bm->sOut);
+    for (int k = 0; k < 2; ++k) { new_event(&bm->evH2D[k]); new_event(&bm->evComp[k]); new_event(&bm->evD2H[k]); }
+    // The runtime maps streams onto its few hardware queues in creation order, and which queue the border side stream shares
+    // shows in the search stage (~1 % at the headline).  The streams are therefore created in the order the handle has always
+    // created them: sSpare are the two idle streams of the retired two-lane layout.
+    new_stream(&bm->sSpare[0]); new_stream(&bm->sBorder); new_stream(&bm->sSpare[1]);
+    new_event(&bm->evFork); new_event(&bm->evJoin);
+    if (e != hipSuccess) { rtdm_bm_destroy(bm); return create_failed("rtdm_bm_create", e); }
+    *out = bm;
+    return RTDM_OK;
+}
+
+void rtdm_bm_destroy(rtdm_bm* bm)
+{
+    if (!bm) return;
+    (void)hipSetDevice(bm->device);
+    if (bm->stream) (void)hipStreamSynchronize(bm->stream);
+    if (bm->sBorder) { (void)hipStreamSynchronize(bm->sBorder); (void)hipStreamDestroy(bm->sBorder); }
+    for (auto& q : bm->sSpare) if (q) (void)hipStreamDestroy(q);
+    for (hipEvent_t e : {bm->evFork, bm->evJoin, bm->evBand[0], bm->evBand[1]}) if (e) (void)hipEventDestroy(e);
+    if (bm->sIn) { (void)hipStreamSynchronize(bm->sIn); (void)hipStreamDestroy(bm->sIn); }
+    if (bm->sOut) { (void)hipStreamSynchronize(bm->sOut); (void)hipStreamDestroy(bm->sOut); }
+    for (int k = 0; k < 2; ++k)
+        for (hipEvent_t e : {bm->evH2D[k], bm->evComp[k], bm->evD2H[k]}) if (e) (void)hipEventDestroy(e);
+    for (auto& ev : bm->pending) { (void)hipEventDestroy(ev.a); (void)hipEventDestroy(ev.b); }
+    bm->mem.release();
+    if (bm->stream) (void)hipStreamDestroy(bm->stream);
+    delete bm;
+}
+
+int rtdm_bm_set_roi(rtdm_bm* bm, int which, int x, int y, int width, int height)
+{
+    if (!bm) return RTDM_ERR_NULL;
+    if (which != 1 && which != 2) return RTDM_ERR_BAD_PARAM;
+    int* r = which == 1 ? bm->roi1 : bm->roi2;
+    r[0] = x; r[1] = y; r[2] = width; r[3] = height;
+    return RTDM_OK;
+}
+
+int rtdm_bm_get_params(const rtdm_bm* bm, rtdm_bm_params* out)
+{
+    if (!bm || !out) return RTDM_ERR_NULL;
+    *out = bm->p;
+    return RTDM_OK;
+}
+
+int rtdm_bm_set_prefilter(rtdm_bm* bm, int preFilterType, int preFilterSize)
+{
+    if (!bm) return RTDM_ERR_NULL;
+    if (preFilterType != RTDM_PREFILTER_NORMALIZED_RESPONSE && preFilterType != RTDM_PREFILTER_XSOBEL) return RTDM_ERR_BAD_PARAM;
+    // (cv::StereoBM::compute checks the size whatever the type)
+    if (preFilterSize < 5 || preFilterSize > 255 || (preFilterSize & 1) == 0) return RTDM_ERR_BAD_PARAM;
+    bm->prefilter_type = preFilterType; bm->prefilter_size = preFilterSize;
+    return RTDM_OK;
+}
+
+int rtdm_bm_get_prefilter(const rtdm_bm* bm, int* preFilterType, int* preFilterSize)
+{
+    if (!bm || !preFilterType || !preFilterSize) return RTDM_ERR_NULL;
+    *preFilterType = bm->prefilter_type; *preFilterSize = bm->prefilter_size;
+    return RTDM_OK;
+}
+
+// offsets, valid rectangle (getValidDisparityROI, clipped to the image and
+// to rows that have a full window).  Returns false when the whole frame is FILTERED.
+static bool make_geom(const rtdm_bm* bm, int W, int H, BMGeom* g)
+{
+    const rtdm_bm_params& p = bm->p;
+    g->W = W; g->H = H; g->Ws = (W + 7) & ~7; g->D = p.numDisparities; g->minD = p.minDisparity;
+    g->w = p.blockSize; g->r = p.blockSize / 2;
+    g->cap = p.preFilterCap; g->tex = p.textureThreshold; g->uniq = p.uniquenessRatio;
+    g->lofs = std::max(g->D - 1 + g->minD, 0);
+    g->rofs = -std::min(g->D - 1 + g->minD, 0);
+    g->width1 = W - g->rofs - g->D + 1;
+    g->filtered = (g->minD - 1) * 16;
+    g->want_cost = p.disp12MaxDiff >= 0;
+    g->cost16 = 2L * p.preFilterCap * p.blockSize * p.blockSize < 65536;
+    g->mask_cols = p.disp12MaxDiff < 0;
+    g->legacy = p.legacy_right_clamp;
+    int r1[4] = {0, 0, W, H}, r2[4] = {0, 0, W, H};
+    if (bm->roi1[2] > 0 && bm->roi1[3] > 0) std::copy(bm->roi1, bm->roi1 + 4, r1);
+    if (bm->roi2[2] > 0 && bm->roi2[3] > 0) std::copy(bm->roi2, bm->roi2 + 4, r2);
+    const int maxD = g->minD + g->D - 1;
+    int xmin = std::max(r1[0], r2[0] + maxD) + g->r;
+    int xmax = std::min(r1[0] + r1[2], r2[0] + r2[2] - g->minD) - g->r;
+    int ymin = std::max(r1[1], r2[1]) + g->r;
+    int ymax = std::min(r1[1] + r1[3], r2[1] + r2[3]) - g->r;
+    xmin = std::max(xmin, 0); xmax = std::min(xmax, W);
+    ymin = std::max(ymin, g->r); ymax = std::min(ymax, H - g->r);
+    g->vx0 = xmin; g->vx1 = xmax; g->vy0 = ymin; g->vy1 = ymax;
+    // Columns worth searching (estimator.cpp:54 shrinks the rectangle every frame with setROI1):
+    // validateDisparity lets column x vote for x - round(d/16) in [x - maxD - 1, x - minD + 1] and
+    // reads the votes of x - floor/ceil(d/16), so a valid column depends on searched columns at
+    // most D + |minD| + 2 away.  Everything else is masked to FILTERED anyway.
+    const int reach = (p.disp12MaxDiff >= 0) ? g->D + std::abs(g->minD) + 2 : 0;
+    g->cx0 = std::max(g->lofs, xmin - reach);
+    g->cx1 = std::min(std::min(W, g->lofs + g->width1), xmax + reach);
+    if (g->lofs >= W || g->rofs >= W || g->width1 < 1) return false;
+    return xmax > xmin && ymax > ymin;
+}
+
+static void stage_begin(rtdm_bm* bm, int stage, int frames, hipStream_t s, StageEvent* ev)
+{
+    if (!bm->profiling) return;
+    ev->stage = stage; ev->frames = frames;
+    (void)hipEventCreate(&ev->a); (void)hipEventCreate(&ev->b);
+    (void)hipEventRecord(ev->a, s);
+}
+static void stage_end(rtdm_bm* bm, hipStream_t s, StageEvent* ev)
+{
+    if (!bm->profiling) return;
+    (void)hipEventRecord(ev->b, s);
+    bm->pending.push_back(*ev);
+}
+
+// Row strips per frame for the fast search of a batch, chosen by measurement and remembered in the handle: the model
+// (fast_strips_model) is right on average, but neighbouring strip counts differ by up to 5 % through scheduling effects it
+// cannot see (profiles/r01_xcd_mapping_sweep.txt).  The search only writes its own outputs, so timing it a few times on
+// the caller's data is harmless.  The key is the SHAPE of the work (frame size, batch, searched columns and rows as
+// counts, not positions): a caller that moves a same-sized ROI around (estimator.cpp:53-54) keeps its entry.  A shape is
+// measured the SECOND time it is seen -- a caller whose ROI changes size every call never pays the ~30 extra launches and
+// the stream synchronisation -- and the table is a 16-entry LRU.  Small batches keep the model.  RTDM_AUTOTUNE=0: off.
+static int tune_strips(rtdm_bm* bm, Plane8 Lpr, Plane8 Rpr, Plane16W disp, const BMGeom& g, int n, hipStream_t s, bool fuse, bool ring)
+{
+    const auto launch = [&](int c) {
+        if (ring) launch_search_ring(Lpr, Rpr, disp, bm->dCost, g, n, s, c, fuse);
+        else launch_search_fast(Lpr, Rpr, disp, bm->dCost, g, n, s, fuse, c);
+    };
+    static const bool enabled = env_int("RTDM_AUTOTUNE", 1) != 0 && getenv("RTDM_FAST_WGS") == nullptr;
+    if (!enabled || n < 16) return 0;
+    TuneKey key{g.W, g.H, n, g.cx1 - g.cx0, g.vy1 - g.vy0, (fuse ? 1 : 0) | (ring ? ring_lanes_per_pixel(g) : 0)};
+    for (size_t i = 0; i < bm->tuned.size(); ++i) {
+        if (!(bm->tuned[i].key == key)) continue;
+        TuneEntry e = bm->tuned[i];
+        bm->tuned.erase(bm->tuned.begin() + (long)i);              // most recently used goes to the back
+        if (e.strips == 0) {
+            e.strips = -1;                                          // being measured: a failure below leaves the model in charge
+            ++bm->tune_shapes;
+            const int model = ring ? ring_strips_model(g, n) : fast_strips_model(g, n), cap = (g.vy1 - g.vy0 + 15) / 16;
+            int best = model;
+            float best_ms = 1e30f;
+            hipEvent_t a, b;
+            if (hipEventCreate(&a) == hipSuccess) {
+                if (hipEventCreate(&b) == hipSuccess) {
+                    static const float f[] = {0.6f, 0.7f, 0.8f, 0.9f, 1.0f, 1.1f, 1.2f, 1.35f, 1.5f, 1.75f};
+                    int seen[10], nseen = 0;
+                    for (float fk : f) {
+                        const int c = std::max(1, std::min(cap, (int)(model * fk + 0.5f)));
+                        bool dup = false;
+                        for (int k = 0; k < nseen; ++k) dup |= seen[k] == c;
+                        if (dup) continue;
+                        seen[nseen++] = c;
+                        launch(c);          // warm
+                        bm->tune_launches += 3;
+                        float ms = 1e30f;
+                        for (int rep = 0; rep < 2; ++rep) {
+                            (void)hipEventRecord(a, s);
+                            launch(c);
+                            (void)hipEventRecord(b, s);
+                            float t = 0.f;
+                            if (hipEventSynchronize(b) == hipSuccess && hipEventElapsedTime(&t, a, b) == hipSuccess) ms = std::min(ms, t);
+                        }
+                        if (ms < best_ms) { best_ms = ms; best = c; }
+                    }
+                    e.strips = best;
+                    (void)hipEventDestroy(b);
+                }
+                (void)hipEventDestroy(a);
+            }
+        }
+        bm->tuned.push_back(e);
+        return e.strips > 0 ? e.strips : 0;
+    }
+    if (bm->tuned.size() >= 16) bm->tuned.erase(bm->tuned.begin());  // least recently used
+    bm->tuned.push_back(TuneEntry{key, 0});                           // first sighting: remember, keep the model
+    return 0;
+}
+
+// Fill + prefilter + SAD search of a chunk (VALU bound); *any = false: the whole frame is FILTERED, nothing follows.
+static int chunk_front(rtdm_bm* bm, int n, Plane8 L, Plane8 R, int W, int H, Plane16W disp, hipStream_t s, BMGeom* gout,
+                       bool* anyout)
+{
+    const rtdm_bm_params& p = bm->p;
+    BMGeom& g = *gout;
+    const bool any = make_geom(bm, W, H, &g);
+    *anyout = any;
+    if (!any) { launch_fill16(disp, 0, W, 0, H, n, g.filtered, s); return RTDM_OK; }
+    // the search kernels write columns [cx0, cx1) of the valid rows; everything else is FILTERED
+    // (+ the speckle filter's run counts = 0); the fill rides in the prefilter's launch
+    const FillJob fill{disp, g.cx0, g.cx1, g.vy0, g.vy1, g.filtered, (p.speckleRange >= 0 && p.speckleWindowSize > 0) ? bm->dRowCnt : nullptr};
+    StageEvent ev;
+    bool u16 = false;
+    // what k_search_generic cannot hold in LDS (D > 256, large windows at large D) -- or everything, when
+    // rtdm_debug_disparity_slice forces it -- is searched by the disparity-sliced kernel over the whole range
+    const bool dslice = !generic_search_supported(g, &u16) || dslice_forced();
+    const bool fast = !dslice && fast_search_supported(g);
+    {
+        const bool ring = fast && ring_search_supported(g);
+        const int lpp = ring ? ring_lanes_per_pixel(g) : 0;
+        bm->variant = dslice ? (u16 ? "generic_dslice_u16" : "generic_dslice_u32")
+                    : ring ? (lpp == 16 ? "fast_ring16_qsad" : lpp == 8 ? "fast_ring8_qsad" : lpp == 4 ? "fast_ring4_qsad" : "fast_ring_qsad") : fast ? "fast_qsad" : (u16 ? "generic_u16" : "generic_u32");
+        Plane8W Lp{bm->dLp, bm->ppitch, bm->ppitch * (size_t)H}, Rp{bm->dRp, bm->ppitch, bm->ppitch * (size_t)H};
+        stage_begin(bm, RTDM_STAGE_PREFILTER, n, s, &ev);
+        launch_prefilter(L, R, Lp, Rp, W, H, p.preFilterCap, n, s, &fill, bm->prefilter_type, bm->prefilter_size);
+        stage_end(bm, s, &ev);
+        Plane8 Lpr{bm->dLp, Lp.pitch, Lp.frame}, Rpr{bm->dRp, Rp.pitch, Rp.frame};
+        stage_begin(bm, RTDM_STAGE_SEARCH, n, s, &ev);
+        if (fast) {
+            int lx0, lx1, rx0, rx1;
+            fast_border_ranges(g, &lx0, &lx1, &rx0, &rx1);
+            // Batches of 16 or more: the border columns run as a kernel of their own on a side stream, concurrently with the
+            // tile kernel.  Its waves need 37-72 VGPRs and fit NEXT to the four tile waves of a SIMD, whereas inside the tile
+            // kernel's grid a border workgroup takes a tile workgroup's slot for the length of its latency-bound walk
+            // (search -2 %).  Smaller batches keep the fused launch (one kernel less).
+            const bool side = border_search_supported(g) && n >= 16;
+            // (the 3.x clamp exists in the stand-alone border kernel only: the fused forms keep their register budget)
+            const bool fuse = border_search_supported(g) && !side && !g.legacy;   // border workgroups inside the tile kernel's grid
+            // (measured, if at all, before the side stream forks: nothing else runs beside the timed launches)
+            const int strips = tune_strips(bm, Lpr, Rpr, disp, g, n, s, fuse, ring);
+            if (side) {
+                HIPC(hipEventRecord(bm->evFork, s));
+                HIPC(hipStreamWaitEvent(bm->sBorder, bm->evFork, 0));
+                launch_search_border(Lpr, Rpr, disp, bm->dCost, g, n, bm->sBorder, lx0, lx1, rx0, rx1);
+                HIPC(hipEventRecord(bm->evJoin, bm->sBorder));
+            }
+            bool fused = fuse;
+            if (ring) fused = launch_search_ring(Lpr, Rpr, disp, bm->dCost, g, n, s, strips, fuse);
+            else launch_search_fast(Lpr, Rpr, disp, bm->dCost, g, n, s, fuse, strips);
+            if (side) {
+                HIPC(hipStreamWaitEvent(s, bm->evJoin, 0));
+            } else if (fused) {
+            } else if (border_search_supported(g)) {
+                launch_search_border(Lpr, Rpr, disp, bm->dCost, g, n, s, lx0, lx1, rx0, rx1);
+            } else {
+                launch_search_generic(Lpr, Rpr, disp, bm->dCost, g, n, s, lx0, lx1);
+                launch_search_generic(Lpr, Rpr, disp, bm->dCost, g, n, s, rx0, rx1);
+            }
+        } else if (dslice) {
+            launch_search_dslice(Lpr, Rpr, disp, bm->dCost, g, n, s, g.cx0 - g.lofs, g.cx1 - g.lofs);
+        } else {
+            launch_search_generic(Lpr, Rpr, disp, bm->dCost, g, n, s, g.cx0 - g.lofs, g.cx1 - g.lofs);
+        }
+        stage_end(bm, s, &ev);
+    }
+    HIPC(hipGetLastError());
+    return RTDM_OK;
+}
+
+// Left-right check + speckle filter of a chunk, in place on `disp` (latency bound).
+static int chunk_back(rtdm_bm* bm, int n, int W, int H, Plane16W disp, const BMGeom& g, hipStream_t s)
+{
+    const rtdm_bm_params& p = bm->p;
+    StageEvent ev;
+    const bool speckle = p.speckleRange >= 0 && p.speckleWindowSize > 0;
+    const bool lr = p.disp12MaxDiff >= 0;
+    int compact_rows = 0;                // > 0: k_lrcheck_vec wrote per-chunk head records and merged blocks of that many rows
+    if (lr) {
+        stage_begin(bm, RTDM_STAGE_LRCHECK, n, s, &ev);
+        if (speckle) compact_rows = launch_lrcheck(disp, bm->dCost, g, p.disp12MaxDiff, n, s, bm->dLabel, bm->dSize, bm->dRuns, bm->dRowCnt, bm->dHead,
+                                                   p.speckleRange);
+        else         launch_lrcheck(disp, bm->dCost, g, p.disp12MaxDiff, n, s);
+        stage_end(bm, s, &ev);
+    }
+    if (speckle) {
+        stage_begin(bm, RTDM_STAGE_SPECKLE, n, s, &ev);
+        launch_speckle(disp, bm->dLabel, bm->dSize, bm->dRuns, bm->dRowCnt, bm->dHead, W, g.Ws, H, n, g.filtered, p.speckleWindowSize,
+                       p.speckleRange, lr, std::max(compact_rows, 1), g.vy0, g.vy1, s, compact_rows > 0);
+        stage_end(bm, s, &ev);
+    }
+    HIPC(hipGetLastError());
+    return RTDM_OK;
+}
+
+// One chunk (n <= maxB) of device-resident frames, enqueued on `s`.  The row kernels move 8 columns per 128-bit
+// access and let a ragged last chunk spill into the row padding, so they need 16-byte aligned rows of at least
+// W rounded up to 8 elements whose padding is ours to write.  A caller's plane qualifies only if W % 8 == 0 and it
+// is aligned; anything else (the reference's own crops are 233, 534 and 934 columns wide) runs on the handle's
+// internal plane and is copied out at the end.
+int rtdm::bm_run_chunk(rtdm_bm* bm, int n, Plane8 L, Plane8 R, int W, int H, Plane16W out, hipStream_t s)
+{
+    const size_t Ws = bm_ws(W);
+    // (the handle's own plane, or a frame-aligned part of it: rows of Ws elements whose padding is ours)
+    const bool internal = out.pitch_e == Ws && out.base >= bm->dOut && out.base < bm->dOut + (size_t)bm->maxB * Ws * (size_t)H &&
+                          (size_t)(out.base - bm->dOut) % (Ws * (size_t)H) == 0;
+    const bool direct = internal || ((W & 7) == 0 && (((size_t)out.base | (out.pitch_e * 2) | (out.frame_e * 2)) & 15) == 0);
+    const Plane16W disp = direct ? out : bm_internal_plane(bm, W, H);
+    BMGeom g;
+    bool any = false;
+    int rc = chunk_front(bm, n, L, R, W, H, disp, s, &g, &any);
+    if (rc) return rc;
+    if (any) { rc = chunk_back(bm, n, W, H, disp, g, s); if (rc) return rc; }
+    if (!direct) launch_copy16(disp, out, W, H, n, s);
+    HIPC(hipGetLastError());
+    return RTDM_OK;
+}
+
+int rtdm::bm_check_frame(const rtdm_bm* bm, int W, int H)
+{
+    if (W <= 0 || H <= 0 || W > bm->maxW || H > bm->maxH) return RTDM_ERR_BAD_SIZE;
+    if (bm->p.blockSize >= std::min(W, H)) return RTDM_ERR_BAD_PARAM;   // cv::StereoBM::compute's check
+    return RTDM_OK;
+}
+
+int rtdm_bm_compute_device(rtdm_bm* bm, int n, const uint8_t* d_left, const uint8_t* d_right,
+                           size_t pitch, size_t frame_stride, int width, int height,
+                           int16_t* d_disp, size_t disp_pitch, size_t disp_frame_stride, void* hip_stream)
+{
+    if (!bm || !d_left || !d_right || !d_disp) return RTDM_ERR_NULL;
+    if (n <= 0) return RTDM_ERR_BAD_SIZE;
+    int rc = bm_check_frame(bm, width, height);
+    if (rc) return rc;
+    if (pitch < (size_t)width || disp_pitch < (size_t)width * 2 || (disp_pitch & 1) || (disp_frame_stride & 1))
+        return RTDM_ERR_BAD_SIZE;
+    HIPC(hipSetDevice(bm->device));
+    hipStream_t s = (hipStream_t)hip_stream;          // NULL = the HIP null stream (what torch's default stream is)
+    for (int i0 = 0; i0 < n; i0 += bm->maxB) {
+        const int m = std::min(bm->maxB, n - i0);
+        Plane8 L{d_left + (size_t)i0 * frame_stride, pitch, frame_stride};
+        Plane8 R{d_right + (size_t)i0 * frame_stride, pitch, frame_stride};
+        Plane16W O{d_disp + (size_t)i0 * (disp_frame_stride / 2), disp_pitch / 2, disp_frame_stride / 2};
+        rc = bm_run_chunk(bm, m, L, R, width, height, O, s);
+        if (rc) return rc;
+    }
+    return RTDM_OK;
+}
+
+int rtdm_bm_compute_batch(rtdm_bm* bm, int n, const uint8_t* left, const uint8_t* right,
+                          size_t pitch, size_t frame_stride, int width, int height,
+                          int16_t* disp, size_t disp_pitch, size_t disp_frame_stride)
+{
+    if (!bm || !left || !right || !disp) return RTDM_ERR_NULL;
+    if (n <= 0) return RTDM_ERR_BAD_SIZE;
+    int rc = bm_check_frame(bm, width, height);
+    if (rc) return rc;
+    if (pitch < (size_t)width || disp_pitch < (size_t)width * 2) return RTDM_ERR_BAD_SIZE;
+    HIPC(hipSetDevice(bm->device));
+    hipStream_t s = bm->stream;
+    DrainOnError drain(bm->sIn, s, bm->sOut);   // (an error exit leaves no DMA in flight from / to the caller's buffers)
+    const size_t dpitch = bm->ppitch, dframe = bm->ppitch * (size_t)height;
+    const size_t Ws = bm_ws(width);                                    // the handle's internal plane (see bm_run_chunk)
+    const size_t opitch = Ws * 2, oframe = opitch * (size_t)height;
+    // Three streams, two halves of the staging planes: while chunk k is computed, chunk k+1 comes in over PCIe and chunk
+    // k-1 goes out (both directions of the bus at once).  It pays for page-locked caller memory (hipHostMalloc /
+    // hipHostRegister: the copies are true DMA); pageable frames are staged by the runtime inside the copy call.
+    // Measured (tools/host_batch_rate.py, 256 x 720p): page-locked 11.6 k -> 21.1 k pairs/s (78 GB/s over PCIe, both ways),
+    // pageable 11.2 k -> 10.5 k: so only for page-locked callers.
+    const int half = std::max(1, bm->maxB / 2);
+    const bool two = bm->maxB >= 2 && page_locked(left) && page_locked(right) && page_locked(disp);
+    const int chunk = two ? half : bm->maxB;
+    int k = 0;
+    for (int i0 = 0; i0 < n; i0 += chunk, ++k) {
+        const int m = std::min(chunk, n - i0), b = two ? (k & 1) : 0;
+        const size_t fo = (size_t)b * (size_t)half;                    // first staging frame of this half
+        hipStream_t si = two ? bm->sIn : s, so = two ? bm->sOut : s;
+        if (two && k >= 2) HIPC(hipStreamWaitEvent(si, bm->evComp[b], 0));      // the half's previous chunk has been consumed
+        uint8_t *dl = bm->dInL + fo * dframe, *dr = bm->dInR + fo * dframe;
+        if (pitch == dpitch && frame_stride == dframe) {               // the caller's frames have the staging layout: one copy per image
+            // (up to the last pixel of the last row: a view that starts at x > 0 of its parent plane ends before the row's pitch does)
+            const size_t nbytes = (size_t)m * dframe - (dpitch - (size_t)width);
+            HIPC(hipMemcpyAsync(dl, left + (size_t)i0 * frame_stride, nbytes, hipMemcpyHostToDevice, si));
+            HIPC(hipMemcpyAsync(dr, right + (size_t)i0 * frame_stride, nbytes, hipMemcpyHostToDevice, si));
+        } else {
+            for (int i = 0; i < m; ++i) {
+                HIPC(hipMemcpy2DAsync(dl + i * dframe, dpitch, left + (size_t)(i0 + i) * frame_stride, pitch, width, height, hipMemcpyHostToDevice, si));
+                HIPC(hipMemcpy2DAsync(dr + i * dframe, dpitch, right + (size_t)(i0 + i) * frame_stride, pitch, width, height, hipMemcpyHostToDevice, si));
+            }
+        }
+        if (two) {
+            HIPC(hipEventRecord(bm->evH2D[b], si));
+            HIPC(hipStreamWaitEvent(s, bm->evH2D[b], 0));
+            if (k >= 2) HIPC(hipStreamWaitEvent(s, bm->evD2H[b], 0));   // ... and its previous result has left
+        }
+        Plane8 L{dl, dpitch, dframe}, R{dr, dpitch, dframe};
+        int16_t* dout = bm->dOut + fo * Ws * (size_t)height;
+        Plane16W O{dout, Ws, Ws * (size_t)height};
+        rc = bm_run_chunk(bm, m, L, R, width, height, O, s);
+        if (rc) return rc;
+        if (two) { HIPC(hipEventRecord(bm->evComp[b], s)); HIPC(hipStreamWaitEvent(so, bm->evComp[b], 0)); }
+        // one linear copy only when the internal rows carry no padding: with width < Ws it would write the pad columns
+        // [width, Ws) of the caller's rows, which are not part of the view
+        if ((size_t)width == Ws && disp_pitch == opitch && disp_frame_stride == oframe) {
+            HIPC(hipMemcpyAsync((uint8_t*)disp + (size_t)i0 * disp_frame_stride, dout, (size_t)m * oframe, hipMemcpyDeviceToHost, so));
+        } else {
+            for (int i = 0; i < m; ++i)
+                HIPC(hipMemcpy2DAsync((uint8_t*)disp + (size_t)(i0 + i) * disp_frame_stride, disp_pitch,
+                                      (uint8_t*)dout + i * oframe, opitch, (size_t)width * 2, height, hipMemcpyDeviceToHost, so));
+        }
+        if (two) HIPC(hipEventRecord(bm->evD2H[b], so));
+        else HIPC(hipStreamSynchronize(s));                            // staging buffers are reused by the next chunk
+    }
+    if (two) { HIPC(hipStreamSynchronize(bm->sOut)); HIPC(hipStreamSynchronize(s)); HIPC(hipStreamSynchronize(bm->sIn)); }
+    drain.armed = false;
+    return RTDM_OK;
+}
+
+int rtdm_bm_compute(rtdm_bm* bm, const uint8_t* left, size_t left_pitch, const uint8_t* right,
+                    size_t right_pitch, int width, int height, int16_t* disp, size_t disp_pitch)
+{
+    if (!bm || !left || !right || !disp) return RTDM_ERR_NULL;
+    int rc = bm_check_frame(bm, width, height);
+    if (rc) return rc;
+    if (left_pitch < (size_t)width || right_pitch < (size_t)width || disp_pitch < (size_t)width * 2)
+        return RTDM_ERR_BAD_SIZE;
+    HIPC(hipSetDevice(bm->device));
+    hipStream_t s = bm->stream;
+    DrainOnError drain{s};
+    const size_t dpitch = bm->ppitch, dframe = bm->ppitch * (size_t)height;
+    // The caller's Mats are pageable ROI views (estimator.cpp:33,36): the rows are gathered into the page-locked staging
+    // area on the host and go over in linear async copies -- in two BANDS of rows per direction, so that the host gathers
+    // band 1 while band 0 is on the bus, and scatters band 0 of the result while band 1 arrives.  720p pair, host to host:
+    // 0.363 ms with one copy per plane and row-by-row gathers, 0.347 with one band, 0.325 with two, 0.375 with four (every
+    // further async copy costs more in the runtime than its overlap hides).  Rows that are contiguous in the caller's plane
+    // move as one memcpy.
+    const Plane16W O = bm_internal_plane(bm, width, height);
+    const size_t Ws = O.pitch_e;
+    if (page_locked(left) && page_locked(right) && page_locked(disp)) {
+        // the caller's planes are page-locked: DMA straight from and to them, no gathers on the host
+        HIPC(hipMemcpy2DAsync(bm->dInL, dpitch, left, left_pitch, (size_t)width, height, hipMemcpyHostToDevice, s));
+        HIPC(hipMemcpy2DAsync(bm->dInR, dpitch, right, right_pitch, (size_t)width, height, hipMemcpyHostToDevice, s));
+        Plane8 Ld{bm->dInL, dpitch, dframe}, Rd{bm->dInR, dpitch, dframe};
+        rc = bm_run_chunk(bm, 1, Ld, Rd, width, height, O, s);
+        if (rc) return rc;
+        HIPC(hipMemcpy2DAsync(disp, disp_pitch, bm->dOut, Ws * sizeof(int16_t), (size_t)width * sizeof(int16_t), height, hipMemcpyDeviceToHost, s));
+        HIPC(hipStreamSynchronize(s));
+        drain.armed = false;
+        return RTDM_OK;
+    }
+    uint8_t *hL = bm->hStage, *hR = hL + dframe;
+    int16_t* hD = bm->hD;
+    const int nb = height >= 256 ? 2 : 1, bh = (height + nb - 1) / nb;
+    const auto gather = [&](uint8_t* dst, const uint8_t* src, size_t spitch, int y0, int y1) {
+        if (spitch == dpitch) { memcpy(dst + (size_t)y0 * dpitch, src + (size_t)y0 * spitch, (size_t)(y1 - y0 - 1) * dpitch + (size_t)width); return; }
+        for (int y = y0; y < y1; ++y) memcpy(dst + (size_t)y * dpitch, src + (size_t)y * spitch, (size_t)width);
+    };
+    for (int b = 0; b < nb; ++b) {
+        const int y0 = b * bh, y1 = std::min(height, y0 + bh);
+        if (y0 >= y1) break;
+        gather(hL, left, left_pitch, y0, y1);
+        HIPC(hipMemcpyAsync(bm->dInL + (size_t)y0 * dpitch, hL + (size_t)y0 * dpitch, (size_t)(y1 - y0) * dpitch, hipMemcpyHostToDevice, s));
+        gather(hR, right, right_pitch, y0, y1);
+        HIPC(hipMemcpyAsync(bm->dInR + (size_t)y0 * dpitch, hR + (size_t)y0 * dpitch, (size_t)(y1 - y0) * dpitch, hipMemcpyHostToDevice, s));
+    }
+    Plane8 L{bm->dInL, dpitch, dframe}, R{bm->dInR, dpitch, dframe};
+    rc = bm_run_chunk(bm, 1, L, R, width, height, O, s);
+    if (rc) return rc;
+    int nbo = 0;
+    for (int b = 0; b < nb; ++b, ++nbo) {
+        const int y0 = b * bh, y1 = std::min(height, y0 + bh);
+        if (y0 >= y1) break;
+        HIPC(hipMemcpyAsync(hD + (size_t)y0 * Ws, bm->dOut + (size_t)y0 * Ws, (size_t)(y1 - y0) * Ws * sizeof(int16_t), hipMemcpyDeviceToHost, s));
+        HIPC(hipEventRecord(bm->evBand[b], s));
+    }
+    for (int b = 0; b < nbo; ++b) {
+        const int y0 = b * bh, y1 = std::min(height, y0 + bh);
+        HIPC(hipEventSynchronize(bm->evBand[b]));
+        if ((size_t)width == Ws && disp_pitch == Ws * sizeof(int16_t)) {   // no pad columns between the rows: one copy per band
+            memcpy((uint8_t*)disp + (size_t)y0 * disp_pitch, hD + (size_t)y0 * Ws, (size_t)(y1 - y0 - 1) * disp_pitch + (size_t)width * sizeof(int16_t));
+        } else {
+            for (int y = y0; y < y1; ++y)
+                memcpy((uint8_t*)disp + (size_t)y * disp_pitch, hD + (size_t)y * Ws, (size_t)width * sizeof(int16_t));
+        }
+    }
+    drain.armed = false;
+    return RTDM_OK;
+}
+
+int rtdm_bm_synchronize(rtdm_bm* bm)
+{
+    if (!bm) return RTDM_ERR_NULL;
+    HIPC(hipSetDevice(bm->device));
+    HIPC(hipStreamSynchronize(bm->stream));
+    return RTDM_OK;
+}
+
+int rtdm_bm_set_profiling(rtdm_bm* bm, int enabled)
+{
+    if (!bm) return RTDM_ERR_NULL;
+    bm->profiling = enabled != 0;
+    return RTDM_OK;
+}
+
+static int drain_events(rtdm_bm* bm)
+{
+    for (auto& ev : bm->pending) {
+        HIPC(hipEventSynchronize(ev.b));
+        float ms = 0.f;
+        HIPC(hipEventElapsedTime(&ms, ev.a, ev.b));
+        bm->stage_ms[ev.stage] += ms;
+        bm->stage_launches[ev.stage] += 1;
+        bm->stage_frames[ev.stage] += ev.frames;
+        (void)hipEventDestroy(ev.a); (void)hipEventDestroy(ev.b);
+    }
+    bm->pending.clear();
+    return RTDM_OK;
+}
+
+int rtdm_bm_get_stage_time(rtdm_bm* bm, int stage, double* total_ms, long* launches, long* frames)
+{
+    if (!bm) return RTDM_ERR_NULL;
+    if (stage < 0 || stage >= RTDM_NUM_STAGES) return RTDM_ERR_BAD_PARAM;
+    HIPC(hipSetDevice(bm->device));
+    int rc = drain_events(bm);
+    if (rc) return rc;
+    if (total_ms) *total_ms = bm->stage_ms[stage];
+    if (launches) *launches = bm->stage_launches[stage];
+    if (frames) *frames = bm->stage_frames[stage];
+    return RTDM_OK;
+}
+
+int rtdm_bm_reset_stage_times(rtdm_bm* bm)
+{
+    if (!bm) return RTDM_ERR_NULL;
+    HIPC(hipSetDevice(bm->device));
+    int rc = drain_events(bm);
+    if (rc) return rc;
+    for (int i = 0; i < RTDM_NUM_STAGES; ++i) { bm->stage_ms[i] = 0; bm->stage_launches[i] = 0; bm->stage_frames[i] = 0; }
+    return RTDM_OK;
+}
+
+const char* rtdm_bm_search_variant(const rtdm_bm* bm) { return bm ? bm->variant.c_str() : ""; }
+int rtdm_bm_get_tuner_stats(const rtdm_bm* bm, long* shapes_measured, long* timing_launches)
+{
+    if (!bm) return RTDM_ERR_NULL;
+    if (shapes_measured) *shapes_measured = bm->tune_shapes;
+    if (timing_launches) *timing_launches = bm->tune_launches;
+    return RTDM_OK;
+}
+void rtdm_debug_search_kernel(int mode) { ring_set_mode(mode); }
+void rtdm_debug_disparity_slice(int dt) { dslice_set_width(dt); }
+
+int rtdm_bm_compute_depth(rtdm_bm* bm, const uint8_t* left, size_t left_pitch, const uint8_t* right, size_t right_pitch,
+                          int width, int height, const double* Q, const uint8_t* mask, size_t mask_pitch,
+                          const rtdm_region* regions, int nregions, double calibration_unit,
+                          double* mean_cm, int* counts, int16_t* disp, size_t disp_pitch)
+{
+    if (!bm || !left || !right || !Q || !mask || !mean_cm || !counts) return RTDM_ERR_NULL;
+    int rc = bm_check_frame(bm, width, height);
+    if (rc) return rc;
+    if (left_pitch < (size_t)width || right_pitch < (size_t)width || mask_pitch < (size_t)width) return RTDM_ERR_BAD_SIZE;
+    if (disp && disp_pitch < (size_t)width * 2) return RTDM_ERR_BAD_SIZE;
+    int flat[4 * RTDM_MAX_REGIONS], maxh = 1;
+    rc = depth_check_regions(regions, nregions, width, height, flat, &maxh);
+    if (rc) return rc;
+    HIPC(hipSetDevice(bm->device));
+    hipStream_t s = bm->stream;
+    const size_t dpitch = bm->ppitch, dframe = bm->ppitch * (size_t)height;
+    uint8_t *hL = bm->hStage, *hR = hL + dframe, *hM = bm->hM;
+    for (int y = 0; y < height; ++y) {
+        memcpy(hL + (size_t)y * dpitch, left + (size_t)y * left_pitch, (size_t)width);
+        memcpy(hR + (size_t)y * dpitch, right + (size_t)y * right_pitch, (size_t)width);
+        memcpy(hM + (size_t)y * width, mask + (size_t)y * mask_pitch, (size_t)width);
+    }
+    HIPC(hipMemcpyAsync(bm->dInL, hL, dframe, hipMemcpyHostToDevice, s));
+    HIPC(hipMemcpyAsync(bm->dInR, hR, dframe, hipMemcpyHostToDevice, s));
+    HIPC(hipMemcpyAsync(bm->dMask, hM, (size_t)width * height, hipMemcpyHostToDevice, s));
+    Plane8 L{bm->dInL, dpitch, dframe}, R{bm->dInR, dpitch, dframe};
+    const Plane16W O = bm_internal_plane(bm, width, height);
+    rc = bm_run_chunk(bm, 1, L, R, width, height, O, s);
+    if (rc) return rc;
+    DepthQ q; std::copy(Q, Q + 16, q.q);
+    launch_depth_stats(bm->dOut, O.pitch_e, width, height, q, bm->dMask, (size_t)width, flat, nregions, bm->maxH,
+                       calibration_unit, bm->dDepth, mean_cm, counts, s);
+    if (disp) { rc = bm_download_disp(bm, width, height, s); if (rc) return rc; }
+    HIPC(hipGetLastError());
+    HIPC(hipStreamSynchronize(s));
+    if (disp) bm_scatter_disp(bm, width, height, disp, disp_pitch);
+    return RTDM_OK;
+}
+
+int rtdm::bm_download_disp(rtdm_bm* bm, int W, int H, hipStream_t s)
+{
+    HIPC(hipMemcpyAsync(bm->hD, bm->dOut, bm_internal_plane(bm, W, H).frame_e * sizeof(int16_t), hipMemcpyDeviceToHost, s));
+    return RTDM_OK;
+}
+
+void rtdm::bm_scatter_disp(const rtdm_bm* bm, int W, int H, int16_t* disp, size_t disp_pitch)
+{
+    const size_t Ws = bm_ws(W);
+    for (int y = 0; y < H; ++y) memcpy((uint8_t*)disp + (size_t)y * disp_pitch, bm->hD + (size_t)y * Ws, (size_t)W * sizeof(int16_t));
+}

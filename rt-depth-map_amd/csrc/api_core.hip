@@ -1,0 +1,94 @@
+// api_core.hip -- status strings, the last-error string, device count; the handle-free device entry points.
+// There is no CPU fallback anywhere in the C ABI layer (api_*.hip): every entry point that computes needs a HIP device.
+#include "rtdm_handles.h"
+
+using namespace rtdm;
+
+thread_local std::string rtdm::g_hip_err;
+
+const char* rtdm_strerror(int s)
+{
+    switch (s) {
+        case RTDM_OK: return "ok";
+        case RTDM_ERR_BAD_PARAM: return "invalid StereoBM parameter";
+        case RTDM_ERR_BAD_SIZE: return "invalid frame size or pitch";
+        case RTDM_ERR_NO_DEVICE: return "no usable HIP device (this library has no CPU fallback)";
+        case RTDM_ERR_HIP: return "HIP runtime error";
+        case RTDM_ERR_NOMEM: return "out of memory";
+        case RTDM_ERR_UNSUPPORTED: return "configuration not supported by this build";
+        case RTDM_ERR_NULL: return "null pointer";
+        case RTDM_ERR_BAD_STREAM: return "damaged or incomplete JPEG stream";
+        default: return "unknown rtdm status";
+    }
+}
+
+const char* rtdm_last_hip_error(void) { return g_hip_err.c_str(); }
+int rtdm_abi_version(void) { return RTDM_ABI_VERSION; }
+
+int rtdm_device_count(int* count)
+{
+    if (!count) return RTDM_ERR_NULL;
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess) n = 0;
+    *count = n;
+    return n > 0 ? RTDM_OK : RTDM_ERR_NO_DEVICE;
+}
+
+// ---- synthetic stream ------------------------------------------------------------------------
+int rtdm_synth_pairs_device(uint64_t seed, int first_frame, int n, int width, int height, int numDisparities,
+                            uint8_t* d_left, uint8_t* d_right, size_t pitch, size_t frame_stride, int device,
+                            void* hip_stream)
+{
+    if (!d_left || !d_right) return RTDM_ERR_NULL;
+    if (n <= 0 || width <= 0 || height <= 0 || pitch < (size_t)width) return RTDM_ERR_BAD_SIZE;
+    int rc = use_device(device);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)hip_stream;
+    void* scratch = nullptr;
+    HIPC(hipMalloc(&scratch, synth_scratch_bytes(n)));
+    Plane8W L{d_left, pitch, frame_stride}, R{d_right, pitch, frame_stride};
+    launch_synth(seed, first_frame, n, width, height, numDisparities, L, R, scratch, s);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    (void)hipFree(scratch);
+    HIPC(e);
+    return RTDM_OK;
+}
+
+// ---- the step after the matcher ---------------------------------------------------------------
+int rtdm::depth_check_regions(const rtdm_region* regions, int n, int W, int H, int* flat, int* maxh)
+{
+    if (n < 0 || n > RTDM_MAX_REGIONS || (n > 0 && !regions)) return RTDM_ERR_BAD_SIZE;
+    *maxh = 1;
+    for (int i = 0; i < n; ++i) {
+        const rtdm_region& r = regions[i];
+        if (r.x < 0 || r.y < 0 || r.width < 0 || r.height < 0 || r.x + r.width > W || r.y + r.height > H) return RTDM_ERR_BAD_SIZE;
+        flat[4 * i] = r.x; flat[4 * i + 1] = r.y; flat[4 * i + 2] = r.width; flat[4 * i + 3] = r.height;
+        *maxh = std::max(*maxh, r.height);
+    }
+    return RTDM_OK;
+}
+
+int rtdm_depth_stats_device(int device, const int16_t* d_disp, size_t disp_pitch, int width, int height, const double* Q,
+                            const uint8_t* d_mask, size_t mask_pitch, const rtdm_region* regions, int nregions,
+                            double calibration_unit, double* mean_cm, int* counts, void* hip_stream)
+{
+    if (!d_disp || !Q || !d_mask || !mean_cm || !counts) return RTDM_ERR_NULL;
+    if (width <= 0 || height <= 0 || disp_pitch < (size_t)width * 2 || (disp_pitch & 1) || mask_pitch < (size_t)width) return RTDM_ERR_BAD_SIZE;
+    int flat[4 * RTDM_MAX_REGIONS], maxh = 1;
+    int rc = depth_check_regions(regions, nregions, width, height, flat, &maxh);
+    if (rc) return rc;
+    rc = use_device(device);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)hip_stream;
+    void* scratch = nullptr;
+    HIPC(hipMalloc(&scratch, depth_scratch_bytes(std::max(nregions, 1), maxh)));
+    DepthQ q; std::copy(Q, Q + 16, q.q);
+    launch_depth_stats(d_disp, disp_pitch / 2, width, height, q, d_mask, mask_pitch, flat, nregions, maxh, calibration_unit,
+                       scratch, mean_cm, counts, s);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    (void)hipFree(scratch);
+    HIPC(e);
+    return RTDM_OK;
+}

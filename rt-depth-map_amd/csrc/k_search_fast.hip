@@ -13,7 +13,7 @@
 //     LDS ring and subtracted with v_pk_sub_u16.
 //   * selection per output pixel, all in registers: rtdm_select.h (shared with k_search_ring).
 //   * launch: 1-D grid, XCD-aware (see FastGeom); row strips per frame from a cost model, measured once per
-//     batch shape by the caller (rtdm_api.hip, tune_strips).
+//     batch shape by the caller (api_bm.hip, tune_strips).
 //   Only columns whose whole window is free of border clamping are handled here; the 2*(w/2)
 //   border columns are searched by extra workgroups of the same grid (rtdm_border.h; they are outside the
 //   valid rectangle but feed the left-right check).  Semantics: SURVEY.md Appendix A.3b; oracle: oracle/bm_oracle.c.
@@ -288,7 +288,7 @@ static void launch_one(Plane8 Lp, Plane8 Rp, Plane16W disp, void* cost, const BM
     // RTDM_FAST_WGS=<total workgroups> overrides (sweeps: tools/sweep_strips.sh, tools/sweep_wgs_small.py).
     static const int target_wgs = env_int("RTDM_FAST_WGS", 0);
     int strips;
-    if (strips_hint > 0) strips = strips_hint;                      // measured choice (rtdm_api.hip, tune_strips)
+    if (strips_hint > 0) strips = strips_hint;                      // measured choice (api_bm.hip, tune_strips)
     else if (target_wgs > 0) strips = (target_wgs + tiles * n - 1) / (tiles * n);
     else strips = fast_strips_model(g, n);
     strips = max(1, min(strips, (nrows + 15) / 16));

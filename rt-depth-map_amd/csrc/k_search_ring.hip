@@ -274,11 +274,11 @@ __global__ __launch_bounds__(256, (RingBounds<D, WS, LPP, FUSE>::WAVES)) void k_
 
     // --- staging: item idx = one dword of the wave's copy; dword m holds copy bytes [4m, 4m+4) (biased planes) ---------
     // Unconditional loads: bytes past a row's end only ever reach lanes that are not `active`, and the prefiltered planes
-    // are allocated with 1 KB of slack behind the last row (rtdm_api.hip).  Two rows of loads are in flight (pre[0/1]).
+    // are allocated with 1 KB of slack behind the last row (api_bm.hip).  Two rows of loads are in flight (pre[0/1]).
     const int row0 = ys0 - r;
     const int Hm1 = g.H - 1;
     // One load per staged dword: address = the left plane's row (wave-uniform: lives in SGPRs and advances on the scalar
-    // unit) + a 32-bit lane offset -- the right plane lies rg.rdelta bytes behind the left one (one allocation, rtdm_api.hip).
+    // unit) + a 32-bit lane offset -- the right plane lies rg.rdelta bytes behind the left one (one allocation, api_bm.hip).
     // The byte phase makes the address unaligned; the memory pipeline takes unaligned dwords, and what arrives is what gets
     // staged: no second dword, no v_alignbyte, no 64-bit pointer arithmetic per lane.
     const uint8_t* rowp = Lb + (size_t)row0 * Lp.pitch;
@@ -655,7 +655,7 @@ bool launch_search_ring(Plane8 Lp, Plane8 Rp, Plane16W disp, void* cost, const B
 {
     const int lpp = ring_lpp(g);
     // the kernel addresses both planes from the left plane's rows with 32-bit lane offsets: they must be one allocation, the
-    // right plane behind the left one, with the same strides (rtdm_api.hip allocates them that way)
+    // right plane behind the left one, with the same strides (api_bm.hip allocates them that way)
     if (!(Rp.base > Lp.base && (size_t)(Rp.base - Lp.base) < ((size_t)1 << 32) - ((size_t)1 << 20) && Rp.pitch == Lp.pitch && Rp.frame == Lp.frame)) {
         launch_search_fast(Lp, Rp, disp, cost, g, n, stream, fuse_border, 0);
         return fuse_border;

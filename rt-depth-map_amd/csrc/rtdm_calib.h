@@ -30,7 +30,7 @@ static const int CB_ZERO_DISPARITY = 1024;          // cv::CALIB_ZERO_DISPARITY
 static const size_t CB_MAX_FILE = 1u << 20;         // a calibration file is a few KB; anything longer is refused
 static const int CB_MAX_DATA = 64;                  // entries of the largest matrix that is kept (Q: 16)
 
-// the layouts of rtdm_calib / rtdm_rectification / rtdm_region (rtdm_api.hip asserts the sizes)
+// the layouts of rtdm_calib / rtdm_rectification / rtdm_region (api_rectify.hip asserts the sizes)
 struct CalibRegion { int x, y, width, height; };
 struct Calib { double M1[9], D1[14], M2[9], D2[14], R[9], T[3]; int width, height; };
 struct Rectification { double R1[9], R2[9], P1[12], P2[12], Q[16]; CalibRegion roi1, roi2; };

@@ -1,0 +1,156 @@
+// rtdm_handles.h -- the handle structs more than one file of the C ABI layer has to see, and the internal functions that
+// cross those files (all in namespace rtdm: the library's global symbols are the entry points of include/rtdm.h alone).
+#pragma once
+#include "rtdm_host.h"
+#include "rtdm_kernels.h"
+#include "rtdm_calib.h"
+#include "rtdm_mjpeg.h"
+
+#include <algorithm>
+#include <cfloat>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <new>
+#include <utility>
+
+struct StageEvent { hipEvent_t a, b; int stage; int frames; };
+
+// Shape of a batched search launch, compared field by field (tune_strips).
+struct TuneKey {
+    int W, H, n, ncols, nrows, fuse;
+    bool operator==(const TuneKey& o) const { return W == o.W && H == o.H && n == o.n && ncols == o.ncols && nrows == o.nrows && fuse == o.fuse; }
+};
+struct TuneEntry { TuneKey key; int strips; };   // strips: 0 = seen once, not measured yet; -1 = measuring failed
+
+struct rtdm_bm {
+    rtdm_bm_params p;
+    int prefilter_type, prefilter_size;   // rtdm_bm_set_prefilter: cv::StereoBM's preFilterType / preFilterSize (XSOBEL, 9)
+    int maxW, maxH, maxB, device;
+    int roi1[4], roi2[4];
+    hipStream_t stream;
+    hipStream_t sBorder;           // batches: the border-column search runs here, next to the tile search
+    hipStream_t sSpare[2];         // idle: they keep the runtime's stream-to-queue layout (rtdm_bm_create)
+    hipEvent_t evFork, evJoin;     // ... behind this event of the compute stream, which then waits for that one
+    hipEvent_t evBand[2];          // rtdm_bm_compute: one per band of the result on its way back
+    hipStream_t sIn, sOut;         // rtdm_bm_compute_batch: copies in / out beside the compute stream
+    hipEvent_t evH2D[2], evComp[2], evD2H[2];   // ... one set per half of the staging planes
+    size_t ppitch;                 // pitch of the internal 8-bit planes
+    uint8_t *dLp, *dRp;            // prefiltered planes   [maxB][maxH][ppitch]
+    uint8_t *dInL, *dInR;          // staging for the host entry points
+    int16_t* dOut;                 // internal disparity plane [maxB][maxH][Ws] (Ws = maxW rounded up to 8)
+    std::vector<TuneEntry> tuned;  // measured strip counts per work shape, least recently used first (<= 16 entries)
+    long tune_shapes, tune_launches;   // rtdm_bm_get_tuner_stats
+    int32_t *dCost, *dLabel, *dSize, *dRowCnt;
+    uint32_t* dRuns;
+    int16_t* dHead;
+    uint8_t* dMask;                // staging for rtdm_bm_compute_depth: mask plane + reduction scratch
+    void* dDepth;
+    // page-locked staging of the single-frame host entry points, laid out by rtdm_bm_create: the left and right planes (rows of
+    // ppitch), then hD, the internal disparity plane of one frame, then hM, the mask of rtdm_bm_compute_depth
+    uint8_t* hStage; int16_t* hD; uint8_t* hM;
+    rtdm::AllocList mem;           // every d* / h* buffer above
+    bool profiling;
+    std::vector<StageEvent> pending;
+    double stage_ms[RTDM_NUM_STAGES];
+    long stage_launches[RTDM_NUM_STAGES], stage_frames[RTDM_NUM_STAGES];
+    std::string variant;
+};
+
+struct rtdm_rectify {
+    int W, H, rx, ry, rw, rh, maxB, device;
+    int16_t* dMap1[2];            // roi part of the maps: rh x rw x 2
+    uint16_t* dMap2[2];           // rh x rw
+    uint8_t* dRgb[2];             // staging for host frames: H x W x 3 (+ padding)
+    uint8_t* dOut;                // staging for host outputs: rh x rw x 3
+    uint8_t* dGray[2];            // rectified gray pair for the chained matcher call: rh x pitch
+    size_t gpitch;
+    uint8_t* hStage;              // pinned: 2 RGB frames in, rh x rw x 3 out
+    rtdm::AllocList mem;
+    hipStream_t stream;
+};
+
+struct rtdm_objects {
+    int W, H, device, maxRec;
+    uint8_t *dRgb, *dMaskIn, *dMaskOut, *dT0, *dT1;
+    void* dScratch;
+    int* hRec;                    // pinned: [0] = count, then the first HEAD records
+    std::vector<int> all;         // host copy of every record when there are more than HEAD
+    rtdm::AllocList mem;
+    hipStream_t stream;
+};
+
+struct rtdm_wls {
+    rtdm_wls_params p;
+    int maxW, maxH, maxB, device;
+    hipStream_t stream;
+    float* dLut;                   // W5: lut[k] = exp(-sqrt(k) / sigma), k = 0 .. 3 * 255^2
+    float2* dF;                    // [maxB][maxH][maxW] the two right-hand sides / solutions
+    float *dWh, *dWv;              // neighbour weights
+    uint8_t* dConf;                // C in {0, 255}
+    rtdm::WlsMM *dMML, *dMMR;            // W3 row windows
+    int16_t *dInL, *dInR, *dOut;   // single-frame staging of the host entry points
+    uint8_t *dGuide, *dImgR;
+    float *dConfOut, *dFilt;
+    rtdm::AllocList mem;
+};
+
+struct rtdm_xyz {
+    rtdm_xyz_params p;
+    int maxW, maxH, maxB, device;
+    hipStream_t stream;
+    int *dMin, *dTile, *dCounts;   // [maxB] frame minima, [maxB][tiles of maxW x maxH] tile counts, [maxB] counts of a host call
+    // single-frame staging of the host entry points
+    int16_t* dDisp;
+    uint8_t *dGuide, *dMask, *dImgL, *dImgR;
+    float *dXYZ, *dZ;
+    rtdm::XyzRec* dPts;
+    rtdm::AllocList mem;
+};
+
+struct rtdm_mjpeg {
+    int maxW, maxH, maxB, device;
+    size_t maxBytes, slot;         // longest stream served; its slot in the staging area (maxBytes rounded up to 16)
+    size_t maxSegs, maxBlocks;     // per frame: entropy segments (one MCU each at worst), 8 x 8 blocks of three full planes
+    hipStream_t stream;
+    hipEvent_t evStaged;           // the staging area is on its way to the device up to here ...
+    bool staged;                   // ... and must not be overwritten before
+    uint8_t* hStreams; rtdm::MjpegDesc* hDesc; rtdm::MjpegSeg* hSegs; int* hStatus;     // page-locked
+    uint8_t* dStreams; rtdm::MjpegDesc* dDesc; rtdm::MjpegSeg* dSegs;
+    int16_t* dCoef;                // [maxB][blocks][64] dequantised coefficients
+    uint8_t* dPlanes;              // [maxB] planar Y, Cb, Cr at their own (padded) resolutions
+    uint8_t* dRgb;                 // one frame for the host entry point
+    int* dStatus;                  // [maxB + 1]
+    rtdm::AllocList mem;
+};
+
+namespace rtdm {
+
+// api_bm.hip.  bm_run_chunk: one chunk (n <= maxB) of device-resident frames, enqueued on s.  bm_download_disp: the internal
+// plane on its way to the staging area; bm_scatter_disp, after the caller's synchronise: its rows into the caller's plane.
+int bm_check_frame(const rtdm_bm* bm, int W, int H);
+int bm_run_chunk(rtdm_bm* bm, int n, Plane8 L, Plane8 R, int W, int H, Plane16W out, hipStream_t s);
+int bm_download_disp(rtdm_bm* bm, int W, int H, hipStream_t s);
+void bm_scatter_disp(const rtdm_bm* bm, int W, int H, int16_t* disp, size_t disp_pitch);
+// the handle's internal disparity plane for W x H frames: rows of Ws = W rounded up to 8 elements (see bm_run_chunk)
+inline size_t bm_ws(int W) { return (size_t)((W + 7) & ~7); }
+inline Plane16W bm_internal_plane(const rtdm_bm* bm, int W, int H) { return Plane16W{bm->dOut, bm_ws(W), bm_ws(W) * (size_t)H}; }
+int depth_check_regions(const rtdm_region* regions, int n, int W, int H, int* flat, int* maxh);   // (api_core.hip)
+// the other handles' files, by prefix
+int rectify_upload(rtdm_rectify* rc, const uint8_t* a, size_t apitch, const uint8_t* b, size_t bpitch, hipStream_t s);
+void rectify_gray_launch(rtdm_rectify* rc, const uint8_t* dl, const uint8_t* dr, int n, Plane8W ol, Plane8W orr, hipStream_t s);
+int objects_run(rtdm_objects* ob, const rtdm_hsv_range* range, int min_area, int zero_border, rtdm_region* boxes, int max_boxes,
+                int* nboxes, rtdm_region* roi, hipStream_t s);
+int wls_check(const rtdm_wls* h, int channels, int W, int H);
+int wls_chunk(rtdm_wls* h, int n, WlsDisp dl, WlsDisp dr, WlsGuide G, WlsOut o, int W, int H, hipStream_t s);
+int wls_download(rtdm_wls* h, int W, int H, int16_t* out, size_t out_pitch, float* conf, size_t conf_pitch, float* filtered,
+                 size_t filtered_pitch, hipStream_t s);
+int xyz_cloud_check(const rtdm_xyz* h, const void* disp, const void* guide, int channels, int width, int height, const void* points,
+                    int capacity, const void* count);
+int xyz_cloud_staged(rtdm_xyz* h, int channels, bool mask, int width, int height, rtdm_point* points, int capacity, int* count,
+                     hipStream_t s);
+int mjpeg_check(const rtdm_mjpeg* h, const uint8_t* stream, size_t len, int W, int H);   // parseable, the call's size, within the handle?
+int mjpeg_chunk(rtdm_mjpeg* h, int m, const uint8_t* const* streams, const size_t* lens, int W, int H, uint8_t* d_rgb, size_t pitch,
+                size_t frame_stride, int* d_status, hipStream_t s, MjpegDesc* shape);
+
+}  // namespace rtdm

@@ -1,4 +1,4 @@
-// rtdm_kernels.h -- internal launch interface between the C-ABI layer (rtdm_api.hip) and the
+// rtdm_kernels.h -- internal launch interface between the C-ABI layer (api_*.hip) and the
 // gfx950 kernels.  Everything here is device-pointer based and asynchronous on `stream`.
 #pragma once
 
@@ -182,7 +182,7 @@ void launch_sgm_wide(const SGMGeom& g, const uint16_t* C, uint16_t* S, int dx, i
 int sgm_wide_waves(int D);
 void sgm_wide_set_mode(int m);
 int sgm_wide_mode();
-// cost_limit > 0: block costs above it set *b.ovf (the caller reads it back: rtdm_api.hip).  cn: 1 (gray) or 3 (interleaved
+// cost_limit > 0: block costs above it set *b.ovf (the caller reads it back: api_sgm.hip).  cn: 1 (gray) or 3 (interleaved
 // colour, reads b.cl / b.cr); ftz: R1's ftzero = max(preFilterCap, 15) | 1, at most 127.  Where a pixel cost can pass 255
 // (sgm_cost16_needed: colour, ftz >= 97, or rtdm_debug_sgm_cost16) the cost stage runs on u16 pixel costs.
 // Returns the name of the path-pass form the call ran ("sweep", "half", "wide_w1", "wide_w4").  D > 256 (or a forced wide

@@ -177,7 +177,7 @@ def test_device_tensors_of_every_alignment_class(pkg, oracle, synth, W, H):
 
 
 def test_batches_large_enough_to_be_autotuned(pkg, oracle, synth):
-    # batches of >= 16 frames time several row-strip counts on the first call (rtdm_api.hip, tune_strips); whatever is
+    # batches of >= 16 frames time several row-strip counts on the first call (api_bm.hip, tune_strips); whatever is
     # chosen, every frame must still be the oracle's, on the tuning call and on the calls after it
     import torch
     n, W, H, D, w = 24, 400, 150, 64, 9
