@@ -1,0 +1,329 @@
+// k_sgm_cost.hip -- the cost stage of the device StereoSGBM (k_sgm.hip: the schedule of passes; oracle/sgm_oracle.c rules R1-R3):
+// from the two frames to the block-cost volume C (u16), laid out [frame][y][x - x0][d] with d fastest on the column domain
+// [x0, x1) = [minD+D, W+min(minD,0)).
+//
+//   k_sgm_bounds x-Sobel (vertical edge replication) clipped to +-ftzero, + ftzero, and the BT bounds of it and of the
+//                intensity (border columns overwritten with ftzero, R1), per pixel and channel  (HBM bound)
+//   k_sgm_pixbox Birchfield-Tomasi pixel cost (gradient + (intensity >> 2), u8, kept in LDS) and the blockSize x blockSize sum
+//                with clamped coordinates -> C (u16), windows <= 7; larger windows: k_sgm_pix (u8 volume) + k_sgm_box / _any
+//                (colour frames and ftzero >= 97, where a pixel cost passes 255: the u16 forms k_sgm_pixbox<Cost16>, k_sgm_pix16)
+#include "rtdm_sgm.h"
+
+#include <atomic>
+
+namespace rtdm {
+
+// R1's ftzero = max(preFilterCap, 15) | 1 comes in at run time: 15 at the default preFilterCap 0, at most 127 (the caller
+// refuses preFilterCap >= 128), so every gradient value, 0 .. 2 ftzero, and every raw value still fits a byte.
+//
+// Per pixel and image, once: the Birchfield-Tomasi bounds (value, min and max against the half-way points to the two
+// neighbours) of the clipped x-gradient and of the raw intensity, packed as two uchar4 -- the pixel-cost kernel then
+// needs one 8-byte load per (pixel, image) instead of six byte loads per (pixel, disparity, image).  CN = 3 (interleaved
+// colour, CV_8UC3): one such uint2 per channel, a 24-byte record per pixel ([f][y][x][c]).
+template <int CN>
+__device__ __forceinline__ int sgm_grad(const uint8_t* r0, const uint8_t* r1, const uint8_t* r2, int x, int W, int ftz)
+{
+    if (x <= 0 || x >= W - 1) return ftz;
+    const int a = (x + 1) * CN, b = (x - 1) * CN;
+    const int g = ((int)r1[a] - (int)r1[b]) * 2 + ((int)r0[a] - (int)r0[b]) + ((int)r2[a] - (int)r2[b]);
+    return min(max(g, -ftz), ftz) + ftz;
+}
+
+template <int CN>
+__global__ __launch_bounds__(256) void k_sgm_bounds(Plane8 L, Plane8 R, uint2* bl, uint2* br, int W, int H, int n, int ftz)
+{
+    const int x = blockIdx.x * 256 + threadIdx.x;
+    if (x >= W) return;
+    const int y = blockIdx.y;
+    int f = blockIdx.z;
+    const bool right = f >= n;
+    if (right) f -= n;
+    const Plane8 S = right ? R : L;
+    const uint8_t* img = S.base + (size_t)f * S.frame;
+    const bool hm = x > 0, hp = x < W - 1;
+#pragma unroll
+    for (int c = 0; c < CN; ++c) {
+        const uint8_t* r1 = img + (size_t)y * S.pitch + c;
+        const uint8_t* r0 = img + (size_t)(y > 0 ? y - 1 : y) * S.pitch + c;
+        const uint8_t* r2 = img + (size_t)(y < H - 1 ? y + 1 : y) * S.pitch + c;
+        const uint32_t gb = bt_pack(sgm_grad<CN>(r0, r1, r2, x, W, ftz), hm ? sgm_grad<CN>(r0, r1, r2, x - 1, W, ftz) : 0,
+                                    hp ? sgm_grad<CN>(r0, r1, r2, x + 1, W, ftz) : 0, hm, hp);
+        // R1: the library overwrites columns 0 and W-1 of the raw-intensity row with ftzero as well, before the bounds are taken
+        const auto raw = [&](int i) -> int { return (i <= 0 || i >= W - 1) ? ftz : (int)r1[i * CN]; };
+        const uint32_t rb = bt_pack(raw(x), hm ? raw(x - 1) : 0, hp ? raw(x + 1) : 0, hm, hp);
+        (right ? br : bl)[(((size_t)f * H + y) * W + x) * CN + c] = make_uint2(gb, rb);
+    }
+}
+
+// A pixel cost is at most M = CN (2 ftzero + 63): 93 for gray at preFilterCap 0, 255 for gray at ftzero 96, 279 .. 951 for colour
+// (CN = 3, interleaved; the channels are summed in packed u16, <= 951 per half: no carry).  Two forms of four consecutive pixel
+// costs (disparities d .. d + 3 of one column; sgm_cost4, rtdm_sgm.h), for the volume and for the fused kernel's LDS tile:
+//   Cost8       four u8 in a dword: gray up to ftzero 96
+//   Cost16<CN>  four u16 in a uint2: colour at any preFilterCap, gray at ftzero >= 97 (and rtdm_debug_sgm_cost16).  Its block
+//               sums are checked against cost_limit (> 0 where a block cost + P2 can pass 32767); Cost8's stay below it.
+struct Cost8 {
+    typedef uint32_t Word;
+    static constexpr bool CHECK = false, ROLL_P = false;
+    static __device__ __forceinline__ Word cost(const uint2* bl, const uint2* br, size_t row, int x, int xr)
+    { const uint2 c = sgm_cost4<1>(bl, br, row, x, xr); return __builtin_amdgcn_perm(c.y, c.x, 0x06040200u); }
+    static __device__ __forceinline__ void widen(Word w, uint32_t& h0, uint32_t& h1)
+    { h0 = __builtin_amdgcn_perm(0u, w, 0x0C010C00u); h1 = __builtin_amdgcn_perm(0u, w, 0x0C030C02u); }   // (d, d + 1), (d + 2, d + 3) as u16
+};
+template <int CN>
+struct Cost16 {
+    typedef uint2 Word;
+    // (colour: the fused kernel's p loop stays rolled, or the whole body of its unrolled k loop grows past what the compiler
+    // unrolls, and then ring[][k] goes to scratch)
+    static constexpr bool CHECK = true, ROLL_P = CN != 1;
+    static __device__ __forceinline__ Word cost(const uint2* bl, const uint2* br, size_t row, int x, int xr) { return sgm_cost4<CN>(bl, br, row, x, xr); }
+    static __device__ __forceinline__ void widen(Word w, uint32_t& h0, uint32_t& h1) { h0 = w.x; h1 = w.y; }
+};
+
+// pixel cost, u8 volume: one thread per (x, four consecutive d); d fastest
+__global__ __launch_bounds__(256) void k_sgm_pix(const uint2* bl, const uint2* br, uint8_t* pix, SGMGeom g)
+{
+    const int dq = g.D >> 2;
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;          // over W1 * D/4
+    if (idx >= (size_t)g.W1 * dq) return;
+    const int d = (int)(idx % dq) * 4, xi = (int)(idx / dq);
+    const int y = blockIdx.y, f = blockIdx.z;
+    const int x = g.x0 + xi, xr = x - (d + g.minD);                     // element j pairs x with xr - j
+    const size_t row = ((size_t)f * g.H + y) * g.W;
+    *(uint32_t*)(pix + (((size_t)f * g.H + y) * g.W1 + xi) * g.D + d) = Cost8::cost(bl, br, row, x, xr);
+}
+
+// k_sgm_pix with u16 pixel costs -> pix [n][H][W1][D] (it lives in S, dead until the first path pass writes it)
+template <int CN>
+__global__ __launch_bounds__(256) void k_sgm_pix16(const uint2* bl, const uint2* br, uint16_t* pix, SGMGeom g)
+{
+    const int dq = g.D >> 2;
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;          // over W1 * D/4
+    if (idx >= (size_t)g.W1 * dq) return;
+    const int d = (int)(idx % dq) * 4, xi = (int)(idx / dq);
+    const int y = blockIdx.y, f = blockIdx.z;
+    const int x = g.x0 + xi, xr = x - (d + g.minD);
+    const size_t row = ((size_t)f * g.H + y) * g.W;
+    *(uint2*)(pix + (((size_t)f * g.H + y) * g.W1 + xi) * g.D + d) = sgm_cost4<CN>(bl, br, row, x, xr);
+}
+
+// four consecutive pixel costs (u8 volume: one dword, u16 volume: one qword) added to s[0..3]
+__device__ __forceinline__ void sgm_acc4(const uint8_t* p, int* s)
+{ const uint32_t w = *(const uint32_t*)p; s[0] += w & 0xff; s[1] += (w >> 8) & 0xff; s[2] += (w >> 16) & 0xff; s[3] += w >> 24; }
+__device__ __forceinline__ void sgm_acc4(const uint16_t* p, int* s)
+{ const uint2 w = *(const uint2*)p; s[0] += w.x & 0xffff; s[1] += w.x >> 16; s[2] += w.y & 0xffff; s[3] += w.y >> 16; }
+
+// block cost: thread = (x, four consecutive d); walks down a strip of rows keeping the last 2R+1 horizontal sums in
+// registers, so every pixel-cost element is read (2R+1) times instead of (2R+1)^2 times.  T: the pixel-cost volume's type
+// (uint8_t, or uint16_t where a pixel cost can pass 255: colour, preFilterCap >= 96)
+template <int R, typename T>
+__global__ __launch_bounds__(256) void k_sgm_box(const T* pix, uint16_t* C, SGMGeom g, int rows_per_strip, int cost_limit, int32_t* ovf)
+{
+    const int dq = g.D >> 2;
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;          // over W1 * D/4
+    if (idx >= (size_t)g.W1 * dq) return;
+    const int d = (int)(idx % dq) * 4, xi = (int)(idx / dq);
+    const int f = blockIdx.z;
+    const int y0 = blockIdx.y * rows_per_strip, y1 = min(y0 + rows_per_strip, g.H);
+    const T* base = pix + (size_t)f * g.H * g.W1 * g.D + d;
+    int xs[2 * R + 1];
+#pragma unroll
+    for (int k = 0; k <= 2 * R; ++k) xs[k] = min(max(xi + k - R, 0), g.W1 - 1) * g.D;
+    struct Sum4 { int v[4]; };
+    const auto hsum = [&](int y) -> Sum4 {
+        const T* row = base + (size_t)min(max(y, 0), g.H - 1) * g.W1 * g.D;
+        Sum4 s = {{0, 0, 0, 0}};
+#pragma unroll
+        for (int k = 0; k <= 2 * R; ++k) sgm_acc4(row + xs[k], s.v);
+        return s;
+    };
+    Sum4 ring[2 * R + 1];
+    int sum[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int k = 0; k <= 2 * R; ++k) {
+        ring[k] = hsum(y0 - R + k);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) sum[j] += ring[k].v[j];
+    }
+    uint16_t* out = C + (((size_t)f * g.H) * g.W1 + xi) * g.D + d;
+    for (int y = y0; y < y1; y += 2 * R + 1) {
+#pragma unroll
+        for (int k = 0; k <= 2 * R; ++k) {
+            if (y + k < y1) {
+                *(uint2*)(out + (size_t)(y + k) * g.W1 * g.D) =
+                    make_uint2((uint32_t)sum[0] | ((uint32_t)sum[1] << 16), (uint32_t)sum[2] | ((uint32_t)sum[3] << 16));
+                if (cost_limit > 0 && max(max(sum[0], sum[1]), max(sum[2], sum[3])) > cost_limit) *ovf = 1;
+                const Sum4 h = hsum(y + k + R + 1);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) { sum[j] += h.v[j] - ring[k].v[j]; }
+                ring[k] = h;
+            }
+        }
+    }
+}
+
+// Pixel cost and block sum in ONE kernel for the small windows (R <= 3; D = 16, 32, 64, 128, 256): a workgroup owns a tile of
+// TX = 4 * CG output columns (CG = 256 / (D / 4) columns per pass of its threads) and walks a strip of rows; per source row every
+// thread computes the Birchfield-Tomasi costs of ~4.5 (column, four disparities) items of the tile + halo into LDS (k_sgm_pix's
+// arithmetic, in the form F: Cost8 or Cost16<CN>), and after one barrier (the tile is double-buffered) sums 2R + 1 of them from
+// LDS for each of its four output columns and slides the vertical window in registers (k_sgm_box's ring, packed u16: block sums
+// stay below 49 * 951 < 65536).  The pixel-cost volume is neither written nor read: 280 MB of HBM traffic per 720p D = 128
+// pair, and k_sgm_box's 2R + 1 trips to L2 per output are LDS reads.  F::CHECK: block sums above cost_limit (> 0) set *ovf.
+template <typename F, int R, int DQ>
+__global__ __launch_bounds__(256) void k_sgm_pixbox(const uint2* bl, const uint2* br, uint16_t* C, SGMGeom g, int rows_per_strip,
+                                                    int cost_limit, int32_t* ovf)
+{
+    constexpr int CG = 256 / DQ, TX = 4 * CG, TW = TX + 2 * R, NP = (TW + CG - 1) / CG, W1R = 2 * R + 1, PU = F::ROLL_P ? 1 : NP;
+    __shared__ typename F::Word tile[2][TW][DQ];            // [row parity][tile column][disparity quad]: four pixel costs
+    const int dqi = threadIdx.x % DQ, cg = threadIdx.x / DQ, d = dqi * 4;
+    const int xt0 = blockIdx.x * TX;                        // first output column of the tile (W1 domain)
+    const int f = blockIdx.z;
+    const int y0 = blockIdx.y * rows_per_strip, y1 = min(y0 + rows_per_strip, g.H);
+    uint32_t ring[4][W1R][2], sum[4][2];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { sum[i][0] = sum[i][1] = 0u; for (int k = 0; k < W1R; ++k) ring[i][k][0] = ring[i][k][1] = 0u; }
+    bool over = false;
+    const int nsrc = (y1 - y0) + 2 * R;                     // source rows y0 - R .. y1 - 1 + R (clamped into the frame)
+    for (int base = 0; base < nsrc; base += W1R) {
+#pragma unroll
+        for (int k = 0; k < W1R; ++k) {
+            const int t = base + k;
+            if (t < nsrc) {                                 // workgroup-uniform
+                const int par = t & 1;
+                const int ysrc = min(max(y0 - R + t, 0), g.H - 1);
+                const size_t row = ((size_t)f * g.H + ysrc) * g.W;
+                // pixel costs of this row's tile columns (+ halo), clamped into [0, W1)
+#pragma unroll PU
+                for (int p = 0; p < NP; ++p) {
+                    const int tc = cg + p * CG;
+                    if (tc < TW) {
+                        const int xi = min(max(xt0 - R + tc, 0), g.W1 - 1);
+                        const int x = g.x0 + xi;
+                        tile[par][tc][dqi] = F::cost(bl, br, row, x, x - (d + g.minD));
+                    }
+                }
+                __syncthreads();
+                const int yo = y0 - 2 * R + t;               // the output row whose window this source row completes
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int tcol = cg + i * CG;            // output column xt0 + tcol: tile columns tcol .. tcol + 2R
+                    uint32_t h0 = 0u, h1 = 0u;
+#pragma unroll
+                    for (int q = 0; q < W1R; ++q) {
+                        uint32_t w0, w1;
+                        F::widen(tile[par][tcol + q][dqi], w0, w1);
+                        h0 = sgm_add2(h0, w0);
+                        h1 = sgm_add2(h1, w1);
+                    }
+                    sum[i][0] = sgm_sub2(sgm_add2(sum[i][0], h0), ring[i][k][0]);
+                    sum[i][1] = sgm_sub2(sgm_add2(sum[i][1], h1), ring[i][k][1]);
+                    ring[i][k][0] = h0; ring[i][k][1] = h1;
+                    const int xo = xt0 + tcol;
+                    if (yo >= y0 && xo < g.W1) {
+                        *(uint2*)(C + (((size_t)f * g.H + yo) * g.W1 + xo) * g.D + d) = make_uint2(sum[i][0], sum[i][1]);
+                        if constexpr (F::CHECK) {
+                            const uint32_t m = sgm_max2(sum[i][0], sum[i][1]);
+                            over |= (int)max(m & 0xffffu, m >> 16) > cost_limit;
+                        }
+                    }
+                }
+            }
+        }
+    }
+    if (F::CHECK && cost_limit > 0 && over) *ovf = 1;
+}
+
+// Any window (R > 8: the register ring of k_sgm_box<R> would not fit): the running vertical sum gains the entering row's
+// horizontal sum and loses the leaving row's, both recomputed -- 2 (2R + 1) loads per output instead of 2R + 1.  Sums are
+// 32-bit; a block cost above cost_limit (> 0) sets *ovf and is stored truncated (the caller refuses the frame).
+template <typename T>
+__global__ __launch_bounds__(256) void k_sgm_box_any(const T* pix, uint16_t* C, SGMGeom g, int R, int rows_per_strip, int cost_limit, int32_t* ovf)
+{
+    const int dq = g.D >> 2;
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;          // over W1 * D/4
+    if (idx >= (size_t)g.W1 * dq) return;
+    const int d = (int)(idx % dq) * 4, xi = (int)(idx / dq);
+    const int f = blockIdx.z;
+    const int y0 = blockIdx.y * rows_per_strip, y1 = min(y0 + rows_per_strip, g.H);
+    const T* base = pix + (size_t)f * g.H * g.W1 * g.D + d;
+    struct Sum4 { int v[4]; };
+    const auto hsum = [&](int y) -> Sum4 {
+        const T* row = base + (size_t)min(max(y, 0), g.H - 1) * g.W1 * g.D;
+        Sum4 s = {{0, 0, 0, 0}};
+        for (int k = -R; k <= R; ++k) sgm_acc4(row + (size_t)min(max(xi + k, 0), g.W1 - 1) * g.D, s.v);
+        return s;
+    };
+    int sum[4] = {0, 0, 0, 0};
+    for (int k = -R; k <= R; ++k) { const Sum4 h = hsum(y0 + k); for (int j = 0; j < 4; ++j) sum[j] += h.v[j]; }
+    uint16_t* out = C + (((size_t)f * g.H) * g.W1 + xi) * g.D + d;
+    for (int y = y0; y < y1; ++y) {
+        *(uint2*)(out + (size_t)y * g.W1 * g.D) =
+            make_uint2((uint32_t)(sum[0] & 0xffff) | ((uint32_t)sum[1] << 16), (uint32_t)(sum[2] & 0xffff) | ((uint32_t)sum[3] << 16));
+        if (cost_limit > 0 && max(max(sum[0], sum[1]), max(sum[2], sum[3])) > cost_limit) *ovf = 1;
+        const Sum4 a = hsum(y + R + 1), b = hsum(y - R);
+        for (int j = 0; j < 4; ++j) sum[j] += a.v[j] - b.v[j];
+    }
+}
+
+// rtdm_debug_sgm_cost16: the u16 cost forms for gray frames as well (they must give what the u8 forms give)
+static std::atomic<int> g_cost16{0};
+void sgm_cost16_set(int on) { g_cost16.store(on ? 1 : 0, std::memory_order_relaxed); }
+bool sgm_cost16_needed(int cn, int ftz) { return cn != 1 || 2 * ftz + 63 > 255 || g_cost16.load(std::memory_order_relaxed); }
+
+// The fused kernel over (form, R, DQ)
+template <typename F>
+static void launch_pixbox(const SGMGeom& g, const SGMBuffers& b, const uint2* bl, const uint2* br, int Rw, int cost_limit, int n, hipStream_t stream)
+{
+    const int dq = g.D / 4, rps = 48, strips = (g.H + rps - 1) / rps, tx = 4 * (256 / dq);
+    const dim3 pgrid((g.W1 + tx - 1) / tx, strips, n), blk(256);
+#define RTDM_PB(RR, QQ) hipLaunchKernelGGL((k_sgm_pixbox<F, RR, QQ>), pgrid, blk, 0, stream, bl, br, b.C, g, rps, cost_limit, b.ovf)
+#define RTDM_PBQ(RR) do { switch (dq) { case 4: RTDM_PB(RR, 4); break; case 8: RTDM_PB(RR, 8); break; case 16: RTDM_PB(RR, 16); break; \
+                                       case 32: RTDM_PB(RR, 32); break; default: RTDM_PB(RR, 64); break; } } while (0)
+    switch (Rw) { case 0: RTDM_PBQ(0); break; case 1: RTDM_PBQ(1); break; case 2: RTDM_PBQ(2); break; default: RTDM_PBQ(3); break; }
+#undef RTDM_PBQ
+#undef RTDM_PB
+}
+
+// The block sum over a pixel-cost volume of type T: the row sums of a strip stay in registers for windows <= 17 (u8) / <= 13
+// (u16: the register ring of k_sgm_box<R> holds 64-bit loads as well; above it would spill), k_sgm_box_any above
+template <typename T>
+static void launch_box(const SGMGeom& g, const SGMBuffers& b, const T* pix, int Rw, int cost_limit, int n, hipStream_t stream)
+{
+    constexpr int RMAX = sizeof(T) == 1 ? 8 : 6;
+    const int rps = 48, strips = (g.H + rps - 1) / rps;
+    const dim3 bgrid((unsigned)(((size_t)g.W1 * (g.D / 4) + 255) / 256), strips, n), blk(256);
+    switch (Rw) {                                       // a case above RMAX launches nothing and leaves the switch for k_sgm_box_any
+#define RTDM_BOX(RR) case RR: if constexpr (RR <= RMAX) { hipLaunchKernelGGL((k_sgm_box<RR, T>), bgrid, blk, 0, stream, pix, b.C, g, rps, cost_limit, b.ovf); return; } break;
+        RTDM_BOX(0) RTDM_BOX(1) RTDM_BOX(2) RTDM_BOX(3) RTDM_BOX(4) RTDM_BOX(5) RTDM_BOX(6) RTDM_BOX(7) RTDM_BOX(8)
+#undef RTDM_BOX
+    }
+    hipLaunchKernelGGL(k_sgm_box_any<T>, bgrid, blk, 0, stream, pix, b.C, g, Rw, rps, cost_limit, b.ovf);
+}
+
+// The whole cost stage: the bounds, then pixel cost and block sum -> b.C -- fused for windows <= 7 and D in {16, 32, 64, 128,
+// 256} (the u8 form: only where no block cost can pass cost_limit; the u16 form checks it itself), otherwise two kernels with
+// the pixel-cost volume between them (u8: b.pix; u16: b.S, which is not written before the first path pass)
+void launch_sgm_cost(Plane8 L, Plane8 R, const SGMGeom& g, const SGMBuffers& b, int blockSize, int cost_limit, int cn, int ftz, int n,
+                     hipStream_t stream)
+{
+    const dim3 blk(256), bnd((g.W + 255) / 256, g.H, 2 * n);
+    if (cn == 3) hipLaunchKernelGGL(k_sgm_bounds<3>, bnd, blk, 0, stream, L, R, (uint2*)b.cl, (uint2*)b.cr, g.W, g.H, n, ftz);
+    else hipLaunchKernelGGL(k_sgm_bounds<1>, bnd, blk, 0, stream, L, R, (uint2*)b.gl, (uint2*)b.gr, g.W, g.H, n, ftz);
+    const uint2 *bl = (const uint2*)(cn == 3 ? b.cl : b.gl), *br = (const uint2*)(cn == 3 ? b.cr : b.gr);
+    const int Rw = blockSize / 2, dq = g.D / 4;                         // D is a multiple of 16
+    const bool fused = Rw <= 3 && (dq == 4 || dq == 8 || dq == 16 || dq == 32 || dq == 64);
+    const dim3 xgrid((unsigned)(((size_t)g.W1 * dq + 255) / 256), g.H, n);
+    if (!sgm_cost16_needed(cn, ftz)) {
+        if (fused && !cost_limit) return launch_pixbox<Cost8>(g, b, bl, br, Rw, 0, n, stream);
+        hipLaunchKernelGGL(k_sgm_pix, xgrid, blk, 0, stream, bl, br, b.pix, g);
+        launch_box<uint8_t>(g, b, b.pix, Rw, cost_limit, n, stream);
+    } else if (fused) {
+        if (cn == 3) launch_pixbox<Cost16<3>>(g, b, bl, br, Rw, cost_limit, n, stream);
+        else launch_pixbox<Cost16<1>>(g, b, bl, br, Rw, cost_limit, n, stream);
+    } else {
+        if (cn == 3) hipLaunchKernelGGL(k_sgm_pix16<3>, xgrid, blk, 0, stream, bl, br, b.S, g);
+        else hipLaunchKernelGGL(k_sgm_pix16<1>, xgrid, blk, 0, stream, bl, br, b.S, g);
+        launch_box<uint16_t>(g, b, b.S, Rw, cost_limit, n, stream);
+    }
+}
+
+}  // namespace rtdm

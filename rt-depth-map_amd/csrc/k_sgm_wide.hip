@@ -1,5 +1,5 @@
 // k_sgm_wide.hip -- the StereoSGBM path pass for wide lines: every numDisparities from 16 to 4080 in steps of 16 (the narrow
-// forms in k_sgm.hip hold at most 256 disparities per line).  Same recurrence as k_sgm_path_h (oracle/sgm_oracle.c R4, R5),
+// forms in k_sgm_paths.hip hold at most 256 disparities per line).  Same recurrence as k_sgm_path_h (oracle/sgm_oracle.c R4, R5),
 // same packed u16 arithmetic, same 0xffff "no neighbour" sentinel; what changes is how a line is spread over lanes:
 //
 //   NW = 1  one WAVE per line (four lines per workgroup), lane l holds the 2 * NP2 consecutive disparities 2 NP2 l .. as NP2
@@ -13,65 +13,11 @@
 // every element, which never wins a minimum against a live value (<= 32767) and acts as the missing d + 1 of d = D - 1.
 // LAST (the frame's last direction) decides the winners with the 12-bit key (S << 12) | d < 2^27 and writes the SgmWin record
 // k_sgm_lrfinal reads, as k_sgm_path_h<.., true> does.
-#include "rtdm_kernels.h"
-#include "rtdm_device.h"
+#include "rtdm_sgm.h"
 
 #include <atomic>
 
 namespace rtdm {
-namespace {
-
-typedef unsigned short wus2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uint32_t w_min2(uint32_t a, uint32_t b)
-{ return __builtin_bit_cast(uint32_t, __builtin_elementwise_min(__builtin_bit_cast(wus2, a), __builtin_bit_cast(wus2, b))); }
-__device__ __forceinline__ uint32_t w_add2(uint32_t a, uint32_t b)
-{ return __builtin_bit_cast(uint32_t, (wus2)(__builtin_bit_cast(wus2, a) + __builtin_bit_cast(wus2, b))); }
-__device__ __forceinline__ uint32_t w_sub2(uint32_t a, uint32_t b)
-{ return __builtin_bit_cast(uint32_t, (wus2)(__builtin_bit_cast(wus2, a) - __builtin_bit_cast(wus2, b))); }
-__device__ __forceinline__ uint32_t w_adds2(uint32_t a, uint32_t b)
-{ return __builtin_bit_cast(uint32_t, __builtin_elementwise_add_sat(__builtin_bit_cast(wus2, a), __builtin_bit_cast(wus2, b))); }
-
-template <int NP2> struct WPack { uint32_t w[NP2]; };
-template <int NP2>
-__device__ __forceinline__ WPack<NP2> w_ld(const uint16_t* p)
-{
-    WPack<NP2> r;
-    if constexpr (NP2 == 1) { r.w[0] = *(const uint32_t*)p; }
-    else if constexpr (NP2 == 2) { const uint2 v = *(const uint2*)p; r.w[0] = v.x; r.w[1] = v.y; }
-    else {
-#pragma unroll
-        for (int q = 0; q < NP2 / 4; ++q) {
-            const uint4 v = *(const uint4*)(p + 8 * q);
-            r.w[4 * q] = v.x; r.w[4 * q + 1] = v.y; r.w[4 * q + 2] = v.z; r.w[4 * q + 3] = v.w;
-        }
-    }
-    return r;
-}
-template <int NP2>
-__device__ __forceinline__ void w_st(uint16_t* p, const uint32_t* o)
-{
-    if constexpr (NP2 == 1) { *(uint32_t*)p = o[0]; }
-    else if constexpr (NP2 == 2) { *(uint2*)p = make_uint2(o[0], o[1]); }
-    else {
-#pragma unroll
-        for (int q = 0; q < NP2 / 4; ++q) *(uint4*)(p + 8 * q) = make_uint4(o[4 * q], o[4 * q + 1], o[4 * q + 2], o[4 * q + 3]);
-    }
-}
-
-// minimum over the whole wave, in every lane (values < 2^31): the row's minimum by four DPP steps, then rows 0|1 and 2|3 by
-// v_permlane16_swap, then the two halves by v_permlane32_swap
-__device__ __forceinline__ int w_wave_min(int v)
-{
-#define RTDM_DPP_MIN(ctrl) v = min(v, __builtin_amdgcn_update_dpp(0x7fffffff, v, ctrl, 0xf, 0xf, false))
-    RTDM_DPP_MIN(0xB1); RTDM_DPP_MIN(0x4E); RTDM_DPP_MIN(0x141); RTDM_DPP_MIN(0x140);
-#undef RTDM_DPP_MIN
-    const auto s = __builtin_amdgcn_permlane16_swap((unsigned)v, (unsigned)v, false, false);
-    v = min((int)s[0], (int)s[1]);
-    const auto t = __builtin_amdgcn_permlane32_swap((unsigned)v, (unsigned)v, false, false);
-    return min((int)t[0], (int)t[1]);
-}
-
-}  // namespace
 
 // One line of direction (dx, dy) per wave (NW = 1) or per workgroup (NW = 4); S (+)= L_r, or (LAST) the winners.
 template <int NP2, int NW, int PF, bool LAST>
@@ -88,13 +34,7 @@ __global__ __launch_bounds__(256) void k_sgm_wide(const uint16_t* C, uint16_t* S
     if (line >= nlines) return;                                   // whole waves (NW = 1) / whole workgroups (NW = 4)
     const int D = g.D, W1 = g.W1, H = g.H;
     int sx, sy;
-    if (dy == 0) { sy = line; sx = dx > 0 ? 0 : W1 - 1; }
-    else if (dx == 0) { sx = line; sy = dy > 0 ? 0 : H - 1; }
-    else if (line < W1) { sx = line; sy = dy > 0 ? 0 : H - 1; }
-    else { const int k = line - W1 + 1; sx = dx > 0 ? 0 : W1 - 1; sy = dy > 0 ? k : H - 1 - k; }
-    const int nx = dx > 0 ? W1 - sx : (dx < 0 ? sx + 1 : 0x7fffffff);
-    const int ny = dy > 0 ? H - sy : (dy < 0 ? sy + 1 : 0x7fffffff);
-    const int nsteps = min(nx, ny);                               // uniform over the line's lanes
+    const int nsteps = sgm_line_start(line, dx, dy, W1, H, sx, sy);   // uniform over the line's lanes
     const int li = NW == 1 ? lane : wv * 64 + lane;               // lane of the line
     const int d0 = li * LPD;
     const bool live = d0 < D;                                     // whole lanes: D is a multiple of 16 >= LPD
@@ -104,14 +44,14 @@ __global__ __launch_bounds__(256) void k_sgm_wide(const uint16_t* C, uint16_t* S
     const uint16_t* cp = C + off0;
     uint16_t* sp = S + off0;
     const uint32_t P1s = (uint32_t)P1 * 0x10001u, P2s = (uint32_t)P2 * 0x10001u;
-    WPack<NP2> cr[PF], sr[PF];
+    PackW<NP2> cr[PF], sr[PF];
 #pragma unroll
     for (int k = 0; k < PF; ++k) {
 #pragma unroll
         for (int r = 0; r < NP2; ++r) cr[k].w[r] = sr[k].w[r] = 0u;
         if (live && k < nsteps) {
-            cr[k] = w_ld<NP2>(cp + (long)k * stride);
-            if (!first_dir) sr[k] = w_ld<NP2>(sp + (long)k * stride);
+            cr[k] = ld_w<NP2>(cp + (long)k * stride);
+            if (!first_dir) sr[k] = ld_w<NP2>(sp + (long)k * stride);
         }
     }
     uint32_t l[NP2];
@@ -122,10 +62,10 @@ __global__ __launch_bounds__(256) void k_sgm_wide(const uint16_t* C, uint16_t* S
         for (int k = 0; k < PF; ++k) {
             const int step = base + k;
             if (step >= nsteps) break;
-            const WPack<NP2> c = cr[k], sv = sr[k];
+            const PackW<NP2> c = cr[k], sv = sr[k];
             if (live && step + PF < nsteps) {
-                cr[k] = w_ld<NP2>(cp + (long)(step + PF) * stride);
-                if (!first_dir) sr[k] = w_ld<NP2>(sp + (long)(step + PF) * stride);
+                cr[k] = ld_w<NP2>(cp + (long)(step + PF) * stride);
+                if (!first_dir) sr[k] = ld_w<NP2>(sp + (long)(step + PF) * stride);
             }
             if (step == 0) {
 #pragma unroll
@@ -139,26 +79,20 @@ __global__ __launch_bounds__(256) void k_sgm_wide(const uint16_t* C, uint16_t* S
                 hi = lane == 63 ? ehi : hi;
                 uint32_t nl[NP2];
 #pragma unroll
-                for (int r = 0; r < NP2; ++r) {
-                    const uint32_t prev = r ? l[r - 1] : lo, next = r + 1 < NP2 ? l[r + 1] : hi;
-                    const uint32_t dn = __builtin_amdgcn_alignbit(l[r], prev, 16);      // {prev.hi, own.lo}: d - 1 of both elements
-                    const uint32_t up = __builtin_amdgcn_alignbit(next, l[r], 16);      // {own.hi, next.lo}: d + 1
-                    const uint32_t best = w_min2(w_min2(l[r], mpP2), w_adds2(w_min2(dn, up), P1s));
-                    nl[r] = w_sub2(w_add2(c.w[r], best), mps);
-                }
+                for (int r = 0; r < NP2; ++r) nl[r] = sgm_pair_step(r ? l[r - 1] : lo, l[r], r + 1 < NP2 ? l[r + 1] : hi, c.w[r], mps, mpP2, P1s);
 #pragma unroll
                 for (int r = 0; r < NP2; ++r) l[r] = live ? nl[r] : NONE;
             }
             uint32_t o[NP2];
 #pragma unroll
-            for (int r = 0; r < NP2; ++r) o[r] = first_dir ? l[r] : w_min2(w_add2(sv.w[r], l[r]), 0x7fff7fffu);   // R5
+            for (int r = 0; r < NP2; ++r) o[r] = first_dir ? l[r] : sgm_min2(sgm_add2(sv.w[r], l[r]), 0x7fff7fffu);   // R5
             if constexpr (!LAST) {
-                if (live) w_st<NP2>(sp + (long)step * stride, o);
+                if (live) st_w<NP2>(sp + (long)step * stride, o);
             }
             uint32_t mm = l[0];
 #pragma unroll
-            for (int r = 1; r < NP2; ++r) mm = w_min2(mm, l[r]);
-            int m = w_wave_min((int)min(mm & 0xffffu, mm >> 16));
+            for (int r = 1; r < NP2; ++r) mm = sgm_min2(mm, l[r]);
+            int m = wave_min_i32((int)min(mm & 0xffffu, mm >> 16));
             int key = 0x7fffffff;
             if constexpr (LAST) {
                 // R6: the first minimum -- key (S << 12) | d, d < 4096, S <= 32767
@@ -167,7 +101,7 @@ __global__ __launch_bounds__(256) void k_sgm_wide(const uint16_t* C, uint16_t* S
                     key = min(key, (int)(((o[r] & 0xffffu) << 12) | (unsigned)(d0 + 2 * r)));
                     key = min(key, (int)(((o[r] >> 16) << 12) | (unsigned)(d0 + 2 * r + 1)));
                 }
-                key = w_wave_min(live ? key : 0x7fffffff);
+                key = wave_min_i32(live ? key : 0x7fffffff);
             }
             if constexpr (NW > 1) {
                 const int p = step & 1;
@@ -183,7 +117,7 @@ __global__ __launch_bounds__(256) void k_sgm_wide(const uint16_t* C, uint16_t* S
                 ehi = wv < NW - 1 ? xlo[p][wv + 1] : NONE;
             }
             mps = (uint32_t)m * 0x10001u;
-            mpP2 = w_add2(mps, P2s);
+            mpP2 = sgm_add2(mps, P2s);
             if constexpr (LAST) {
                 const int mins = key >> 12, bd = key & 0xfff;
                 bool hit = false;
@@ -220,14 +154,7 @@ __global__ __launch_bounds__(256) void k_sgm_wide(const uint16_t* C, uint16_t* S
                 // every aggregated cost saturated at 32767: the library finds no winner (sgm_wta_half)
                 rejected |= mins >= 32767;
                 if (wv == 0 || NW == 1) {
-                    int d16 = bd * 16;
-                    if (bd > 0 && bd < D - 1) {
-                        const int den = max(s_n + s_p - 2 * mins, 1);
-                        d16 += div_trunc_rcp((s_n - s_p) * 16 + den, den * 2);        // |numerator| < 2^21
-                    }
-                    SgmWin w;
-                    w.d16 = (int16_t)((g.minD - 1) * 16); w.bd = (int16_t)(g.minD - 1); w.mins = 0; w.pad = 0;
-                    if (!rejected) { w.d16 = (int16_t)(d16 + g.minD * 16); w.bd = (int16_t)(bd + g.minD); w.mins = (uint16_t)mins; }
+                    const SgmWin w = sgm_win_record(bd, mins, s_p, s_n, rejected, D, g.minD);
                     if (lane == 0) {
                         const int xi = sx + step * dx, yy = sy + step * dy;
                         win[((size_t)blockIdx.y * H + yy) * W1 + xi] = w;
@@ -270,7 +197,7 @@ void launch_sgm_wide(const SGMGeom& g, const uint16_t* C, uint16_t* S, int dx, i
     const int nw = sgm_wide_waves(g.D);
     int np2 = 1;
     while (nw * 128 * np2 < g.D) np2 *= 2;                        // D <= 4080 < 4 * 128 * 8
-    const int lines = dy == 0 ? g.H : (dx == 0 ? g.W1 : g.W1 + g.H - 1);
+    const int lines = sgm_line_count(g, dx, dy);
 #define RTDM_WIDE(N, W) launch_wide_t<N, W>(g, C, S, dx, dy, P1, P2, first, last, lines, n, win, uniq, stream)
     if (nw == 1) {
         switch (np2) { case 1: RTDM_WIDE(1, 1); break; case 2: RTDM_WIDE(2, 1); break; case 4: RTDM_WIDE(4, 1); break; default: RTDM_WIDE(8, 1); break; }

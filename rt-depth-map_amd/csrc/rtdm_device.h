@@ -1,4 +1,4 @@
-// rtdm_device.h -- device-side helpers shared by the row kernels (k_basic.hip, k_sgm.hip):
+// rtdm_device.h -- device-side helpers shared by the row kernels (k_basic.hip, k_sgm.hip; the StereoSGBM units' own: rtdm_sgm.h):
 // workgroup scans over a row held in LDS, union-find primitives, the speckle filter's per-row init.
 #pragma once
 

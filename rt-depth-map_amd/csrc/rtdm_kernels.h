@@ -182,6 +182,21 @@ void launch_sgm_wide(const SGMGeom& g, const uint16_t* C, uint16_t* S, int dx, i
 int sgm_wide_waves(int D);
 void sgm_wide_set_mode(int m);
 int sgm_wide_mode();
+// The cost stage (k_sgm_cost.hip): bounds, pixel cost and block sum of n pairs -> b.C; cost_limit, cn, ftz as for launch_sgm.
+void launch_sgm_cost(Plane8 L, Plane8 R, const SGMGeom& g, const SGMBuffers& b, int blockSize, int cost_limit, int cn, int ftz, int n,
+                     hipStream_t stream);
+// The path passes for lines of at most 256 disparities (k_sgm_paths.hip).  launch_path_h: one direction per launch, or (S2 !=
+// null, first = 1) (dx, 0) -> S and (-dx, 0) -> S2 side by side.  launch_vert: (0, dy) column-parallel, S2 != null (never with
+// last) added to S on the way.  launch_sweep: (0, dy), (+1, dy), (-1, dy) in one row-synchronous pass, S2in != null added on
+// the way; false = not launched (the caller runs the three passes); probe: only say whether it would be launched.
+// launch_sgm_add_s2: S = min(S + S2, 32767).  last: the pass decides the winners -> win instead of writing S.
+void launch_path_h(const SGMGeom& g, const SGMBuffers& b, int dx, int dy, int P1, int P2, int first, bool last, int n, SgmWin* win,
+                   int uniq, hipStream_t stream, uint16_t* S2 = nullptr);
+void launch_vert(const SGMGeom& g, const SGMBuffers& b, int dy, int P1, int P2, bool last, int n, SgmWin* win, int uniq,
+                 hipStream_t stream, const uint16_t* S2);
+bool launch_sweep(bool last, const SGMGeom& g, const SGMBuffers& b, int dy, int P1, int P2, int n, SgmWin* win, int uniq,
+                  hipStream_t stream, const uint16_t* S2in = nullptr, bool probe = false);
+void launch_sgm_add_s2(const SGMGeom& g, const SGMBuffers& b, int n, hipStream_t stream);
 // cost_limit > 0: block costs above it set *b.ovf (the caller reads it back: api_sgm.hip).  cn: 1 (gray) or 3 (interleaved
 // colour, reads b.cl / b.cr); ftz: R1's ftzero = max(preFilterCap, 15) | 1, at most 127.  Where a pixel cost can pass 255
 // (sgm_cost16_needed: colour, ftz >= 97, or rtdm_debug_sgm_cost16) the cost stage runs on u16 pixel costs.

@@ -521,7 +521,7 @@ def test_sgm_row_synchronous_sweep_is_what_runs(pkg, oracle, synth, paths, W, H,
 def test_two_sgm_handles_on_two_threads_and_a_clean_exit():
     # the sweeps of one process share one stream per device (their workgroups wait for each other, so two sweeps must never be
     # half resident each); the process must also END cleanly -- with hipLaunchCooperativeKernel called from worker threads it
-    # died in the runtime's exit handlers, which is why the sweep is an ordinary launch (k_sgm.hip: launch_sweep_c)
+    # died in the runtime's exit handlers, which is why the sweep is an ordinary launch (k_sgm_paths.hip: launch_sweep_c)
     import json, subprocess, sys
     p = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "sgm_two_threads.py"), "3", "3"], stdout=subprocess.PIPE,
                        stderr=subprocess.PIPE, text=True, timeout=600)
