@@ -1058,15 +1058,38 @@ __global__ __launch_bounds__(256) void k_spk_merge(Plane16W disp, int32_t* label
 // COMPACT: the heads come as one record per 8-column chunk and row (k_lrcheck_vec: carried head + 1 | run starts << 16)
 // instead of one int16 per pixel: a quarter of the head bytes, and "same two runs as the pixel to the left" becomes bit
 // arithmetic (neither pixel of the pair starts a run).
+// COMPACT forms settle most (chunk, row pair) items from the head records and one entry of the row's run list (`runs`)
+// and read the disparity rows only for the others -- see "SETTLED PAIRS" in the kernel: 3.06 -> 1.43 MB per 720p pair.
 // RS == 1: the pairs are (y, y + 1) for y = y_lo + k * ystep -- what is left when k_lrcheck_vec has merged the pairs inside
 // blocks of ystep rows itself.
 // REC: the first ra.blocks workgroups do k_spk_merge_rec's work instead (the contacts k_lrcheck_vec<.., NIT > 1> left in the head
 // records: row pairs inside its blocks of rows) -- same queue, same drain, one launch less for a single frame.
+// Packed forms of the contact test (helpers of k_lrcheck_pk): bit k = column k of the chunk.
+__device__ __forceinline__ unsigned spk_invalid_pk(const Short8& r, uint32_t INVpk)          // the column holds newVal
+{
+    const uint4 q = __builtin_bit_cast(uint4, r);
+    const uint32_t z[4] = {pk_is_zero(q.x ^ INVpk), pk_is_zero(q.y ^ INVpk), pk_is_zero(q.z ^ INVpk), pk_is_zero(q.w ^ INVpk)};
+    return lr_bits8(z);
+}
+__device__ __forceinline__ unsigned spk_close_pk(const Short8& a, const Short8& b, uint32_t Spk)   // |a - b| <= S, S < 32767
+{
+    const uint4 qa = __builtin_bit_cast(uint4, a), qb = __builtin_bit_cast(uint4, b);
+    const uint32_t A[4] = {qa.x, qa.y, qa.z, qa.w}, B[4] = {qb.x, qb.y, qb.z, qb.w};
+    uint32_t c[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const lr_s2 df = __builtin_elementwise_sub_sat(lr_s(A[k]), lr_s(B[k]));                  // saturating: no wrap-around
+        const uint32_t ad = lr_w(__builtin_elementwise_max(df, __builtin_elementwise_sub_sat(lr_s(0u), df)));   // 0 .. 32767
+        c[k] = pk_is_zero(pk_subsat_u(ad, Spk));
+    }
+    return lr_bits8(c);
+}
+
 struct MergeRecArgs { int blocks, vy0, nrows, blk, nch; };
 template <int RS, bool COMPACT, bool REC = false>
 __global__ __launch_bounds__(256) void k_spk_merge_strip(Plane16W disp, int32_t* label, const int16_t* headmap, int W, int Ws, int H,
                                                          int y_lo, int npairs, int newVal, int maxDiff, int32_t* size, int maxSize,
-                                                         int ystep, MergeRecArgs ra)
+                                                         int ystep, MergeRecArgs ra, const uint32_t* runs)
 {
     // contacts found by the 256 threads are queued in LDS and united afterwards by the first threads, one union per
     // lane: a union is a chain of dependent global accesses, and a wave with a single busy lane stalls as long as a full one
@@ -1118,32 +1141,85 @@ __global__ __launch_bounds__(256) void k_spk_merge_strip(Plane16W disp, int32_t*
     int base = (f * H + y) * Ws;
     const int16_t* h = headmap + base + x0;
     const unsigned colmask = x0 + 8 <= W ? 0xffu : (0xffu >> (x0 + 8 - W));
-    Short8 a8, b8, ha8, hb8;
-    if (inb) a8 = *(const Short8*)d;
+    Short8 a8{}, b8{}, ha8, hb8;
+    if (!COMPACT && inb) a8 = *(const Short8*)d;
     bool ha_loaded = false;
     const uint32_t* hc = (const uint32_t*)headmap + (size_t)(f * H + y) * (Ws >> 3) + (x0 >> 3);   // COMPACT: this chunk's records
     uint32_t ca = (COMPACT && inb) ? hc[0] : 0u;
-    // COMPACT: the strip's RS further rows and head records are requested up front (with a load, a wait and the union
-    // queue's atomics per row, a wave kept one row in flight); rows past the strip's end repeat its last one and are not used
+    // COMPACT: the strip's RS + 1 head records are requested up front, then one run-list entry per chunk-row, then the rows
+    // that are needed (with a load, a wait and the union queue's atomics per row, a wave kept one row in flight); records
+    // past the strip's end repeat its last one and are not used.
+    // SETTLED PAIRS.  A chunk-row is classified from its record before any disparity is read: no run start in the chunk and
+    // none left of it -- EMPTY (no valid pixel); no run start in the chunk, cnt > 0 runs started left of it -- every valid
+    // pixel of the chunk belongs to run cnt - 1 of the row, whose (x, len) is in the row's run list: x + len <= x0 -- EMPTY,
+    // else LONG iff len > maxSize (the run list's length, not size[]: a marked short run is not long); a chunk with a run
+    // start stays undecided.  The pair (r, r + 1) is settled when either chunk-row is empty or both are long: its contact mask
+    // is taken as 0 and a row is loaded only if an unsettled pair touches it -- disparity maps are made of long runs, and the
+    // second read of the plane was what this kernel spent its time on.  Exact: a settled pair has no contact or only contacts
+    // between two long runs, which uf_union_contact drops without a union or a mark (only "size <= maxSize" is ever asked; the
+    // overflow path's plain uf_union of two long runs joins two components that are both large, which changes no such answer
+    // either -- so nothing here assumes that a long run is a root).  A long run over a short one is never settled, so the mark
+    // still arrives.  The left-neighbour bit reads 0 behind a settled neighbour (and is fetched from memory by the first lane
+    // of a wave): a contact at this thread's first pixel may then be queued although it continues the neighbour's contact --
+    // only when neither pixel starts a run, so both runs are the neighbour's, hence long, and the duplicate is dropped as
+    // long-long.
     Short8 rows[COMPACT ? RS : 1];
     uint32_t heads[COMPACT ? RS : 1];
+    unsigned unsettled = 0, need = 0;                     // bit r: the pair (r, r + 1) has to be compared; bit j: row j is loaded
+    // The contact mask in packed 16-bit arithmetic, two columns per instruction (the settled pairs took the kernel off the HBM
+    // limit and left it bound by its VALU instructions, most of them this mask's per-column compares): one mask of invalid
+    // columns per loaded row, |a - b| <= maxDiff per pair.  Differences saturate at 32767, so maxDiff must stay below that,
+    // and newVal must be an int16 to be met at all (uniform; the per-column compares serve everything else).
+    const bool pk = COMPACT && maxDiff >= 0 && maxDiff < 32767 && newVal == (int)(int16_t)newVal;
+    const uint32_t INVpk = (uint32_t)(newVal & 0xffff) * 0x00010001u, Spk = (uint32_t)(maxDiff & 0xffff) * 0x00010001u;
+    unsigned inva = 0, invb = 0;                          // bit k: column k of the upper / lower row is newVal
     if constexpr (COMPACT) {
+        const int hp = Ws >> 3;
+#pragma unroll
+        for (int r = 0; r < RS; ++r) heads[r] = inb ? hc[(size_t)(r < nr ? r + 1 : nr) * hp] : 0u;
+        // one look-up per chunk-row, all in flight together and without a branch: where cnt == 0 or the chunk has run
+        // starts, entry 0 / cnt - 1 of the row is read (inside the row's part of the list) and not used
+        uint32_t look[RS + 1];
+#pragma unroll
+        for (int j = 0; j <= RS; ++j) {
+            const uint32_t rec = j ? heads[j - 1] : ca;
+            look[j] = runs[(size_t)base + (size_t)(j <= nr ? j : nr) * Ws + (max((int)(rec & 0xffffu), 1) - 1)];
+        }
+        unsigned empty = 0, lng = 0;
+#pragma unroll
+        for (int j = 0; j <= RS; ++j) {
+            const uint32_t rec = j ? heads[j - 1] : ca;
+            const int cnt = (int)(rec & 0xffffu), rx = (int)(look[j] & 0xffffu), rlen = (int)(look[j] >> 16);
+            const bool nostart = (rec & 0xff0000u) == 0u;
+            const bool e = nostart && (cnt == 0 || rx + rlen <= x0);
+            empty |= (unsigned)e << j;
+            lng |= (unsigned)(nostart && !e && rlen > maxSize) << j;
+        }
+        unsettled = ~(empty | (empty >> 1) | (lng & (lng >> 1))) & ((1u << nr) - 1u);
+        need = unsettled | (unsettled << 1);
+        if (need & 1u) a8 = *(const Short8*)d;
 #pragma unroll
         for (int r = 0; r < RS; ++r) {
-            const int rr = r < nr ? r + 1 : nr;
-            rows[r] = a8; heads[r] = 0u;
-            if (inb) { rows[r] = *(const Short8*)(d + (size_t)rr * disp.pitch_e); heads[r] = hc[(size_t)rr * (Ws >> 3)]; }
+            rows[r] = Short8{};
+            if ((need >> (r + 1)) & 1u) rows[r] = *(const Short8*)(d + (size_t)(r + 1) * disp.pitch_e);
         }
+        if (pk && (need & 1u)) inva = spk_invalid_pk(a8, INVpk);
     }
 #pragma unroll
     for (int r = 0; r < RS; ++r) {
         unsigned cm = 0;
-        if (r < nr) {
-            if constexpr (COMPACT) b8 = rows[r]; else b8 = *(const Short8*)(d + disp.pitch_e);
+        if constexpr (COMPACT) b8 = rows[r];              // (zeros where no unsettled pair touches the row)
+        if constexpr (COMPACT) if (pk && ((need >> (r + 1)) & 1u)) invb = spk_invalid_pk(b8, INVpk);
+        if (COMPACT ? ((unsettled >> r) & 1u) != 0 : r < nr) {
+            if constexpr (!COMPACT) b8 = *(const Short8*)(d + disp.pitch_e);
+            if (COMPACT && pk) cm = spk_close_pk(a8, b8, Spk) & ~(inva | invb);
+            else {
 #pragma unroll
-            for (int k = 0; k < 8; ++k) cm |= (unsigned)conn(a8.v[k], b8.v[k], newVal, maxDiff) << k;
+                for (int k = 0; k < 8; ++k) cm |= (unsigned)conn(a8.v[k], b8.v[k], newVal, maxDiff) << k;
+            }
             cm &= colmask;
         }
+        inva = invb;
         if constexpr (COMPACT) {
             const uint32_t cb = r < nr ? heads[r] : 0u;
             // contact bit of the pixel left of the chunk: lane-1's bit 7, or (first lane of a wave) from memory
@@ -1286,8 +1362,8 @@ void launch_speckle(Plane16W disp, int32_t* label, int32_t* size, uint32_t* runs
                          disp.pitch_e >= (size_t)((W + 7) & ~7);   // a ragged last chunk reads (never writes) padding columns
         if (compact_heads && step > 1) {           // k_lrcheck_vec<.., NIT > 1> has found the contacts inside blocks of `step` rows
             dim3 sgrid((nxb * npairs + 255) / 256 + rec.blocks, n);
-            if (rec.blocks) hipLaunchKernelGGL((k_spk_merge_strip<1, true, true>), sgrid, block, 0, stream, disp, label, headmap, W, Ws, H, first, npairs, newVal, maxDiff, size, maxSize, step, rec);
-            else hipLaunchKernelGGL((k_spk_merge_strip<1, true>), sgrid, block, 0, stream, disp, label, headmap, W, Ws, H, first, npairs, newVal, maxDiff, size, maxSize, step, MergeRecArgs{});
+            if (rec.blocks) hipLaunchKernelGGL((k_spk_merge_strip<1, true, true>), sgrid, block, 0, stream, disp, label, headmap, W, Ws, H, first, npairs, newVal, maxDiff, size, maxSize, step, rec, runs);
+            else hipLaunchKernelGGL((k_spk_merge_strip<1, true>), sgrid, block, 0, stream, disp, label, headmap, W, Ws, H, first, npairs, newVal, maxDiff, size, maxSize, step, MergeRecArgs{}, runs);
         } else
         if (compact_heads) {                       // written by k_lrcheck_vec, whose alignment conditions imply `vec`
             // Strips of four row pairs read every row 1.25 times instead of twice -- what a batch wants (the kernel streams the
@@ -1297,12 +1373,12 @@ void launch_speckle(Plane16W disp, int32_t* label, int32_t* size, uint32_t* runs
             int rsc = 4;
             while (rsc > 1 && (long)((nxb * ((npairs + rsc - 1) / rsc) + 255) / 256) * n < 1024) rsc >>= 1;
             dim3 sgrid((nxb * ((npairs + rsc - 1) / rsc) + 255) / 256, n);
-            if (rsc == 4)      hipLaunchKernelGGL((k_spk_merge_strip<4, true>), sgrid, block, 0, stream, disp, label, headmap, W, Ws, H, first, npairs, newVal, maxDiff, size, maxSize, 1, MergeRecArgs{});
-            else if (rsc == 2) hipLaunchKernelGGL((k_spk_merge_strip<2, true>), sgrid, block, 0, stream, disp, label, headmap, W, Ws, H, first, npairs, newVal, maxDiff, size, maxSize, 1, MergeRecArgs{});
-            else               hipLaunchKernelGGL((k_spk_merge_strip<1, true>), sgrid, block, 0, stream, disp, label, headmap, W, Ws, H, first, npairs, newVal, maxDiff, size, maxSize, 1, MergeRecArgs{});
+            if (rsc == 4)      hipLaunchKernelGGL((k_spk_merge_strip<4, true>), sgrid, block, 0, stream, disp, label, headmap, W, Ws, H, first, npairs, newVal, maxDiff, size, maxSize, 1, MergeRecArgs{}, runs);
+            else if (rsc == 2) hipLaunchKernelGGL((k_spk_merge_strip<2, true>), sgrid, block, 0, stream, disp, label, headmap, W, Ws, H, first, npairs, newVal, maxDiff, size, maxSize, 1, MergeRecArgs{}, runs);
+            else               hipLaunchKernelGGL((k_spk_merge_strip<1, true>), sgrid, block, 0, stream, disp, label, headmap, W, Ws, H, first, npairs, newVal, maxDiff, size, maxSize, 1, MergeRecArgs{}, runs);
         } else if (vec) {                          // (step == 1: without compact heads nothing was merged in blocks)
             dim3 sgrid((nxb * ((npairs + 3) / 4) + 255) / 256, n);
-            hipLaunchKernelGGL((k_spk_merge_strip<4, false>), sgrid, block, 0, stream, disp, label, headmap, W, Ws, H, first, npairs, newVal, maxDiff, size, maxSize, 1, MergeRecArgs{});
+            hipLaunchKernelGGL((k_spk_merge_strip<4, false>), sgrid, block, 0, stream, disp, label, headmap, W, Ws, H, first, npairs, newVal, maxDiff, size, maxSize, 1, MergeRecArgs{}, runs);
         } else {
             hipLaunchKernelGGL(k_spk_merge, dim3((nxb * npairs + 255) / 256, n), block, 0, stream, disp, label, headmap, W, Ws, H, first, npairs, step, newVal, maxDiff);
         }
