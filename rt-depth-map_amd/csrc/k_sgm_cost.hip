@@ -211,17 +211,17 @@ __global__ __launch_bounds__(256) void k_sgm_pixbox(const uint2* bl, const uint2
                     for (int q = 0; q < W1R; ++q) {
                         uint32_t w0, w1;
                         F::widen(tile[par][tcol + q][dqi], w0, w1);
-                        h0 = sgm_add2(h0, w0);
-                        h1 = sgm_add2(h1, w1);
+                        h0 = pk_add(h0, w0);
+                        h1 = pk_add(h1, w1);
                     }
-                    sum[i][0] = sgm_sub2(sgm_add2(sum[i][0], h0), ring[i][k][0]);
-                    sum[i][1] = sgm_sub2(sgm_add2(sum[i][1], h1), ring[i][k][1]);
+                    sum[i][0] = pk_sub(pk_add(sum[i][0], h0), ring[i][k][0]);
+                    sum[i][1] = pk_sub(pk_add(sum[i][1], h1), ring[i][k][1]);
                     ring[i][k][0] = h0; ring[i][k][1] = h1;
                     const int xo = xt0 + tcol;
                     if (yo >= y0 && xo < g.W1) {
                         *(uint2*)(C + (((size_t)f * g.H + yo) * g.W1 + xo) * g.D + d) = make_uint2(sum[i][0], sum[i][1]);
                         if constexpr (F::CHECK) {
-                            const uint32_t m = sgm_max2(sum[i][0], sum[i][1]);
+                            const uint32_t m = pk_max_u(sum[i][0], sum[i][1]);
                             over |= (int)max(m & 0xffffu, m >> 16) > cost_limit;
                         }
                     }

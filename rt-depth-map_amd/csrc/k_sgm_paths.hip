@@ -124,7 +124,7 @@ __global__ __launch_bounds__(256) void k_sgm_path_h(const uint16_t* C, uint16_t*
             sgm_line_step<NP2, true>(l, mps, l, mps, c.w, step == 0, live, hl, P1s, P2s);
             uint32_t o[NP2];
 #pragma unroll
-            for (int r = 0; r < NP2; ++r) o[r] = first_dir ? l[r] : sgm_min2(sgm_add2(sv.w[r], l[r]), 0x7fff7fffu);   // R5
+            for (int r = 0; r < NP2; ++r) o[r] = first_dir ? l[r] : pk_min_u(pk_add(sv.w[r], l[r]), 0x7fff7fffu);   // R5
             if constexpr (!LAST) {
                 if (live && step < nsteps) st_w<NP2>(sp + (long)step * stride, o);
             } else {
@@ -203,7 +203,7 @@ __global__ __launch_bounds__(256) void k_sgm_sweep(const uint16_t* C, uint16_t* 
 #pragma unroll
             for (int c = 0; c < CPH; ++c) {
                 cc[c] = cn[c]; sc[c] = sn[c];
-                if constexpr (ADD2) { for (int r = 0; r < NP2; ++r) sc[c].w[r] = sgm_min2(sgm_add2(sc[c].w[r], tn[c].w[r]), 0x7fff7fffu); }   // R5
+                if constexpr (ADD2) { for (int r = 0; r < NP2; ++r) sc[c].w[r] = pk_min_u(pk_add(sc[c].w[r], tn[c].w[r]), 0x7fff7fffu); }   // R5
             }
             if (t + 1 < H) {
                 const int yn = y + dy;
@@ -218,7 +218,7 @@ __global__ __launch_bounds__(256) void k_sgm_sweep(const uint16_t* C, uint16_t* 
             uint32_t acc[CPH][NP2];
             const auto add_to = [&](int c, const uint32_t* L) {
 #pragma unroll
-                for (int r = 0; r < NP2; ++r) acc[c][r] = sgm_min2(sgm_add2(acc[c][r], L[r]), 0x7fff7fffu);   // R5
+                for (int r = 0; r < NP2; ++r) acc[c][r] = pk_min_u(pk_add(acc[c][r], L[r]), 0x7fff7fffu);   // R5
             };
 #pragma unroll
             for (int c = 0; c < CPH; ++c) for (int r = 0; r < NP2; ++r) acc[c][r] = sc[c].w[r];
@@ -292,7 +292,7 @@ __global__ __launch_bounds__(256) void k_sgm_sweep(const uint16_t* C, uint16_t* 
                 // the minimum of a line that came through the ring is not sent along: take it here (both halves do, one needs it)
                 uint32_t mmL = NONE, mmR = NONE;
 #pragma unroll
-                for (int r = 0; r < NP2; ++r) { mmL = sgm_min2(mmL, live ? inL[r] : NONE); mmR = sgm_min2(mmR, live ? inR[r] : NONE); }
+                for (int r = 0; r < NP2; ++r) { mmL = pk_min_u(mmL, live ? inL[r] : NONE); mmR = pk_min_u(mmR, live ? inR[r] : NONE); }
                 const uint32_t hmL = (uint32_t)half_min_i32((int)min(mmL & 0xffffu, mmL >> 16)) * 0x10001u;
                 const uint32_t hmR = (uint32_t)half_min_i32((int)min(mmR & 0xffffu, mmR >> 16)) * 0x10001u;
                 if (poll_l) inLm = hmL;
@@ -370,7 +370,7 @@ __global__ __launch_bounds__(256) void k_sgm_vert(const uint16_t* C, uint16_t* S
             for (int r = 0; r < NP2; ++r) o[r] = sr[k].w[r];
             if constexpr (ADD2) {
 #pragma unroll
-                for (int r = 0; r < NP2; ++r) o[r] = sgm_min2(sgm_add2(o[r], tr[k].w[r]), 0x7fff7fffu);       // R5
+                for (int r = 0; r < NP2; ++r) o[r] = pk_min_u(pk_add(o[r], tr[k].w[r]), 0x7fff7fffu);       // R5
             }
             if (step + PF < H) {
                 cr[k] = ld_w<NP2>(cp + (long)(step + PF) * stride);
@@ -379,7 +379,7 @@ __global__ __launch_bounds__(256) void k_sgm_vert(const uint16_t* C, uint16_t* S
             }
             sgm_line_step<NP2, true>(l, mps, l, mps, c.w, step == 0, live, hl, P1s, P2s);
 #pragma unroll
-            for (int r = 0; r < NP2; ++r) o[r] = sgm_min2(sgm_add2(o[r], l[r]), 0x7fff7fffu);                  // R5
+            for (int r = 0; r < NP2; ++r) o[r] = pk_min_u(pk_add(o[r], l[r]), 0x7fff7fffu);                  // R5
             if constexpr (!LAST) {
                 if (live && ok) st_w<NP2>(sp + (long)step * stride, o);
             } else {
@@ -395,7 +395,7 @@ __global__ __launch_bounds__(256) void k_sgm_vert(const uint16_t* C, uint16_t* S
 __global__ __launch_bounds__(256) void k_sgm_add_s2(uint32_t* S, const uint32_t* S2, size_t npairs)
 {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < npairs) S[i] = sgm_min2(sgm_add2(S[i], S2[i]), 0x7fff7fffu);
+    if (i < npairs) S[i] = pk_min_u(pk_add(S[i], S2[i]), 0x7fff7fffu);
 }
 
 static inline int sgm_np2(int D) { return D <= 64 ? 1 : (D <= 128 ? 2 : 4); }

@@ -85,13 +85,13 @@ __global__ __launch_bounds__(256) void k_sgm_wide(const uint16_t* C, uint16_t* S
             }
             uint32_t o[NP2];
 #pragma unroll
-            for (int r = 0; r < NP2; ++r) o[r] = first_dir ? l[r] : sgm_min2(sgm_add2(sv.w[r], l[r]), 0x7fff7fffu);   // R5
+            for (int r = 0; r < NP2; ++r) o[r] = first_dir ? l[r] : pk_min_u(pk_add(sv.w[r], l[r]), 0x7fff7fffu);   // R5
             if constexpr (!LAST) {
                 if (live) st_w<NP2>(sp + (long)step * stride, o);
             }
             uint32_t mm = l[0];
 #pragma unroll
-            for (int r = 1; r < NP2; ++r) mm = sgm_min2(mm, l[r]);
+            for (int r = 1; r < NP2; ++r) mm = pk_min_u(mm, l[r]);
             int m = wave_min_i32((int)min(mm & 0xffffu, mm >> 16));
             int key = 0x7fffffff;
             if constexpr (LAST) {
@@ -117,7 +117,7 @@ __global__ __launch_bounds__(256) void k_sgm_wide(const uint16_t* C, uint16_t* S
                 ehi = wv < NW - 1 ? xlo[p][wv + 1] : NONE;
             }
             mps = (uint32_t)m * 0x10001u;
-            mpP2 = sgm_add2(mps, P2s);
+            mpP2 = pk_add(mps, P2s);
             if constexpr (LAST) {
                 const int mins = key >> 12, bd = key & 0xfff;
                 bool hit = false;

@@ -1,5 +1,6 @@
-// rtdm_device.h -- device-side helpers shared by the row kernels (k_basic.hip, k_sgm.hip; the StereoSGBM units' own: rtdm_sgm.h):
-// workgroup scans over a row held in LDS, union-find primitives, the speckle filter's per-row init.
+// rtdm_device.h -- device-side helpers shared by the row kernels (k_lrcheck.hip, k_speckle.hip, k_sgm.hip; packed 16-bit
+// arithmetic: rtdm_pk16.h; the StereoSGBM units' own: rtdm_sgm.h): workgroup scans over a row held in LDS, union-find
+// primitives, the speckle filter's per-row init.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -96,7 +97,13 @@ __device__ __forceinline__ void uf_union(int32_t* parent, int a, int b)
 // "large run" shortcut of the speckle filter folded in -- all four first reads (both parents, both sizes) are issued
 // together.  Agent-scope accesses cost a trip to memory each (~1 us), and a merge kernel on ONE frame is nothing but such
 // chains: sizes -> find a -> find b -> hook was four trips per contact, this is two.
-// Returns without uniting if at least one run is longer than maxSize; the other one is then marked (see spk_large_contact).
+// A contact between two runs of which at least one is longer than maxSize needs no union: only "component size <= maxSize"
+// is ever asked, the long run's component is large whatever else it touches, and so is the other run's -- which is MARKED
+// instead (its size becomes maxSize + 1: no find, no hook; k_spk_count adds a non-root's size to its root, so the mark
+// reaches the root of whatever small runs are united with it, and a later contact of a marked run marks its neighbour in
+// turn).  Exact: marks only ever appear in components that contain a long run, and every short run of such a component is
+// reached from the long run through contacts that either united the two trees or marked the far end.  size[] holds the run
+// lengths (and marks) until k_spk_count runs.
 __device__ __forceinline__ void uf_union_contact(int32_t* parent, int32_t* size, int a, int b, int maxSize)
 {
     int pa = ld_relaxed(&parent[a]), pb = ld_relaxed(&parent[b]);
@@ -121,12 +128,9 @@ __device__ __forceinline__ void uf_union_contact(int32_t* parent, int32_t* size,
 // its own parent with the run length as its size, appends (x | len << 16) to the row's run list and
 // writes the per-pixel head map (x of the run head, int16) that the merge step reads.
 // sc is a W-element int32 scratch array.  Whole workgroup.
-// hm_lds (optional): the head map is also kept in LDS; hm_global = false skips the global head map
-// (rows whose both neighbours are merged by the same workgroup never need it).
 __device__ __forceinline__ void spk_row_init(const int16_t* d, int* sc, int* wsum, int W, int base,
                                              int32_t* label, int32_t* size, uint32_t* runs, int32_t* rowcnt,
-                                             int16_t* headmap, int newVal, int maxDiff,
-                                             int16_t* hm_lds = nullptr, bool hm_global = true)
+                                             int16_t* headmap, int newVal, int maxDiff)
 {
     for (int x = threadIdx.x; x < W; x += blockDim.x) {
         const int v = d[x];
@@ -138,8 +142,7 @@ __device__ __forceinline__ void spk_row_init(const int16_t* d, int* sc, int* wsu
     for (int x = threadIdx.x; x < W; x += blockDim.x) {
         const int v = d[x];
         const int h = (sc[x] & 0xffff) - 1;
-        if (hm_global) headmap[base + x] = (int16_t)h;
-        if (hm_lds) hm_lds[x] = (int16_t)h;
+        headmap[base + x] = (int16_t)h;
         if (v == newVal) continue;
         const bool last = (x == W - 1) || !conn(v, d[x + 1], newVal, maxDiff);
         if (!last) continue;

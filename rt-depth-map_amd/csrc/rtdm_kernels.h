@@ -66,7 +66,7 @@ struct Plane16W { int16_t* base; size_t pitch_e, frame_e; };  // strides in elem
 static constexpr int PREFILTER_BIAS = 1;
 
 // K1: prefilter of n left and n right frames in one launch (writes biased values, see above).  type: RTDM_PREFILTER_XSOBEL
-// (k_basic.hip; ws is not read) or RTDM_PREFILTER_NORMALIZED_RESPONSE with window ws (k_prefilter_norm.hip).
+// (k_prefilter.hip; ws is not read) or RTDM_PREFILTER_NORMALIZED_RESPONSE with window ws (k_prefilter_norm.hip).
 // fill != null: launch_fill_frame's job (below) for the same n frames rides in the same launch where the strip form runs
 // (a single frame is bound by the number of its launches), and is launched by itself before the other forms.
 struct FillJob { Plane16W disp; int cx0, cx1, vy0, vy1, value; int32_t* rowcnt; };

@@ -1,28 +1,17 @@
 // rtdm_sgm.h -- device-side pieces shared by the StereoSGBM units (k_sgm_cost.hip, k_sgm_paths.hip, k_sgm_wide.hip):
-// packed u16 arithmetic, the vector loads and stores of a lane's disparities, the DPP minima, the Birchfield-Tomasi pixel
+// the vector loads and stores of a lane's disparities, the DPP minima, the Birchfield-Tomasi pixel
 // cost and the path recurrence.  One copy of each: a fix to the recurrence, to R5 or to R6 is made here.
 #pragma once
 
 #include "rtdm_kernels.h"
 #include "rtdm_device.h"
+#include "rtdm_pk16.h"
 
 namespace rtdm {
 
-// Two u16 in a dword: max(0, u - v1, v0 - u) is max(u -sat v1, v0 -sat u), so a Birchfield-Tomasi cost is 11 VALU per two
-// disparities; the path recurrence and the block sums use the wrapping / saturating sums and differences.
-typedef unsigned short sgm_us2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ uint32_t sgm_subs(uint32_t a, uint32_t b)
-{ return __builtin_bit_cast(uint32_t, __builtin_elementwise_sub_sat(__builtin_bit_cast(sgm_us2, a), __builtin_bit_cast(sgm_us2, b))); }
-__device__ __forceinline__ uint32_t sgm_max2(uint32_t a, uint32_t b)
-{ return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(sgm_us2, a), __builtin_bit_cast(sgm_us2, b))); }
-__device__ __forceinline__ uint32_t sgm_min2(uint32_t a, uint32_t b)
-{ return __builtin_bit_cast(uint32_t, __builtin_elementwise_min(__builtin_bit_cast(sgm_us2, a), __builtin_bit_cast(sgm_us2, b))); }
-__device__ __forceinline__ uint32_t sgm_add2(uint32_t a, uint32_t b)
-{ return __builtin_bit_cast(uint32_t, (sgm_us2)(__builtin_bit_cast(sgm_us2, a) + __builtin_bit_cast(sgm_us2, b))); }
-__device__ __forceinline__ uint32_t sgm_sub2(uint32_t a, uint32_t b)
-{ return __builtin_bit_cast(uint32_t, (sgm_us2)(__builtin_bit_cast(sgm_us2, a) - __builtin_bit_cast(sgm_us2, b))); }
-__device__ __forceinline__ uint32_t sgm_adds2(uint32_t a, uint32_t b)
-{ return __builtin_bit_cast(uint32_t, __builtin_elementwise_add_sat(__builtin_bit_cast(sgm_us2, a), __builtin_bit_cast(sgm_us2, b))); }
+// Two u16 in a dword (the pk_* helpers of rtdm_pk16.h): max(0, u - v1, v0 - u) is max(u -sat v1, v0 -sat u), so a
+// Birchfield-Tomasi cost is 11 VALU per two disparities; the path recurrence and the block sums use the wrapping /
+// saturating sums and differences.
 
 // The 2 * NP2 consecutive disparities of a lane as NP2 u16 pairs (NP2 = 1, 2, 4, 8), loaded and stored in the widest pieces
 template <int NP2> struct PackW { uint32_t w[NP2]; };
@@ -83,7 +72,7 @@ __device__ __forceinline__ uint32_t bt_pack(int v, int m, int p, bool has_m, boo
 }
 // the cost of one left pixel (u, u0, u1 replicated into both halves) against two right pixels (low / high half)
 __device__ __forceinline__ uint32_t bt_cost2(uint32_t U, uint32_t U0, uint32_t U1, uint32_t V, uint32_t V0, uint32_t V1)
-{ return sgm_min2(sgm_max2(sgm_subs(U, V1), sgm_subs(V0, U)), sgm_max2(sgm_subs(V, U1), sgm_subs(U0, V))); }
+{ return pk_min_u(pk_max_u(pk_subsat_u(U, V1), pk_subsat_u(V0, U)), pk_max_u(pk_subsat_u(V, U1), pk_subsat_u(U0, V))); }
 
 // packed u16 pixel cost (gradient + (intensity >> 2)) of one left record a against two right records (low half: lo, high half: hi)
 __device__ __forceinline__ uint32_t sgm_cost2(uint2 a, uint2 lo, uint2 hi)
@@ -121,8 +110,8 @@ __device__ __forceinline__ uint32_t sgm_pair_step(uint32_t prev, uint32_t own, u
 {
     const uint32_t dn = __builtin_amdgcn_alignbit(own, prev, 16);       // {prev.hi, own.lo}: d - 1 of both elements
     const uint32_t up = __builtin_amdgcn_alignbit(next, own, 16);       // {own.hi, next.lo}: d + 1
-    const uint32_t best = sgm_min2(sgm_min2(own, mpP2), sgm_adds2(sgm_min2(dn, up), P1s));
-    return sgm_sub2(sgm_add2(c, best), mps);
+    const uint32_t best = pk_min_u(pk_min_u(own, mpP2), pk_addsat_u(pk_min_u(dn, up), P1s));
+    return pk_sub(pk_add(c, best), mps);
 }
 
 // one step of one line for both half-waves of the wave: sgm_pair_step on every pair, or C where the line starts; the pairs at
@@ -137,7 +126,7 @@ __device__ __forceinline__ void sgm_line_step(uint32_t* L, uint32_t& mps, const 
     uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp((int)NONE, (int)Lp[0], 0x130, 0xf, 0xf, false);         // wave_shl:1
     lo = hl == 0 ? NONE : lo;
     hi = hl == 31 ? NONE : hi;
-    const uint32_t mpP2 = sgm_add2(mpsp, P2s);
+    const uint32_t mpP2 = pk_add(mpsp, P2s);
     uint32_t nl[NP2];
 #pragma unroll
     for (int r = 0; r < NP2; ++r) {
@@ -146,7 +135,7 @@ __device__ __forceinline__ void sgm_line_step(uint32_t* L, uint32_t& mps, const 
     }
     uint32_t mm = NONE;
 #pragma unroll
-    for (int r = 0; r < NP2; ++r) { L[r] = live ? nl[r] : NONE; mm = sgm_min2(mm, L[r]); }
+    for (int r = 0; r < NP2; ++r) { L[r] = live ? nl[r] : NONE; mm = pk_min_u(mm, L[r]); }
     mps = (uint32_t)half_min_i32((int)min(mm & 0xffffu, mm >> 16)) * 0x10001u;
 }
 
