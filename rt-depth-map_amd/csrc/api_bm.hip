@@ -256,16 +256,11 @@ static int chunk_front(rtdm_bm* bm, int n, Plane8 L, Plane8 R, int W, int H, Pla
     // (+ the speckle filter's run counts = 0); the fill rides in the prefilter's launch
     const FillJob fill{disp, g.cx0, g.cx1, g.vy0, g.vy1, g.filtered, (p.speckleRange >= 0 && p.speckleWindowSize > 0) ? bm->dRowCnt : nullptr};
     StageEvent ev;
-    bool u16 = false;
-    // what k_search_generic cannot hold in LDS (D > 256, large windows at large D) -- or everything, when
+    // what the single-pass generic kernel cannot hold in LDS (D > 256, large windows at large D) -- or everything, when
     // rtdm_debug_disparity_slice forces it -- is searched by the disparity-sliced kernel over the whole range
-    const bool dslice = !generic_search_supported(g, &u16) || dslice_forced();
-    const bool fast = !dslice && fast_search_supported(g);
+    const bool fast = !generic_search_sliced(g) && fast_search_supported(g);
     {
         const bool ring = fast && ring_search_supported(g);
-        const int lpp = ring ? ring_lanes_per_pixel(g) : 0;
-        bm->variant = dslice ? (u16 ? "generic_dslice_u16" : "generic_dslice_u32")
-                    : ring ? (lpp == 16 ? "fast_ring16_qsad" : lpp == 8 ? "fast_ring8_qsad" : lpp == 4 ? "fast_ring4_qsad" : "fast_ring_qsad") : fast ? "fast_qsad" : (u16 ? "generic_u16" : "generic_u32");
         Plane8W Lp{bm->dLp, bm->ppitch, bm->ppitch * (size_t)H}, Rp{bm->dRp, bm->ppitch, bm->ppitch * (size_t)H};
         stage_begin(bm, RTDM_STAGE_PREFILTER, n, s, &ev);
         launch_prefilter(L, R, Lp, Rp, W, H, p.preFilterCap, n, s, &fill, bm->prefilter_type, bm->prefilter_size);
@@ -273,6 +268,8 @@ static int chunk_front(rtdm_bm* bm, int n, Plane8 L, Plane8 R, int W, int H, Pla
         Plane8 Lpr{bm->dLp, Lp.pitch, Lp.frame}, Rpr{bm->dRp, Rp.pitch, Rp.frame};
         stage_begin(bm, RTDM_STAGE_SEARCH, n, s, &ev);
         if (fast) {
+            const int lpp = ring ? ring_lanes_per_pixel(g) : 0;
+            bm->variant = !ring ? "fast_qsad" : lpp == 16 ? "fast_ring16_qsad" : lpp == 8 ? "fast_ring8_qsad" : lpp == 4 ? "fast_ring4_qsad" : "fast_ring_qsad";
             int lx0, lx1, rx0, rx1;
             fast_border_ranges(g, &lx0, &lx1, &rx0, &rx1);
             // Batches of 16 or more: the border columns run as a kernel of their own on a side stream, concurrently with the
@@ -302,10 +299,8 @@ static int chunk_front(rtdm_bm* bm, int n, Plane8 L, Plane8 R, int W, int H, Pla
                 launch_search_generic(Lpr, Rpr, disp, bm->dCost, g, n, s, lx0, lx1);
                 launch_search_generic(Lpr, Rpr, disp, bm->dCost, g, n, s, rx0, rx1);
             }
-        } else if (dslice) {
-            launch_search_dslice(Lpr, Rpr, disp, bm->dCost, g, n, s, g.cx0 - g.lofs, g.cx1 - g.lofs);
         } else {
-            launch_search_generic(Lpr, Rpr, disp, bm->dCost, g, n, s, g.cx0 - g.lofs, g.cx1 - g.lofs);
+            bm->variant = launch_search_generic(Lpr, Rpr, disp, bm->dCost, g, n, s, g.cx0 - g.lofs, g.cx1 - g.lofs);
         }
         stage_end(bm, s, &ev);
     }

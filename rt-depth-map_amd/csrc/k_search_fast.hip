@@ -254,7 +254,7 @@ __global__ __launch_bounds__(256) void k_search_fast(Plane8 Lp, Plane8 Rp, Plane
 }
 
 // ---- host side ----------------------------------------------------------------------------
-static bool fast_range(const BMGeom& g, int* x0, int* nx)
+bool search_interior_range(const BMGeom& g, int* x0, int* nx)
 {
     const int r = g.r;
     int xl = 0, xh = g.width1 - 1;
@@ -277,7 +277,7 @@ static void launch_one(Plane8 Lp, Plane8 Rp, Plane16W disp, void* cost, const BM
 {
     using C = FastCfg<D, NP>;
     FastGeom fg;
-    fast_range(g, &fg.x0, &fg.nx);
+    search_interior_range(g, &fg.x0, &fg.nx);
     const int rem = g.w - 4 * (NP - 1);
     fg.lastmask = rem >= 4 ? 0xffffffffu : ((1u << (8 * rem)) - 1u);
     const int nrows = g.vy1 - g.vy0;
@@ -324,7 +324,7 @@ static void launch_one(Plane8 Lp, Plane8 Rp, Plane16W disp, void* cost, const BM
 bool fast_search_supported(const BMGeom& g)
 {
     if (2L * g.cap * g.w * g.w > 32766) return false;       // packed u16 sums + the T+1 <= 32767 argument
-    if (!fast_range(g, nullptr, nullptr)) return false;
+    if (!search_interior_range(g, nullptr, nullptr)) return false;
     const int np = fast_np(g);
 #define X(DD, PP) if (g.D == DD && np == PP) return true;
     RTDM_FAST_TABLE(X)
@@ -335,7 +335,7 @@ bool fast_search_supported(const BMGeom& g)
 int fast_strips_model(const BMGeom& g, int n)
 {
     int x0 = 0, nx = 0;
-    if (!fast_range(g, &x0, &nx)) return 1;
+    if (!search_interior_range(g, &x0, &nx)) return 1;
     const int tiles = (nx + 255) / 256, nrows = g.vy1 - g.vy0;
     const int s = (int)(sqrtf((float)nrows * 1024.0f / ((float)(g.w - 1) * (float)tiles * (float)n)) + 0.5f);
     return max(1, min(s, (nrows + 15) / 16));
@@ -353,7 +353,7 @@ void launch_search_fast(Plane8 Lp, Plane8 Rp, Plane16W disp, void* cost, const B
 void fast_border_ranges(const BMGeom& g, int* lx0, int* lx1, int* rx0, int* rx1)
 {
     int x0 = 0, nx = 0;
-    fast_range(g, &x0, &nx);
+    search_interior_range(g, &x0, &nx);
     *lx0 = max(0, g.cx0 - g.lofs); *lx1 = x0; *rx0 = x0 + nx; *rx1 = min(g.width1, g.cx1 - g.lofs);
 }
 

@@ -468,17 +468,6 @@ __global__ __launch_bounds__(256, (RingBounds<D, WS, LPP, FUSE>::WAVES)) void k_
 }
 
 // ---- host side ----------------------------------------------------------------------------
-static bool ring_range(const BMGeom& g, int* x0, int* nx)
-{
-    const int r = g.r;
-    int xl = 0, xh = g.width1 - 1;
-    xl = max(xl, r - g.lofs); xl = max(xl, r - g.rofs);
-    xh = min(xh, g.W - 1 - g.lofs - r); xh = min(xh, g.W - g.D - g.rofs - r);
-    xl = max(xl, g.cx0 - g.lofs); xh = min(xh, g.cx1 - g.lofs - 1);      // setROI1: only the needed columns
-    if (x0) *x0 = xl;
-    if (nx) *nx = xh - xl + 1;
-    return xh >= xl;
-}
 
 // rows a strip may have so that no prefix sum leaves 16 bits: a row adds at most w * 2 cap per disparity, and a strip of
 // rs output rows walks rs + w - 1 rows plus up to seven padded rows (groups of eight)
@@ -552,7 +541,7 @@ static int ring_wgs_per_cu(const BMGeom& g)
 int ring_strips_model(const BMGeom& g, int n)
 {
     int x0 = 0, nx = 0;
-    if (!ring_range(g, &x0, &nx) || !ring_lpp(g)) return 1;
+    if (!search_interior_range(g, &x0, &nx) || !ring_lpp(g)) return 1;
     const int tile = ring_tile(g), tiles = (nx + tile - 1) / tile, nrows = g.vy1 - g.vy0;
     const int slots = 256 * ring_wgs_per_cu(g);             // workgroups in flight on the chip
     const int smin = ring_min_strips(g, nrows), smax = max(smin, (nrows + 15) / 16);
@@ -582,7 +571,7 @@ static bool ring_launch_one(Plane8 Lp, Plane8 Rp, Plane16W disp, void* cost, con
     using C = RingCfg<D, WS, LPP>;
     RingGeom rg;
     rg.rdelta = (uint32_t)(Rp.base - Lp.base);       // (launch_search_ring has checked that it fits)
-    ring_range(g, &rg.x0, &rg.nx);
+    search_interior_range(g, &rg.x0, &rg.nx);
     const int rem = g.w - 4 * (C::NP - 1);
     rg.lastmask = rem >= 4 ? 0xffffffffu : ((1u << (8 * rem)) - 1u);
     const int nrows = g.vy1 - g.vy0;
@@ -645,7 +634,7 @@ bool ring_search_supported(const BMGeom& g)
     if (2L * g.cap * g.w * g.w >= 0x7C00) return false;     // ... and positive finite f16 for the group minima (sel_pk_min3_h; cap <= 63
                                                             //     keeps every ring form below: 2 * 63 * 15^2 = 28350)
     if (ring_rows_cap(g) < 2) return false;
-    if (!ring_range(g, nullptr, nullptr)) return false;
+    if (!search_interior_range(g, nullptr, nullptr)) return false;
     if ((size_t)g.H * (size_t)g.Ws * 2 >= ((size_t)1 << 32)) return false;   // 32-bit byte offsets inside a frame (pitch <= Ws)
     return ring_lpp(g) != 0;
 }

@@ -81,21 +81,16 @@ void launch_fill16(Plane16W disp, int x0, int x1, int y0, int y1, int n, int val
 void launch_fill_frame(Plane16W disp, int W, int H, int cx0, int cx1, int vy0, int vy1, int n, int value, int32_t* rowcnt,
                        hipStream_t stream);
 
-// K2 (generic variant): D <= 256 and any odd w whose column sums fit LDS; writes disp (+ int32 cost).
-// Returns false if the configuration does not fit (the caller runs launch_search_dslice instead).
-bool generic_search_supported(const BMGeom& g, bool* use16);
-// [gx0, gx1) restricts the output-column range (gx1 < 0: all of [0, width1)).
-void launch_search_generic(Plane8 Lp, Plane8 Rp, Plane16W disp, void* cost, const BMGeom& g,
-                           int n, hipStream_t stream, int gx0 = 0, int gx1 = -1);
-
-// K2 (disparity-sliced generic variant, k_search_dslice.hip): every valid configuration (D a multiple of 16 up to 4080,
-// any odd w); the reversed disparity range is walked in slices whose results are folded in index order per pixel.  Same
-// outputs as launch_search_generic, bit for bit.  [gx0, gx1) as there.
-void launch_search_dslice(Plane8 Lp, Plane8 Rp, Plane16W disp, void* cost, const BMGeom& g,
-                          int n, hipStream_t stream, int gx0 = 0, int gx1 = -1);
-int dslice_width(const BMGeom& g, bool use16, int TC);   // the slice width a launch uses
-void dslice_set_width(int dt);   // rtdm_debug_disparity_slice
-bool dslice_forced();            // a slice width is forced: every configuration goes to launch_search_dslice
+// K2 (generic variants, k_search_generic.hip): every valid configuration (D a multiple of 16 up to 4080, any odd w); writes
+// disp (+ the cost plane, uint16 or int32 by g.cost16).  Runs the single-pass form where its LDS fits (D <= 256, not every w
+// at large D) and no slice width is forced, else the sliced form: the reversed disparity range walked in slices whose
+// results are folded in index order per pixel, the same outputs bit for bit.  [gx0, gx1) restricts the output-column range
+// (gx1 < 0: all of [0, width1)).  Returns the variant name: "generic_u16", "generic_u32", "generic_dslice_u16",
+// "generic_dslice_u32".
+const char* launch_search_generic(Plane8 Lp, Plane8 Rp, Plane16W disp, void* cost, const BMGeom& g,
+                                  int n, hipStream_t stream, int gx0 = 0, int gx1 = -1);
+bool generic_search_sliced(const BMGeom& g);   // the sliced form is needed or forced (no packed kernel runs then)
+void dslice_set_width(int dt);                 // rtdm_debug_disparity_slice
 
 // K2 (fast variant): packed-u8 quad-SAD kernel for the common configurations.  Works on the
 // prefiltered planes and covers the output columns whose window needs no border clamping; the
@@ -116,6 +111,8 @@ bool launch_search_ring(Plane8 Lp, Plane8 Rp, Plane16W disp, void* cost, const B
 int ring_strips_model(const BMGeom& g, int n);
 void ring_set_mode(int mode);   // rtdm_debug_search_kernel
 int ring_lanes_per_pixel(const BMGeom& g);   // 2 / 4: the form of k_search_ring this configuration runs (0: none)
+// The output columns [*x0, *x0 + *nx) whose window needs no border clamping (either pointer may be null); false: none.
+bool search_interior_range(const BMGeom& g, int* x0, int* nx);
 void fast_border_ranges(const BMGeom& g, int* lx0, int* lx1, int* rx0, int* rx1);
 // wave-per-column kernel for those border columns (falls back to the generic kernel if unsupported)
 bool border_search_supported(const BMGeom& g);

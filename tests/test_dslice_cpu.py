@@ -1,4 +1,4 @@
-"""The disparity-sliced search (k_search_dslice.hip) on the CPU side.
+"""The disparity-sliced search (k_search_dslice in k_search_generic.hip) on the CPU side.
 
 1. The oracle against the brute-force model at numDisparities > 256 (the ground the sliced kernel opens), negative minD,
    thresholds on: the yardstick the GPU tests compare against is itself pinned there.

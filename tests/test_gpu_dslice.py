@@ -1,5 +1,6 @@
 """StereoBM configurations the generic search kernel cannot hold in LDS -- numDisparities > 256, large windows at large D --
-run on the disparity-sliced search kernel (k_search_dslice.hip).  Every result is compared bit for bit with the oracle.
+run on the disparity-sliced search kernel (k_search_dslice in k_search_generic.hip).  Every result is compared bit for bit
+with the oracle.
 rtdm_debug_disparity_slice forces the sliced kernel with a given slice width on any configuration, so that slice
 boundaries can be put anywhere; it is reset in `finally` everywhere."""
 import contextlib

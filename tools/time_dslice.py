@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Time of rtdm_bm_compute_device with the disparity-sliced search kernel (k_search_dslice.hip) against the generic kernel,
-1280x720, batches of 8 synthetic pairs, HIP events on the torch stream (run on the GPU box):
+"""Time of rtdm_bm_compute_device with the disparity-sliced search kernel (k_search_dslice in k_search_generic.hip) against
+the generic kernel, 1280x720, batches of 8 synthetic pairs, HIP events on the torch stream (run on the GPU box):
     python3 tools/time_dslice.py [reps=10]
 Per row: ms per pair for the whole call and for the search stage alone (the library's stage events, a separate run), both
 divided by numDisparities, and the search divided by the searched column-disparities (W - D + 1 columns at minD = 0: the
