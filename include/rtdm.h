@@ -506,7 +506,8 @@ typedef struct rtdm_mjpeg_info {
     int components;         /* 1 | 3 */
     int h_samp, v_samp;     /* luma sampling factors; 1, 1 for one component */
     int restart_interval;   /* MCUs per entropy segment as DRI gives it; 0: none */
-    int segments;           /* entropy segments = what the device decodes in parallel */
+    int segments;           /* entropy segments (1 without DRI); each is decoded on its own, and a frame of one segment is
+                             * itself cut among lanes (rtdm_mjpeg_set_split) */
     int has_dht;            /* 0: the frame relies on the standard tables */
 } rtdm_mjpeg_info;
 typedef struct rtdm_mjpeg rtdm_mjpeg;
@@ -526,6 +527,18 @@ int rtdm_mjpeg_decode(rtdm_mjpeg* h, const uint8_t* stream, size_t len, int widt
  * per frame.  Calls that share a handle must be ordered on one stream: they share its scratch. */
 int rtdm_mjpeg_decode_batch_device(rtdm_mjpeg* h, int n, const uint8_t* const* streams, const size_t* lens, int width, int height,
                                    uint8_t* d_rgb, size_t pitch, size_t frame_stride, int* d_status, void* hip_stream);
+/* A frame without restart intervals -- what UVC cameras send -- is one entropy segment.  The decoder cuts it into subsequences
+ * of `subsequence_bytes` bytes (at least len / 1024, so that there are at most 1024) and gives one lane of a workgroup to each;
+ * the lanes find the symbol boundaries by decoding speculatively until their hand-over states stop changing (DESIGN.md section
+ * 4.12).  The result is that of one lane per segment, bit for bit.  subsequence_bytes: 0 = off (one lane per segment), 8 ..
+ * 65536, or -1 for the built-in default; anything else is RTDM_ERR_BAD_PARAM (judged before the handle is looked at).  Takes
+ * effect from the next call; a new handle starts at the default, which is on.  Frames with restart intervals are not affected. */
+int rtdm_mjpeg_set_split(rtdm_mjpeg* h, int subsequence_bytes);
+int rtdm_mjpeg_get_split(const rtdm_mjpeg* h, int* subsequence_bytes);
+/* Totals since the handle was created: frames decoded the split way, the subsequences they were cut into, and the most rounds
+ * of speculative decoding one of them took (never more than its subsequences).  SYNCHRONISES the stream of the handle's last
+ * call, then reads the counters the kernel keeps on the device.  Any pointer may be NULL. */
+int rtdm_mjpeg_get_split_stats(rtdm_mjpeg* h, long* frames_split, long* subsequences, int* max_rounds);
 /* estimator.cpp:24-36 + 56 in one call: decode both frames, gray, remap, crop, match.  The RGB frames never leave HBM.  width x
  * height is the rectifier's frame; the three handles live on one device.  Synchronous. */
 int rtdm_bm_compute_mjpeg(rtdm_bm* bm, rtdm_rectify* rc, rtdm_mjpeg* dec, const uint8_t* left, size_t left_len,

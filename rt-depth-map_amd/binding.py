@@ -187,6 +187,9 @@ def lib():
         "rtdm_mjpeg_decode_batch_device": (C.c_int, [vp, C.c_int, C.POINTER(C.c_void_p), C.POINTER(sz), C.c_int, C.c_int, u8p,
                                                      sz, sz, vp, vp]),
         "rtdm_bm_compute_mjpeg": (C.c_int, [vp, vp, vp, u8p, sz, u8p, sz, C.c_int, C.c_int, i16p, sz]),
+        "rtdm_mjpeg_set_split": (C.c_int, [vp, C.c_int]),
+        "rtdm_mjpeg_get_split": (C.c_int, [vp, C.POINTER(C.c_int)]),
+        "rtdm_mjpeg_get_split_stats": (C.c_int, [vp, C.POINTER(C.c_long), C.POINTER(C.c_long), C.POINTER(C.c_int)]),
         "rtdm_synth_pairs_device": (C.c_int, [C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, u8p, u8p,
                                               sz, sz, C.c_int, vp]),
     }
@@ -212,7 +215,7 @@ EXPORTS = ("rtdm_strerror rtdm_last_hip_error rtdm_abi_version rtdm_device_count
            "rtdm_bm_compute_filtered rtdm_xyz_default_params rtdm_xyz_create rtdm_xyz_destroy rtdm_xyz_set_params "
            "rtdm_xyz_get_params rtdm_xyz_map rtdm_xyz_map_device rtdm_xyz_cloud rtdm_xyz_cloud_device rtdm_bm_compute_cloud "
            "rtdm_mjpeg_probe rtdm_mjpeg_create rtdm_mjpeg_destroy rtdm_mjpeg_decode rtdm_mjpeg_decode_batch_device "
-           "rtdm_bm_compute_mjpeg rtdm_calib_load rtdm_stereo_rectify rtdm_undistort_rectify_map "
+           "rtdm_bm_compute_mjpeg rtdm_mjpeg_set_split rtdm_mjpeg_get_split rtdm_mjpeg_get_split_stats rtdm_calib_load rtdm_stereo_rectify rtdm_undistort_rectify_map "
            "rtdm_undistort_rectify_map_device rtdm_rectify_create_calib").split()
 
 

@@ -54,6 +54,11 @@ int rtdm_mjpeg_create(int max_width, int max_height, int max_batch, size_t max_s
     m.dev(&h->dCoef, h->maxBlocks * 128 * B); m.dev(&h->dPlanes, h->maxBlocks * 64 * B);
     m.dev(&h->dRgb, (size_t)max_width * max_height * 3);
     m.dev(&h->dStatus, sizeof(int) * (B + 1));
+    m.dev(&h->dSplitTotals, sizeof(unsigned long long) * 2); m.dev(&h->dSplitRounds, sizeof(int));
+    if (m.err == hipSuccess) m.err = hipMemsetAsync(h->dSplitTotals, 0, sizeof(unsigned long long) * 2, h->stream);
+    if (m.err == hipSuccess) m.err = hipMemsetAsync(h->dSplitRounds, 0, sizeof(int), h->stream);
+    if (m.err == hipSuccess) m.err = hipStreamSynchronize(h->stream);
+    h->splitBytes = MJ_SPLIT_DEFAULT;
     if (m.err != hipSuccess) { const hipError_t e = m.err; rtdm_mjpeg_destroy(h); return create_failed("rtdm_mjpeg_create", e); }
     *out = h;
     return RTDM_OK;
@@ -83,6 +88,7 @@ int rtdm::mjpeg_chunk(rtdm_mjpeg* h, int m, const uint8_t* const* streams, const
     if (h->staged) { HIPC(hipEventSynchronize(h->evStaged)); h->staged = false; }
     size_t nsegs = 0, bytes = 0;
     unsigned max_nseg = 1;
+    MjpegSplitCall split = {(uint32_t)h->splitBytes, 0, 0, h->dSplitTotals, h->dSplitRounds};
     for (int k = 0; k < m; ++k) {
         if (!streams[k]) return RTDM_ERR_NULL;
         MjpegDesc& d = h->hDesc[k];
@@ -97,6 +103,13 @@ int rtdm::mjpeg_chunk(rtdm_mjpeg* h, int m, const uint8_t* const* streams, const
         bytes += ((size_t)d.stream_len + 15) & ~(size_t)15;
         nsegs += d.nseg;
         max_nseg = std::max(max_nseg, (unsigned)d.nseg);
+        if (d.nseg == 1) {                                   // what k_mjpeg_huff_split works out for itself from the same figures
+            const MjpegSeg sg = h->hSegs[d.seg_first];
+            const uint32_t end = std::min(sg.end, d.stream_len), begin = std::min(sg.begin, end);
+            uint32_t sp;
+            const uint32_t nsub = mjpeg_split_plan(end - begin, split.bytes, &sp);
+            if (nsub >= 2) { ++split.frames; split.max_nsub = std::max(split.max_nsub, nsub); }
+        }
     }
     const size_t nb = mjpeg_frame_blocks(*shape);
     HIPC(hipMemcpyAsync(h->dStreams, h->hStreams, bytes, hipMemcpyHostToDevice, s));
@@ -106,7 +119,9 @@ int rtdm::mjpeg_chunk(rtdm_mjpeg* h, int m, const uint8_t* const* streams, const
     h->staged = true;
     HIPC(hipMemsetAsync(h->dCoef, 0, nb * 128 * m, s));
     HIPC(hipMemsetAsync(d_status, 0, sizeof(int) * m, s));
-    launch_mjpeg(h->dStreams, h->dDesc, h->dSegs, m, *shape, max_nseg, h->dCoef, h->dPlanes, d_rgb, pitch, frame_stride, d_status, s);
+    h->lastStream = s;
+    h->used = true;
+    launch_mjpeg(h->dStreams, h->dDesc, h->dSegs, m, *shape, max_nseg, split, h->dCoef, h->dPlanes, d_rgb, pitch, frame_stride, d_status, s);
     HIPC(hipGetLastError());
     return RTDM_OK;
 }
@@ -164,4 +179,36 @@ int rtdm_mjpeg_decode(rtdm_mjpeg* h, const uint8_t* stream, size_t len, int widt
     HIPC(hipStreamSynchronize(s));
     drain.armed = false;
     return h->hStatus[0] ? RTDM_ERR_BAD_STREAM : RTDM_OK;
+}
+
+int rtdm_mjpeg_set_split(rtdm_mjpeg* h, int subsequence_bytes)
+{
+    // the value first: what it may be does not depend on the handle
+    if (subsequence_bytes != 0 && subsequence_bytes != -1 && (subsequence_bytes < MJ_SPLIT_MIN || subsequence_bytes > MJ_SPLIT_MAX))
+        return RTDM_ERR_BAD_PARAM;
+    if (!h) return RTDM_ERR_NULL;
+    h->splitBytes = subsequence_bytes == -1 ? MJ_SPLIT_DEFAULT : subsequence_bytes;
+    return RTDM_OK;
+}
+
+int rtdm_mjpeg_get_split(const rtdm_mjpeg* h, int* subsequence_bytes)
+{
+    if (!h || !subsequence_bytes) return RTDM_ERR_NULL;
+    *subsequence_bytes = h->splitBytes;
+    return RTDM_OK;
+}
+
+int rtdm_mjpeg_get_split_stats(rtdm_mjpeg* h, long* frames_split, long* subsequences, int* max_rounds)
+{
+    if (!h) return RTDM_ERR_NULL;
+    HIPC(hipSetDevice(h->device));
+    if (h->used) HIPC(hipStreamSynchronize(h->lastStream));
+    unsigned long long tot[2];
+    int rounds;
+    HIPC(hipMemcpy(tot, h->dSplitTotals, sizeof tot, hipMemcpyDeviceToHost));
+    HIPC(hipMemcpy(&rounds, h->dSplitRounds, sizeof rounds, hipMemcpyDeviceToHost));
+    if (frames_split) *frames_split = (long)tot[0];
+    if (subsequences) *subsequences = (long)tot[1];
+    if (max_rounds) *max_rounds = rounds;
+    return RTDM_OK;
 }

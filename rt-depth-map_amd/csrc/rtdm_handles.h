@@ -121,6 +121,11 @@ struct rtdm_mjpeg {
     uint8_t* dPlanes;              // [maxB] planar Y, Cb, Cr at their own (padded) resolutions
     uint8_t* dRgb;                 // one frame for the host entry point
     int* dStatus;                  // [maxB + 1]
+    int splitBytes;                // subsequence bytes asked for a frame without restart intervals; 0: one lane per segment
+    unsigned long long* dSplitTotals;   // {frames, subsequences} k_mjpeg_huff_split decoded since creation ...
+    int* dSplitRounds;             // ... and the most rounds one of them took
+    hipStream_t lastStream;        // where the last call enqueued (what rtdm_mjpeg_get_split_stats waits for)
+    bool used;                     // a call has enqueued work
     rtdm::AllocList mem;
 };
 

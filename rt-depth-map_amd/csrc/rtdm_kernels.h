@@ -286,11 +286,15 @@ void launch_xyz_cloud(const XyzCloudIn& I, int n, int W, int H, const XyzParams&
 // any of their descriptors), descriptors, segment table and stream bytes on the device.  d_coef: m * blocks * 64 int16,
 // ZEROED by the caller; d_planes: m * blocks * 64 bytes; d_status: m ints, zeroed by the caller, MJ_BAD_STREAM where the
 // entropy data of a frame is damaged.  max_nseg: the largest segment count among the frames.  (Types: rtdm_mjpeg.h.)
+// split: which frames k_mjpeg_huff_split decodes -- those of ONE segment that `bytes` per subsequence (mjpeg_split_plan) cut into
+// two subsequences or more; the caller has counted them (`frames` of the m, the most subsequences of one: max_nsub).  totals
+// (two counters: frames, subsequences) and max_rounds (device) are added to by that kernel.
 struct MjpegDesc;
 struct MjpegSeg;
+struct MjpegSplitCall { uint32_t bytes; int frames; uint32_t max_nsub; unsigned long long* totals; int* max_rounds; };
 void launch_mjpeg(const uint8_t* d_streams, const MjpegDesc* d_desc, const MjpegSeg* d_segs, int m, const MjpegDesc& shape,
-                  unsigned max_nseg, int16_t* d_coef, uint8_t* d_planes, uint8_t* d_rgb, size_t pitch, size_t frame_stride,
-                  int* d_status, hipStream_t stream);
+                  unsigned max_nseg, const MjpegSplitCall& split, int16_t* d_coef, uint8_t* d_planes, uint8_t* d_rgb, size_t pitch,
+                  size_t frame_stride, int* d_status, hipStream_t stream);
 
 // Synthetic stream generator (bit-identical to synth.py).
 void launch_synth(uint64_t seed, int first_frame, int n, int W, int H, int D, Plane8W L, Plane8W R,

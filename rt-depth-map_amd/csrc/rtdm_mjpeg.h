@@ -193,6 +193,217 @@ MJ_HD int mjpeg_decode_segment(const uint8_t* stream, const MjpegDesc& d, const 
     return MJ_OK;
 }
 
+// ---- one segment among many lanes ("A frame without restart intervals") -------------------------------
+// A frame without DRI is ONE segment.  Its bytes [begin, end) are cut into nsub subsequences of sp bytes, one lane each.  Lane 0
+// knows where it starts; every other lane guesses (its first byte, unit 0, index 0), decodes without storing to the end of its
+// subsequence and hands the state it arrived in to the next lane, which starts over from it; Huffman codes self-synchronise, so
+// after a few rounds nothing changes any more (lane i is right after round i at the latest).  A scan over the lanes' block
+// counts and DC walks then gives every lane its first block and its predictors, and one more pass stores the coefficients.
+// k_mjpeg_huff_split (k_mjpeg.hip) runs this with a workgroup; tests/mjpeg_split_host.cpp replays it with loops.
+static const uint32_t MJ_SPLIT_LANES = 1024;     // the most subsequences a frame is cut into
+static const int MJ_SPLIT_MIN = 8, MJ_SPLIT_MAX = 65536, MJ_SPLIT_DEFAULT = 64;   // subsequence bytes a caller may ask for
+
+// -> the number of subsequences of a segment of len bytes when S bytes are asked for (0: no splitting), *sp: their size
+MJ_HD uint32_t mjpeg_split_plan(uint32_t len, uint32_t S, uint32_t* sp)
+{
+    *sp = 0;
+    if (S == 0 || len == 0) return 0;
+    const uint32_t least = (len + MJ_SPLIT_LANES - 1) / MJ_SPLIT_LANES;
+    *sp = S > least ? S : least;
+    return (len + *sp - 1) / *sp;
+}
+MJ_HD uint32_t mjpeg_split_lanes(uint32_t nsub) { uint32_t l = 64; while (l < nsub && l < MJ_SPLIT_LANES) l *= 2; return l; }
+
+// The decoder's state at a symbol boundary, as lanes hand it over.  pos / bit: the next unconsumed bit in the RAW stream, never
+// inside the 00 of an FF 00 pair (the pair counts as the byte at its FF); u: the block inside the MCU (luma blocks first);
+// k: 0 = a DC symbol is next, 1..63 = an AC symbol for that zigzag index.  The DC predictors are not part of it.  It is
+// canonical: whatever a reader buffered ahead does not show, so two lanes that reach the same boundary hold equal states.
+struct MjpegState { uint32_t pos, w; };          // w: bit | u << 3 | k << 6 | 1 << 12; every invalid state is {~0, 0}
+MJ_HD MjpegState mjpeg_state(uint32_t pos, uint32_t bit, uint32_t u, uint32_t k)
+{
+    MjpegState s; s.pos = pos; s.w = bit | (u << 3) | (k << 6) | (1u << 12); return s;
+}
+MJ_HD MjpegState mjpeg_state_invalid() { MjpegState s; s.pos = 0xFFFFFFFFu; s.w = 0; return s; }
+MJ_HD bool mjpeg_state_same(MjpegState a, MjpegState b) { return a.pos == b.pos && a.w == b.w; }
+
+// mjpeg_fill reads ahead, so (p, n) of a reader says nothing another reader could start from.  This reader notes for each of the
+// eight bytes its buffer can hold whether it came from the stream (`real`; not a zero supplied past the end) and whether it was
+// an FF 00 pair (`pair`), newest byte in bit 0; the raw position of the next unconsumed bit follows from p.  At a marker or a
+// lone 0xFF it stays where it is (mjpeg_fill jumps to the end; both supply zeros from there on).
+struct MjpegSplitBits : MjpegBits { uint32_t real, pair; };
+
+MJ_HD void mjpeg_split_fill(MjpegSplitBits& b)
+{
+    while (b.n <= 56) {
+        uint32_t byte = 0, real = 0, pair = 0;
+        if (b.p < b.end) {
+            byte = b.s[b.p];
+            if (byte == 0xFF) {
+                if (b.p + 1 < b.end && b.s[b.p + 1] == 0) { b.p += 2; real = 1; pair = 1; }
+                else { byte = 0; ++b.fed; }
+            } else { ++b.p; real = 1; }
+        } else ++b.fed;
+        b.acc = (b.acc << 8) | byte;
+        b.n += 8;
+        b.real = (b.real << 1) | real;
+        b.pair = (b.pair << 1) | pair;
+    }
+}
+MJ_HD void mjpeg_split_open(MjpegSplitBits& b, const uint8_t* s, uint32_t pos, uint32_t bit, uint32_t end)
+{
+    b.s = s; b.p = pos < end ? pos : end; b.end = end; b.acc = 0; b.n = 0; b.fed = 0; b.real = 0; b.pair = 0;
+    mjpeg_split_fill(b);
+    b.n -= (int)bit;
+}
+// where the next unconsumed bit is.  Only asked while no bit from beyond the data was consumed (fed * 8 <= n): the byte that
+// holds the bit is then a real one, or it is the first one past the data and the answer is (p, 0).
+MJ_HD void mjpeg_split_pos(const MjpegSplitBits& b, uint32_t* pos, uint32_t* bit)
+{
+    if (b.n <= 0) { *pos = b.p; *bit = 0; return; }
+    const uint32_t mask = (2u << ((b.n - 1) >> 3)) - 1u;       // the bytes not yet consumed to their end
+    *pos = b.p - (uint32_t)__builtin_popcount(b.real & mask) - (uint32_t)__builtin_popcount(b.pair & mask);
+    *bit = (uint32_t)(8 - (b.n & 7)) & 7u;
+}
+
+// where lane i > 0 tries first: the first byte of its subsequence, one further where that is the 00 of an FF 00 pair
+MJ_HD MjpegState mjpeg_split_guess(const uint8_t* s, uint32_t begin, uint32_t end, uint32_t sp, uint32_t i)
+{
+    uint32_t p = begin + i * sp;
+    if (i == 0) return mjpeg_state(begin, 0, 0, 0);
+    if (p < end && s[p] == 0 && s[p - 1] == 0xFF) ++p;
+    return mjpeg_state(p, 0, 0, 0);
+}
+
+// The DC predictor after a block is  min(max(pred + diff, -32768), 32767).  Maps  x -> min(max(x + a, l), h)  are closed under
+// composition, so a lane records one per component for the blocks it decoded and a scan composes them.  Only x in
+// [-32768, 32767] is ever asked for and l, h stay inside that range: once |a| >= 65536 the map is constant, it is stored as
+// l = h, and a is pinned, so a never leaves 18 bits however many blocks are composed.
+struct MjpegClamp { int a, l, h; };
+MJ_HD MjpegClamp mjpeg_clamp_id() { MjpegClamp f; f.a = 0; f.l = -32768; f.h = 32767; return f; }
+MJ_HD int mjpeg_clamp_to(int v, int l, int h) { return v < l ? l : (v > h ? h : v); }
+MJ_HD MjpegClamp mjpeg_clamp_then(MjpegClamp f, MjpegClamp g)      // x -> g(f(x))
+{
+    MjpegClamp r;
+    r.a = f.a + g.a;
+    r.l = mjpeg_clamp_to(f.l + g.a, g.l, g.h);
+    r.h = mjpeg_clamp_to(f.h + g.a, g.l, g.h);
+    if (r.a >= 65536) { r.a = 65536; r.l = r.h; }
+    else if (r.a <= -65536) { r.a = -65536; r.h = r.l; }
+    return r;
+}
+MJ_HD int mjpeg_clamp_apply(MjpegClamp f, int x) { return mjpeg_clamp_to(x + f.a, f.l, f.h); }
+
+// what a pass of a lane leaves: the state it stopped in, the blocks whose DC symbol it decoded and its DC walk per component
+struct MjpegLane { MjpegState out; uint32_t blocks; MjpegClamp m0, m1, m2; };
+MJ_HD void mjpeg_lane_clear(MjpegLane& r)
+{
+    r.out = mjpeg_state_invalid(); r.blocks = 0; r.m0 = r.m1 = r.m2 = mjpeg_clamp_id();
+}
+
+// One pass of one lane over s[.., end) from the state `in`, up to the first symbol boundary at or beyond byte `stop` (the last
+// lane: ~0u, it never gets there).
+//   coef == NULL   nothing is stored; *res gets the exit state and the counts.  Nothing is an error here.  A bit pattern that is
+//                  no code is passed over one bit further and an index past 63 ends the block: a lane that guessed wrong
+//                  meets both all the time, and it has to go on to fall into step (an invalid exit would be handed down the
+//                  lanes and undo what they had found; measured, the rounds then equal the lanes).  From a true state the
+//                  same two are real damage: what lies behind them is never used, because the final pass of this lane refuses
+//                  the frame there.  A bit taken from beyond the data makes the exit state invalid; an invalid `in` gives an
+//                  invalid exit with zero counts.  Returns MJ_OK.
+//   coef != NULL   the final pass: `in` is the true state, ord the number of DC symbols before it (the block a DC symbol
+//                  opens), pred0..2 the predictors.  Coefficients are stored as mjpeg_decode_segment stores them.  The pass also
+//                  ends where a DC symbol would open block nblocks: the frame is complete, as the one-lane loop judges it.
+//                  Returns MJ_BAD_STREAM for what that loop refuses (met inside a block below nblocks), else MJ_OK.
+// The one-lane loop looks for bits taken from beyond the data at the end of a block; here every symbol boundary looks.  The
+// count of such bits never falls, so both refuse the same streams.
+MJ_HD int mjpeg_split_pass(const uint8_t* stream, const MjpegDesc& d, uint32_t end, const MjpegHuff* tabs, const uint8_t* zz,
+                           MjpegState in, uint32_t stop, uint32_t ord, int pred0, int pred1, int pred2, int16_t* coef, MjpegLane* res)
+{
+    const bool store = coef != nullptr;
+    mjpeg_lane_clear(*res);
+    if (!(in.w >> 12)) return MJ_OK;
+    const uint32_t hv = (uint32_t)(d.hs * d.vs), units = hv + (uint32_t)d.ncomp - 1u, nblocks = mjpeg_frame_blocks(d);
+    uint32_t u = (in.w >> 3) & 7u, k = (in.w >> 6) & 63u;
+    if (u >= units) return store ? MJ_BAD_STREAM : MJ_OK;
+    MjpegSplitBits b;
+    mjpeg_split_open(b, stream, in.pos, in.w & 7u, end);
+    int c = u < hv ? 0 : (int)(u - hv) + 1;
+    int16_t* out = nullptr;
+    if (store && k > 0) {                                   // inside a block that an earlier lane opened
+        if (ord == 0) return MJ_BAD_STREAM;                 // cannot happen: lane 0 starts with a DC symbol
+        if (ord - 1 >= nblocks) return MJ_OK;               // what lies behind the frame's last block is not looked at
+    }
+    // every symbol takes at least one bit and the pass ends once a bit from beyond the data was taken: a counted loop
+    for (uint64_t left = 8ull * (end - b.p) + 72; left; --left) {
+        if (b.fed * 8 > b.n) return store ? MJ_BAD_STREAM : MJ_OK;
+        if (store && k == 0 && ord >= nblocks) return MJ_OK;
+        uint32_t pos, bit;
+        mjpeg_split_pos(b, &pos, &bit);
+        if (pos >= stop) { res->out = mjpeg_state(pos, bit, u, k); return MJ_OK; }
+        if (store && !out) {                                // the block this lane is in: ord (a DC symbol is next) or ord - 1
+            const uint32_t o = k == 0 ? ord : ord - 1, mcu = o / units, my = mcu / (uint32_t)d.mcux, mx = mcu - my * (uint32_t)d.mcux;
+            const uint32_t h = c == 0 ? (uint32_t)d.hs : 1u, v = c == 0 ? (uint32_t)d.vs : 1u, j = c == 0 ? u / h : 0u, i = c == 0 ? u - j * h : 0u;
+            const uint32_t blk = mjpeg_comp_first_block(d, c) + (my * v + j) * (uint32_t)d.mcux * h + mx * h + i;
+            if (blk >= nblocks || o % units != u) return MJ_BAD_STREAM;      // cannot happen from a true state; the guard stays
+            out = coef + (size_t)blk * 64;
+        }
+        const uint8_t* q = d.qt[c];
+        mjpeg_split_fill(b);
+        if (k == 0) {
+            const int s = mjpeg_symbol(b, tabs + 2 * c);
+            if (s < 0 || s > 15) {
+                if (store) return MJ_BAD_STREAM;
+                b.n -= 1;                                   // a guess went wrong: one bit further, and on
+                continue;
+            }
+            const int diff = mjpeg_extend(mjpeg_take(b, s), s);
+            if (store) {
+                int pred = (c == 0 ? pred0 : (c == 1 ? pred1 : pred2)) + diff;
+                pred = pred < -32768 ? -32768 : (pred > 32767 ? 32767 : pred);
+                if (c == 0) pred0 = pred; else if (c == 1) pred1 = pred; else pred2 = pred;
+                const int16_t dcv = mjpeg_sat16(pred * (int)q[0]);
+                if (dcv) out[0] = dcv;
+                ++ord;
+            } else {
+                MjpegClamp g = mjpeg_clamp_id();
+                g.a = diff;
+                if (c == 0) res->m0 = mjpeg_clamp_then(res->m0, g);
+                else if (c == 1) res->m1 = mjpeg_clamp_then(res->m1, g);
+                else res->m2 = mjpeg_clamp_then(res->m2, g);
+                ++res->blocks;
+            }
+            k = 1;
+        } else {
+            const int rs = mjpeg_symbol(b, tabs + 2 * c + 1);
+            if (rs < 0) {
+                if (store) return MJ_BAD_STREAM;
+                b.n -= 1;
+                continue;
+            }
+            const uint32_t r = (uint32_t)rs >> 4;
+            const int s = rs & 15;
+            if (s == 0) k = r != 15 ? 64 : k + 16;
+            else {
+                k += r;
+                if (k > 63) {
+                    if (store) return MJ_BAD_STREAM;
+                    k = 64;                                 // a guess went wrong: the block ends here, and on
+                } else {
+                    const int16_t val = mjpeg_sat16(mjpeg_extend(mjpeg_take(b, s), s) * (int)q[k]);
+                    if (store && val) out[zz[k] & 63] = val;
+                    ++k;
+                }
+            }
+        }
+        if (k >= 64) {                                      // the block is complete
+            k = 0;
+            u = u + 1 == units ? 0 : u + 1;
+            c = u < hv ? 0 : (int)(u - hv) + 1;
+            out = nullptr;
+        }
+    }
+    return store ? MJ_BAD_STREAM : MJ_OK;                   // cannot happen: the count above is an upper bound
+}
+
 // ---- host only (plain functions: a HIP compilation treats them as host code): headers -> MjpegDesc + segment table --------------------------------------------------------------------
 struct MjpegInfo {       // rtdm_mjpeg_info of include/rtdm.h, field for field
     int width, height, components, h_samp, v_samp, restart_interval, segments, has_dht;

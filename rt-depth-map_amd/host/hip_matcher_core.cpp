@@ -322,6 +322,17 @@ int HIPMJPEGCore::compute(HIPMatcherCore& matcher, HIPRectifierCore& rectifier, 
                                  outStep);
 }
 
+int HIPMJPEGCore::setSplit(int subsequenceBytes)
+{
+    if (!dec_) return status_ != RTDM_OK ? status_ : RTDM_ERR_NO_DEVICE;
+    return rtdm_mjpeg_set_split(dec_, subsequenceBytes);
+}
+int HIPMJPEGCore::splitStats(long* framesSplit, long* subsequences, int* maxRounds)
+{
+    if (!dec_) return status_ != RTDM_OK ? status_ : RTDM_ERR_NO_DEVICE;
+    return rtdm_mjpeg_get_split_stats(dec_, framesSplit, subsequences, maxRounds);
+}
+
 HIPMorphCore::HIPMorphCore(int w, int h, int bpp, int device) : width_(w), height_(h), bpp_(bpp)
 {
     status_ = (bpp == 8) ? rtdm_morph_create(w, h, 1, device, &mf_) : RTDM_ERR_UNSUPPORTED;

@@ -266,6 +266,11 @@ public:
     int compute(HIPMatcherCore& matcher, HIPRectifierCore& rectifier, const uint8_t* left, size_t leftLen, const uint8_t* right,
                 size_t rightLen, int width, int height, int16_t* out, size_t outStep);
     static int probe(const uint8_t* in, size_t len, rtdm_mjpeg_info* info) { return rtdm_mjpeg_probe(in, len, info); }
+    // a frame without restart intervals is cut into subsequences of this many bytes, one lane each (rtdm_mjpeg_set_split):
+    // 0 off, 8 .. 65536, -1 the built-in default (which a new decoder starts with)
+    int setSplit(int subsequenceBytes);
+    // totals since construction; synchronises the last call's stream (rtdm_mjpeg_get_split_stats)
+    int splitStats(long* framesSplit, long* subsequences, int* maxRounds);
     int status() const { return status_; }
     rtdm_mjpeg* handle() { return dec_; }
 

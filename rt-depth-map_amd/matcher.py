@@ -873,14 +873,36 @@ class HIPMJPEGDecoder:
     """The reference's DecoderDevice (include/decoder/decoder.h, estimator.cpp:24-27) on the device: baseline MJPEG frames ->
     interleaved RGB, byte for byte what libjpeg gives with its defaults (JDCT_ISLOW, fancy upsampling).
 
-    width x height: the largest frame; max_stream_bytes: the longest stream (SOI .. EOI)."""
+    width x height: the largest frame; max_stream_bytes: the longest stream (SOI .. EOI).  split: the bytes per subsequence a
+    frame without restart intervals is cut into, one lane each (rtdm_mjpeg_set_split): None or -1 = the built-in default,
+    0 = off, 8 .. 65536."""
 
-    def __init__(self, width, height, max_batch=1, max_stream_bytes=None, device=0):
+    def __init__(self, width, height, max_batch=1, max_stream_bytes=None, device=0, split=None):
         self.width, self.height, self.max_batch, self.device = int(width), int(height), int(max_batch), device
         self.max_stream_bytes = int(max_stream_bytes) if max_stream_bytes else max(4096, self.width * self.height * 3)
         self._h = C.c_void_p()
         B.check(B.lib().rtdm_mjpeg_create(self.width, self.height, self.max_batch, self.max_stream_bytes, device,
                                           C.byref(self._h)), "rtdm_mjpeg_create")
+        if split is not None:
+            self.split = split
+
+    @property
+    def split(self):
+        v = C.c_int()
+        B.check(B.lib().rtdm_mjpeg_get_split(self._h, C.byref(v)), "rtdm_mjpeg_get_split")
+        return v.value
+
+    @split.setter
+    def split(self, subsequence_bytes):
+        B.check(B.lib().rtdm_mjpeg_set_split(self._h, -1 if subsequence_bytes is None else int(subsequence_bytes)),
+                "rtdm_mjpeg_set_split")
+
+    def split_stats(self):
+        """(frames decoded the split way, their subsequences, the most rounds one took) since creation.  Synchronises the stream
+        of the last call."""
+        f, n, r = C.c_long(), C.c_long(), C.c_int()
+        B.check(B.lib().rtdm_mjpeg_get_split_stats(self._h, C.byref(f), C.byref(n), C.byref(r)), "rtdm_mjpeg_get_split_stats")
+        return f.value, n.value, r.value
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
