@@ -180,69 +180,6 @@ static void stage_end(rtdm_bm* bm, hipStream_t s, StageEvent* ev)
     bm->pending.push_back(*ev);
 }
 
-// Row strips per frame for the fast search of a batch, chosen by measurement and remembered in the handle: the model
-// (fast_strips_model) is right on average, but neighbouring strip counts differ by up to 5 % through scheduling effects it
-// cannot see (profiles/r01_xcd_mapping_sweep.txt).  The search only writes its own outputs, so timing it a few times on
-// the caller's data is harmless.  The key is the SHAPE of the work (frame size, batch, searched columns and rows as
-// counts, not positions): a caller that moves a same-sized ROI around (estimator.cpp:53-54) keeps its entry.  A shape is
-// measured the SECOND time it is seen -- a caller whose ROI changes size every call never pays the ~30 extra launches and
-// the stream synchronisation -- and the table is a 16-entry LRU.  Small batches keep the model.  RTDM_AUTOTUNE=0: off.
-static int tune_strips(rtdm_bm* bm, Plane8 Lpr, Plane8 Rpr, Plane16W disp, const BMGeom& g, int n, hipStream_t s, bool fuse, bool ring)
-{
-    const auto launch = [&](int c) {
-        if (ring) launch_search_ring(Lpr, Rpr, disp, bm->dCost, g, n, s, c, fuse);
-        else launch_search_fast(Lpr, Rpr, disp, bm->dCost, g, n, s, fuse, c);
-    };
-    static const bool enabled = env_int("RTDM_AUTOTUNE", 1) != 0 && getenv("RTDM_FAST_WGS") == nullptr;
-    if (!enabled || n < 16) return 0;
-    TuneKey key{g.W, g.H, n, g.cx1 - g.cx0, g.vy1 - g.vy0, (fuse ? 1 : 0) | (ring ? ring_lanes_per_pixel(g) : 0)};
-    for (size_t i = 0; i < bm->tuned.size(); ++i) {
-        if (!(bm->tuned[i].key == key)) continue;
-        TuneEntry e = bm->tuned[i];
-        bm->tuned.erase(bm->tuned.begin() + (long)i);              // most recently used goes to the back
-        if (e.strips == 0) {
-            e.strips = -1;                                          // being measured: a failure below leaves the model in charge
-            ++bm->tune_shapes;
-            const int model = ring ? ring_strips_model(g, n) : fast_strips_model(g, n), cap = (g.vy1 - g.vy0 + 15) / 16;
-            int best = model;
-            float best_ms = 1e30f;
-            hipEvent_t a, b;
-            if (hipEventCreate(&a) == hipSuccess) {
-                if (hipEventCreate(&b) == hipSuccess) {
-                    static const float f[] = {0.6f, 0.7f, 0.8f, 0.9f, 1.0f, 1.1f, 1.2f, 1.35f, 1.5f, 1.75f};
-                    int seen[10], nseen = 0;
-                    for (float fk : f) {
-                        const int c = std::max(1, std::min(cap, (int)(model * fk + 0.5f)));
-                        bool dup = false;
-                        for (int k = 0; k < nseen; ++k) dup |= seen[k] == c;
-                        if (dup) continue;
-                        seen[nseen++] = c;
-                        launch(c);          // warm
-                        bm->tune_launches += 3;
-                        float ms = 1e30f;
-                        for (int rep = 0; rep < 2; ++rep) {
-                            (void)hipEventRecord(a, s);
-                            launch(c);
-                            (void)hipEventRecord(b, s);
-                            float t = 0.f;
-                            if (hipEventSynchronize(b) == hipSuccess && hipEventElapsedTime(&t, a, b) == hipSuccess) ms = std::min(ms, t);
-                        }
-                        if (ms < best_ms) { best_ms = ms; best = c; }
-                    }
-                    e.strips = best;
-                    (void)hipEventDestroy(b);
-                }
-                (void)hipEventDestroy(a);
-            }
-        }
-        bm->tuned.push_back(e);
-        return e.strips > 0 ? e.strips : 0;
-    }
-    if (bm->tuned.size() >= 16) bm->tuned.erase(bm->tuned.begin());  // least recently used
-    bm->tuned.push_back(TuneEntry{key, 0});                           // first sighting: remember, keep the model
-    return 0;
-}
-
 // Fill + prefilter + SAD search of a chunk (VALU bound); *any = false: the whole frame is FILTERED, nothing follows.
 static int chunk_front(rtdm_bm* bm, int n, Plane8 L, Plane8 R, int W, int H, Plane16W disp, hipStream_t s, BMGeom* gout,
                        bool* anyout)
@@ -256,54 +193,17 @@ static int chunk_front(rtdm_bm* bm, int n, Plane8 L, Plane8 R, int W, int H, Pla
     // (+ the speckle filter's run counts = 0); the fill rides in the prefilter's launch
     const FillJob fill{disp, g.cx0, g.cx1, g.vy0, g.vy1, g.filtered, (p.speckleRange >= 0 && p.speckleWindowSize > 0) ? bm->dRowCnt : nullptr};
     StageEvent ev;
-    // what the single-pass generic kernel cannot hold in LDS (D > 256, large windows at large D) -- or everything, when
-    // rtdm_debug_disparity_slice forces it -- is searched by the disparity-sliced kernel over the whole range
-    const bool fast = !generic_search_sliced(g) && fast_search_supported(g);
-    {
-        const bool ring = fast && ring_search_supported(g);
-        Plane8W Lp{bm->dLp, bm->ppitch, bm->ppitch * (size_t)H}, Rp{bm->dRp, bm->ppitch, bm->ppitch * (size_t)H};
-        stage_begin(bm, RTDM_STAGE_PREFILTER, n, s, &ev);
-        launch_prefilter(L, R, Lp, Rp, W, H, p.preFilterCap, n, s, &fill, bm->prefilter_type, bm->prefilter_size);
-        stage_end(bm, s, &ev);
-        Plane8 Lpr{bm->dLp, Lp.pitch, Lp.frame}, Rpr{bm->dRp, Rp.pitch, Rp.frame};
-        stage_begin(bm, RTDM_STAGE_SEARCH, n, s, &ev);
-        if (fast) {
-            const int lpp = ring ? ring_lanes_per_pixel(g) : 0;
-            bm->variant = !ring ? "fast_qsad" : lpp == 16 ? "fast_ring16_qsad" : lpp == 8 ? "fast_ring8_qsad" : lpp == 4 ? "fast_ring4_qsad" : "fast_ring_qsad";
-            int lx0, lx1, rx0, rx1;
-            fast_border_ranges(g, &lx0, &lx1, &rx0, &rx1);
-            // Batches of 16 or more: the border columns run as a kernel of their own on a side stream, concurrently with the
-            // tile kernel.  Its waves need 37-72 VGPRs and fit NEXT to the four tile waves of a SIMD, whereas inside the tile
-            // kernel's grid a border workgroup takes a tile workgroup's slot for the length of its latency-bound walk
-            // (search -2 %).  Smaller batches keep the fused launch (one kernel less).
-            const bool side = border_search_supported(g) && n >= 16;
-            // (the 3.x clamp exists in the stand-alone border kernel only: the fused forms keep their register budget)
-            const bool fuse = border_search_supported(g) && !side && !g.legacy;   // border workgroups inside the tile kernel's grid
-            // (measured, if at all, before the side stream forks: nothing else runs beside the timed launches)
-            const int strips = tune_strips(bm, Lpr, Rpr, disp, g, n, s, fuse, ring);
-            if (side) {
-                HIPC(hipEventRecord(bm->evFork, s));
-                HIPC(hipStreamWaitEvent(bm->sBorder, bm->evFork, 0));
-                launch_search_border(Lpr, Rpr, disp, bm->dCost, g, n, bm->sBorder, lx0, lx1, rx0, rx1);
-                HIPC(hipEventRecord(bm->evJoin, bm->sBorder));
-            }
-            bool fused = fuse;
-            if (ring) fused = launch_search_ring(Lpr, Rpr, disp, bm->dCost, g, n, s, strips, fuse);
-            else launch_search_fast(Lpr, Rpr, disp, bm->dCost, g, n, s, fuse, strips);
-            if (side) {
-                HIPC(hipStreamWaitEvent(s, bm->evJoin, 0));
-            } else if (fused) {
-            } else if (border_search_supported(g)) {
-                launch_search_border(Lpr, Rpr, disp, bm->dCost, g, n, s, lx0, lx1, rx0, rx1);
-            } else {
-                launch_search_generic(Lpr, Rpr, disp, bm->dCost, g, n, s, lx0, lx1);
-                launch_search_generic(Lpr, Rpr, disp, bm->dCost, g, n, s, rx0, rx1);
-            }
-        } else {
-            bm->variant = launch_search_generic(Lpr, Rpr, disp, bm->dCost, g, n, s, g.cx0 - g.lofs, g.cx1 - g.lofs);
-        }
-        stage_end(bm, s, &ev);
-    }
+    Plane8W Lp{bm->dLp, bm->ppitch, bm->ppitch * (size_t)H}, Rp{bm->dRp, bm->ppitch, bm->ppitch * (size_t)H};
+    stage_begin(bm, RTDM_STAGE_PREFILTER, n, s, &ev);
+    launch_prefilter(L, R, Lp, Rp, W, H, p.preFilterCap, n, s, &fill, bm->prefilter_type, bm->prefilter_size);
+    stage_end(bm, s, &ev);
+    Plane8 Lpr{bm->dLp, Lp.pitch, Lp.frame}, Rpr{bm->dRp, Rp.pitch, Rp.frame};
+    stage_begin(bm, RTDM_STAGE_SEARCH, n, s, &ev);
+    // (the two planes share their strides; rtdm_bm_create puts the right ones behind the left ones in one allocation)
+    const SearchPlan plan = plan_search(g, n, bm->dRp > bm->dLp && (size_t)(bm->dRp - bm->dLp) < ((size_t)1 << 32) - ((size_t)1 << 20));
+    bm->variant = plan.variant;
+    HIPC(launch_search(plan, Lpr, Rpr, disp, bm->dCost, g, n, s, SearchSide{bm->sBorder, bm->evFork, bm->evJoin}, &bm->tuner));
+    stage_end(bm, s, &ev);
     HIPC(hipGetLastError());
     return RTDM_OK;
 }
@@ -583,8 +483,8 @@ const char* rtdm_bm_search_variant(const rtdm_bm* bm) { return bm ? bm->variant.
 int rtdm_bm_get_tuner_stats(const rtdm_bm* bm, long* shapes_measured, long* timing_launches)
 {
     if (!bm) return RTDM_ERR_NULL;
-    if (shapes_measured) *shapes_measured = bm->tune_shapes;
-    if (timing_launches) *timing_launches = bm->tune_launches;
+    if (shapes_measured) *shapes_measured = bm->tuner.shapes;
+    if (timing_launches) *timing_launches = bm->tuner.launches;
     return RTDM_OK;
 }
 void rtdm_debug_search_kernel(int mode) { ring_set_mode(mode); }

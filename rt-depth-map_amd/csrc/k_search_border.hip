@@ -14,16 +14,12 @@
 //   * selection with wave-level operations: min-reduce of the key sad<<8|e (first minimum),
 //     __any() for the uniqueness test, readlane for sad[mind +- 1].
 #include "rtdm_border.h"
+#include "rtdm_search.h"
 
 #include <cstdlib>
 #include <type_traits>
 
 namespace rtdm {
-
-bool border_search_supported(const BMGeom& g)
-{
-    return g.w <= 21 && g.D <= 256 && 2L * g.cap * g.w * g.w <= 65535;
-}
 
 // Rows per border workgroup: 128 for batches (the w-1 halo rows are then 6 % of the visits), shorter when the whole launch
 // would otherwise consist of a handful of long, latency-bound walks (single frames: the reference's real-time case).
@@ -43,32 +39,33 @@ size_t border_lds_bytes(int D, int w)
     return per_wave * 4;
 }
 
-// Geometry + LDS bytes of the border work; returns the grid (x = column groups, y = strips), 0 columns -> false.
-bool border_geometry(const BMGeom& g, int lx0, int lx1, int rx0, int rx1, int n, BorderGeom* out, int* gx, int* gy, size_t* lds_bytes)
+BorderPlan plan_border(const BMGeom& g, int n, int lx0, int lx1, int rx0, int rx1, bool allow_rows, bool allow_disp)
 {
-    const int ncols = max(0, lx1 - lx0) + max(0, rx1 - rx0);
-    if (ncols <= 0) return false;
-    BorderGeom bg;
-    bg.lx0 = lx0; bg.lx1 = max(lx1, lx0); bg.rx0 = rx0; bg.rx1 = max(rx1, rx0);
-    const int nrows = g.vy1 - g.vy0;
-    bg.rs = border_rows(nrows, ncols, n);
-    bg.rsp = border_rsp(g.D, g.w);
-    *out = bg; *gx = (ncols + 3) / 4; *gy = (nrows + bg.rs - 1) / bg.rs; *lds_bytes = border_lds_bytes(g.D, g.w);
-    return true;
+    BorderPlan b{};
+    lx1 = max(lx1, lx0); rx1 = max(rx1, rx0);
+    const int ncols = (lx1 - lx0) + (rx1 - rx0), nrows = g.vy1 - g.vy0;
+    b.form = ncols <= 0 ? BorderForm::NONE : BorderForm::GENERIC;
+    if (ncols <= 0) return b;
+    if (allow_rows && border_rows_form(g, lx0, lx1, rx0, rx1)) {
+        b.form = BorderForm::ROWS;
+        b.rows = Border2Geom{lx0, lx1, rx0, rx1, 64 - (g.w - 1)};
+        b.gy = (nrows + b.rows.ro - 1) / b.rows.ro;
+    } else if (allow_disp && g.w <= 21 && g.D <= 256 && 2L * g.cap * g.w * g.w <= 65535) {   // (32 left bytes per row, four chunks, u16 SADs)
+        b.form = BorderForm::DISP;
+        b.disp = BorderGeom{lx0, lx1, rx0, rx1, border_rows(nrows, ncols, n), border_rsp(g.D, g.w)};
+        b.gy = (nrows + b.disp.rs - 1) / b.disp.rs;
+        b.lds = border_lds_bytes(g.D, g.w);
+    }
+    if (b.form != BorderForm::GENERIC) b.gx = (ncols + 3) / 4;        // both forms: workgroups of four columns
+    return b;
 }
 
-void launch_search_border(Plane8 Lp, Plane8 Rp, Plane16W disp, void* cost, const BMGeom& g, int n,
-                          hipStream_t stream, int lx0, int lx1, int rx0, int rx1)
+void launch_border_disp(const BorderPlan& b, Plane8 Lp, Plane8 Rp, Plane16W disp, void* cost, const BMGeom& g, int n, hipStream_t stream)
 {
-    const int ncols = max(0, lx1 - lx0) + max(0, rx1 - rx0);
-    if (ncols <= 0) return;
-    if (launch_search_border2(Lp, Rp, disp, cost, g, n, stream, lx0, lx1, rx0, rx1)) return;   // rows in the lanes: far fewer instructions
-    BorderGeom bg;
-    int gx = 0, gy = 0;
-    size_t lds = 0;
-    border_geometry(g, lx0, lx1, rx0, rx1, n, &bg, &gx, &gy, &lds);
+    const BorderGeom bg = b.disp;
+    const size_t lds = b.lds;
     const int nch = (g.D + 63) / 64;
-    dim3 grid(gx, gy, n), block(256);
+    dim3 grid(b.gx, b.gy, n), block(256);
     const auto go = [&](auto nc, auto lg) {
         hipLaunchKernelGGL((k_search_border<decltype(nc)::value, decltype(lg)::value>), grid, block, lds, stream, Lp, Rp, disp, (uint16_t*)cost, g, bg);
     };

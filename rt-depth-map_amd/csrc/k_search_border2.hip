@@ -20,6 +20,7 @@
 // Not covered (k_search_border keeps them): the 3.x right-border rule (legacy_right_clamp), windows that clamp at both
 // edges, w > 16, prefix sums that could leave 16 bits (64 w 2 cap > 65535), D outside the table below.
 #include "rtdm_border2.h"
+#include "rtdm_search.h"
 
 namespace rtdm {
 
@@ -52,9 +53,7 @@ static bool border2_columns_ok(const BMGeom& g, int lx0, int lx1, int rx0, int r
     return true;
 }
 
-// Does this form cover the configuration?  If so: its geometry and its grid (gx workgroups of four columns x gy row blocks
-// per frame; gx = 0: no border columns at all).  Also used by k_search_ring to put these workgroups in front of its own.
-bool border2_plan(const BMGeom& g, int lx0, int lx1, int rx0, int rx1, Border2Geom* bg, int* gx, int* gy)
+bool border_rows_form(const BMGeom& g, int lx0, int lx1, int rx0, int rx1)
 {
     // RTDM_BORDER2=0 (test hook): k_search_border for everything -- what serves legacy clamp, w > 16 and D outside the table
     static const int enabled = env_int("RTDM_BORDER2", 1);
@@ -66,37 +65,23 @@ bool border2_plan(const BMGeom& g, int lx0, int lx1, int rx0, int rx1, Border2Ge
 #define X(DD) have |= g.D == DD;
     RTDM_BORDER2_TABLE(X)
 #undef X
-    if (!have) return false;
-    lx1 = max(lx1, lx0); rx1 = max(rx1, rx0);
-    const int ncols = (lx1 - lx0) + (rx1 - rx0);
-    *bg = Border2Geom{lx0, lx1, rx0, rx1, 64 - (g.w - 1)};
-    *gx = *gy = 0;
-    if (ncols <= 0) return true;
-    if (!border2_columns_ok(g, lx0, lx1, rx0, rx1)) return false;
-    *gx = (ncols + 3) / 4;
-    *gy = ((g.vy1 - g.vy0) + bg->ro - 1) / bg->ro;
-    return true;
+    return have && border2_columns_ok(g, lx0, lx1, rx0, rx1);
 }
 
-bool launch_search_border2(Plane8 Lp, Plane8 Rp, Plane16W disp, void* cost, const BMGeom& g, int n, hipStream_t stream,
-                           int lx0, int lx1, int rx0, int rx1)
+void launch_border_rows(const BorderPlan& b, Plane8 Lp, Plane8 Rp, Plane16W disp, void* cost, const BMGeom& g, int n, hipStream_t stream)
 {
-    Border2Geom bg;
-    int gx = 0, gy = 0;
-    if (!border2_plan(g, lx0, lx1, rx0, rx1, &bg, &gx, &gy)) return false;
-    if (gx == 0) return true;
-    const dim3 grid(gx, gy, n), block(256);
+    const Border2Geom bg = b.rows;
+    const dim3 grid(b.gx, b.gy, n), block(256);
     const int nsp = border2_nsp(g);
 #define X(DD)                                                                                                                   \
     if (g.D == DD) {                                                                                                            \
         if (nsp == 2) hipLaunchKernelGGL((k_search_border2<DD, 2>), grid, block, 0, stream, Lp, Rp, disp, (uint16_t*)cost, g, bg);       \
         else if (nsp == 3) hipLaunchKernelGGL((k_search_border2<DD, 3>), grid, block, 0, stream, Lp, Rp, disp, (uint16_t*)cost, g, bg);  \
         else hipLaunchKernelGGL((k_search_border2<DD, 4>), grid, block, 0, stream, Lp, Rp, disp, (uint16_t*)cost, g, bg);                \
-        return true;                                                                                                            \
+        return;                                                                                                                 \
     }
     RTDM_BORDER2_TABLE(X)
 #undef X
-    return false;
 }
 
 }  // namespace rtdm

@@ -13,11 +13,12 @@
 //     LDS ring and subtracted with v_pk_sub_u16.
 //   * selection per output pixel, all in registers: rtdm_select.h (shared with k_search_ring).
 //   * launch: 1-D grid, XCD-aware (see FastGeom); row strips per frame from a cost model, measured once per
-//     batch shape by the caller (api_bm.hip, tune_strips).
+//     batch shape by the caller (k_search.hip, StripTuner).
 //   Only columns whose whole window is free of border clamping are handled here; the 2*(w/2)
 //   border columns are searched by extra workgroups of the same grid (rtdm_border.h; they are outside the
 //   valid rectangle but feed the left-right check).  Semantics: SURVEY.md Appendix A.3b; oracle: oracle/bm_oracle.c.
 #include "rtdm_border.h"
+#include "rtdm_search.h"
 #include "rtdm_select.h"
 
 #include <cmath>
@@ -254,30 +255,15 @@ __global__ __launch_bounds__(256) void k_search_fast(Plane8 Lp, Plane8 Rp, Plane
 }
 
 // ---- host side ----------------------------------------------------------------------------
-bool search_interior_range(const BMGeom& g, int* x0, int* nx)
-{
-    const int r = g.r;
-    int xl = 0, xh = g.width1 - 1;
-    xl = max(xl, r - g.lofs); xl = max(xl, r - g.rofs);
-    xh = min(xh, g.W - 1 - g.lofs - r); xh = min(xh, g.W - g.D - g.rofs - r);
-    xl = max(xl, g.cx0 - g.lofs); xh = min(xh, g.cx1 - g.lofs - 1);      // setROI1: only the needed columns
-    if (x0) *x0 = xl;
-    if (nx) *nx = xh - xl + 1;
-    return xh >= xl;
-}
-
-void fast_border_ranges(const BMGeom& g, int* lx0, int* lx1, int* rx0, int* rx1);
-int fast_strips_model(const BMGeom& g, int n);
-
 static int fast_np(const BMGeom& g) { return (g.w + 3) / 4; }
 
 template <int D, int NP>
-static void launch_one(Plane8 Lp, Plane8 Rp, Plane16W disp, void* cost, const BMGeom& g, int n, hipStream_t stream, bool fuse_border,
+static void launch_one(const SearchPlan& plan, Plane8 Lp, Plane8 Rp, Plane16W disp, void* cost, const BMGeom& g, int n, hipStream_t stream,
                        int strips_hint)
 {
     using C = FastCfg<D, NP>;
     FastGeom fg;
-    search_interior_range(g, &fg.x0, &fg.nx);
+    fg.x0 = plan.x0; fg.nx = plan.nx;
     const int rem = g.w - 4 * (NP - 1);
     fg.lastmask = rem >= 4 ? 0xffffffffu : ((1u << (8 * rem)) - 1u);
     const int nrows = g.vy1 - g.vy0;
@@ -288,20 +274,18 @@ static void launch_one(Plane8 Lp, Plane8 Rp, Plane16W disp, void* cost, const BM
     // RTDM_FAST_WGS=<total workgroups> overrides (sweeps: tools/sweep_strips.sh, tools/sweep_wgs_small.py).
     static const int target_wgs = env_int("RTDM_FAST_WGS", 0);
     int strips;
-    if (strips_hint > 0) strips = strips_hint;                      // measured choice (api_bm.hip, tune_strips)
+    if (strips_hint > 0) strips = strips_hint;                      // measured choice (StripTuner)
     else if (target_wgs > 0) strips = (target_wgs + tiles * n - 1) / (tiles * n);
-    else strips = fast_strips_model(g, n);
+    else strips = fast_strips_model(plan, g, n);
     strips = max(1, min(strips, (nrows + 15) / 16));
     fg.rs = (nrows + strips - 1) / strips;
     strips = (nrows + fg.rs - 1) / fg.rs;
     size_t ldsb = (size_t)(g.w + 2) * C::SLOT * 4;
     BorderGeom bg = {};
     fg.tiles = tiles; fg.strips = strips; fg.bgx = fg.bgy = 0;
-    if (fuse_border) {
-        int lx0, lx1, rx0, rx1; size_t blds = 0;
-        fast_border_ranges(g, &lx0, &lx1, &rx0, &rx1);
-        if (border_geometry(g, lx0, lx1, rx0, rx1, n, &bg, &fg.bgx, &fg.bgy, &blds)) ldsb = max(ldsb, blds);
-        else fg.bgx = fg.bgy = 0;
+    if (plan.place == BorderPlace::FUSED && plan.border.form == BorderForm::DISP) {
+        bg = plan.border.disp; fg.bgx = plan.border.gx; fg.bgy = plan.border.gy;
+        ldsb = max(ldsb, plan.border.lds);
     }
     fg.nfast = (unsigned)tiles * strips * n; fg.nborder = (unsigned)(fg.bgx * fg.bgy) * n;
     fg.gfast = (fg.nfast + 7) / 8; fg.gborder = (fg.nborder + 7) / 8;
@@ -321,10 +305,9 @@ static void launch_one(Plane8 Lp, Plane8 Rp, Plane16W disp, void* cost, const BM
     X(16, 5) X(16, 6) X(48, 5) X(48, 6) X(80, 5) X(80, 6) X(96, 5) X(96, 6) X(112, 5) X(112, 6) X(144, 5) X(144, 6)          \
     X(160, 5) X(160, 6) X(176, 5) X(176, 6) X(192, 5) X(192, 6)
 
-bool fast_search_supported(const BMGeom& g)
+bool fast_form(const BMGeom& g)
 {
     if (2L * g.cap * g.w * g.w > 32766) return false;       // packed u16 sums + the T+1 <= 32767 argument
-    if (!search_interior_range(g, nullptr, nullptr)) return false;
     const int np = fast_np(g);
 #define X(DD, PP) if (g.D == DD && np == PP) return true;
     RTDM_FAST_TABLE(X)
@@ -332,29 +315,20 @@ bool fast_search_supported(const BMGeom& g)
     return false;
 }
 
-int fast_strips_model(const BMGeom& g, int n)
+int fast_strips_model(const SearchPlan& plan, const BMGeom& g, int n)
 {
-    int x0 = 0, nx = 0;
-    if (!search_interior_range(g, &x0, &nx)) return 1;
-    const int tiles = (nx + 255) / 256, nrows = g.vy1 - g.vy0;
+    const int tiles = (plan.nx + 255) / 256, nrows = g.vy1 - g.vy0;
     const int s = (int)(sqrtf((float)nrows * 1024.0f / ((float)(g.w - 1) * (float)tiles * (float)n)) + 0.5f);
     return max(1, min(s, (nrows + 15) / 16));
 }
 
-void launch_search_fast(Plane8 Lp, Plane8 Rp, Plane16W disp, void* cost, const BMGeom& g, int n, hipStream_t stream, bool fuse_border,
-                        int strips_hint)
+void launch_search_fast(const SearchPlan& plan, Plane8 Lp, Plane8 Rp, Plane16W disp, void* cost, const BMGeom& g, int n, hipStream_t stream,
+                        int strips)
 {
     const int np = fast_np(g);
-#define X(DD, PP) if (g.D == DD && np == PP) { launch_one<DD, PP>(Lp, Rp, disp, cost, g, n, stream, fuse_border, strips_hint); return; }
+#define X(DD, PP) if (g.D == DD && np == PP) { launch_one<DD, PP>(plan, Lp, Rp, disp, cost, g, n, stream, strips); return; }
     RTDM_FAST_TABLE(X)
 #undef X
-}
-
-void fast_border_ranges(const BMGeom& g, int* lx0, int* lx1, int* rx0, int* rx1)
-{
-    int x0 = 0, nx = 0;
-    search_interior_range(g, &x0, &nx);
-    *lx0 = max(0, g.cx0 - g.lofs); *lx1 = x0; *rx0 = x0 + nx; *rx1 = min(g.width1, g.cx1 - g.lofs);
 }
 
 }  // namespace rtdm

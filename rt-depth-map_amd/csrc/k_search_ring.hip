@@ -28,7 +28,7 @@
 // x_tile + phi + 4 p.  The four waves never synchronise: each stages ITS byte-shifted copy of the entering rows (64 or 128
 // dwords, padded) into its own LDS slice, two rows ahead of their use, and the LDS queue of a wave is in order.  The
 // texture sum is a prefix ring too (one dword per pixel and slot, in LDS).  Only columns whose window needs no border
-// clamping are handled here; the border columns go to k_search_border.
+// clamping are handled here; the border columns ride in front of the tiles or go to a launch of their own (k_search.hip).
 // Semantics: SURVEY.md Appendix A.3b; oracle: oracle/bm_oracle.c.
 //
 // Measured instruction costs on gfx950 that shaped this (tools/ubench_valu.hip, SIMD cycles per wave-instruction):
@@ -37,6 +37,7 @@
 #include "rtdm_select.h"
 #include "rtdm_border.h"
 #include "rtdm_border2.h"
+#include "rtdm_search.h"
 
 #include <cmath>
 #include <cstdlib>
@@ -472,19 +473,16 @@ __global__ __launch_bounds__(256, (RingBounds<D, WS, LPP, FUSE>::WAVES)) void k_
 // rows a strip may have so that no prefix sum leaves 16 bits: a row adds at most w * 2 cap per disparity, and a strip of
 // rs output rows walks rs + w - 1 rows plus up to seven padded rows (groups of eight)
 static int ring_rows_cap(const BMGeom& g) { return 65535 / (g.w * 2 * g.cap) - g.w - 6; }
-static int ring_lpp(const BMGeom& g);
 // trips of the row loop between two rebases of the ring (0: one trip is longer than the cap -- no rebasing, short strips)
-static int ring_rebase_trips(const BMGeom& g)
+static int ring_rebase_trips(const BMGeom& g, int lpp)
 {
-    const int lpp = ring_lpp(g);
-    if (!lpp) return 0;
     const int W1 = g.w + 1, rpg = ring_rpg(g.D, lpp);
     const int trip = (W1 % rpg == 0) ? W1 : (2 * W1 % rpg == 0) ? 2 * W1 : 4 * W1;   // RingCfg::TRIP
     return ring_rows_cap(g) / trip;
 }
 // strips a frame must at least be cut into
-static int ring_min_strips(const BMGeom& g, int nrows)
-{ return ring_rebase_trips(g) > 0 ? 1 : max(1, (nrows + ring_rows_cap(g) - 1) / ring_rows_cap(g)); }
+static int ring_min_strips(const BMGeom& g, int lpp, int nrows)
+{ return ring_rebase_trips(g, lpp) > 0 ? 1 : max(1, (nrows + ring_rows_cap(g) - 1) / ring_rows_cap(g)); }
 
 // Instantiations: (D, blockSize, lanes per pixel).  Two lanes per pixel: every (D, blockSize) whose ring (blockSize+1) * D/4
 // registers per lane leaves room for two waves per SIMD.  Four lanes per pixel: the D = 64 ones, whose two-lane ring holds
@@ -524,27 +522,32 @@ static int ring_lpp(const BMGeom& g)
     return (have & 16) ? 16 : (have & 8) ? 8 : (have & 4) ? 4 : (have & 2) ? 2 : 0;
 }
 
-int ring_lanes_per_pixel(const BMGeom& g) { return ring_lpp(g); }
-
-static int ring_tile(const BMGeom& g) { return 256 / ring_lpp(g); }
-
-// workgroups resident per CU (= waves per SIMD: a workgroup is four waves, one per SIMD) of the form (D, w) runs
-static int ring_wgs_per_cu(const BMGeom& g)
+// the instantiation (D, w, lpp).  waves = workgroups resident per CU (a workgroup is four waves, one per SIMD)
+static RingForm ring_form_of(const BMGeom& g, int lpp)
 {
-    const int lpp = ring_lpp(g);
-#define X(DD, WW, LL) if (g.D == DD && g.w == WW && lpp == LL) return RingCfg<DD, WW, LL>::WAVES;
+#define X(DD, WW, LL) if (g.D == DD && g.w == WW && lpp == LL) { using C = RingCfg<DD, WW, LL>; return RingForm{LL, C::WAVES, C::FUSE_BORDER2, C::FUSE_BORDER, C::TILE}; }
     RTDM_RING_TABLE(X)
 #undef X
-    return 2;
+    return RingForm{};
 }
 
-int ring_strips_model(const BMGeom& g, int n)
+RingForm ring_form(const BMGeom& g)
 {
-    int x0 = 0, nx = 0;
-    if (!search_interior_range(g, &x0, &nx) || !ring_lpp(g)) return 1;
-    const int tile = ring_tile(g), tiles = (nx + tile - 1) / tile, nrows = g.vy1 - g.vy0;
-    const int slots = 256 * ring_wgs_per_cu(g);             // workgroups in flight on the chip
-    const int smin = ring_min_strips(g, nrows), smax = max(smin, (nrows + 15) / 16);
+    const RingForm none{};
+    if (ring_mode() == 0) return none;
+    if (2L * g.cap * g.w * g.w > 32766) return none;       // packed u16 sums + the T+1 <= 32767 argument of the selection
+    if (2L * g.cap * g.w * g.w >= 0x7C00) return none;     // ... and positive finite f16 for the group minima (sel_pk_min3_h; cap <= 63
+                                                           //     keeps every ring form below: 2 * 63 * 15^2 = 28350)
+    if (ring_rows_cap(g) < 2) return none;
+    if ((size_t)g.H * (size_t)g.Ws * 2 >= ((size_t)1 << 32)) return none;   // 32-bit byte offsets inside a frame (pitch <= Ws)
+    return ring_form_of(g, ring_lpp(g));
+}
+
+int ring_strips_model(const SearchPlan& plan, const BMGeom& g, int n)
+{
+    const int tile = 256 / plan.lanes, tiles = (plan.nx + tile - 1) / tile, nrows = g.vy1 - g.vy0;
+    const int slots = 256 * ring_form_of(g, plan.lanes).waves;            // workgroups in flight on the chip
+    const int smin = ring_min_strips(g, plan.lanes, nrows), smax = max(smin, (nrows + 15) / 16);
     // a strip pays w-1 filling rows at about half the price of an output row
     const float fill = 0.5f * (float)(g.w - 1);
     int s = (int)(sqrtf((float)nrows * (float)slots / (fill * (float)tiles * (float)n)) + 0.5f);
@@ -565,20 +568,20 @@ int ring_strips_model(const BMGeom& g, int n)
 }
 
 template <int D, int WS, int LPP>
-static bool ring_launch_one(Plane8 Lp, Plane8 Rp, Plane16W disp, void* cost, const BMGeom& g, int n, hipStream_t stream, int strips_hint,
-                            bool fuse_border)
+static void ring_launch_one(const SearchPlan& plan, Plane8 Lp, Plane8 Rp, Plane16W disp, void* cost, const BMGeom& g, int n, hipStream_t stream,
+                            int strips_hint)
 {
     using C = RingCfg<D, WS, LPP>;
     RingGeom rg;
-    rg.rdelta = (uint32_t)(Rp.base - Lp.base);       // (launch_search_ring has checked that it fits)
-    search_interior_range(g, &rg.x0, &rg.nx);
+    rg.rdelta = (uint32_t)(Rp.base - Lp.base);       // (plan_search's planes_contiguous: it fits)
+    rg.x0 = plan.x0; rg.nx = plan.nx;
     const int rem = g.w - 4 * (C::NP - 1);
     rg.lastmask = rem >= 4 ? 0xffffffffu : ((1u << (8 * rem)) - 1u);
     const int nrows = g.vy1 - g.vy0;
     const int tiles = (rg.nx + C::TILE - 1) / C::TILE;
-    int strips = strips_hint > 0 ? strips_hint : ring_strips_model(g, n);
-    strips = max(strips, ring_min_strips(g, nrows));
-    rg.rebase = ring_rebase_trips(g);                 // (= ring_rows_cap / C::TRIP)
+    int strips = strips_hint > 0 ? strips_hint : ring_strips_model(plan, g, n);
+    strips = max(strips, ring_min_strips(g, LPP, nrows));
+    rg.rebase = ring_rebase_trips(g, LPP);            // (= ring_rows_cap / C::TRIP)
     strips = max(1, min(strips, nrows));
     rg.rs = (nrows + strips - 1) / strips;
     strips = (nrows + rg.rs - 1) / rg.rs;
@@ -590,16 +593,12 @@ static bool ring_launch_one(Plane8 Lp, Plane8 Rp, Plane16W disp, void* cost, con
     Border2Geom b2g{};
     size_t blds = 0;
     rg.nborder = 0; rg.bgx = rg.bgy = 0; rg.b2 = 0;
-    bool fused = false;                               // the border columns are dealt with by this launch
-    if (fuse_border) {
-        int lx0, lx1, rx0, rx1;
-        fast_border_ranges(g, &lx0, &lx1, &rx0, &rx1);
-        if (C::FUSE_BORDER2 && border2_plan(g, lx0, lx1, rx0, rx1, &b2g, &rg.bgx, &rg.bgy)) {
-            rg.b2 = 1; fused = true;
-            rg.nborder = (unsigned)(rg.bgx * rg.bgy) * (unsigned)n;
-        } else if constexpr (C::FUSE_BORDER) {
-            if (border_geometry(g, lx0, lx1, rx0, rx1, n, &bg, &rg.bgx, &rg.bgy, &blds)) { rg.nborder = (unsigned)(rg.bgx * rg.bgy) * (unsigned)n; fused = true; }
-        }
+    if (plan.place == BorderPlace::FUSED && plan.border.form != BorderForm::NONE) {   // (ROWS or DISP, as ring_form allowed)
+        const BorderPlan& b = plan.border;
+        if (b.form == BorderForm::ROWS) { b2g = b.rows; rg.b2 = 1; }
+        else { bg = b.disp; blds = b.lds; }
+        rg.bgx = b.gx; rg.bgy = b.gy;
+        rg.nborder = (unsigned)(rg.bgx * rg.bgy) * (unsigned)n;
     }
     const size_t ldsb = max((size_t)4 * C::WAVE_LDS * sizeof(uint32_t), blds);
     const auto launch = [&](auto Fc) {
@@ -622,37 +621,16 @@ static bool ring_launch_one(Plane8 Lp, Plane8 Rp, Plane16W disp, void* cost, con
         }
         hipLaunchKernelGGL((k_search_ring<D, WS, LPP, F>), dim3(grid + rg.nborder), dim3(256), ldsb, stream, Lp, Rp, disp, (uint16_t*)cost, g, rg, bg, b2g);
     };
-    if (rg.nborder) { launch(std::true_type{}); return true; }
-    launch(std::false_type{});
-    return fused;                                     // (true without border workgroups: there are no border columns)
+    if (rg.nborder) launch(std::true_type{});
+    else launch(std::false_type{});
 }
 
-bool ring_search_supported(const BMGeom& g)
+void launch_search_ring(const SearchPlan& plan, Plane8 Lp, Plane8 Rp, Plane16W disp, void* cost, const BMGeom& g, int n, hipStream_t stream,
+                        int strips)
 {
-    if (ring_mode() == 0) return false;
-    if (2L * g.cap * g.w * g.w > 32766) return false;       // packed u16 sums + the T+1 <= 32767 argument of the selection
-    if (2L * g.cap * g.w * g.w >= 0x7C00) return false;     // ... and positive finite f16 for the group minima (sel_pk_min3_h; cap <= 63
-                                                            //     keeps every ring form below: 2 * 63 * 15^2 = 28350)
-    if (ring_rows_cap(g) < 2) return false;
-    if (!search_interior_range(g, nullptr, nullptr)) return false;
-    if ((size_t)g.H * (size_t)g.Ws * 2 >= ((size_t)1 << 32)) return false;   // 32-bit byte offsets inside a frame (pitch <= Ws)
-    return ring_lpp(g) != 0;
-}
-
-bool launch_search_ring(Plane8 Lp, Plane8 Rp, Plane16W disp, void* cost, const BMGeom& g, int n, hipStream_t stream, int strips_hint,
-                        bool fuse_border)
-{
-    const int lpp = ring_lpp(g);
-    // the kernel addresses both planes from the left plane's rows with 32-bit lane offsets: they must be one allocation, the
-    // right plane behind the left one, with the same strides (api_bm.hip allocates them that way)
-    if (!(Rp.base > Lp.base && (size_t)(Rp.base - Lp.base) < ((size_t)1 << 32) - ((size_t)1 << 20) && Rp.pitch == Lp.pitch && Rp.frame == Lp.frame)) {
-        launch_search_fast(Lp, Rp, disp, cost, g, n, stream, fuse_border, 0);
-        return fuse_border;
-    }
-#define X(DD, WW, LL) if (g.D == DD && g.w == WW && lpp == LL) return ring_launch_one<DD, WW, LL>(Lp, Rp, disp, cost, g, n, stream, strips_hint, fuse_border);
+#define X(DD, WW, LL) if (g.D == DD && g.w == WW && plan.lanes == LL) { ring_launch_one<DD, WW, LL>(plan, Lp, Rp, disp, cost, g, n, stream, strips); return; }
     RTDM_RING_TABLE(X)
 #undef X
-    return false;
 }
 
 }  // namespace rtdm

@@ -1,6 +1,6 @@
-// rtdm_border.h -- device body of the border-column search (see k_search_border.hip for the design);
-// shared by the stand-alone kernel and by k_search_fast, which runs it in extra workgroups of its own grid
-// so that this latency-bound work overlaps the VALU-bound main search.
+// rtdm_border.h -- device body of the border-column search, form DISP (see k_search_border.hip for the design); shared by
+// the stand-alone kernel and by k_search_fast and k_search_ring, which run it in extra workgroups of their own grids so that
+// this latency-bound work overlaps the VALU-bound main search (which launch carries it: plan_search, k_search.hip).
 #pragma once
 
 #include "rtdm_kernels.h"
@@ -8,12 +8,6 @@
 namespace rtdm {
 
 static constexpr int RB = 8;   // rows staged per batch
-
-struct BorderGeom { int lx0, lx1, rx0, rx1, rs, rsp; };
-
-// host side (k_search_border.hip): geometry, grid and LDS bytes of the border work; false if there is none
-bool border_geometry(const BMGeom& g, int lx0, int lx1, int rx0, int rx1, int n, BorderGeom* out, int* gx, int* gy, size_t* lds_bytes);
-size_t border_lds_bytes(int D, int w);   // the dynamic LDS border_geometry reports, for any frame of (D, w)
 
 // Wave-wide unsigned minimum with DPP row operations (no LDS round trips); result is uniform.
 __device__ __forceinline__ unsigned wave_min_u32(unsigned v)

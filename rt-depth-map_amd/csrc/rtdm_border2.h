@@ -1,7 +1,7 @@
 // rtdm_border2.h -- the device side of k_search_border2.hip (border columns with the ROWS in the lanes; see that file's
-// header for the method), as a per-wave body: k_search_border2 runs it as a kernel of its own (batches: on a side stream),
-// k_search_ring<.., FUSE> as the first workgroups of its own grid (single frames and small batches: a second launch costs a
-// single 720p frame 8 us of its 84).
+// header for the method), form ROWS, as a per-wave body.  Two launches carry it: k_search_border2, a kernel of its own (batches
+// of 16 and more, on the side stream), and k_search_ring<.., FUSE> for D <= 192, as the first workgroups of its own grid (single frames and small batches: a second launch costs a single 720p
+// frame 8 us of its 84).  Which one: plan_search, k_search.hip.
 #pragma once
 #include "rtdm_select.h"
 
@@ -9,8 +9,6 @@
 #include <utility>
 
 namespace rtdm {
-
-struct Border2Geom { int lx0, lx1, rx0, rx1, ro; };   // output-column ranges (as BorderGeom), output rows per wave
 
 __device__ __forceinline__ uint32_t b2_scan_add(uint32_t t)   // inclusive prefix sum over the 64 lanes
 {

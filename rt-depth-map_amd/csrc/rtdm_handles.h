@@ -16,13 +16,6 @@
 
 struct StageEvent { hipEvent_t a, b; int stage; int frames; };
 
-// Shape of a batched search launch, compared field by field (tune_strips).
-struct TuneKey {
-    int W, H, n, ncols, nrows, fuse;
-    bool operator==(const TuneKey& o) const { return W == o.W && H == o.H && n == o.n && ncols == o.ncols && nrows == o.nrows && fuse == o.fuse; }
-};
-struct TuneEntry { TuneKey key; int strips; };   // strips: 0 = seen once, not measured yet; -1 = measuring failed
-
 struct rtdm_bm {
     rtdm_bm_params p;
     int prefilter_type, prefilter_size;   // rtdm_bm_set_prefilter: cv::StereoBM's preFilterType / preFilterSize (XSOBEL, 9)
@@ -39,8 +32,7 @@ struct rtdm_bm {
     uint8_t *dLp, *dRp;            // prefiltered planes   [maxB][maxH][ppitch]
     uint8_t *dInL, *dInR;          // staging for the host entry points
     int16_t* dOut;                 // internal disparity plane [maxB][maxH][Ws] (Ws = maxW rounded up to 8)
-    std::vector<TuneEntry> tuned;  // measured strip counts per work shape, least recently used first (<= 16 entries)
-    long tune_shapes, tune_launches;   // rtdm_bm_get_tuner_stats
+    rtdm::StripTuner tuner;        // measured strip counts of the batched search per work shape
     int32_t *dCost, *dLabel, *dSize, *dRowCnt;
     uint32_t* dRuns;
     int16_t* dHead;

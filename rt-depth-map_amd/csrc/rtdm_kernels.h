@@ -7,6 +7,7 @@
 #include <stdlib.h>
 
 #include <atomic>
+#include <vector>
 
 namespace rtdm {
 
@@ -81,49 +82,55 @@ void launch_fill16(Plane16W disp, int x0, int x1, int y0, int y1, int n, int val
 void launch_fill_frame(Plane16W disp, int W, int H, int cx0, int cx1, int vy0, int vy1, int n, int value, int32_t* rowcnt,
                        hipStream_t stream);
 
-// K2 (generic variants, k_search_generic.hip): every valid configuration (D a multiple of 16 up to 4080, any odd w); writes
-// disp (+ the cost plane, uint16 or int32 by g.cost16).  Runs the single-pass form where its LDS fits (D <= 256, not every w
-// at large D) and no slice width is forced, else the sliced form: the reversed disparity range walked in slices whose
-// results are folded in index order per pixel, the same outputs bit for bit.  [gx0, gx1) restricts the output-column range
-// (gx1 < 0: all of [0, width1)).  Returns the variant name: "generic_u16", "generic_u32", "generic_dslice_u16",
-// "generic_dslice_u32".
-const char* launch_search_generic(Plane8 Lp, Plane8 Rp, Plane16W disp, void* cost, const BMGeom& g,
-                                  int n, hipStream_t stream, int gx0 = 0, int gx1 = -1);
-bool generic_search_sliced(const BMGeom& g);   // the sliced form is needed or forced (no packed kernel runs then)
-void dslice_set_width(int dt);                 // rtdm_debug_disparity_slice
-
-// K2 (fast variant): packed-u8 quad-SAD kernel for the common configurations.  Works on the
-// prefiltered planes and covers the output columns whose window needs no border clamping; the
-// remaining border columns [lx0,lx1) and [rx0,rx1) go to the generic kernel.
-bool fast_search_supported(const BMGeom& g);
-// fuse_border: the border columns are searched by extra workgroups of the same launch.
-// strips_hint > 0: row strips per frame to use (a measured choice); 0: fast_strips_model(g, n).
-void launch_search_fast(Plane8 Lp, Plane8 Rp, Plane16W disp, void* cost, const BMGeom& g,
-                        int n, hipStream_t stream, bool fuse_border, int strips_hint = 0);
-int fast_strips_model(const BMGeom& g, int n);
-// K2 (ring variant, k_search_ring.hip): the same columns as the fast variant, prefix sums in a register ring instead of a
-// leaving-row recomputation; covers the (D, blockSize) pairs whose ring fits two waves per SIMD.  fuse_border: the border
-// columns may ride in front of the tile workgroups of the same launch; returns whether they did (otherwise they go to
-// launch_search_border).  ring_search_supported implies fast_search_supported's column range.
-bool ring_search_supported(const BMGeom& g);
-bool launch_search_ring(Plane8 Lp, Plane8 Rp, Plane16W disp, void* cost, const BMGeom& g, int n, hipStream_t stream,
-                        int strips_hint = 0, bool fuse_border = false);
-int ring_strips_model(const BMGeom& g, int n);
-void ring_set_mode(int mode);   // rtdm_debug_search_kernel
-int ring_lanes_per_pixel(const BMGeom& g);   // 2 / 4: the form of k_search_ring this configuration runs (0: none)
-// The output columns [*x0, *x0 + *nx) whose window needs no border clamping (either pointer may be null); false: none.
-bool search_interior_range(const BMGeom& g, int* x0, int* nx);
-void fast_border_ranges(const BMGeom& g, int* lx0, int* lx1, int* rx0, int* rx1);
-// wave-per-column kernel for those border columns (falls back to the generic kernel if unsupported)
-bool border_search_supported(const BMGeom& g);
-void launch_search_border(Plane8 Lp, Plane8 Rp, Plane16W disp, void* cost, const BMGeom& g, int n,
-                          hipStream_t stream, int lx0, int lx1, int rx0, int rx1);
-// second form (k_search_border2.hip): one wave = one border column x 64 rows, rows in the lanes, disparities unrolled; 4-5x
-// fewer instructions per pixel.  Returns false (nothing launched) for what it does not cover; launch_search_border tries it first.
-struct Border2Geom;
-bool border2_plan(const BMGeom& g, int lx0, int lx1, int rx0, int rx1, Border2Geom* bg, int* gx, int* gy);
-bool launch_search_border2(Plane8 Lp, Plane8 Rp, Plane16W disp, void* cost, const BMGeom& g, int n,
-                           hipStream_t stream, int lx0, int lx1, int rx0, int rx1);
+// K2: the SAD search (k_search.hip): writes disp (+ the cost plane, uint16 or int32 by g.cost16) for every valid configuration
+// (D a multiple of 16 up to 4080, any odd w).  plan_search decides, once per call and without touching the runtime, what
+// launch_search then issues: the kernel of the interior columns (whose windows need no border clamping), the form of the
+// border columns and where they run.  The route table is in DESIGN.md ("K2: routes").
+struct BorderGeom { int lx0, lx1, rx0, rx1, rs, rsp; };   // kernel arguments of the two border forms: output-column ranges,
+struct Border2Geom { int lx0, lx1, rx0, rx1, ro; };       // rows per workgroup / output rows per wave
+enum class SearchTiles { GENERIC, FAST, RING };           // k_search_generic / k_search_dslice, k_search_fast, k_search_ring
+enum class BorderForm { NONE, ROWS, DISP, GENERIC };      // no border columns, border2_body, border_body, launch_search_generic
+enum class BorderPlace { FUSED, SIDE, AFTER };            // in the tile kernel's grid, own launch on the side stream, own launch behind
+struct BorderPlan {
+    BorderForm form;
+    Border2Geom rows; BorderGeom disp;     // the geometry of form ROWS / DISP (DISP + g.legacy: the LEGACY instantiation)
+    int gx, gy;                            // its grid per frame
+    size_t lds;                            // its dynamic LDS
+};
+struct SearchPlan {
+    SearchTiles tiles; int lanes;          // RING: lanes per pixel (2 / 4 / 8 / 16), else 0
+    int x0, nx;                            // output columns [x0, x0 + nx) of the tile kernel (GENERIC: every searched column)
+    int lx0, lx1, rx0, rx1;                // the border columns [lx0, lx1) and [rx0, rx1)
+    BorderPlan border; BorderPlace place;
+    const char* variant;                   // "generic_u16", "generic_u32", "generic_dslice_u16", "generic_dslice_u32", "fast_qsad",
+};                                         // "fast_ring_qsad", "fast_ring4_qsad", "fast_ring8_qsad", "fast_ring16_qsad"
+// planes_contiguous: the right prefiltered planes lie behind the left ones in one allocation, less than 4 GB - 1 MB apart and
+// with the same strides (k_search_ring addresses both from the left plane's rows with 32-bit offsets).
+SearchPlan plan_search(const BMGeom& g, int n, bool planes_contiguous);
+struct SearchSide { hipStream_t stream; hipEvent_t fork, join; };   // where BorderPlace::SIDE runs, and how it leaves and rejoins
+// Row strips per frame for the packed search of a batch, chosen by measurement and remembered: the models are right on average,
+// but neighbouring strip counts differ by up to 5 % through scheduling effects they cannot see
+// (profiles/r01_xcd_mapping_sweep.txt).  The search only writes its own outputs, so timing it a few times on the caller's data
+// is harmless.  The key is the SHAPE of the work (frame size, batch, searched columns and rows as counts, not positions): a
+// caller that moves a same-sized ROI around (estimator.cpp:53-54) keeps its entry.  A shape is measured the SECOND time it is
+// seen -- a caller whose ROI changes size every call never pays the ~30 extra launches and the stream synchronisation -- and
+// the table is a 16-entry LRU.  Small batches keep the model.  RTDM_AUTOTUNE=0: off.
+struct StripTuner {
+    struct Key {
+        int W, H, n, ncols, nrows, fuse;
+        bool operator==(const Key& o) const { return W == o.W && H == o.H && n == o.n && ncols == o.ncols && nrows == o.nrows && fuse == o.fuse; }
+    };
+    struct Entry { Key key; int strips; };   // strips: 0 = seen once, not measured yet; -1 = measuring failed
+    std::vector<Entry> tuned;                // least recently used first
+    long shapes = 0, launches = 0;           // rtdm_bm_get_tuner_stats
+    // the strip count to launch the plan's tile kernel with (0: its model's), after timing it on stream s where that is due
+    int tune_strips(const SearchPlan& plan, Plane8 Lp, Plane8 Rp, Plane16W disp, void* cost, const BMGeom& g, int n, hipStream_t s);
+};
+// Issues the plan on `stream` (BorderPlace::SIDE: the border launch on side.stream between side.fork and side.join).
+hipError_t launch_search(const SearchPlan& plan, Plane8 Lp, Plane8 Rp, Plane16W disp, void* cost, const BMGeom& g, int n,
+                         hipStream_t stream, const SearchSide& side, StripTuner* tuner);
+void ring_set_mode(int mode);      // rtdm_debug_search_kernel
+void dslice_set_width(int dt);     // rtdm_debug_disparity_slice
 
 // K3: row-local left-right consistency check (+ column masking to the valid rectangle).  With
 // label != nullptr the speckle filter's per-row init runs on the checked row in the same pass.

@@ -307,7 +307,7 @@ struct GroupSelectRec {
         for (int i = 0; i < NRL; i += 4) st4(wr + i, u4{sv[i], sv[i + 1], sv[i + 2], sv[i + 3]});
 #pragma unroll
         for (int gq = 0; gq < NGH; ++gq) {
-            // two packed minima per group of eight instead of three (window sums < 0x7C00: k_search_ring's ring_search_supported)
+            // two packed minima per group of eight instead of three (window sums < 0x7C00: k_search_ring's ring_form)
             const uint32_t m = sel_pk_min(sel_pk_min3_h(sv[4 * gq], sv[4 * gq + 1], sv[4 * gq + 2]), sv[4 * gq + 3]);
             wm[gq] = (unsigned short)min(m & 0xffffu, m >> 16);
         }

@@ -63,7 +63,7 @@ def test_group_select_rec_equals_the_plain_rule(D):
 
 
 def test_bounds_of_the_switches():
-    # every ring form: cap <= 63 (rtdm_bm_create) and 2 cap w^2 <= 32766 (ring_search_supported) => w <= 15
+    # every ring form: cap <= 63 (rtdm_bm_create) and 2 cap w^2 <= 32766 (ring_form) => w <= 15
     assert max(2 * 63 * w * w for w in range(1, 17, 2) if 2 * 63 * w * w <= 32766) < 0x7C00
     # positive finite f16 (u16 < 0x7C00, denormals included) sort as their bit patterns do
     h = np.arange(0x7C00, dtype=np.uint16).view(np.float16)
