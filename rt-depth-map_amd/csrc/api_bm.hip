@@ -49,8 +49,10 @@ int rtdm_bm_create(const rtdm_bm_params* params, int max_width, int max_height, 
     m.err = hipStreamCreateWithFlags(&bm->stream, hipStreamNonBlocking);
     // + slack: the search kernels stage whole dwords of whole tiles and may read past the last row's end
     // (one allocation, the right planes behind the left ones: k_search_ring addresses both from the left plane's rows)
-    const size_t plane_al = (plane + 1024 + 255) & ~(size_t)255;
-    if (m.dev(&bm->dLp, 2 * plane_al)) bm->dRp = bm->dLp + plane_al;
+    // ... and, in front, up to three bytes before the first row's start: the paired form of k_search_ring starts a wave's copy
+    // three bytes left of its first window (256 bytes of slack keep the planes' alignment; the list frees what it allocated)
+    const size_t plane_al = (plane + 1024 + 255) & ~(size_t)255, front = 256;
+    if (m.dev(&bm->dLp, front + 2 * plane_al)) { bm->dLp += front; bm->dRp = bm->dLp + plane_al; }
     m.dev(&bm->dInL, plane); m.dev(&bm->dInR, plane); m.dev(&bm->dOut, px * sizeof(int16_t));
     m.dev(&bm->dCost, px * sizeof(int32_t)); m.dev(&bm->dLabel, px * sizeof(int32_t)); m.dev(&bm->dSize, px * sizeof(int32_t));
     m.dev(&bm->dRuns, px * sizeof(uint32_t)); m.dev(&bm->dHead, px * sizeof(int16_t));

@@ -15,7 +15,10 @@
 // of a wave -- p + h * 64/LPP, h = 0..LPP-1, each with a slice of D/LPP disparities -- and rows are processed in GROUPS of LPP:
 // the lane with h = k owns row k of the group and produces its output pixel.
 //   LPP = 2 (D <= 48; D = 64 as an A/B form): ring 160 registers at D = 64, w = 9 => two waves per SIMD
-//   LPP = 4 (D = 64, 96): ring 80 registers at (64, 9), 148 VGPRs => three waves (four for w <= 7; two for D = 96)
+//   LPP = 4 (D = 64, 96): ring 80 registers at (64, 9) => three waves (four for w <= 7; two for D = 96)
+//            (64, 9) -- the headline -- in the PAIRED layout: a lane holds two adjacent columns and an eighth of their
+//            disparities each, the same 80 ring registers, and pays four window pieces per row for the pair instead of six
+//            (RingCfg::PAIR, ring_step_pair)
 //   LPP = 8 (D = 128): ring 96 registers at w = 11; two waves (the selection records, 17 KB per wave, allow no more)
 // Selection wants all D values of a pixel in one place.  Two forms (rtdm_select.h):
 //   * transposing (LPP = 2, D <= 32): one v_permlane32_swap per register hands the lower lane both halves of row t and the
@@ -25,9 +28,10 @@
 //     nothing crosses between the lanes, and the owner selects from its record alone.
 //
 // Mapping: workgroup = 4 * 64/LPP output columns x `rs` rows of one frame; wave = byte phase phi, lane (p, h) = column
-// x_tile + phi + 4 p.  The four waves never synchronise: each stages ITS byte-shifted copy of the entering rows (64 or 128
-// dwords, padded) into its own LDS slice, two rows ahead of their use, and the LDS queue of a wave is in order.  The
-// texture sum is a prefix ring too (one dword per pixel and slot, in LDS).  Only columns whose window needs no border
+// x_tile + phi + 4 p (PAIR: wave = half of the tile and one of two 2-byte phases, lane (p, h) = the columns x0, x0 + 1 with
+// x0 = x_tile + 32 (phi >> 1) + 2 (phi & 1) + 4 p).  The four waves never synchronise: each stages ITS byte-shifted copy
+// of the entering rows (64 or 128 dwords, padded) into its own LDS slice, two rows ahead of their use, and the LDS queue of
+// a wave is in order.  The texture sum is a prefix ring too (one dword per pixel and slot, in LDS).  Only columns whose window needs no border
 // clamping are handled here; the border columns ride in front of the tiles or go to a launch of their own (k_search.hip).
 // Semantics: SURVEY.md Appendix A.3b; oracle: oracle/bm_oracle.c.
 //
@@ -83,12 +87,19 @@ struct RingCfg {
     static constexpr int NP = (WS + 3) / 4;        // 4-byte pieces of a window row
     static constexpr int W1 = WS + 1;              // ring slots
     static constexpr int PPW = 64 / LPP;           // pixels (columns) per wave
-    static constexpr int DL = D / LPP;             // disparities per lane
-    static constexpr int NGL = DL / 4;             // quad-SAD groups per lane
-    static constexpr int NRL = DL / 2;             // packed u16x2 registers per lane and slot
-    static constexpr int NW = NGL + NP - 1;        // distinct 8-byte right windows per lane and row
-    static constexpr int LWD = PPW + NP;           // dwords of the wave's copy of the left row
-    static constexpr int RWD = PPW + D / 4 + NP;   //                                 right row
+    // PAIR: a lane holds TWO adjacent columns x0, x0 + 1 and, for both, half as many disparities.  With w = 4 (NP - 1) + 1 the
+    // two windows share their NP - 1 middle dwords: the pair costs NP + 1 window pieces instead of 2 NP -- two shared ones, and
+    // per column one masked piece with a single live byte (the header of ring_step_pair has the layout).  The headline form.
+    static constexpr bool PAIR = D == 64 && WS == 9 && LPP == 4;
+    static constexpr int LPG = PAIR ? 2 * LPP : LPP;   // lanes per group: they split the D disparities of a column (of a pair's two)
+    static constexpr int GPW = 64 / LPG;           // lane groups per wave (= PPW columns, or PPW / 2 pairs)
+    static constexpr int DL = D / LPG;             // disparities per lane (and column)
+    static constexpr int NGL = DL / 4;             // quad-SAD groups per lane (and column)
+    static constexpr int NRL = DL / 2;             // packed u16x2 registers per lane, slot (and column)
+    static constexpr int NL = PAIR ? NP + 1 : NP;  // left dwords a lane reads of a row
+    static constexpr int NW = NGL + NL - 1;        // distinct 8-byte right windows per lane and row
+    static constexpr int LWD = GPW + NP;           // dwords of the wave's copy of the left row
+    static constexpr int RWD = GPW + D / 4 + NP;   //                                 right row
     static constexpr int ITEMS = (LWD + RWD + 63) / 64;
     static constexpr int SLOT = ITEMS * 64;        // padded: every lane stores every item, no exec masking
     // rows per trip of the unrolled row loop: whole rounds of the ring AND whole groups
@@ -101,19 +112,32 @@ struct RingCfg {
     static constexpr int NSLOT = STATIC_SLOTS ? 4 : 3;
     // dwords per wave: staged rows + the texture prefix ring [W1][PPW] + the window texture sums of a group's rows [RPG][PPW] (u16)
     static constexpr int STG = (NSLOT * SLOT + (W1 + RPG) * PPW / 2 + 3) & ~3;
-    static constexpr int WAVE_LDS = STG + PPW * RPG * Rec::DWORDS;   // + the selection's records, one per owner lane (rtdm_select.h)
+    // PAIR: the records of a pair's LPG owners lie one behind the other at the bare record size (D/2 + D/16 = 36 dwords: 4 banks
+    // on per owner) and pair p starts 2 (p & 1) + 8 (p >> 1) dwords behind that.  An 8-byte LDS access serves 16 lanes per cycle
+    // from 32 banks; the 16 lanes here are the 8 pairs x 2 lanes whose slices lie 4 dwords apart in the target record, so the
+    // pairs' records have to start at the banks {0, 2, 8, 10, 16, 18, 24, 26} + 4 x owner -- which the owners' own reads of
+    // 16 neighbouring records cover without a conflict as well.  No record stride does that (with GPW records of stride 38
+    // next to each other the bank-conflict cycles of the kernel rose sevenfold and ate the whole gain of the layout).
+    static constexpr int PREC = D / 2 + D / 16;
+    static constexpr int PREC_PAIR = LPG * PREC;   // from pair to pair
+    __host__ __device__ static constexpr int pair_rec(int p, int o) { return p * PREC_PAIR + o * PREC + 2 * (p & 1) + 8 * (p >> 1); }
+    static constexpr int REC_DWORDS = PAIR ? pair_rec(GPW - 1, LPG - 1) + PREC + 2 : PPW * RPG * Rec::DWORDS;
+    static constexpr int WAVE_LDS = STG + REC_DWORDS;   // + the selection's records, one per owner lane (rtdm_select.h)
     // waves per SIMD the register budget is set for: the ring takes W1 * NRL registers, the rest of the kernel about 50
-    static constexpr int RING_REGS = W1 * NRL;
+    static constexpr int RING_REGS = W1 * NRL * (PAIR ? 2 : 1);
     // two-lane forms: most ring registers a three-wave form may hold.  (32, 13) sits AT 112 and spills ten dwords at 168 VGPRs
     // -- and is still 9 % faster than as a two-wave form without (111): profiles/r03_ring_spills.txt
     static constexpr int W3_LIMIT = 112;
     // (tighter bounds spill; eight lanes per pixel = D = 128: the selection records, 17 KB per wave, allow two workgroups per CU)
-    static constexpr int WAVES = LPP >= 8 ? 2 : LPP == 4 ? (RING_REGS <= 80 ? 4 : (RING_REGS <= 96 && NRL <= 8) ? 3 : 2) : (RING_REGS <= 72 && NRL <= 8) ? 4 : RING_REGS <= W3_LIMIT ? 3 : 2;
+    // (PAIR: three.  The 128 registers of four waves have no room for the shared sums and the fourth left piece, the records
+    //  let three workgroups share a CU anyway, and four measured no faster when they fitted.  ring_strips_model sizes its
+    //  strips by this value: it now counts the 768 workgroups the chip really holds, not 1024)
+    static constexpr int WAVES = PAIR ? 3 : LPP >= 8 ? 2 : LPP == 4 ? (RING_REGS <= 80 ? 4 : (RING_REGS <= 96 && NRL <= 8) ? 3 : 2) : (RING_REGS <= 72 && NRL <= 8) ? 4 : RING_REGS <= W3_LIMIT ? 3 : 2;
     static constexpr int TILE = 4 * PPW;           // four byte phases
     // border-column workgroups may ride in this kernel's grid (small launches): border2_body in every form (it needs no LDS
     // and 52-120 VGPRs for D <= 64); border_body (configurations border2 does not cover) not in the four-wave forms, whose
-    // 128 registers its code would overflow
-    static constexpr bool FUSE_BORDER = WAVES < 4;
+    // 128 registers its code would overflow (nor in the paired form that took the place of one)
+    static constexpr bool FUSE_BORDER = WAVES < 4 && !PAIR;
     static constexpr bool FUSE_BORDER2 = D <= 192;  // (border2_body<256, 4> needs 261 VGPRs: it stays a launch of its own)
     // LDS read addresses of a row: three registers that advance (3 VALU per row) or recomputed from the slot index (6 VALU,
     // no registers held) -- the latter for the two-lane configurations that sit at their three-wave register limit
@@ -124,14 +148,21 @@ struct RingCfg {
 // where the occupancy bound buys nothing) is compiled for one wave per SIMD less: border2_body on top of a form that sits at
 // its register limit spilled two dwords ((64, 9, 4) at 128 VGPRs, (192, 15, 8) at 256).
 template <int D, int WS, int LPP, bool BORDER>
-struct RingBounds { static constexpr int WAVES = BORDER && RingCfg<D, WS, LPP>::WAVES > 1 ? RingCfg<D, WS, LPP>::WAVES - 1 : RingCfg<D, WS, LPP>::WAVES; };
+struct RingBounds {
+    using C = RingCfg<D, WS, LPP>;
+    // (the paired form sits well below its three-wave limit: it keeps its bound)
+    static constexpr int WAVES = BORDER && C::WAVES > 1 && !C::PAIR ? C::WAVES - 1 : C::WAVES;
+};
 
 template <int D, int WS, int LPP = 2>
-struct RingState { uint64_t P[RingCfg<D, WS, LPP>::W1][RingCfg<D, WS, LPP>::NGL]; };   // only ever indexed with constants: registers
+struct RingState {                                                                       // only ever indexed with constants: registers
+    uint64_t P[RingCfg<D, WS, LPP>::W1][RingCfg<D, WS, LPP>::NGL];
+    uint64_t P2[RingCfg<D, WS, LPP>::PAIR ? RingCfg<D, WS, LPP>::W1 : 1][RingCfg<D, WS, LPP>::NGL];   // PAIR: the ring of column x0 + 1
+};
 
 // The registers a lane needs of one staged row: its NW right windows (8 bytes each) and its NP left pieces.
 template <int D, int WS, int LPP = 2>
-struct RowRegs { uint64_t win[RingCfg<D, WS, LPP>::NW]; uint32_t l[RingCfg<D, WS, LPP>::NP]; };
+struct RowRegs { uint64_t win[RingCfg<D, WS, LPP>::NW]; uint32_t l[RingCfg<D, WS, LPP>::NL]; };
 
 typedef __attribute__((address_space(3))) const uint32_t* lds_cptr;    // an LDS address held as what it is: 32 bits
 __device__ __forceinline__ uint32_t lds_addr(const uint32_t* q) { return (uint32_t)(uintptr_t)(lds_cptr)q; }
@@ -146,7 +177,7 @@ __device__ __forceinline__ void ring_load_row(PTR lp, PTR rp, PTR rpo, RowRegs<D
     // (laundered by the caller), so that they get their own ds_read2_b32 instead of v_mov rebuilds.
     // Issue order = order of first use (the LDS returns data in order): the left pieces, then the windows by index.
 #pragma unroll
-    for (int k = 0; k < C::NP; ++k) rw.l[k] = lp[k];
+    for (int k = 0; k < C::NL; ++k) rw.l[k] = lp[k];
 #pragma unroll
     for (int j = 0; j < C::NW; ++j) {
         const PTR wp = (j & 1) ? rpo + (j - 1) : rp + j;
@@ -193,6 +224,65 @@ __device__ __forceinline__ void ring_step(RingState<D, WS, LPP>& st, const RowRe
     }
 }
 
+// two packed u16 pairs each; plain 32-bit additions (v_add_u32 issues at 1.6x the rate of v_pk_add_u16): the caller knows that
+// no 16-bit half overflows
+__device__ __forceinline__ uint64_t ring_add_halves(uint64_t a, uint64_t b)
+{
+    // (as a two-dword vector: written with shifts and an OR the upper half becomes a 64-bit addition with a zeroed low dword)
+    typedef uint32_t u2 __attribute__((ext_vector_type(2)));
+    return __builtin_bit_cast(uint64_t, __builtin_bit_cast(u2, a) + __builtin_bit_cast(u2, b));
+}
+
+// The row step of the PAIRED layout (RingCfg::PAIR, w = 4 (NP - 1) + 1): the lane holds the columns x0 and x0 + 1.  Its left
+// dwords are l[0] = image bytes [x0-r-3, x0-r], l[1] .. l[NP-1] the 4 (NP - 1) bytes behind, l[NP] = [x0+r+1, x0+r+4]:
+//   window of x0     = byte 3 of l[0] | l[1] .. l[NP-1]
+//   window of x0 + 1 =                  l[1] .. l[NP-1] | byte 0 of l[NP]
+// and piece k of quad-group gi meets the right window win[gi + k] for both columns (one staged copy, one alignment).  Per
+// quad-group: the shared pieces are summed once (sh, from 0), each column adds its one-byte piece (v_mqsad skips the zeroed
+// reference bytes) on top of its own prefix sum, and sh joins both with plain additions -- NP + 1 quad-SADs for the pair
+// instead of 2 NP.  No carry between the packed halves: e + sh IS the column's new prefix sum, which stays below 2^16
+// (ring_rows_cap, rebase).  tpk = the texture terms of the row (the caller adds them to its packed prefix sums): x0 in the
+// low half, x0 + 1 in the high half.
+template <int D, int WS, int LPP, int K, int NRLc>
+__device__ __forceinline__ void ring_step_pair(RingState<D, WS, LPP>& st, const RowRegs<D, WS, LPP>& rw, uint32_t capb,
+                                               uint32_t& tpk, uint32_t (&S)[NRLc], uint32_t (&S2)[NRLc])
+{
+    using C = RingCfg<D, WS, LPP>;
+    static_assert(C::PAIR && WS % 4 == 1, "the two windows share whole dwords only for w = 1 (mod 4)");
+    constexpr int NP = C::NP, NGL = C::NGL, W1 = C::W1;
+    constexpr int KP = (K + W1 - 1) % W1, KO = (K + 1) % W1;
+    const uint32_t lf = rw.l[0] & 0xff000000u, ll = rw.l[NP] & 0x000000ffu;
+    uint32_t tsh = 0;
+#pragma unroll
+    for (int k = 1; k < NP; ++k) tsh = __builtin_amdgcn_sad_u8(rw.l[k], capb, tsh);
+    const uint32_t t1 = __builtin_amdgcn_msad_u8(capb, lf, tsh), t2 = __builtin_amdgcn_msad_u8(capb, ll, tsh);   // (zero reference bytes are skipped)
+    tpk = t1 | (t2 << 16);
+    uint64_t sh[NGL], e1[NGL], e2[NGL];
+    // issue order = window index (the LDS returns the windows in order)
+#pragma unroll
+    for (int j = 0; j < C::NW; ++j) {
+#pragma unroll
+        for (int k = 0; k <= NP; ++k) {
+            const int gi = j - k;
+            if (gi >= 0 && gi < NGL) {
+                if (k == 0)       e1[gi] = __builtin_amdgcn_mqsad_pk_u16_u8(rw.win[j], lf, st.P[KP][gi]);
+                else if (k == NP) e2[gi] = __builtin_amdgcn_mqsad_pk_u16_u8(rw.win[j], ll, st.P2[KP][gi]);
+                else              sh[gi] = __builtin_amdgcn_qsad_pk_u16_u8(rw.win[j], rw.l[k], k == 1 ? (uint64_t)0 : sh[gi]);
+            }
+        }
+    }
+#pragma unroll
+    for (int gi = 0; gi < NGL; ++gi) {
+        st.P[K][gi] = ring_add_halves(e1[gi], sh[gi]);
+        st.P2[K][gi] = ring_add_halves(e2[gi], sh[gi]);
+        // (no borrow between the halves: as in ring_step)
+        S[2 * gi] = (uint32_t)st.P[K][gi] - (uint32_t)st.P[KO][gi];
+        S[2 * gi + 1] = (uint32_t)(st.P[K][gi] >> 32) - (uint32_t)(st.P[KO][gi] >> 32);
+        S2[2 * gi] = (uint32_t)st.P2[K][gi] - (uint32_t)st.P2[KO][gi];
+        S2[2 * gi + 1] = (uint32_t)(st.P2[K][gi] >> 32) - (uint32_t)(st.P2[KO][gi] >> 32);
+    }
+}
+
 // Orders everything that produces v[] before whatever follows (no instruction is emitted).
 template <int N>
 __device__ __forceinline__ void pin(uint32_t (&v)[N])
@@ -217,7 +307,9 @@ __global__ __launch_bounds__(256, (RingBounds<D, WS, LPP, FUSE>::WAVES)) void k_
 {
     using C = RingCfg<D, WS, LPP>;
     constexpr int NGL = C::NGL, NRL = C::NRL, W1 = C::W1, LWD = C::LWD, SLOT = C::SLOT, ITEMS = C::ITEMS, PPW = C::PPW, RPG = C::RPG;
-    constexpr bool SPLIT = C::SPLIT;
+    constexpr int GPW = C::GPW;
+    constexpr bool SPLIT = C::SPLIT, PAIR = C::PAIR;
+    static_assert(!PAIR || (SPLIT && C::STATIC_SLOTS && C::LPG == 2 * RPG), "the paired layout: one owner lane per (column, row) of a group");
     constexpr int RECD = C::Rec::DWORDS;
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
 
@@ -245,17 +337,25 @@ __global__ __launch_bounds__(256, (RingBounds<D, WS, LPP, FUSE>::WAVES)) void k_
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int phi = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int p = lane & (PPW - 1), h = lane / PPW;
+    const int p = lane & (GPW - 1), h = lane / GPW;
     const int x_tile = rg.x0 + b_tile * C::TILE;
-    const int x = x_tile + phi + 4 * p;
+    // PAIR: wave phi = (half, psi) takes the pairs x0 = x_tile + 32 half + 2 psi + 4 p; the lane with h = 2 k + j owns column
+    // x0 + j in row k of every group -- `x`, `active`, the output offsets and the column mask below are those of the OWNED column
+    const int xw = PAIR ? x_tile + (phi >> 1) * (C::TILE / 2) + 2 * (phi & 1) : x_tile + phi;   // the wave's first column
+    const int hrow = PAIR ? h >> 1 : h;            // the row of a group this lane owns
+    const int x = xw + 4 * p + (PAIR ? h & 1 : 0);
     const bool active = x < rg.x0 + rg.nx;
     const int ys0 = g.vy0 + b_strip * rg.rs;
     const int ys1 = min(ys0 + rg.rs, g.vy1);
     if (ys0 >= ys1) return;
     const int r = g.r;
     const uint8_t* Lb = Lp.base + (size_t)f * Lp.frame;
-    const int Lbase = g.lofs + x_tile - r + phi;   // image column of byte 0 of this wave's copy (left)
-    const int Rbase = g.rofs + x_tile - r + phi;   //                                            (right)
+    // (PAIR: the copy starts PAIR_SHIFT = 3 bytes further left than that, so that a pair's shared window bytes are whole dwords
+    //  of it: ring_step_pair.  The shift is part of the row POINTER below, not of these offsets: they are zero-extended 32-bit
+    //  lane offsets and must not go negative -- with lofs = 0 (minDisparity <= 1 - D: createRightMatcher) the first tile's would)
+    constexpr int PAIR_SHIFT = PAIR ? 3 : 0;
+    const int Lbase = g.lofs + xw - r;             // image column of byte 0 (PAIR: byte 3) of this wave's copy (left)
+    const int Rbase = g.rofs + xw - r;             //                                                            (right)
     const uint32_t capb = (uint32_t)(g.cap + PREFILTER_BIAS) * 0x01010101u;
 
     uint32_t* stg = lds + phi * C::WAVE_LDS;       // this wave's slice: nothing below is shared between waves
@@ -265,12 +365,19 @@ __global__ __launch_bounds__(256, (RingBounds<D, WS, LPP, FUSE>::WAVES)) void k_
     // the window texture sum of row R of a group goes to ptw[R][p] (every lane of the pixel writes the same 16 bits) and the
     // row's owner reads its own at the end of the group: no per-row select in registers
     unsigned short* ptw = ptr + W1 * PPW;
-    const bool owner = RPG == LPP || h < RPG;       // this lane owns row h of every group
-    const unsigned short* ptw_own = ptw + (owner ? h : 0) * PPW + p;
-    uint32_t* scr = stg + C::STG + (owner ? lane : 0) * RECD;        // this lane's selection record (lanes that own nothing: never used)
-    uint32_t* scr_w = stg + C::STG + p * RECD + h * NRL;             // SPLIT: where this lane's slice of the group's first row goes
-    using GSel = GroupSelectRec<D, LPP, C::B64>;
-    unsigned short* scr_m = (unsigned short*)(stg + C::STG + p * RECD + D / 2) + h * (NRL / 4);   // ... and the minima of its groups
+    // (PAIR: a pair's two 16-bit entries are one dword, x0 in the low half -- written and read as such by the row step)
+    uint32_t* const ptr2 = (uint32_t*)ptr;
+    uint32_t* const ptw2 = (uint32_t*)ptw;
+    const bool owner = PAIR || RPG == LPP || h < RPG;   // this lane owns row h of every group
+    const unsigned short* ptw_own = ptw + (owner ? hrow : 0) * PPW + (PAIR ? 2 * p + (h & 1) : p);
+    // this lane's selection record (lanes that own nothing: never used); rec0: the record of the lane group's first owner
+    uint32_t* scr = stg + C::STG + (PAIR ? C::pair_rec(p, h) : (owner ? lane : 0) * RECD);
+    uint32_t* const rec0 = stg + C::STG + (PAIR ? C::pair_rec(p, 0) : p * RECD);
+    // SPLIT: where this lane's slice of the group's first row goes (PAIR: of column x0; the record of the owner with h = 2 k + j,
+    // for column x0 + j in row k, lies 2 k + j records further)
+    uint32_t* scr_w = rec0 + h * NRL;
+    using GSel = GroupSelectRec<D, C::LPG, C::B64>;
+    unsigned short* scr_m = (unsigned short*)(rec0 + D / 2) + h * (NRL / 4);   // ... and the minima of its groups
     if constexpr (SPLIT) GSel::init(scr);
 
     // --- staging: item idx = one dword of the wave's copy; dword m holds copy bytes [4m, 4m+4) (biased planes) ---------
@@ -282,13 +389,16 @@ __global__ __launch_bounds__(256, (RingBounds<D, WS, LPP, FUSE>::WAVES)) void k_
     // unit) + a 32-bit lane offset -- the right plane lies rg.rdelta bytes behind the left one (one allocation, api_bm.hip).
     // The byte phase makes the address unaligned; the memory pipeline takes unaligned dwords, and what arrives is what gets
     // staged: no second dword, no v_alignbyte, no 64-bit pointer arithmetic per lane.
-    const uint8_t* rowp = Lb + (size_t)row0 * Lp.pitch;
+    // (PAIR: row 0 of the first frame starts three bytes in front of the planes: api_bm.hip allocates slack there)
+    const uint8_t* rowp = Lb + (size_t)row0 * Lp.pitch - PAIR_SHIFT;
     uint32_t loff[ITEMS];
 #pragma unroll
     for (int it = 0; it < ITEMS; ++it) {
         const int idx = lane + it * 64;
         const bool isr = idx >= LWD;
-        const int m = isr ? idx - LWD : idx;
+        // (PAIR: the lanes behind the copy's last dword repeat it -- the copy starts further right in the tile than a
+        //  byte-phase copy does, and nothing may be read further behind a row's end than before)
+        const int m = isr ? (PAIR ? min(idx - LWD, C::RWD - 1) : idx - LWD) : idx;
         loff[it] = (uint32_t)((isr ? Rbase : Lbase) + 4 * m) + (isr ? rg.rdelta : 0u);
     }
     int next_row = row0;
@@ -318,10 +428,16 @@ __global__ __launch_bounds__(256, (RingBounds<D, WS, LPP, FUSE>::WAVES)) void k_
 #pragma unroll
     for (int k = 0; k < W1; ++k)
 #pragma unroll
-        for (int i = 0; i < NGL; ++i) st.P[k][i] = 0;
+        for (int i = 0; i < NGL; ++i) {
+            st.P[k][i] = 0;
+            if constexpr (PAIR) st.P2[k][i] = 0;
+        }
 #pragma unroll
-    for (int k = 0; k < W1; ++k) ptr[k * PPW + p] = 0;
-    uint32_t pt = 0;                                // texture prefix sum of the rows so far
+    for (int k = 0; k < W1; ++k) {
+        if constexpr (PAIR) ptr2[k * GPW + p] = 0;
+        else ptr[k * PPW + p] = 0;
+    }
+    uint32_t pt = 0;                                // texture prefix sum of the rows so far (PAIR: both columns', packed)
 
     const int nsteps = (ys1 - ys0) + WS - 1;
     const int nstepsg = (nsteps + RPG - 1) / RPG * RPG;   // rows go in groups of RPG; padded last rows are computed and dropped
@@ -335,8 +451,8 @@ __global__ __launch_bounds__(256, (RingBounds<D, WS, LPP, FUSE>::WAVES)) void k_
     char* const cb = (char*)(cost + (size_t)f * g.H * g.Ws);
     const int col = g.lofs + x;
     constexpr int TF = (WS - 1) / RPG * RPG;        // first group with an output row; its row h is strip row TF + h - (WS - 1)
-    uint32_t dofs = (uint32_t)(((long long)(ys0 + TF + h - (WS - 1)) * (long long)disp.pitch_e + col) * 2);   // (mod 2^32; a row
-    uint32_t cofs = (uint32_t)(((long long)(ys0 + TF + h - (WS - 1)) * (long long)g.Ws + col) * 2);           //  above the strip is never stored)
+    uint32_t dofs = (uint32_t)(((long long)(ys0 + TF + hrow - (WS - 1)) * (long long)disp.pitch_e + col) * 2);   // (mod 2^32; a row
+    uint32_t cofs = (uint32_t)(((long long)(ys0 + TF + hrow - (WS - 1)) * (long long)g.Ws + col) * 2);           //  above the strip is never stored)
     const uint32_t dstep = (uint32_t)(disp.pitch_e * 2 * RPG), cstep = (uint32_t)(g.Ws * 2 * RPG);
     const bool masked_col = g.mask_cols && (col < g.vx0 || col >= g.vx1);
 
@@ -370,18 +486,28 @@ __global__ __launch_bounds__(256, (RingBounds<D, WS, LPP, FUSE>::WAVES)) void k_
             ring_load_row<D, WS, LPP, const uint32_t*>(stg + li, stg + ri, stg + ri + one, rw);
         }
     };
-    auto step = [&](auto Kc, auto SLc, auto Rc, const RowRegs<D, WS, LPP>& rw, uint32_t (&Sr)[NRL]) {
+    // Sr / Sr2: the window sums of the row (PAIR: of column x0 / x0 + 1; Sr2 is not written otherwise)
+    auto step = [&](auto Kc, auto SLc, auto Rc, const RowRegs<D, WS, LPP>& rw, uint32_t (&Sr)[NRL], uint32_t (&Sr2)[NRL]) {
         constexpr int K = decltype(Kc)::value;            // ring slot of row t: a compile-time register set
         using SetIn = std::integral_constant<int, (K + 1) & 1>;    // row t+3 goes where row t+1 was (W1 is even: K and t have the same parity)
         using SetOut = std::integral_constant<int, K & 1>;         // row t+2
         issue(SetIn{});
         uint32_t tnew = 0;
-        ring_step<D, WS, LPP, K>(st, rw, rg.lastmask, capb, tnew, Sr);
         constexpr int KO = (K + 1) % W1;
-        pt += tnew;
-        const uint32_t told = ptr[KO * PPW + p];                  // prefix sum w rows back (0 while the window fills)
-        ptr[K * PPW + p] = (unsigned short)pt;
-        ptw[decltype(Rc)::value * PPW + p] = (unsigned short)(pt - told);   // (mod 2^16: the window sum itself is < 2^16)
+        if constexpr (PAIR) {
+            ring_step_pair<D, WS, LPP, K>(st, rw, capb, tnew, Sr, Sr2);
+            pt = __builtin_bit_cast(uint32_t, __builtin_bit_cast(sel_us2, pt) + __builtin_bit_cast(sel_us2, tnew));
+            const uint32_t told = ptr2[KO * GPW + p];
+            ptr2[K * GPW + p] = pt;
+            ptw2[decltype(Rc)::value * GPW + p] = __builtin_bit_cast(uint32_t, __builtin_bit_cast(sel_us2, pt) - __builtin_bit_cast(sel_us2, told));
+            pin(Sr2);
+        } else {
+            ring_step<D, WS, LPP, K>(st, rw, rg.lastmask, capb, tnew, Sr);
+            pt += tnew;
+            const uint32_t told = ptr[KO * PPW + p];                  // prefix sum w rows back (0 while the window fills)
+            ptr[K * PPW + p] = (unsigned short)pt;
+            ptw[decltype(Rc)::value * PPW + p] = (unsigned short)(pt - told);   // (mod 2^16: the window sum itself is < 2^16)
+        }
         pin(Sr);
         if constexpr (C::STATIC_SLOTS) {
             commit(SetOut{}, std::integral_constant<int, (decltype(SLc)::value + 2) % 4>{});   // row t+2
@@ -410,6 +536,14 @@ __global__ __launch_bounds__(256, (RingBounds<D, WS, LPP, FUSE>::WAVES)) void k_
                     const uint32_t lo = (uint32_t)st.P[k][i] - blo, hi = (uint32_t)(st.P[k][i] >> 32) - bhi;
                     st.P[k][i] = (uint64_t)lo | ((uint64_t)hi << 32);
                 }
+                if constexpr (PAIR) {                                // the second column's ring likewise, by ITS oldest prefix sum
+                    const uint32_t blo2 = (uint32_t)st.P2[1][i], bhi2 = (uint32_t)(st.P2[1][i] >> 32);
+#pragma unroll
+                    for (int k = 1; k < W1; ++k) {
+                        const uint32_t lo = (uint32_t)st.P2[k][i] - blo2, hi = (uint32_t)(st.P2[k][i] >> 32) - bhi2;
+                        st.P2[k][i] = (uint64_t)lo | ((uint64_t)hi << 32);
+                    }
+                }
             }
         }
         ring_for_groups(std::make_integer_sequence<int, C::TRIP / RPG>{}, [&](auto Uc) -> bool {
@@ -422,14 +556,18 @@ __global__ __launch_bounds__(256, (RingBounds<D, WS, LPP, FUSE>::WAVES)) void k_
                 RowRegs<D, WS, LPP> rw;
                 using SL = std::integral_constant<int, (U + R) % 4>;    // (static slots: TRIP % 4 == 0, so t % 4 == (U + R) % 4)
                 lds_row(SL{}, rw);
-                step(std::integral_constant<int, (U + R) % W1>{}, SL{}, Rc, rw, S[R]);
+                uint32_t S2[NRL] = {};                                  // (PAIR only: column x0 + 1)
+                step(std::integral_constant<int, (U + R) % W1>{}, SL{}, Rc, rw, S[R], S2);
                 // the row's slice and the minima of its groups go to its owner's record at once: S[R] is dead after this
                 // (also while the window fills: no branch around it)
-                if constexpr (SPLIT) gsel.template row<R>(S[R], scr_w + R * (PPW * RECD), scr_m + R * (PPW * RECD * 2));
+                if constexpr (PAIR) {
+                    gsel.template row<R>(S[R], scr_w + 2 * R * C::PREC, scr_m + 2 * R * (C::PREC * 2));
+                    gsel.template row<R>(S2, scr_w + (2 * R + 1) * C::PREC, scr_m + (2 * R + 1) * (C::PREC * 2));
+                } else if constexpr (SPLIT) gsel.template row<R>(S[R], scr_w + R * (PPW * RECD), scr_m + R * (PPW * RECD * 2));
             });
             if (t + RPG - 1 < WS - 1) return true;                  // the window is still filling
             // the lanes p + h PPW hold the LPP slices of a pixel for the rows t .. t+RPG-1; the lane with h = k < RPG owns row t+k
-            const int y = ys0 + (t - (WS - 1)) + h;
+            const int y = ys0 + (t - (WS - 1)) + hrow;
             const bool row_ok = owner && y >= ys0 && y < ys1;
             const uint32_t dof = dofs, cof = cofs;
             dofs += dstep; cofs += cstep;

@@ -17,7 +17,7 @@ h = collections.Counter(body)
 valu = sum(c for k, c in h.items() if k.startswith("v_"))
 groups = h["v_qsad_pk_u16_u8"] + h["v_mqsad_pk_u16_u8"]
 import os
-per = int(os.environ.get("RING_QSAD_PER_GROUP", "48"))     # quad-SADs per 64 pixel-rows: D/4 * ceil(w/4)
+per = int(os.environ.get("RING_QSAD_PER_GROUP", "32"))     # quad-SADs per 64 pixel-rows: D/4 * ceil(w/4); the paired headline form: D/8 * (ceil(w/4) + 1)
 print("instructions %d, VALU %d, quad-SADs %d (=> %.1f x 64 pixel-rows), VALU per 64 pixel-rows %.1f" % (len(body), valu, groups, groups / per, valu / max(1, groups / per)))
 for k, c in h.most_common(60):
     print("  %-28s %5d  %6.1f / 64 pixel-rows" % (k, c, c / max(1, groups / per)))
