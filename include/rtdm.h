@@ -145,15 +145,59 @@ void rtdm_debug_search_kernel(int mode);
  * never depend on it; it exists so that tests can put slice boundaries anywhere. */
 void rtdm_debug_disparity_slice(int dt);
 
-/* ---- VideoFilterDevice (morphological open + close, 10x10 ellipse) -----------------------
+/* ---- VideoFilterDevice (morphological filter; default: open + close, 10x10 ellipse) -------
  * rtdm_morph_create      <- SWMorphologicalFilter::SWMorphologicalFilter (filter/mf-sw.cpp:10-17)
  * rtdm_morph_in_buffer / _out_buffer
  *                        <- VideoFilterDevice::getVideoInBuffer / getVideoOutBuffer
  *                           (filter/filter.cpp:45-53): width*height bytes each, owned by the
  *                           device object, here page-locked host memory.
  * rtdm_morph_run         <- SWMorphologicalFilter::run (filter/mf-sw.cpp:19-28): erode, dilate,
- *                           dilate, erode with MORPH_ELLIPSE 10x10 (mf-sw.h:11-12).  Synchronous.
+ *                           dilate, erode with MORPH_ELLIPSE 10x10 (mf-sw.h:11-12) unless rtdm_morph_set_op
+ *                           chose another operation, element or iteration count.  Synchronous.
+ * rtdm_morph_make_element <- cv::getStructuringElement(shape, Size(width, height)) with the default anchor
+ *                           (width/2, height/2).  Host only: no device is touched.
+ * rtdm_morph_set_op      <- what the reference fixes with MORPH_FILTER_DX / MORPH_FILTER_DY and the four calls of run():
+ *                           cv::morphologyEx(src, dst, op, element, anchor, iterations) with the default constant border
+ *                           (out-of-image samples never win), plus RTDM_MORPH_OPEN_CLOSE, the reference's own sequence.
+ *                           Rules M1-M7, DESIGN.md section 4.14 (restated from memory: parity with the library unpinned).
+ *                           Takes effect from the next call on; no reallocation, no device synchronisation; work already
+ *                           enqueued keeps the setting it was enqueued with.  A new handle reports
+ *                           (RTDM_MORPH_OPEN_CLOSE, 1, ELLIPSE 10x10).  d_out == d_in is served for every operation.
+ *                           Every setting but the default passes its intermediate results through the handle's two scratch
+ *                           planes: calls of rtdm_morph_run_device on ONE handle must then be ordered by their streams (the
+ *                           same stream, or events between them); calls that overlap on different streams race on those
+ *                           planes.  The default setting touches no scratch plane and has no such rule.
+ *                           Refusals are decided before the handle is looked at: RTDM_ERR_NULL for a NULL element (then
+ *                           for a NULL handle); RTDM_ERR_BAD_PARAM for an unknown op (cv::MORPH_HITMISS = 7 included),
+ *                           iterations outside 1..16, a side below 1, an anchor outside the element, an all-zero mask;
+ *                           RTDM_ERR_UNSUPPORTED for a side above RTDM_MORPH_MAX_SIZE, which the library would take.
+ * rtdm_debug_morph_general  Diagnostic switch, process wide: 1 = even the default setting runs the general kernel
+ *                           (k_morph_general.hip) instead of the fused 10x10 one; 0 (default) = the library's choice.
+ *                           Results never depend on it.
  */
+#define RTDM_MORPH_RECT 0      /* cv::MorphShapes */
+#define RTDM_MORPH_CROSS 1
+#define RTDM_MORPH_ELLIPSE 2
+#define RTDM_MORPH_ERODE 0     /* cv::MorphTypes 0..6 */
+#define RTDM_MORPH_DILATE 1
+#define RTDM_MORPH_OPEN 2
+#define RTDM_MORPH_CLOSE 3
+#define RTDM_MORPH_GRADIENT 4
+#define RTDM_MORPH_TOPHAT 5
+#define RTDM_MORPH_BLACKHAT 6
+#define RTDM_MORPH_OPEN_CLOSE 100   /* SWMorphologicalFilter::run: open, then close; the default */
+#define RTDM_MORPH_MAX_SIZE 63
+#define RTDM_MORPH_MAX_ITERATIONS 16
+/* mask: width x height bytes, row major with pitch `width`; nonzero = member.  Any mask is legal (several runs per row,
+ * empty rows and columns), with the anchor anywhere inside the element. */
+typedef struct rtdm_morph_element {
+    int width, height, anchor_x, anchor_y;
+    uint8_t mask[RTDM_MORPH_MAX_SIZE * RTDM_MORPH_MAX_SIZE];
+} rtdm_morph_element;
+int rtdm_morph_make_element(int shape, int width, int height, rtdm_morph_element* out);
+int rtdm_morph_set_op(rtdm_morph* mf, int op, int iterations, const rtdm_morph_element* el);
+int rtdm_morph_get_op(const rtdm_morph* mf, int* op, int* iterations, rtdm_morph_element* el);   /* any pointer may be NULL */
+void rtdm_debug_morph_general(int on);
 int rtdm_morph_create(int width, int height, int max_batch, int device, rtdm_morph** out);
 void rtdm_morph_destroy(rtdm_morph* mf);
 uint8_t* rtdm_morph_in_buffer(rtdm_morph* mf);
@@ -351,6 +395,8 @@ int rtdm_rectify_create_calib(const rtdm_calib* calib, const rtdm_rectification*
  *                        crop (height x width x 3, R first).  boxes come in the order of the reference's obj_boundings;
  *                        *nboxes = how many there are (only max_boxes are stored).  zero_border = 1 restates
  *                        OpenCV <= 3.1's findContours, which clears the outermost rows/columns first; 0 = OpenCV >= 3.2.
+ * rtdm_objects_set_morph / _get_morph: the detector's morphFilter setting, exactly as rtdm_morph_set_op / _get_op (same
+ *                        values, refusals and default); rtdm_objects_detect and rtdm_estimate_frame filter with it.
  * rtdm_estimate_frame <- one iteration of Estimator::run without capture, decode and drawing (estimator.cpp:29-77):
  *                        raw RGB frames in, per object the box, mean Z [cm] and pixel count out.  Everything between
  *                        stays in HBM; one small read-back (the boxes) decides the matcher's ROI1.  If no box survives
@@ -359,6 +405,8 @@ typedef struct rtdm_objects rtdm_objects;
 typedef struct rtdm_hsv_range { int low[3], high[3]; } rtdm_hsv_range;   /* H, S, V inclusive; estimator.cpp:110-115: {0,150,0}..{9,255,255} */
 int rtdm_objects_create(int width, int height, int device, rtdm_objects** out);
 void rtdm_objects_destroy(rtdm_objects* ob);
+int rtdm_objects_set_morph(rtdm_objects* ob, int op, int iterations, const rtdm_morph_element* el);
+int rtdm_objects_get_morph(const rtdm_objects* ob, int* op, int* iterations, rtdm_morph_element* el);
 int rtdm_objects_detect(rtdm_objects* ob, const uint8_t* rgb, size_t pitch, const rtdm_hsv_range* range, int min_area,
                         int zero_border, uint8_t* mask_out, size_t mask_pitch, rtdm_region* boxes, int max_boxes,
                         int* nboxes, rtdm_region* roi);

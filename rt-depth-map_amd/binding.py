@@ -78,6 +78,16 @@ class Rectification(C.Structure):       # rtdm_rectification
 CALIB_ZERO_DISPARITY = 1024              # RTDM_CALIB_ZERO_DISPARITY
 CALIB_HAS = {"Width": 1, "Height": 2, "ROI1": 4, "ROI2": 8, "R1": 16, "R2": 32, "P1": 64, "P2": 128, "Q": 256}   # RTDM_CALIB_HAS_*
 
+MORPH_RECT, MORPH_CROSS, MORPH_ELLIPSE = 0, 1, 2          # cv::MorphShapes (RTDM_MORPH_* in rtdm.h)
+MORPH_ERODE, MORPH_DILATE, MORPH_OPEN, MORPH_CLOSE, MORPH_GRADIENT, MORPH_TOPHAT, MORPH_BLACKHAT = range(7)   # cv::MorphTypes
+MORPH_OPEN_CLOSE = 100                                    # SWMorphologicalFilter::run, the default
+MORPH_MAX_SIZE = 63
+
+
+class MorphElement(C.Structure):        # rtdm_morph_element
+    _fields_ = [(n, C.c_int) for n in ("width", "height", "anchor_x", "anchor_y")] + [("mask", C.c_uint8 * (MORPH_MAX_SIZE * MORPH_MAX_SIZE))]
+
+
 _lib = None
 
 
@@ -113,6 +123,12 @@ def lib():
         "rtdm_bm_get_tuner_stats": (C.c_int, [vp, C.POINTER(C.c_long), C.POINTER(C.c_long)]),
         "rtdm_debug_search_kernel": (None, [C.c_int]),
         "rtdm_debug_disparity_slice": (None, [C.c_int]),
+        "rtdm_morph_make_element": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(MorphElement)]),
+        "rtdm_morph_set_op": (C.c_int, [vp, C.c_int, C.c_int, C.POINTER(MorphElement)]),
+        "rtdm_morph_get_op": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(MorphElement)]),
+        "rtdm_objects_set_morph": (C.c_int, [vp, C.c_int, C.c_int, C.POINTER(MorphElement)]),
+        "rtdm_objects_get_morph": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(MorphElement)]),
+        "rtdm_debug_morph_general": (None, [C.c_int]),
         "rtdm_morph_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]),
         "rtdm_morph_destroy": (None, [vp]),
         "rtdm_morph_in_buffer": (vp, [vp]),
@@ -216,7 +232,8 @@ EXPORTS = ("rtdm_strerror rtdm_last_hip_error rtdm_abi_version rtdm_device_count
            "rtdm_xyz_get_params rtdm_xyz_map rtdm_xyz_map_device rtdm_xyz_cloud rtdm_xyz_cloud_device rtdm_bm_compute_cloud "
            "rtdm_mjpeg_probe rtdm_mjpeg_create rtdm_mjpeg_destroy rtdm_mjpeg_decode rtdm_mjpeg_decode_batch_device "
            "rtdm_bm_compute_mjpeg rtdm_mjpeg_set_split rtdm_mjpeg_get_split rtdm_mjpeg_get_split_stats rtdm_calib_load rtdm_stereo_rectify rtdm_undistort_rectify_map "
-           "rtdm_undistort_rectify_map_device rtdm_rectify_create_calib").split()
+           "rtdm_undistort_rectify_map_device rtdm_rectify_create_calib rtdm_morph_make_element rtdm_morph_set_op rtdm_morph_get_op "
+           "rtdm_objects_set_morph rtdm_objects_get_morph rtdm_debug_morph_general").split()
 
 
 def check(status, where):

@@ -8,8 +8,112 @@ struct rtdm_morph {
     hipStream_t stream;
     uint8_t *hIn, *hOut;           // page-locked host buffers handed to the application
     uint8_t *dIn, *dOut, *dT0, *dT1;
+    MorphSetting set;              // rtdm_morph_set_op
     AllocList mem;
 };
+
+static std::atomic<int> g_morph_general{0};   // rtdm_debug_morph_general
+
+int rtdm_morph_make_element(int shape, int width, int height, rtdm_morph_element* out)
+{
+    if (!out) return RTDM_ERR_NULL;
+    if (shape != RTDM_MORPH_RECT && shape != RTDM_MORPH_CROSS && shape != RTDM_MORPH_ELLIPSE) return RTDM_ERR_BAD_PARAM;
+    if (width < 1 || height < 1) return RTDM_ERR_BAD_PARAM;
+    if (width > RTDM_MORPH_MAX_SIZE || height > RTDM_MORPH_MAX_SIZE) return RTDM_ERR_UNSUPPORTED;
+    if (width == 1 && height == 1) shape = RTDM_MORPH_RECT;
+    memset(out, 0, sizeof *out);
+    out->width = width; out->height = height; out->anchor_x = width / 2; out->anchor_y = height / 2;
+    const int r = height / 2, c = width / 2;
+    const double inv_r2 = r ? 1.0 / ((double)r * r) : 0.0;
+    for (int i = 0; i < height; ++i) {
+        int j1 = 0, j2 = 0;                                        // members [j1, j2)
+        if (shape == RTDM_MORPH_RECT || (shape == RTDM_MORPH_CROSS && i == out->anchor_y)) j2 = width;
+        else if (shape == RTDM_MORPH_CROSS) { j1 = out->anchor_x; j2 = j1 + 1; }
+        else {
+            const int dy = i - r;
+            if (std::abs(dy) <= r) {
+                const int dx = (int)lrint(c * sqrt((r * r - dy * dy) * inv_r2));      // cvRound: ties to even
+                j1 = std::max(c - dx, 0); j2 = std::min(c + dx + 1, width);
+            }
+        }
+        for (int j = j1; j < j2; ++j) out->mask[i * width + j] = 1;
+    }
+    return RTDM_OK;
+}
+
+int rtdm::morph_setting_check(int op, int iterations, const rtdm_morph_element* el)
+{
+    if (!el) return RTDM_ERR_NULL;
+    if (!((op >= RTDM_MORPH_ERODE && op <= RTDM_MORPH_BLACKHAT) || op == RTDM_MORPH_OPEN_CLOSE)) return RTDM_ERR_BAD_PARAM;
+    if (iterations < 1 || iterations > RTDM_MORPH_MAX_ITERATIONS) return RTDM_ERR_BAD_PARAM;
+    if (el->width < 1 || el->height < 1) return RTDM_ERR_BAD_PARAM;
+    if (el->width > RTDM_MORPH_MAX_SIZE || el->height > RTDM_MORPH_MAX_SIZE) return RTDM_ERR_UNSUPPORTED;
+    if (el->anchor_x < 0 || el->anchor_x >= el->width || el->anchor_y < 0 || el->anchor_y >= el->height) return RTDM_ERR_BAD_PARAM;
+    for (int i = 0; i < el->width * el->height; ++i) if (el->mask[i]) return RTDM_OK;
+    return RTDM_ERR_BAD_PARAM;
+}
+
+static bool same_bits(const MorphBits& a, const MorphBits& b)
+{
+    return a.w == b.w && a.h == b.h && a.ax == b.ax && a.ay == b.ay && !memcmp(a.rows, b.rows, sizeof a.rows);
+}
+
+void rtdm::morph_setting_store(MorphSetting* s, int op, int iterations, const rtdm_morph_element* el)
+{
+    static_assert(MORPH_MAX_SIZE == RTDM_MORPH_MAX_SIZE, "one limit");
+    s->op = op; s->iterations = iterations;
+    memset(&s->el, 0, sizeof s->el);
+    s->el.width = el->width; s->el.height = el->height; s->el.anchor_x = el->anchor_x; s->el.anchor_y = el->anchor_y;
+    for (int i = 0; i < el->width * el->height; ++i) s->el.mask[i] = el->mask[i] ? 1 : 0;
+    (void)morph_element_bits(s->el.mask, el->width, el->height, el->anchor_x, el->anchor_y, &s->bits);
+    rtdm_morph_element d;
+    MorphBits db;
+    (void)rtdm_morph_make_element(RTDM_MORPH_ELLIPSE, 10, 10, &d);
+    (void)morph_element_bits(d.mask, d.width, d.height, d.anchor_x, d.anchor_y, &db);
+    s->is_default = op == RTDM_MORPH_OPEN_CLOSE && iterations == 1 && same_bits(s->bits, db);
+}
+
+void rtdm::morph_setting_default(MorphSetting* s)
+{
+    rtdm_morph_element d;
+    (void)rtdm_morph_make_element(RTDM_MORPH_ELLIPSE, 10, 10, &d);
+    morph_setting_store(s, RTDM_MORPH_OPEN_CLOSE, 1, &d);
+}
+
+void rtdm::morph_setting_get(const MorphSetting& s, int* op, int* iterations, rtdm_morph_element* el)
+{
+    if (op) *op = s.op;
+    if (iterations) *iterations = s.iterations;
+    if (el) *el = s.el;
+}
+
+int rtdm::morph_run(const MorphSetting& s, Plane8 in, Plane8W out, uint8_t* t0, uint8_t* t1, int W, int H, int n, hipStream_t stream)
+{
+    if (s.is_default && !g_morph_general.load(std::memory_order_relaxed)) {
+        launch_morph_open_close(in, out, t0, t1, W, H, n, stream);
+        return RTDM_OK;
+    }
+    HIPC(launch_morph_general(s.op, s.iterations, s.bits, in, out, t0, t1, W, H, n, stream));
+    return RTDM_OK;
+}
+
+void rtdm_debug_morph_general(int on) { g_morph_general.store(on ? 1 : 0, std::memory_order_relaxed); }
+
+int rtdm_morph_set_op(rtdm_morph* mf, int op, int iterations, const rtdm_morph_element* el)
+{
+    const int rc = morph_setting_check(op, iterations, el);
+    if (rc) return rc;
+    if (!mf) return RTDM_ERR_NULL;
+    morph_setting_store(&mf->set, op, iterations, el);
+    return RTDM_OK;
+}
+
+int rtdm_morph_get_op(const rtdm_morph* mf, int* op, int* iterations, rtdm_morph_element* el)
+{
+    if (!mf) return RTDM_ERR_NULL;
+    morph_setting_get(mf->set, op, iterations, el);
+    return RTDM_OK;
+}
 
 int rtdm_morph_create(int width, int height, int max_batch, int device, rtdm_morph** out)
 {
@@ -21,6 +125,7 @@ int rtdm_morph_create(int width, int height, int max_batch, int device, rtdm_mor
     rtdm_morph* mf = new (std::nothrow) rtdm_morph();
     if (!mf) return RTDM_ERR_NOMEM;
     mf->W = width; mf->H = height; mf->maxB = max_batch; mf->device = device;
+    morph_setting_default(&mf->set);
     const size_t px = (size_t)width * height, all = px * max_batch;
     AllocList& m = mf->mem;
     m.err = hipStreamCreateWithFlags(&mf->stream, hipStreamNonBlocking);
@@ -57,7 +162,8 @@ int rtdm_morph_run_device(rtdm_morph* mf, int n, const uint8_t* d_in, size_t in_
         const int m = std::min(mf->maxB, n - i0);
         Plane8 in{d_in + (size_t)i0 * in_frame_stride, in_pitch, in_frame_stride};
         Plane8W out{d_out + (size_t)i0 * out_frame_stride, out_pitch, out_frame_stride};
-        launch_morph_open_close(in, out, mf->dT0, mf->dT1, width, height, m, s);
+        const int rc = morph_run(mf->set, in, out, mf->dT0, mf->dT1, width, height, m, s);
+        if (rc) return rc;
     }
     HIPC(hipGetLastError());
     return RTDM_OK;

@@ -26,6 +26,7 @@ int rtdm_objects_create(int width, int height, int device, rtdm_objects** out)
     rtdm_objects* ob = new (std::nothrow) rtdm_objects();
     if (!ob) return RTDM_ERR_NOMEM;
     ob->W = width; ob->H = height; ob->device = device;
+    morph_setting_default(&ob->morph);
     ob->maxRec = ((width + 1) / 2 + 1) * ((height + 1) / 2 + 1);          // more 8-connected components cannot exist
     const size_t px = (size_t)width * height;
     AllocList& m = ob->mem;
@@ -39,14 +40,31 @@ int rtdm_objects_create(int width, int height, int device, rtdm_objects** out)
     return RTDM_OK;
 }
 
+int rtdm_objects_set_morph(rtdm_objects* ob, int op, int iterations, const rtdm_morph_element* el)
+{
+    const int rc = morph_setting_check(op, iterations, el);
+    if (rc) return rc;
+    if (!ob) return RTDM_ERR_NULL;
+    morph_setting_store(&ob->morph, op, iterations, el);
+    return RTDM_OK;
+}
+
+int rtdm_objects_get_morph(const rtdm_objects* ob, int* op, int* iterations, rtdm_morph_element* el)
+{
+    if (!ob) return RTDM_ERR_NULL;
+    morph_setting_get(ob->morph, op, iterations, el);
+    return RTDM_OK;
+}
+
 // dRgb (crop, pitch 3W) -> mask -> morphology -> component boxes; synchronises `s` to read the boxes back.
 int rtdm::objects_run(rtdm_objects* ob, const rtdm_hsv_range* range, int min_area, int zero_border, rtdm_region* boxes, int max_boxes,
                       int* nboxes, rtdm_region* roi, hipStream_t s)
 {
     const int W = ob->W, H = ob->H;
     launch_hsv_inrange(ob->dRgb, (size_t)W * 3, W, H, range->low, range->high, ob->dMaskIn, (size_t)W, s);
-    launch_morph_open_close(Plane8{ob->dMaskIn, (size_t)W, (size_t)W * H}, Plane8W{ob->dMaskOut, (size_t)W, (size_t)W * H},
-                            ob->dT0, ob->dT1, W, H, 1, s);
+    const int mrc = morph_run(ob->morph, Plane8{ob->dMaskIn, (size_t)W, (size_t)W * H}, Plane8W{ob->dMaskOut, (size_t)W, (size_t)W * H},
+                              ob->dT0, ob->dT1, W, H, 1, s);
+    if (mrc) return mrc;
     int *dCount = nullptr, *dRec = nullptr;
     launch_cc_boxes(ob->dMaskOut, (size_t)W, W, H, zero_border, ob->dScratch, ob->maxRec, &dCount, &dRec, s);
     HIPC(hipGetLastError());

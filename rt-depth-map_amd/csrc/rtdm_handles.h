@@ -16,6 +16,11 @@
 
 struct StageEvent { hipEvent_t a, b; int stage; int frames; };
 
+namespace rtdm {
+// What rtdm_morph_set_op / rtdm_objects_set_morph keep: the caller's values and the element as the kernels take it.
+struct MorphSetting { int op, iterations; rtdm_morph_element el; MorphBits bits; bool is_default; };
+}
+
 struct rtdm_bm {
     rtdm_bm_params p;
     int prefilter_type, prefilter_size;   // rtdm_bm_set_prefilter: cv::StereoBM's preFilterType / preFilterSize (XSOBEL, 9)
@@ -65,6 +70,7 @@ struct rtdm_rectify {
 struct rtdm_objects {
     int W, H, device, maxRec;
     uint8_t *dRgb, *dMaskIn, *dMaskOut, *dT0, *dT1;
+    rtdm::MorphSetting morph;     // rtdm_objects_set_morph
     void* dScratch;
     int* hRec;                    // pinned: [0] = count, then the first HEAD records
     std::vector<int> all;         // host copy of every record when there are more than HEAD
@@ -134,6 +140,14 @@ inline size_t bm_ws(int W) { return (size_t)((W + 7) & ~7); }
 inline Plane16W bm_internal_plane(const rtdm_bm* bm, int W, int H) { return Plane16W{bm->dOut, bm_ws(W), bm_ws(W) * (size_t)H}; }
 int depth_check_regions(const rtdm_region* regions, int n, int W, int H, int* flat, int* maxh);   // (api_core.hip)
 // the other handles' files, by prefix
+// api_morph.hip.  morph_setting_check: the refusals of rtdm_morph_set_op, no device needed.  morph_run: THE routing of the
+// morphological filter -- the default setting with rtdm_debug_morph_general off runs launch_morph_open_close, everything
+// else launch_morph_general; t0 / t1: n * W * H bytes of scratch each.
+int morph_setting_check(int op, int iterations, const rtdm_morph_element* el);
+void morph_setting_default(MorphSetting* s);
+void morph_setting_store(MorphSetting* s, int op, int iterations, const rtdm_morph_element* el);
+void morph_setting_get(const MorphSetting& s, int* op, int* iterations, rtdm_morph_element* el);
+int morph_run(const MorphSetting& s, Plane8 in, Plane8W out, uint8_t* t0, uint8_t* t1, int W, int H, int n, hipStream_t stream);
 int rectify_upload(rtdm_rectify* rc, const uint8_t* a, size_t apitch, const uint8_t* b, size_t bpitch, hipStream_t s);
 void rectify_gray_launch(rtdm_rectify* rc, const uint8_t* dl, const uint8_t* dr, int n, Plane8W ol, Plane8W orr, hipStream_t s);
 int objects_run(rtdm_objects* ob, const rtdm_hsv_range* range, int min_area, int zero_border, rtdm_region* boxes, int max_boxes,

@@ -156,6 +156,37 @@ void launch_copy16(Plane16W src, Plane16W dst, int W, int H, int n, hipStream_t 
 // K5: erode / dilate / dilate / erode with the 10x10 ellipse; tmp = n*W*H bytes scratch.
 void launch_morph_open_close(Plane8 in, Plane8W out, uint8_t* tmp0, uint8_t* tmp1, int W, int H,
                              int n, hipStream_t stream);
+// The general morphology path (k_morph_general.hip, rules M1-M7 in DESIGN.md section 4.14): any element up to 63 x 63, the
+// operations of cv::morphologyEx plus OPEN_CLOSE, 1..16 iterations; one launch per erosion / dilation.  The element travels
+// BY VALUE in the kernel arguments as one 64-bit word of members per row (a launch in flight never sees a later setting);
+// the workgroup expands it into its run table.  nruns, kmax: what morph_element_bits counted (runs of all rows; log2 of the
+// longest run, rounded down).
+#define MORPH_MAX_SIZE 63
+struct MorphBits { unsigned long long rows[MORPH_MAX_SIZE]; int w, h, ax, ay, nruns, kmax; };
+// mask: w x h bytes with pitch w, 1 <= w, h <= MORPH_MAX_SIZE; false = no member at all.  (Plain host code, inline so that
+// tests/morph_bits_host.cpp can run it under the sanitizers.)
+inline bool morph_element_bits(const uint8_t* mask, int w, int h, int ax, int ay, MorphBits* out)
+{
+    MorphBits b{};
+    b.w = w; b.h = h; b.ax = ax; b.ay = ay;
+    int longest = 0;
+    for (int i = 0; i < h; ++i) {
+        int run = 0;
+        for (int j = 0; j < w; ++j) {
+            if (mask[i * w + j]) {
+                b.rows[i] |= 1ull << j;
+                if (!run) ++b.nruns;
+                if (++run > longest) longest = run;
+            } else run = 0;
+        }
+    }
+    while (longest >> (b.kmax + 1)) ++b.kmax;
+    *out = b;
+    return b.nruns > 0;
+}
+// tmp0 / tmp1: n * W * H bytes each.  in.base == out.base (with equal strides) is served; other overlaps are not.
+hipError_t launch_morph_general(int op, int iterations, const MorphBits& el, Plane8 in, Plane8W out, uint8_t* tmp0, uint8_t* tmp1,
+                                int W, int H, int n, hipStream_t stream);
 
 // SGM-8 (BASELINE config 5).  Cost volumes live on the column domain [x0, x0+W1).
 struct SGMGeom { int W, H, D, minD, x0, W1; };

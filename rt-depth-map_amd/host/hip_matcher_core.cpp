@@ -347,5 +347,22 @@ int HIPMorphCore::run(const uint8_t* in, size_t inStep, uint8_t* out, size_t out
     status_ = rtdm_morph_run(mf_, in, inStep, out, outStep, cols, rows);
     return status_;
 }
+int HIPMorphCore::setElement(int shape, int width, int height)
+{
+    rtdm_morph_element el;
+    int op = 0, iterations = 0;
+    int rc = rtdm_morph_make_element(shape, width, height, &el);
+    if (rc != RTDM_OK) return rc;
+    if (!mf_) return status_ != RTDM_OK ? status_ : RTDM_ERR_NO_DEVICE;
+    rc = rtdm_morph_get_op(mf_, &op, &iterations, NULL);
+    return rc != RTDM_OK ? rc : rtdm_morph_set_op(mf_, op, iterations, &el);
+}
+int HIPMorphCore::setOperation(int op, int iterations)
+{
+    if (!mf_) return status_ != RTDM_OK ? status_ : RTDM_ERR_NO_DEVICE;
+    rtdm_morph_element el;
+    const int rc = rtdm_morph_get_op(mf_, NULL, NULL, &el);
+    return rc != RTDM_OK ? rc : rtdm_morph_set_op(mf_, op, iterations, &el);
+}
 
 }  // namespace rtdm

@@ -291,6 +291,10 @@ public:
     char* getVideoOutBuffer();
     int getFrameSize() const { return width_ * height_ * (bpp_ >> 3); }
     int run(const uint8_t* in, size_t inStep, uint8_t* out, size_t outStep, int rows, int cols);
+    // cv::getStructuringElement(shape, Size(width, height)) / the operation and iteration count of cv::morphologyEx
+    // (RTDM_MORPH_*), from the next run on (rtdm_morph_set_op); each keeps what the other one set.
+    int setElement(int shape, int width, int height);
+    int setOperation(int op, int iterations = 1);
     int status() const { return status_; }
 
 private:

@@ -1,7 +1,8 @@
 /*
  * mf-hip.cpp -- install as filter/mf-hip.cpp and add mf-hip.o to filter/Makefile.
  * Mirrors filter/mf-sw.cpp: the constructor publishes width/height/bpp and the two frame buffers
- * (page-locked here), run() performs erode, dilate, dilate, erode with the 10x10 ellipse.
+ * (page-locked here), run() performs erode, dilate, dilate, erode with the 10x10 ellipse unless
+ * setElement / setOperation chose otherwise.
  */
 #include "filter/mf-hip.h"
 
@@ -28,4 +29,14 @@ int HIPMorphologicalFilter::run(cv::InputArray in, cv::OutputArray out)
 	out.create(src.size(), CV_8UC1);
 	cv::Mat dst = out.getMat();
 	return core->run(src.data, src.step, dst.data, dst.step, src.rows, src.cols);
+}
+
+int HIPMorphologicalFilter::setElement(int shape, int width, int height)
+{
+	return core->setElement(shape, width, height);
+}
+
+int HIPMorphologicalFilter::setOperation(int op, int iterations)
+{
+	return core->setOperation(op, iterations);
 }

@@ -15,6 +15,11 @@ public:
 	explicit HIPMorphologicalFilter(int w, int h, int bpp);
 	~HIPMorphologicalFilter();
 	int run(cv::InputArray in, cv::OutputArray out);
+	/* beyond the reference's MORPH_FILTER_DX / MORPH_FILTER_DY: cv::getStructuringElement(shape, Size(width, height)) and
+	 * cv::morphologyEx's operation (cv::MORPH_ERODE .. cv::MORPH_BLACKHAT, or RTDM_MORPH_OPEN_CLOSE, the default) from the
+	 * next run on; an rtdm_status comes back. */
+	int setElement(int shape, int width, int height);
+	int setOperation(int op, int iterations = 1);
 private:
 	rtdm::HIPMorphCore* core;
 };
