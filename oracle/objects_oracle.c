@@ -40,6 +40,14 @@ static void init_tabs(void)
     tabs_ready = 1;
 }
 
+/* the two division tables as the conversion uses them (256 entries each), for the tests that check their rounding */
+void orc_hsv_tables(int* sdiv, int* hdiv)
+{
+    init_tabs();
+    memcpy(sdiv, sdiv_tab, sizeof sdiv_tab);
+    memcpy(hdiv, hdiv_tab, sizeof hdiv_tab);
+}
+
 void orc_rgb2hsv(const uint8_t* rgb, size_t sstep, int W, int H, uint8_t* hsv, size_t dstep)
 {
     init_tabs();

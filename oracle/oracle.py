@@ -116,6 +116,8 @@ def lib():
         L.orc_init_undistort_rectify_map.restype = C.c_int
         L.orc_rgb2hsv.argtypes = [u8p, C.c_size_t, C.c_int, C.c_int, u8p, C.c_size_t]
         L.orc_rgb2hsv.restype = None
+        L.orc_hsv_tables.argtypes = [ip, ip]
+        L.orc_hsv_tables.restype = None
         L.orc_hsv_inrange.argtypes = [u8p, C.c_size_t, C.c_int, C.c_int, ip, ip, u8p, C.c_size_t]
         L.orc_hsv_inrange.restype = None
         L.orc_external_boxes.argtypes = [u8p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, ip, C.c_int]
@@ -342,6 +344,13 @@ def init_undistort_rectify_map(M, D, R, P, W, H):
 
 # ---- object detection -> ROI (objects_oracle.c) ---------------------------------------------------------------
 HSV_LOW, HSV_HIGH = (0, 150, 0), (9, 255, 255)          # estimator.cpp:110-115
+
+
+def hsv_tables():
+    """-> (sdiv, hdiv): the conversion's two division tables, 256 ints each."""
+    sdiv = np.zeros(256, np.int32); hdiv = np.zeros(256, np.int32)
+    lib().orc_hsv_tables(_p(sdiv, C.c_int), _p(hdiv, C.c_int))
+    return sdiv, hdiv
 
 
 def rgb2hsv(rgb):
