@@ -415,6 +415,59 @@ int rtdm_estimate_frame(rtdm_bm* bm, rtdm_rectify* rc, rtdm_objects* ob, const u
                         int min_area, int zero_border, double calibration_unit, rtdm_region* boxes, double* mean_cm,
                         int* counts, int max_boxes, int* nboxes, int16_t* disp, size_t disp_pitch);
 
+/* ---- the same detector on frame batches and for several colour classes per call (rules O1-O6) ----
+ * A call names nranges HSV ranges (1 .. RTDM_MAX_HSV_RANGES) and a class range_class[r] in [0, nclasses) for each; every
+ * class owns at least one range.  The raw mask of a class is 255 where at least one of its ranges holds (each range by the
+ * rule of rtdm_objects_detect: inclusive, no hue wrap-around inside a range -- red is {0..9} OR {170..179}), each class mask
+ * is filtered with the handle's morphological setting and labelled like the single mask of rtdm_objects_detect.
+ * rtdm_object:           one kept box, its class and first_pixel = y * width + x of the first pixel of its component in
+ *                        raster order (what orders a class's list: descending); reserved is written as 0.
+ * rtdm_objects_create_batch: a handle that takes up to max_batch (1 .. 64) frames x max_classes (1 .. 8) class planes per
+ *                        launch; rtdm_objects_create is create_batch(width, height, 1, 1, ...).  Device memory grows with
+ *                        max_batch * max_classes planes of about 30 bytes per pixel.
+ * rtdm_objects_detect_device: n device-resident frames (frame f at d_rgb + f * frame_stride, rows of pitch bytes) ->
+ *                        frame f's object list at d_objects + f * capacity: the per-class lists, class ascending; the first
+ *                        min(total, capacity) entries are stored and the rest of the array is left untouched (d_objects
+ *                        needs no more than the alignment of an int).
+ *                        d_counts[f * nclasses + c] = kept objects of class c (never clipped to capacity); d_rois[f] = union
+ *                        box of all kept objects of the frame (with none: x = y = 1000000, width = height = -2000000, as
+ *                        rtdm_objects_detect reports an empty frame).  d_masks (optional): the filtered masks (filter_out),
+ *                        plane f * nclasses + c at d_masks + (f * nclasses + c) * mask_plane_stride; only width bytes of a
+ *                        row are written.  Enqueued on hip_stream and never synchronised; ranges and range_class are host
+ *                        arrays that are read before the call returns.  n may exceed max_batch (chunks); n = 0 is RTDM_OK.
+ *                        The work planes belong to the handle: calls that share a handle must be ordered on one stream.
+ *                        All outputs are bit-identical from run to run and do not depend on n, on the frame's position, on
+ *                        max_batch or on the chunking.  Refusals, before any device use and in this order: RTDM_ERR_NULL
+ *                        (ranges, range_class, d_rgb, d_counts, d_rois; d_objects with capacity > 0), RTDM_ERR_BAD_PARAM
+ *                        (nranges outside 1 .. 16, nclasses outside 1 .. 8, a class id outside [0, nclasses), a class without a range),
+ *                        RTDM_ERR_BAD_SIZE (n < 0, capacity < 0), RTDM_ERR_NULL (the handle), RTDM_ERR_BAD_PARAM (nclasses
+ *                        above the handle's max_classes), RTDM_ERR_BAD_SIZE (pitch < 3 * width, mask_pitch < width, a frame
+ *                        stride below pitch * height or a plane stride below mask_pitch * height where a second frame or
+ *                        plane follows).
+ * rtdm_objects_detect_batch: the same with host pointers; synchronous.
+ * rtdm_estimate_frame_classes: rtdm_estimate_frame for several classes: ROI1 is the union box over all classes; object i is
+ *                        measured over its box where the filtered mask of its own class is non-zero.  *nobjects = how many
+ *                        there are; the first min(*nobjects, max_objects) are stored and the first min(*nobjects,
+ *                        max_objects, RTDM_MAX_REGIONS) get mean_cm[i] / counts[i].  With one class and one range the boxes,
+ *                        means, counts and disparity map are rtdm_estimate_frame's. */
+#define RTDM_MAX_HSV_RANGES 16
+#define RTDM_MAX_CLASSES 8
+typedef struct rtdm_object { int x, y, width, height, cls, first_pixel, reserved[2]; } rtdm_object;
+int rtdm_objects_create_batch(int width, int height, int max_batch, int max_classes, int device, rtdm_objects** out);
+int rtdm_objects_detect_device(rtdm_objects* ob, int n, const uint8_t* d_rgb, size_t pitch, size_t frame_stride,
+                               const rtdm_hsv_range* ranges, const int* range_class, int nranges, int nclasses, int min_area,
+                               int zero_border, uint8_t* d_masks, size_t mask_pitch, size_t mask_plane_stride,
+                               rtdm_object* d_objects, int capacity, int* d_counts, rtdm_region* d_rois, void* hip_stream);
+int rtdm_objects_detect_batch(rtdm_objects* ob, int n, const uint8_t* rgb, size_t pitch, size_t frame_stride,
+                              const rtdm_hsv_range* ranges, const int* range_class, int nranges, int nclasses, int min_area,
+                              int zero_border, uint8_t* masks, size_t mask_pitch, size_t mask_plane_stride,
+                              rtdm_object* objects, int capacity, int* counts, rtdm_region* rois);
+int rtdm_estimate_frame_classes(rtdm_bm* bm, rtdm_rectify* rc, rtdm_objects* ob, const uint8_t* rgb_left, size_t left_pitch,
+                                const uint8_t* rgb_right, size_t right_pitch, const double* Q, const rtdm_hsv_range* ranges,
+                                const int* range_class, int nranges, int nclasses, int min_area, int zero_border,
+                                double calibration_unit, rtdm_object* objects, double* mean_cm, int* counts, int max_objects,
+                                int* nobjects, int16_t* disp, size_t disp_pitch);
+
 /* ---- the step after the matcher that the reference keeps switched off: the disparity WLS post-filter -------------------
  * ENABLE_POST_FILTER (estimator.cpp:57-70, 106-109; include/estimator.h:32,116) -- cv::ximgproc's createRightMatcher,
  * createDisparityWLSFilter, setLambda(8000), setSigmaColor(1.5) and filter(left_disp, left_rect, filtered, right_disp).

@@ -31,6 +31,14 @@ class HsvRange(C.Structure):
     _fields_ = [("low", C.c_int * 3), ("high", C.c_int * 3)]
 
 
+class Object(C.Structure):              # rtdm_object, 32 bytes
+    _fields_ = [(n, C.c_int) for n in ("x", "y", "width", "height", "cls", "first_pixel")] + [("reserved", C.c_int * 2)]
+
+
+MAX_HSV_RANGES, MAX_CLASSES = 16, 8      # RTDM_MAX_HSV_RANGES, RTDM_MAX_CLASSES
+MAX_REGIONS = 64                         # RTDM_MAX_REGIONS: objects of a frame that get a depth
+
+
 class SGMParams(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("blockSize", "minDisparity", "numDisparities", "P1", "P2", "uniquenessRatio",
                                        "speckleWindowSize", "speckleRange", "disp12MaxDiff", "paths")]
@@ -172,6 +180,14 @@ def lib():
         "rtdm_estimate_frame": (C.c_int, [vp, vp, vp, u8p, sz, u8p, sz, C.POINTER(C.c_double), C.POINTER(HsvRange), C.c_int, C.c_int,
                                           C.c_double, C.POINTER(Region), C.POINTER(C.c_double), C.POINTER(C.c_int), C.c_int,
                                           C.POINTER(C.c_int), i16p, sz]),
+        "rtdm_objects_create_batch": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]),
+        "rtdm_objects_detect_device": (C.c_int, [vp, C.c_int, u8p, sz, sz, C.POINTER(HsvRange), C.POINTER(C.c_int), C.c_int, C.c_int,
+                                                 C.c_int, C.c_int, u8p, sz, sz, vp, C.c_int, vp, vp, vp]),
+        "rtdm_objects_detect_batch": (C.c_int, [vp, C.c_int, u8p, sz, sz, C.POINTER(HsvRange), C.POINTER(C.c_int), C.c_int, C.c_int,
+                                                C.c_int, C.c_int, u8p, sz, sz, vp, C.c_int, vp, vp]),
+        "rtdm_estimate_frame_classes": (C.c_int, [vp, vp, vp, u8p, sz, u8p, sz, C.POINTER(C.c_double), C.POINTER(HsvRange),
+                                                  C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, vp,
+                                                  C.POINTER(C.c_double), C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), i16p, sz]),
         "rtdm_wls_params_for_bm": (C.c_int, [C.POINTER(BMParams), C.POINTER(WLSParams)]),
         "rtdm_wls_params_for_sgm": (C.c_int, [C.POINTER(SGMParams), C.POINTER(WLSParams)]),
         "rtdm_bm_right_params": (C.c_int, [C.POINTER(BMParams), C.POINTER(BMParams)]),
@@ -233,7 +249,8 @@ EXPORTS = ("rtdm_strerror rtdm_last_hip_error rtdm_abi_version rtdm_device_count
            "rtdm_mjpeg_probe rtdm_mjpeg_create rtdm_mjpeg_destroy rtdm_mjpeg_decode rtdm_mjpeg_decode_batch_device "
            "rtdm_bm_compute_mjpeg rtdm_mjpeg_set_split rtdm_mjpeg_get_split rtdm_mjpeg_get_split_stats rtdm_calib_load rtdm_stereo_rectify rtdm_undistort_rectify_map "
            "rtdm_undistort_rectify_map_device rtdm_rectify_create_calib rtdm_morph_make_element rtdm_morph_set_op rtdm_morph_get_op "
-           "rtdm_objects_set_morph rtdm_objects_get_morph rtdm_debug_morph_general").split()
+           "rtdm_objects_set_morph rtdm_objects_get_morph rtdm_debug_morph_general rtdm_objects_create_batch "
+           "rtdm_objects_detect_device rtdm_objects_detect_batch rtdm_estimate_frame_classes").split()
 
 
 def check(status, where):

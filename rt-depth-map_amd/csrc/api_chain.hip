@@ -102,6 +102,79 @@ int rtdm_estimate_frame(rtdm_bm* bm, rtdm_rectify* rc, rtdm_objects* ob, const u
     return RTDM_OK;
 }
 
+// rtdm_estimate_frame with several colour classes: the batched detector on the one rectified frame, selection on the device;
+// the read-back that decides ROI1 brings the per-class counts, the union box and the stored objects.
+int rtdm_estimate_frame_classes(rtdm_bm* bm, rtdm_rectify* rc, rtdm_objects* ob, const uint8_t* rgb_left, size_t left_pitch,
+                                const uint8_t* rgb_right, size_t right_pitch, const double* Q, const rtdm_hsv_range* ranges,
+                                const int* range_class, int nranges, int nclasses, int min_area, int zero_border,
+                                double calibration_unit, rtdm_object* objects, double* mean_cm, int* counts, int max_objects,
+                                int* nobjects, int16_t* disp, size_t disp_pitch)
+{
+    if (!rgb_left || !rgb_right || !Q || !objects || !mean_cm || !counts || !nobjects) return RTDM_ERR_NULL;
+    HsvClasses C;
+    int st = objects_classes_check(ranges, range_class, nranges, nclasses, &C);
+    if (st) return st;
+    if (!bm || !rc || !ob) return RTDM_ERR_NULL;
+    if (bm->device != rc->device || bm->device != ob->device || nclasses > ob->maxC) return RTDM_ERR_BAD_PARAM;
+    if (ob->W != rc->rw || ob->H != rc->rh || max_objects <= 0) return RTDM_ERR_BAD_SIZE;
+    st = bm_check_frame(bm, rc->rw, rc->rh);
+    if (st) return st;
+    const int W = rc->rw, H = rc->rh, K = nclasses;
+    const size_t row = (size_t)rc->W * 3, fbytes = row * rc->H;
+    if (left_pitch < row || right_pitch < row || (disp && disp_pitch < (size_t)W * 2)) return RTDM_ERR_BAD_SIZE;
+    HIPC(hipSetDevice(bm->device));
+    hipStream_t s = bm->stream;
+    const int cap = (int)std::min((size_t)max_objects, (size_t)K * ob->maxRec);
+    st = objects_stage(ob, (size_t)cap);
+    if (st) return st;
+    st = rectify_upload(rc, rgb_left, left_pitch, rgb_right, right_pitch, s);
+    if (st) return st;
+    const size_t gframe = rc->gpitch * H, cp = objects_rgb_pitch(ob);
+    rectify_gray_launch(rc, rc->dRgb[0], rc->dRgb[1], 1, Plane8W{rc->dGray[0], rc->gpitch, gframe}, Plane8W{rc->dGray[1], rc->gpitch, gframe}, s);
+    launch_rectify_rgb(RectifySrc{rc->dRgb[0], row, fbytes}, rc->dMap1[0], rc->dMap2[0], rc->W, rc->H, W, H,
+                       Plane8W{ob->dRgb, cp, cp * H}, 1, s);
+    int* dCounts = ob->dMeta;
+    int* dRoi = ob->dMeta + (size_t)ob->maxB * ob->maxC;
+    st = objects_run_chunk(ob, 1, ob->dRgb, cp, cp * H, C, min_area, zero_border, nullptr, 0, 0, ob->dObj, cap, dCounts, dRoi, s);
+    if (st) return st;
+    int* hCounts = ob->hRec;
+    int* hRoi = ob->hRec + K;
+    HIPC(hipMemcpyAsync(hCounts, dCounts, (size_t)K * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPC(hipMemcpyAsync(hRoi, dRoi, 4 * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPC(hipStreamSynchronize(s));
+    long total = 0;
+    for (int c = 0; c < K; ++c) total += hCounts[c];
+    *nobjects = (int)total;
+    if (total == 0) return RTDM_OK;                       // estimator.cpp:48: nothing to measure in this frame
+    const int stored = (int)std::min<long>(total, cap);
+    HIPC(hipMemcpy(objects, ob->dObj, (size_t)stored * sizeof(rtdm_object), hipMemcpyDeviceToHost));
+    const int nreg = std::min(stored, RTDM_MAX_REGIONS);
+    st = rtdm_bm_set_roi(bm, 1, hRoi[0], hRoi[1], hRoi[2], hRoi[3]);
+    if (st) return st;
+    const Plane16W O = bm_internal_plane(bm, W, H);
+    st = bm_run_chunk(bm, 1, Plane8{rc->dGray[0], rc->gpitch, gframe}, Plane8{rc->dGray[1], rc->gpitch, gframe}, W, H, O, s);
+    if (st) return st;
+    // every class's objects over that class's filtered mask; the lists lie class after class
+    rtdm_region boxes[RTDM_MAX_REGIONS];
+    for (int i = 0; i < nreg; ++i) boxes[i] = rtdm_region{objects[i].x, objects[i].y, objects[i].width, objects[i].height};
+    int flat[4 * RTDM_MAX_REGIONS], maxh = 1;
+    st = depth_check_regions(boxes, nreg, W, H, flat, &maxh);
+    if (st) return st;
+    DepthQ q; std::copy(Q, Q + 16, q.q);
+    for (int i0 = 0; i0 < nreg;) {
+        int i1 = i0 + 1;
+        while (i1 < nreg && objects[i1].cls == objects[i0].cls) ++i1;
+        launch_depth_stats(bm->dOut, O.pitch_e, W, H, q, ob->dMaskOut + (size_t)objects[i0].cls * ob->mpitch * H, ob->mpitch, flat + 4 * i0,
+                           i1 - i0, bm->maxH, calibration_unit, bm->dDepth, mean_cm + i0, counts + i0, s, i0 > 0);   // one minimum per map
+        i0 = i1;
+    }
+    if (disp) { st = bm_download_disp(bm, W, H, s); if (st) return st; }
+    HIPC(hipGetLastError());
+    HIPC(hipStreamSynchronize(s));
+    if (disp) bm_scatter_disp(bm, W, H, disp, disp_pitch);
+    return RTDM_OK;
+}
+
 int rtdm_bm_compute_filtered(rtdm_bm* left_bm, rtdm_bm* right_bm, rtdm_wls* wls, const uint8_t* left, size_t left_pitch,
                              const uint8_t* right, size_t right_pitch, int width, int height, int16_t* out, size_t out_pitch,
                              int16_t* raw_left, size_t raw_left_pitch)

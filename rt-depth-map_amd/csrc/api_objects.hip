@@ -4,6 +4,7 @@
 using namespace rtdm;
 
 static const int OBJ_HEAD = 512;  // records fetched together with the count
+static const int OBJ_MAX_BATCH = 64;
 
 void rtdm_objects_destroy(rtdm_objects* ob)
 {
@@ -11,33 +12,47 @@ void rtdm_objects_destroy(rtdm_objects* ob)
     (void)hipSetDevice(ob->device);
     if (ob->stream) (void)hipStreamSynchronize(ob->stream);
     ob->mem.release();
+    if (ob->dObj) (void)hipFree(ob->dObj);
     if (ob->stream) (void)hipStreamDestroy(ob->stream);
     delete ob;
 }
 
-int rtdm_objects_create(int width, int height, int device, rtdm_objects** out)
+int rtdm_objects_create_batch(int width, int height, int max_batch, int max_classes, int device, rtdm_objects** out)
 {
+    static_assert(sizeof(rtdm_object) == 32 && sizeof(CcObject) == sizeof(rtdm_object), "one record layout");
+    static_assert(HSV_MAX_RANGES == RTDM_MAX_HSV_RANGES && HSV_MAX_CLASSES == RTDM_MAX_CLASSES, "one limit");
     if (!out) return RTDM_ERR_NULL;
     *out = nullptr;
     if (width <= 0 || height <= 0 || width > 32767 || height > 32767 || (long)width * height >= (1L << 30)) return RTDM_ERR_BAD_SIZE;
+    if (max_batch < 1 || max_batch > OBJ_MAX_BATCH) return RTDM_ERR_BAD_SIZE;
+    if (max_classes < 1 || max_classes > RTDM_MAX_CLASSES) return RTDM_ERR_BAD_PARAM;
     if (width > 8192) return RTDM_ERR_UNSUPPORTED;      // the component labelling keeps one row of ints in LDS
     int st = use_device(device);
     if (st) return st;
     rtdm_objects* ob = new (std::nothrow) rtdm_objects();
     if (!ob) return RTDM_ERR_NOMEM;
-    ob->W = width; ob->H = height; ob->device = device;
+    ob->W = width; ob->H = height; ob->device = device; ob->maxB = max_batch; ob->maxC = max_classes;
     morph_setting_default(&ob->morph);
     ob->maxRec = ((width + 1) / 2 + 1) * ((height + 1) / 2 + 1);          // more 8-connected components cannot exist
-    const size_t px = (size_t)width * height;
+    ob->mpitch = ((size_t)width + 3) & ~(size_t)3;
+    const size_t px = (size_t)width * height, planes = (size_t)max_batch * max_classes;
     AllocList& m = ob->mem;
     m.err = hipStreamCreateWithFlags(&ob->stream, hipStreamNonBlocking);
-    m.dev(&ob->dRgb, px * 3 + 16);
-    m.dev(&ob->dMaskIn, px); m.dev(&ob->dMaskOut, px); m.dev(&ob->dT0, px); m.dev(&ob->dT1, px);
-    m.dev(&ob->dScratch, cc_scratch_bytes(width, height, ob->maxRec));
+    m.dev(&ob->dRgb, max_batch * objects_rgb_pitch(ob) * height + 16);
+    m.dev(&ob->dMaskIn, planes * ob->mpitch * height); m.dev(&ob->dMaskOut, planes * ob->mpitch * height);
+    m.dev(&ob->dT0, planes * px); m.dev(&ob->dT1, planes * px);
+    m.dev(&ob->dScratch, planes * cc_plane_bytes(width, height, ob->maxRec));
+    m.dev(&ob->dMeta, (planes + 4 * (size_t)max_batch) * sizeof(int));
     m.host(&ob->hRec, (size_t)(1 + 6 * OBJ_HEAD) * sizeof(int) + px * 3);
     if (m.err != hipSuccess) { const hipError_t e = m.err; rtdm_objects_destroy(ob); return create_failed("rtdm_objects_create", e); }
+    hsv_tables_ready(ob->stream);                       // so that no later call has to wait for them
     *out = ob;
     return RTDM_OK;
+}
+
+int rtdm_objects_create(int width, int height, int device, rtdm_objects** out)
+{
+    return rtdm_objects_create_batch(width, height, 1, 1, device, out);
 }
 
 int rtdm_objects_set_morph(rtdm_objects* ob, int op, int iterations, const rtdm_morph_element* el)
@@ -116,5 +131,145 @@ int rtdm_objects_detect(rtdm_objects* ob, const uint8_t* rgb, size_t pitch, cons
         HIPC(hipStreamSynchronize(s));
         for (int y = 0; y < ob->H; ++y) memcpy(mask_out + (size_t)y * mask_pitch, h + (size_t)y * ob->W, (size_t)ob->W);
     }
+    return RTDM_OK;
+}
+
+// ---- frame batches and colour classes (rules O1-O6) ----------------------------------------------------------------------
+// the handle's colour staging for the batched calls: rows (and so frames) start on dwords, k_hsv_classes reads three per lane
+size_t rtdm::objects_rgb_pitch(const rtdm_objects* ob) { return ((size_t)ob->W * 3 + 3) & ~(size_t)3; }
+
+// O1 / O6: the ranges and their classes as the kernel takes them; needs no handle
+int rtdm::objects_classes_check(const rtdm_hsv_range* ranges, const int* range_class, int nranges, int nclasses, HsvClasses* C)
+{
+    if (!ranges || !range_class) return RTDM_ERR_NULL;
+    if (nranges < 1 || nranges > RTDM_MAX_HSV_RANGES || nclasses < 1 || nclasses > RTDM_MAX_CLASSES) return RTDM_ERR_BAD_PARAM;
+    memset(C, 0, sizeof *C);
+    C->nranges = nranges; C->nclasses = nclasses;
+    unsigned owned = 0;
+    for (int i = 0; i < nranges; ++i) {
+        if (range_class[i] < 0 || range_class[i] >= nclasses) return RTDM_ERR_BAD_PARAM;
+        owned |= 1u << range_class[i];
+        C->cls[i] = range_class[i];
+        for (int k = 0; k < 3; ++k) { C->lo[i][k] = ranges[i].low[k]; C->hi[i][k] = ranges[i].high[k]; }
+    }
+    return owned == (1u << nclasses) - 1 ? RTDM_OK : RTDM_ERR_BAD_PARAM;       // every class owns a range
+}
+
+// The refusals of the two batched entry points, in the order include/rtdm.h gives: what needs no handle comes first.
+static int objects_batch_check(const rtdm_objects* ob, int n, const void* rgb, size_t pitch, size_t frame_stride,
+                               const rtdm_hsv_range* ranges, const int* range_class, int nranges, int nclasses, const void* masks,
+                               size_t mask_pitch, size_t mask_plane_stride, const void* objects, int capacity, const void* counts,
+                               const void* rois, HsvClasses* C)
+{
+    if (!rgb || !counts || !rois || (capacity > 0 && !objects)) return RTDM_ERR_NULL;
+    const int rc = objects_classes_check(ranges, range_class, nranges, nclasses, C);
+    if (rc) return rc;
+    if (n < 0 || capacity < 0) return RTDM_ERR_BAD_SIZE;
+    if (!ob) return RTDM_ERR_NULL;
+    if (nclasses > ob->maxC) return RTDM_ERR_BAD_PARAM;
+    if (pitch < (size_t)ob->W * 3 || (masks && mask_pitch < (size_t)ob->W)) return RTDM_ERR_BAD_SIZE;
+    if (n > 1 && frame_stride < pitch * ob->H) return RTDM_ERR_BAD_SIZE;
+    if (masks && (size_t)n * nclasses > 1 && mask_plane_stride < mask_pitch * ob->H) return RTDM_ERR_BAD_SIZE;
+    return RTDM_OK;
+}
+
+// One chunk (m <= maxB frames) on s: class masks -> filter -> labelling -> selection.  d_masks == null: the filtered planes
+// stay in the handle (dMaskOut, rows of ob->mpitch).
+int rtdm::objects_run_chunk(rtdm_objects* ob, int m, const uint8_t* d_rgb, size_t pitch, size_t frame_stride, const HsvClasses& C,
+                            int min_area, int zero_border, uint8_t* d_masks, size_t mask_pitch, size_t mask_plane_stride,
+                            CcObject* d_objects, int capacity, int* d_counts, int* d_rois, hipStream_t s)
+{
+    const int W = ob->W, H = ob->H, planes = m * C.nclasses;
+    const size_t ip = ob->mpitch, iplane = ip * H;
+    launch_hsv_classes(d_rgb, pitch, frame_stride, m, W, H, C, ob->dMaskIn, ip, iplane, s);
+    const Plane8W out = d_masks ? Plane8W{d_masks, mask_pitch, mask_plane_stride} : Plane8W{ob->dMaskOut, ip, iplane};
+    const int rc = morph_run(ob->morph, Plane8{ob->dMaskIn, ip, iplane}, out, ob->dT0, ob->dT1, W, H, planes, s);
+    if (rc) return rc;
+    launch_cc_objects(out.base, out.pitch, out.frame, m, C.nclasses, W, H, zero_border, min_area, ob->dScratch, ob->maxRec, d_objects,
+                      capacity, d_counts, d_rois, s);
+    HIPC(hipGetLastError());
+    return RTDM_OK;
+}
+
+int rtdm_objects_detect_device(rtdm_objects* ob, int n, const uint8_t* d_rgb, size_t pitch, size_t frame_stride,
+                               const rtdm_hsv_range* ranges, const int* range_class, int nranges, int nclasses, int min_area,
+                               int zero_border, uint8_t* d_masks, size_t mask_pitch, size_t mask_plane_stride,
+                               rtdm_object* d_objects, int capacity, int* d_counts, rtdm_region* d_rois, void* hip_stream)
+{
+    HsvClasses C;
+    const int rc = objects_batch_check(ob, n, d_rgb, pitch, frame_stride, ranges, range_class, nranges, nclasses, d_masks, mask_pitch,
+                                       mask_plane_stride, d_objects, capacity, d_counts, d_rois, &C);
+    if (rc) return rc;
+    if (n == 0) return RTDM_OK;
+    HIPC(hipSetDevice(ob->device));
+    hipStream_t s = (hipStream_t)hip_stream;          // NULL = the HIP null stream
+    for (int i0 = 0; i0 < n; i0 += ob->maxB) {
+        const int m = std::min(ob->maxB, n - i0);
+        const int st = objects_run_chunk(ob, m, d_rgb + (size_t)i0 * frame_stride, pitch, frame_stride, C, min_area, zero_border,
+                                         d_masks ? d_masks + (size_t)i0 * nclasses * mask_plane_stride : nullptr, mask_pitch,
+                                         mask_plane_stride, (CcObject*)d_objects + (size_t)i0 * capacity, capacity,
+                                         d_counts + (size_t)i0 * nclasses, (int*)(d_rois + i0), s);
+        if (st) return st;
+    }
+    return RTDM_OK;
+}
+
+// room for `entries` records in the handle's device staging of the host entry points
+int rtdm::objects_stage(rtdm_objects* ob, size_t entries)
+{
+    if (entries <= ob->objCap) return RTDM_OK;
+    if (ob->dObj) { HIPC(hipStreamSynchronize(ob->stream)); HIPC(hipFree(ob->dObj)); }
+    ob->dObj = nullptr; ob->objCap = 0;
+    HIPC(hipMalloc(&ob->dObj, entries * sizeof(CcObject)));
+    ob->objCap = entries;
+    return RTDM_OK;
+}
+
+int rtdm_objects_detect_batch(rtdm_objects* ob, int n, const uint8_t* rgb, size_t pitch, size_t frame_stride,
+                              const rtdm_hsv_range* ranges, const int* range_class, int nranges, int nclasses, int min_area,
+                              int zero_border, uint8_t* masks, size_t mask_pitch, size_t mask_plane_stride,
+                              rtdm_object* objects, int capacity, int* counts, rtdm_region* rois)
+{
+    HsvClasses C;
+    int rc = objects_batch_check(ob, n, rgb, pitch, frame_stride, ranges, range_class, nranges, nclasses, masks, mask_pitch,
+                                 mask_plane_stride, objects, capacity, counts, rois, &C);
+    if (rc) return rc;
+    if (n == 0) return RTDM_OK;
+    HIPC(hipSetDevice(ob->device));
+    hipStream_t s = ob->stream;
+    DrainOnError drain{s};
+    const int W = ob->W, H = ob->H, K = nclasses;
+    const size_t rp = objects_rgb_pitch(ob), rf = rp * H, ip = ob->mpitch, iplane = ip * H;
+    // a frame never has more than K * maxRec objects: the staging need not follow a larger capacity
+    const int cap = (int)std::min((size_t)capacity, (size_t)K * ob->maxRec);
+    rc = objects_stage(ob, (size_t)std::min(ob->maxB, n) * cap);
+    if (rc) return rc;
+    int* dCounts = ob->dMeta;
+    int* dRois = ob->dMeta + (size_t)ob->maxB * ob->maxC;
+    for (int i0 = 0; i0 < n; i0 += ob->maxB) {
+        const int m = std::min(ob->maxB, n - i0);
+        for (int j = 0; j < m; ++j)
+            HIPC(hipMemcpy2DAsync(ob->dRgb + j * rf, rp, rgb + (size_t)(i0 + j) * frame_stride, pitch, (size_t)W * 3, H, hipMemcpyHostToDevice, s));
+        rc = objects_run_chunk(ob, m, ob->dRgb, rp, rf, C, min_area, zero_border, nullptr, 0, 0, ob->dObj, cap, dCounts, dRois, s);
+        if (rc) return rc;
+        int* hCounts = ob->hRec;
+        int* hRois = ob->hRec + m * K;
+        HIPC(hipMemcpyAsync(hCounts, dCounts, (size_t)m * K * sizeof(int), hipMemcpyDeviceToHost, s));
+        HIPC(hipMemcpyAsync(hRois, dRois, (size_t)m * 4 * sizeof(int), hipMemcpyDeviceToHost, s));
+        HIPC(hipStreamSynchronize(s));
+        for (int j = 0; j < m; ++j) {
+            long total = 0;
+            for (int c = 0; c < K; ++c) { counts[(size_t)(i0 + j) * K + c] = hCounts[j * K + c]; total += hCounts[j * K + c]; }
+            rois[i0 + j] = rtdm_region{hRois[4 * j], hRois[4 * j + 1], hRois[4 * j + 2], hRois[4 * j + 3]};
+            const size_t stored = (size_t)std::min<long>(total, cap);                  // O4: the rest of the caller's array stays as it is
+            if (stored) HIPC(hipMemcpyAsync(objects + (size_t)(i0 + j) * capacity, ob->dObj + (size_t)j * cap, stored * sizeof(rtdm_object),
+                                            hipMemcpyDeviceToHost, s));
+            for (int c = 0; masks && c < K; ++c)
+                HIPC(hipMemcpy2DAsync(masks + ((size_t)(i0 + j) * K + c) * mask_plane_stride, mask_pitch,
+                                      ob->dMaskOut + ((size_t)j * K + c) * iplane, ip, (size_t)W, H, hipMemcpyDeviceToHost, s));
+        }
+        HIPC(hipStreamSynchronize(s));
+    }
+    drain.armed = false;
     return RTDM_OK;
 }

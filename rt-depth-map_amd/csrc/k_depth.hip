@@ -82,7 +82,7 @@ size_t depth_scratch_bytes(int max_regions, int maxH)
 // scratch layout: [minval | regions n*4 int | psum n*maxH double | pcnt n*maxH int | mean n double | counts n int]
 void launch_depth_stats(const int16_t* disp, size_t pitch_e, int W, int H, const DepthQ& q, const uint8_t* mask, size_t mpitch,
                         const int* h_regions, int n, int maxH, double unit, void* scratch, double* h_mean, int* h_counts,
-                        hipStream_t stream)
+                        hipStream_t stream, bool reuse_min)
 {
     unsigned char* p = (unsigned char*)scratch;
     int* minval = (int*)p; p += 16;
@@ -94,9 +94,9 @@ void launch_depth_stats(const int16_t* disp, size_t pitch_e, int W, int H, const
     int* counts = (int*)p;
     // initial minimum written on the device (0x7f7f7f7f is above any int16): an async copy from a stack local would
     // only be safe if the runtime staged pageable sources at enqueue time
-    (void)hipMemsetAsync(minval, 0x7f, 4, stream);
+    if (!reuse_min) (void)hipMemsetAsync(minval, 0x7f, 4, stream);
     (void)hipMemcpyAsync(dreg, h_regions, (size_t)n * 16, hipMemcpyHostToDevice, stream);
-    hipLaunchKernelGGL(k_depth_min, dim3(256), dim3(256), 0, stream, disp, pitch_e, W, H, minval);
+    if (!reuse_min) hipLaunchKernelGGL(k_depth_min, dim3(256), dim3(256), 0, stream, disp, pitch_e, W, H, minval);
     if (n > 0) {
         hipLaunchKernelGGL(k_depth_rows, dim3(maxH, n), dim3(256), 0, stream, disp, pitch_e, mask, mpitch, q, dreg, minval, maxH, psum, pcnt);
         hipLaunchKernelGGL(k_depth_final, dim3((n + 63) / 64), dim3(64), 0, stream, psum, pcnt, dreg, n, maxH, unit, mean, counts);

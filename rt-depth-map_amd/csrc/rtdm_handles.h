@@ -69,10 +69,15 @@ struct rtdm_rectify {
 
 struct rtdm_objects {
     int W, H, device, maxRec;
-    uint8_t *dRgb, *dMaskIn, *dMaskOut, *dT0, *dT1;
+    int maxB, maxC;               // frames x class planes of one launch (rtdm_objects_create_batch)
+    size_t mpitch;                // row pitch of the class planes in dMaskIn / dMaskOut: W rounded up to 4
+    uint8_t *dRgb, *dMaskIn, *dMaskOut, *dT0, *dT1;   // [maxB] frames, [maxB * maxC] planes each
     rtdm::MorphSetting morph;     // rtdm_objects_set_morph
-    void* dScratch;
-    int* hRec;                    // pinned: [0] = count, then the first HEAD records
+    void* dScratch;               // [maxB * maxC] x cc_plane_bytes
+    int* dMeta;                   // host entry points: [maxB * maxC] counts, then [maxB] union boxes
+    rtdm::CcObject* dObj;         // host entry points: object lists, grown on demand (objCap entries; not in `mem`)
+    size_t objCap;
+    int* hRec;                    // pinned: [0] = count, then the first HEAD records (the batched calls: counts, union boxes)
     std::vector<int> all;         // host copy of every record when there are more than HEAD
     rtdm::AllocList mem;
     hipStream_t stream;
@@ -152,6 +157,15 @@ int rectify_upload(rtdm_rectify* rc, const uint8_t* a, size_t apitch, const uint
 void rectify_gray_launch(rtdm_rectify* rc, const uint8_t* dl, const uint8_t* dr, int n, Plane8W ol, Plane8W orr, hipStream_t s);
 int objects_run(rtdm_objects* ob, const rtdm_hsv_range* range, int min_area, int zero_border, rtdm_region* boxes, int max_boxes,
                 int* nboxes, rtdm_region* roi, hipStream_t s);
+// api_objects.hip, the batched detector.  objects_classes_check: the refusals that concern ranges and classes (no handle
+// needed) and the kernel's form of them.  objects_run_chunk: one chunk (m <= maxB) of device frames enqueued on s; d_masks
+// null: the filtered planes stay in ob->dMaskOut (rows of ob->mpitch).  objects_stage: ob->dObj holds `entries` records.
+size_t objects_rgb_pitch(const rtdm_objects* ob);
+int objects_classes_check(const rtdm_hsv_range* ranges, const int* range_class, int nranges, int nclasses, HsvClasses* C);
+int objects_run_chunk(rtdm_objects* ob, int m, const uint8_t* d_rgb, size_t pitch, size_t frame_stride, const HsvClasses& C,
+                      int min_area, int zero_border, uint8_t* d_masks, size_t mask_pitch, size_t mask_plane_stride,
+                      CcObject* d_objects, int capacity, int* d_counts, int* d_rois, hipStream_t s);
+int objects_stage(rtdm_objects* ob, size_t entries);
 int wls_check(const rtdm_wls* h, int channels, int W, int H);
 int wls_chunk(rtdm_wls* h, int n, WlsDisp dl, WlsDisp dr, WlsGuide G, WlsOut o, int W, int H, hipStream_t s);
 int wls_download(rtdm_wls* h, int W, int H, int16_t* out, size_t out_pitch, float* conf, size_t conf_pitch, float* filtered,

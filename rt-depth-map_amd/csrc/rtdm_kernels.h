@@ -247,10 +247,11 @@ void sgm_cost16_set(int on);
 struct DepthQ { double q[16]; };
 size_t depth_scratch_bytes(int max_regions, int maxH);
 // h_regions: n x (x, y, w, h) on the host, inside the image; rows of a region are summed by one workgroup each
-// (maxH >= the tallest region).  Results arrive in h_mean / h_counts after the stream is synchronised.
+// (maxH >= the tallest region).  Results arrive in h_mean / h_counts after the stream is synchronised.  reuse_min: the
+// map's minimum is still in `scratch` from the call before on the same stream, map and scratch (another mask, other regions).
 void launch_depth_stats(const int16_t* disp, size_t pitch_e, int W, int H, const DepthQ& q, const uint8_t* mask, size_t mpitch,
                         const int* h_regions, int n, int maxH, double unit, void* scratch, double* h_mean, int* h_counts,
-                        hipStream_t stream);
+                        hipStream_t stream, bool reuse_min = false);
 
 // Rectification in front of the matcher (estimator.cpp:29-39).  RectifySrc: n RGB frames, pitch/frame in bytes.
 struct RectifySrc { const uint8_t* base; size_t pitch, frame; };
@@ -275,6 +276,23 @@ size_t cc_scratch_bytes(int W, int H, int max_records);
 // records: (first pixel index, x, y, w, h, external) per 8-connected foreground component, in no particular order
 void launch_cc_boxes(const uint8_t* mask, size_t mpitch, int W, int H, int zero_border, void* scratch, int max_records,
                      int** d_count, int** d_records, hipStream_t stream);
+// Frame batches and colour classes (rules O1-O6).  HsvClasses travels BY VALUE in the kernel
+// arguments: nranges ranges (H, S, V inclusive), each owned by class cls[i] < nclasses.
+#define HSV_MAX_RANGES 16
+#define HSV_MAX_CLASSES 8
+struct HsvClasses { int lo[HSV_MAX_RANGES][3], hi[HSV_MAX_RANGES][3], cls[HSV_MAX_RANGES], nranges, nclasses; };
+void hsv_tables_ready(hipStream_t stream);   // the conversion's tables of this device are filled (synchronises the first time)
+// n frames -> n * nclasses raw class masks, plane f * nclasses + c at mask + (f * nclasses + c) * mplane
+void launch_hsv_classes(const uint8_t* rgb, size_t pitch, size_t frame, int n, int W, int H, const HsvClasses& C, uint8_t* mask,
+                        size_t mpitch, size_t mplane, hipStream_t stream);
+struct CcObject { int x, y, w, h, cls, first_pixel, reserved[2]; };          // rtdm_object
+size_t cc_plane_bytes(int W, int H, int max_records);                        // cc_scratch_bytes, rounded up to 64
+// Labels the n * nclasses planes (scratch: cc_plane_bytes each) and selects on the device: frame f's kept boxes, class
+// ascending and first pixel descending inside a class, at objects + f * capacity (positions >= capacity are not written);
+// counts[f * nclasses + c]: kept boxes of the plane; rois: 4 ints per frame, the union box (x, y, w, h) of all of them.
+void launch_cc_objects(const uint8_t* mask, size_t mpitch, size_t mplane, int n, int nclasses, int W, int H, int zero_border,
+                       int min_area, void* scratch, int max_records, CcObject* objects, int capacity, int* counts, int* rois,
+                       hipStream_t stream);
 
 // Disparity WLS post-filter (k_wls.hip, rules W1-W8 in DESIGN.md section 4.9).  Internal planes (F, weights, confidence,
 // window statistics) share one layout: element (f, y, x) at f * frame + y * pitch + x.

@@ -102,7 +102,42 @@ HIPObjectsCore::HIPObjectsCore(int cols, int rows, int device)
     status_ = rtdm_objects_create(cols, rows, device, &ob_);
     if (status_ != RTDM_OK) std::fprintf(stderr, "HIPObjects: %s\n", rtdm_strerror(status_));
 }
+HIPObjectsCore::HIPObjectsCore(int cols, int rows, int device, int maxBatch, int maxClasses)
+{
+    setRange(0, 150, 0, 9, 255, 255);
+    status_ = rtdm_objects_create_batch(cols, rows, maxBatch, maxClasses, device, &ob_);
+    if (status_ != RTDM_OK) std::fprintf(stderr, "HIPObjects: %s\n", rtdm_strerror(status_));
+}
 HIPObjectsCore::~HIPObjectsCore() { rtdm_objects_destroy(ob_); }
+int HIPObjectsCore::setRanges(const rtdm_hsv_range* ranges, const int* cls, int nranges, int nclasses)
+{
+    if (!ranges || !cls) return RTDM_ERR_NULL;
+    if (nranges < 1 || nranges > RTDM_MAX_HSV_RANGES || nclasses < 1 || nclasses > RTDM_MAX_CLASSES) return RTDM_ERR_BAD_PARAM;
+    for (int i = 0; i < nranges; ++i) { ranges_[i] = ranges[i]; cls_[i] = cls[i]; }
+    nranges_ = nranges; nclasses_ = nclasses;
+    return RTDM_OK;
+}
+int HIPObjectsCore::detectDevice(int n, const uint8_t* dRgb, size_t step, size_t frameStride, int minObjSize, bool zeroBorder,
+                                 uint8_t* dMasks, size_t maskStep, size_t maskPlaneStride, rtdm_object* dObjects, int capacity,
+                                 int* dCounts, Rect* dRois, void* hipStream)
+{
+    if (!ob_) return status_ != RTDM_OK ? status_ : RTDM_ERR_NO_DEVICE;
+    return status_ = rtdm_objects_detect_device(ob_, n, dRgb, step, frameStride, ranges_, cls_, nranges_, nclasses_, minObjSize,
+                                                zeroBorder ? 1 : 0, dMasks, maskStep, maskPlaneStride, dObjects, capacity, dCounts,
+                                                reinterpret_cast<rtdm_region*>(dRois), hipStream);
+}
+int HIPObjectsCore::estimateFrameClasses(HIPMatcherCore& matcher, HIPRectifierCore& rectifier, const uint8_t* rgbLeft, size_t leftStep,
+                                         const uint8_t* rgbRight, size_t rightStep, const double* Q, int minObjSize, bool zeroBorder,
+                                         double calibrationUnit, rtdm_object* objects, double* meanCm, int* counts, int maxObjects,
+                                         int16_t* disp, size_t dispStep)
+{
+    if (!ob_ || !matcher.handle() || !rectifier.handle()) return status_ != RTDM_OK ? status_ : RTDM_ERR_NO_DEVICE;
+    int n = 0;
+    status_ = rtdm_estimate_frame_classes(matcher.handle(), rectifier.handle(), ob_, rgbLeft, leftStep, rgbRight, rightStep, Q, ranges_,
+                                          cls_, nranges_, nclasses_, minObjSize, zeroBorder ? 1 : 0, calibrationUnit, objects, meanCm,
+                                          counts, maxObjects, &n, disp, dispStep);
+    return status_ == RTDM_OK ? n : status_;
+}
 void HIPObjectsCore::setRange(int lowH, int lowS, int lowV, int highH, int highS, int highV)
 {
     range_.low[0] = lowH; range_.low[1] = lowS; range_.low[2] = lowV;

@@ -229,6 +229,8 @@ private:
 class HIPObjectsCore {
 public:
     HIPObjectsCore(int cols, int rows, int device = 0);       // size of the crop (roif)
+    // for frame batches and several colour classes: up to maxBatch frames x maxClasses class planes per launch
+    HIPObjectsCore(int cols, int rows, int device, int maxBatch, int maxClasses);
     ~HIPObjectsCore();
     HIPObjectsCore(const HIPObjectsCore&) = delete;
     HIPObjectsCore& operator=(const HIPObjectsCore&) = delete;
@@ -242,11 +244,30 @@ public:
                       const uint8_t* rgbRight, size_t rightStep, const double* Q, int minObjSize, bool zeroBorder,
                       double calibrationUnit, Rect* boxes, double* meanCm, int* counts, int maxBoxes,
                       int16_t* disp = nullptr, size_t dispStep = 0);
+    // Several colour classes (include/rtdm.h, rules O1-O6): nranges ranges, cls[r] in [0, nclasses) the class of range r, every
+    // class with a range of its own (red: {0..9} and {170..179} in one class).  Kept for detectDevice / estimateFrameClasses;
+    // setRange and detect / estimateFrame are not touched by it.  Returns a status.
+    int setRanges(const rtdm_hsv_range* ranges, const int* cls, int nranges, int nclasses);
+    int classes() const { return nclasses_; }
+    // n device-resident frames on hipStream, not synchronised: frame f's objects at dObjects + f * capacity (class ascending),
+    // dCounts[f * classes() + c], dRois[f]; dMasks (plane f * classes() + c) may be null.  Returns a status.
+    int detectDevice(int n, const uint8_t* dRgb, size_t step, size_t frameStride, int minObjSize, bool zeroBorder, uint8_t* dMasks,
+                     size_t maskStep, size_t maskPlaneStride, rtdm_object* dObjects, int capacity, int* dCounts, Rect* dRois,
+                     void* hipStream);
+    // estimateFrame for the classes of setRanges: every object with its class, measured under its class's mask.  Returns the
+    // number of objects (only maxObjects are stored) or a negative status.
+    int estimateFrameClasses(HIPMatcherCore& matcher, HIPRectifierCore& rectifier, const uint8_t* rgbLeft, size_t leftStep,
+                             const uint8_t* rgbRight, size_t rightStep, const double* Q, int minObjSize, bool zeroBorder,
+                             double calibrationUnit, rtdm_object* objects, double* meanCm, int* counts, int maxObjects,
+                             int16_t* disp = nullptr, size_t dispStep = 0);
     int status() const { return status_; }
 
 private:
     rtdm_objects* ob_ = nullptr;
     rtdm_hsv_range range_;
+    rtdm_hsv_range ranges_[RTDM_MAX_HSV_RANGES];
+    int cls_[RTDM_MAX_HSV_RANGES];
+    int nranges_ = 0, nclasses_ = 0;
     int status_ = RTDM_OK;
 };
 

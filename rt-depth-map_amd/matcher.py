@@ -1029,14 +1029,31 @@ def _hsv_range(low, high):
     return B.HsvRange((C.c_int * 3)(*[int(v) for v in low]), (C.c_int * 3)(*[int(v) for v in high]))
 
 
+OBJECT_DTYPE = np.dtype([(n, "<i4") for n in ("x", "y", "width", "height", "cls", "first_pixel")] + [("reserved", "<i4", (2,))])   # rtdm_object
+
+
+def _hsv_classes(ranges, classes):
+    """ranges: [(low, high)], classes: one class id per range (None: one class per range) -> (HsvRange[], int[], nranges, nclasses)."""
+    ranges = list(ranges)
+    classes = list(range(len(ranges))) if classes is None else [int(c) for c in classes]
+    if len(classes) != len(ranges):
+        raise ValueError("%d ranges but %d class ids" % (len(ranges), len(classes)))
+    n = len(ranges)
+    rng = (B.HsvRange * max(n, 1))(*[_hsv_range(lo, hi) for lo, hi in ranges])
+    cls = (C.c_int * max(n, 1))(*classes)
+    return rng, cls, n, (max(classes) + 1 if classes else 0)
+
+
 class HIPObjectDetector:
     """estimator.cpp:40-53 on the device: HSV threshold -> morphological filter -> external components -> boxes.  The filter
-    is the reference's open + close with the 10x10 ellipse unless set_op chose another (as HIPMorphologicalFilter.set_op)."""
+    is the reference's open + close with the 10x10 ellipse unless set_op chose another (as HIPMorphologicalFilter.set_op).
+    max_batch frames x max_classes colour classes go through one launch of the batched calls (detect_classes, detect_device)."""
 
-    def __init__(self, width, height, device=0):
-        self.width, self.height = width, height
+    def __init__(self, width, height, device=0, max_batch=1, max_classes=1):
+        self.width, self.height, self.max_batch, self.max_classes = width, height, max_batch, max_classes
         self._h = C.c_void_p()
-        B.check(B.lib().rtdm_objects_create(width, height, device, C.byref(self._h)), "rtdm_objects_create")
+        B.check(B.lib().rtdm_objects_create_batch(width, height, max_batch, max_classes, device, C.byref(self._h)),
+                "rtdm_objects_create_batch")
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
@@ -1067,6 +1084,66 @@ class HIPObjectDetector:
         out = [(b.x, b.y, b.width, b.height) for b in boxes[:min(n.value, max_boxes)]]
         return out, (roi.x, roi.y, roi.width, roi.height), mask
 
+    def detect_classes(self, rgbs, ranges, classes=None, min_area=100, zero_border=True, capacity=256, want_masks=True):
+        """rgbs: n x H x W x 3 uint8 (R first); ranges: [(low, high)]; classes: the class id of every range (None: one class
+        per range) -> (objects, rois, counts, masks): per frame the list of (x, y, w, h, cls) -- class ascending, at most
+        `capacity` of them --, the union box (x, y, w, h) of all of the frame's objects, counts n x nclasses (not clipped) and
+        the filtered masks n x nclasses x H x W (None without want_masks)."""
+        rgbs = np.asarray(rgbs)
+        if rgbs.dtype != np.uint8 or rgbs.ndim != 4 or rgbs.shape[1:] != (self.height, self.width, 3):
+            raise ValueError("rgbs must be uint8 n x %d x %d x 3; got %s %s" % (self.height, self.width, rgbs.dtype, rgbs.shape))
+        if rgbs.strides[2] != 3 or rgbs.strides[3] != 1 or rgbs.strides[1] < 3 * self.width or rgbs.strides[0] < 0:
+            raise ValueError("the pixels of a row must be contiguous; got strides %s" % (rgbs.strides,))
+        rng, cls, nr, K = _hsv_classes(ranges, classes)
+        n, H, W = rgbs.shape[0], self.height, self.width
+        objs = np.zeros((n, capacity), OBJECT_DTYPE)
+        counts = np.zeros((n, max(K, 1)), np.int32); rois = np.zeros((n, 4), np.int32)
+        masks = np.empty((n, max(K, 1), H, W), np.uint8) if want_masks else None
+        B.check(B.lib().rtdm_objects_detect_batch(self._h, n, rgbs.ctypes.data, rgbs.strides[1], rgbs.strides[0], rng, cls, nr, K,
+                                                  int(min_area), int(zero_border), masks.ctypes.data if want_masks else None, W, W * H,
+                                                  objs.ctypes.data, capacity, counts.ctypes.data, rois.ctypes.data),
+                "rtdm_objects_detect_batch")
+        out = []
+        for f in range(n):
+            o = objs[f, :min(int(counts[f].sum()), capacity)]
+            out.append(list(zip(o["x"].tolist(), o["y"].tolist(), o["width"].tolist(), o["height"].tolist(), o["cls"].tolist())))
+        return out, [tuple(int(v) for v in r) for r in rois], counts, masks
+
+    def detect_device(self, d_rgb, ranges, classes, d_objects, d_counts, d_rois, d_masks=None, min_area=100, zero_border=True,
+                      capacity=None, stream=None):
+        """torch device tensors: uint8 [n,H,W,3] frames (row pitch and frame stride free); d_objects: uint8 [n, >= capacity * 32]
+        (frame i's records in row i, rows contiguous; view it as OBJECT_DTYPE on the host); d_counts: int32 [n, nclasses];
+        d_rois: int32 [n, 4]; optional d_masks: uint8 [n, nclasses, H, W] (row pitch and plane stride free).  capacity: records
+        per frame, what a row of d_objects holds when None.  Enqueued on `stream` (a raw hipStream_t value; None = the null
+        stream), not synchronised."""
+        import torch
+        rng, cls, nr, K = _hsv_classes(ranges, classes)
+        if d_rgb.dtype != torch.uint8 or d_rgb.dim() != 4 or tuple(d_rgb.shape[1:]) != (self.height, self.width, 3):
+            raise ValueError("d_rgb must be uint8 n x %d x %d x 3; got %s %s" % (self.height, self.width, d_rgb.dtype, tuple(d_rgb.shape)))
+        rp, rpitch, rframe = HIPReprojector._dev(d_rgb, "d_rgb", torch.uint8)
+        n, H, W = d_rgb.shape[0], self.height, self.width
+        if d_objects.dtype != torch.uint8 or d_objects.dim() != 2 or d_objects.shape[0] != n or not d_objects.is_contiguous():
+            raise ValueError("d_objects must be a contiguous uint8 tensor of n rows; got %s %s" % (d_objects.dtype, tuple(d_objects.shape)))
+        if capacity is None:
+            capacity = d_objects.shape[1] // 32
+        if capacity < 0 or capacity * 32 != d_objects.shape[1]:
+            raise ValueError("rows of d_objects must hold exactly capacity * 32 bytes; got %d for capacity %d" % (d_objects.shape[1], capacity))
+        if d_counts.dtype != torch.int32 or tuple(d_counts.shape) != (n, K) or not d_counts.is_contiguous():
+            raise ValueError("d_counts must be a contiguous int32 tensor n x nclasses")
+        if d_rois.dtype != torch.int32 or tuple(d_rois.shape) != (n, 4) or not d_rois.is_contiguous():
+            raise ValueError("d_rois must be a contiguous int32 tensor n x 4")
+        mp, mpitch, mplane = None, 0, 0
+        if d_masks is not None:
+            if d_masks.dtype != torch.uint8 or tuple(d_masks.shape) != (n, K, H, W):
+                raise ValueError("d_masks must be uint8 n x nclasses x H x W; got %s %s" % (d_masks.dtype, tuple(d_masks.shape)))
+            st = d_masks.stride()
+            if st[3] != 1 or st[2] < W or st[1] < st[2] * H or (n > 1 and st[0] != K * st[1]):
+                raise ValueError("d_masks: contiguous rows and one stride from plane to plane; got strides %s" % (tuple(st),))
+            mp, mpitch, mplane = d_masks.data_ptr(), st[2], st[1]
+        B.check(B.lib().rtdm_objects_detect_device(self._h, n, rp, rpitch, rframe, rng, cls, nr, K, int(min_area), int(zero_border),
+                                                   mp, mpitch, mplane, d_objects.data_ptr(), capacity, d_counts.data_ptr(),
+                                                   d_rois.data_ptr(), stream), "rtdm_objects_detect_device")
+
 
 def estimate_frame(matcher, rectifier, detector, rgb_left, rgb_right, Q, low=HSV_LOW, high=HSV_HIGH, min_area=100,
                    zero_border=True, calibration_unit=25.0, max_boxes=64, want_disp=False):
@@ -1087,6 +1164,31 @@ def estimate_frame(matcher, rectifier, detector, rgb_left, rgb_right, Q, low=HSV
             "rtdm_estimate_frame")
     k = min(n.value, max_boxes)
     out = [(b.x, b.y, b.width, b.height) for b in boxes[:k]]
+    return (out, mean[:k], cnt[:k], disp) if want_disp else (out, mean[:k], cnt[:k])
+
+
+def estimate_frame_classes(matcher, rectifier, detector, rgb_left, rgb_right, Q, ranges, classes=None, min_area=100,
+                           zero_border=True, calibration_unit=25.0, max_objects=64, want_disp=False):
+    """estimate_frame for several colour classes (ranges / classes as HIPObjectDetector.detect_classes): the matcher's ROI is
+    the union box over all classes, every object is measured under the mask of its own class
+    -> (objects [(x, y, w, h, cls)], mean_cm, counts[, disp])."""
+    rectifier._check_rgb(rgb_left); rectifier._check_rgb(rgb_right)
+    rw, rh = rectifier.roi[2], rectifier.roi[3]
+    objs = np.zeros(max_objects, OBJECT_DTYPE); n = C.c_int()
+    mean = np.zeros(max_objects, np.float64); cnt = np.zeros(max_objects, np.int32)
+    q = np.ascontiguousarray(Q, np.float64).reshape(16)
+    disp = np.empty((rh, rw), np.int16) if want_disp else None
+    rng, cls, nr, K = _hsv_classes(ranges, classes)
+    B.check(B.lib().rtdm_estimate_frame_classes(matcher._h, rectifier._h, detector._h, rgb_left.ctypes.data, rgb_left.strides[0],
+                                                rgb_right.ctypes.data, rgb_right.strides[0], q.ctypes.data_as(C.POINTER(C.c_double)),
+                                                rng, cls, nr, K, int(min_area), int(zero_border), calibration_unit, objs.ctypes.data,
+                                                mean.ctypes.data_as(C.POINTER(C.c_double)), cnt.ctypes.data_as(C.POINTER(C.c_int)),
+                                                max_objects, C.byref(n), disp.ctypes.data if want_disp else None, rw * 2),
+            "rtdm_estimate_frame_classes")
+    k = min(n.value, max_objects)
+    o = objs[:k]
+    out = list(zip(o["x"].tolist(), o["y"].tolist(), o["width"].tolist(), o["height"].tolist(), o["cls"].tolist()))
+    k = min(k, B.MAX_REGIONS)
     return (out, mean[:k], cnt[:k], disp) if want_disp else (out, mean[:k], cnt[:k])
 
 
