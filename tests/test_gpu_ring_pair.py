@@ -6,6 +6,7 @@ border workgroups in the grid: batch 1; tile-only: batches of 16 and 17)."""
 import numpy as np
 import pytest
 
+import hostile_pairs
 from conftest import load
 
 pytestmark = pytest.mark.gpu
@@ -16,6 +17,7 @@ HEIGHTS = (10, 11, 12, 13, 17)                 # valid rows H - 8: 2 .. 5 and 9 
 # ONE valid row: a frame of 9 rows is refused like cv::StereoBM refuses it (blockSize >= height), so the search gets its single
 # row from a frame of 10 rows whose setROI1 rectangle is 9 rows high (the valid rectangle loses 4 rows at either end)
 ONE_ROW = (10, 9)
+HOSTILE_OFF = dict(uniquenessRatio=0, textureThreshold=0, speckleWindowSize=0, disp12MaxDiff=-1)
 HIGH_TEX = 600                                 # noise sums to ~2000 per window, a plateau to 0: plateau waves skip the selection
 
 
@@ -27,26 +29,12 @@ def pkg():
 
 
 def _noise(seed, W, H, n=1):
-    rng = np.random.default_rng(seed)
-    L = rng.integers(0, 256, (n, H, W + D), dtype=np.uint8)
-    # the right view: the left one shifted by a few disparities per band of rows, plus a little noise of its own
-    R = np.empty((n, H, W), np.uint8)
-    for y in range(H):
-        d = 3 + (y // 5 * 7) % (D - 6)
-        R[:, y] = L[:, y, d:d + W]
-    R ^= (rng.random((n, H, W)) < 0.05).astype(np.uint8) * 8
-    return np.ascontiguousarray(L[:, :, D:]), R
+    return hostile_pairs.noise_bands(seed, W, H, D, n)
 
 
 def _plateaus(seed, W, H, n=1):
     # constant blocks in both views: zero texture, and every SAD inside them ties (the FIRST minimum has to win)
-    L, R = _noise(seed, W, H, n)
-    rng = np.random.default_rng(seed + 1)
-    for img in (L, R):
-        for _ in range(3 + W * H // 1500):
-            x, y = int(rng.integers(0, W)), int(rng.integers(0, H))
-            img[:, y:y + int(rng.integers(2, 24)), x:x + int(rng.integers(3, 90))] = int(rng.integers(0, 256))
-    return L, R
+    return hostile_pairs.plateau_noise_n(seed, W, H, D, n)
 
 
 def _synth(seed, W, H, n=1):
@@ -166,16 +154,20 @@ def test_strips_longer_than_the_rebase_interval(pkg, oracle, cap):
     # rebases of both rings; at cap 31 (100 rows) one.  The frames are copies of four: every frame must be its source's map.
     import torch
     n, W, H = 8192, 128, 200
-    L, R = _plateaus(900 + cap, W, H, 4)
-    dL = torch.from_numpy(L).cuda().repeat(n // 4, 1, 1)
-    dR = torch.from_numpy(R).cuda().repeat(n // 4, 1, 1)
-    dD = torch.full((n, H, W), 12345, dtype=torch.int16, device="cuda")
-    m = pkg.HIPMatcher(numOfDisparities=D, blockSize=WS, preFilterCap=cap, width=W, height=H, max_batch=n)
-    m.compute_device(dL, dR, dD, torch.cuda.current_stream().cuda_stream)
-    torch.cuda.synchronize()
-    assert m.search_variant == "fast_ring4_qsad"
-    m.close()
-    want = np.stack([oracle.bm_compute(L[i], R[i], numDisparities=D, blockSize=WS, preFilterCap=cap) for i in range(4)])
-    dW = torch.from_numpy(want).cuda().repeat(n // 4, 1, 1)
-    bad = (dD != dW).flatten(1).any(1).nonzero().flatten()
-    assert bad.numel() == 0, "cap %d: %d frames differ, first %d" % (cap, bad.numel(), int(bad[0]))
+    # (plateaus; then the two families of tests/hostile_pairs.py whose window sums attain 2 cap w w -- the prefix sums grow as
+    # fast as the rebase interval allows -- with every threshold off, or uniqueness would filter their tied minima)
+    for content, kw in (("plateaus", {}), ("worst", HOSTILE_OFF), ("worst_noise", HOSTILE_OFF)):
+        L, R = _plateaus(900 + cap, W, H, 4) if content == "plateaus" else hostile_pairs.make_n(content, 0, 4, W, H, D, 0, WS)
+        dL = torch.from_numpy(L).cuda().repeat(n // 4, 1, 1)
+        dR = torch.from_numpy(R).cuda().repeat(n // 4, 1, 1)
+        dD = torch.full((n, H, W), 12345, dtype=torch.int16, device="cuda")
+        m = pkg.HIPMatcher(numOfDisparities=D, blockSize=WS, preFilterCap=cap, width=W, height=H, max_batch=n, **kw)
+        m.compute_device(dL, dR, dD, torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+        assert m.search_variant == "fast_ring4_qsad"
+        m.close()
+        want = np.stack([oracle.bm_compute(L[i], R[i], numDisparities=D, blockSize=WS, preFilterCap=cap, **kw) for i in range(4)])
+        dW = torch.from_numpy(want).cuda().repeat(n // 4, 1, 1)
+        bad = (dD != dW).flatten(1).any(1).nonzero().flatten()
+        assert bad.numel() == 0, "%s cap %d: %d frames differ, first %d" % (content, cap, bad.numel(), int(bad[0]))
+        del dL, dR, dD, dW

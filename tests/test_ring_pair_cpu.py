@@ -85,20 +85,19 @@ def _unpack(p):
     return np.stack([p[..., 0] & 0xffff, p[..., 0] >> 16, p[..., 1] & 0xffff, p[..., 1] >> 16], -1).astype(np.int64)
 
 
-@pytest.mark.parametrize("cap,rows,worst", [(31, 230, False), (63, 104, False), (31, 230, True), (63, 104, True)])
-def test_packed_prefix_rings_give_the_window_sums_across_rebases(cap, rows, worst):
-    # the host's arithmetic: ring_rows_cap / TRIP trips between two rebases (k_search_ring.hip)
-    rows_cap = 65535 // (WS * 2 * cap) - WS - 6
-    rebase = rows_cap // TRIP
-    assert rebase > 0 and rows > 2 * rebase * TRIP           # the strip crosses at least two rebases
-    rng = np.random.default_rng(100 + cap)
-    Lr, Rr = _rows(rng, rows, cap, worst)
+def prefix_ring_window_sums(Lr, Rr, rebase, strict=True):
+    """The packed prefix rings of both columns of the pairs walked down the rows Lr [rows, 44], Rr [rows, 108] (one wave's
+    copies, biased bytes), rebased every `rebase` trips as the kernel rebases them (None: never).  Returns (got, want):
+    the window sums read from the rings and the exact ones, [rows - 8, 2, 8, 8, 2, 4].  strict: assert on the way that no
+    16-bit half overflows and every window sum is exact."""
+    rows = len(Lr)
     H1, H2 = [], []                                          # the rows' horizontal SADs per column, exact
     P = np.zeros((2, W1, 8, 8, 2, 2), np.uint32)             # [column of the pair][ring slot][q][h][gi][dword]: packed prefix sums
     since = 0
+    got, wanted = [], []
     for t in range(rows):
         K, KP, KO = t % W1, (t - 1) % W1, (t + 1) % W1
-        if t % TRIP == 0:
+        if t % TRIP == 0 and rebase is not None:
             since += 1
             if since > rebase:                               # a trip starts on slot 0; slot 1 holds the oldest live prefix sum
                 since = 1
@@ -109,12 +108,32 @@ def test_packed_prefix_rings_give_the_window_sums_across_rebases(cap, rows, wors
         e1, e2, sh = _row_pieces(Lr[t], Rr[t])
         H1.append(e1 + sh); H2.append(e2 + sh)
         shp = _pack(sh)
+        row_got, row_want = [], []
         for j, e in ((0, e1), (1, e2)):
             acc = _unpack(P[j, KP]) + e                      # v_mqsad on top of the column's previous prefix sum
-            assert acc.max() < 65536
+            if strict:
+                assert acc.max() < 65536
             P[j, K] = _pack(acc) + shp                       # v_add_u32 per dword: no carry may cross the halves
-            assert np.array_equal(_unpack(P[j, K]), acc + sh), "a 16-bit half overflowed at row %d" % t
+            if strict:
+                assert np.array_equal(_unpack(P[j, K]), acc + sh), "a 16-bit half overflowed at row %d" % t
             S = P[j, K] - P[j, KO]                           # v_sub_u32 per dword
             if t >= WS - 1:
                 want = sum((H1, H2)[j][t - WS + 1:t + 1])
-                assert np.array_equal(_unpack(S), want), (t, j)
+                if strict:
+                    assert np.array_equal(_unpack(S), want), (t, j)
+                row_got.append(_unpack(S)); row_want.append(want)
+        if t >= WS - 1:
+            got.append(np.stack(row_got)); wanted.append(np.stack(row_want))
+    return np.stack(got), np.stack(wanted)
+
+
+@pytest.mark.parametrize("cap,rows,worst", [(31, 230, False), (63, 104, False), (31, 230, True), (63, 104, True)])
+def test_packed_prefix_rings_give_the_window_sums_across_rebases(cap, rows, worst):
+    # the host's arithmetic: ring_rows_cap / TRIP trips between two rebases (k_search_ring.hip)
+    rows_cap = 65535 // (WS * 2 * cap) - WS - 6
+    rebase = rows_cap // TRIP
+    assert rebase > 0 and rows > 2 * rebase * TRIP           # the strip crosses at least two rebases
+    rng = np.random.default_rng(100 + cap)
+    Lr, Rr = _rows(rng, rows, cap, worst)
+    got, want = prefix_ring_window_sums(Lr, Rr, rebase)
+    assert got.shape[0] == rows - WS + 1 and np.array_equal(got, want)

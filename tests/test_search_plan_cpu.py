@@ -8,6 +8,7 @@ import subprocess
 
 import pytest
 
+import hostile_cases
 from conftest import PKG, ROOT
 
 # (W, H, D, w, minD, cap, legacy) -> at n = 1: (tiles, lanes, border form, placement, border grid, variant)
@@ -45,23 +46,36 @@ def exe(tmp_path_factory):
     return out
 
 
-def plans(exe, n, contiguous=1, env=None):
-    """-> {row: dict(tiles, lanes, interior, border, place, left, right, grid, variant)} in a child process"""
-    args = [str(v) for row, _ in TABLE for v in row]
+def plans(exe, n, contiguous=1, env=None, rows=None):
+    """-> {row: dict(tiles, lanes, interior, border, place, left, right, grid, variant)} in a child process; rows: the rows of
+    TABLE unless given"""
+    rows = [row for row, _ in TABLE] if rows is None else list(rows)
     e = dict(os.environ)
     e.pop("RTDM_BORDER2", None)
     e.update(env or {})
-    run = subprocess.run([exe, str(n), str(contiguous)] + args, capture_output=True, text=True, env=e)
+    run = subprocess.run([exe, str(n), str(contiguous)] + [str(v) for row in rows for v in row], capture_output=True, text=True, env=e)
     assert run.returncode == 0, run.stdout + run.stderr
     lines = run.stdout.splitlines()
-    assert len(lines) == len(TABLE)
+    assert len(lines) == len(rows)
     out = {}
-    for (row, _), line in zip(TABLE, lines):
+    for row, line in zip(rows, lines):
         m = LINE.search(line)
         assert m, line
         out[row] = dict(zip(("tiles", "lanes", "interior", "border", "place", "left", "right", "grid", "variant"), m.groups()))
         out[row]["lanes"] = int(out[row]["lanes"])
     return out
+
+
+STRIPS = re.compile(r"n=(\d+): lanes=(\d+) strips=(\d+) rows_per_strip=(\d+) rebase_rows=(\d+)$")
+
+
+def strips(exe, n, row):
+    """-> (lanes per pixel, strips, output rows per strip, rows between two rebases) of the ring launch of a batch of n"""
+    run = subprocess.run([exe, "strips", str(n)] + [str(v) for v in row], capture_output=True, text=True)
+    assert run.returncode == 0, run.stdout + run.stderr
+    m = STRIPS.search(run.stdout.strip())
+    assert m and int(m.group(1)) == n, run.stdout
+    return tuple(int(v) for v in m.groups()[1:])
 
 
 def key(p):
@@ -127,3 +141,63 @@ def test_planes_that_are_not_one_allocation_plan_the_fast_kernel(exe):
         # k_search_fast carries DISP only, and not the 3.x clamp
         assert (b["border"], b["place"]) == (("DISP+LEGACY", "AFTER") if row[6] else ("DISP", "FUSED")), (row, b)
     assert nring == 8
+
+
+def test_largest_cap_of_every_route(exe):
+    # hostile_cases.MAXCAP: the route of a row is the same at that cap, at n = 1 and n = 16, and (below 63) not one step up
+    assert set(hostile_cases.MAXCAP) == {row for row, _ in TABLE[:10]}
+    for n in (1, 16):
+        base = plans(exe, n)
+        top = plans(exe, n, rows=[hostile_cases.with_cap(r, c) for r, c in hostile_cases.MAXCAP.items()])
+        over = plans(exe, n, rows=[hostile_cases.with_cap(r, c + 1) for r, c in hostile_cases.MAXCAP.items() if c < 63])
+        same = lambda a, b: all(a[f] == b[f] for f in ("tiles", "lanes", "border", "place", "grid", "variant"))
+        for r, c in hostile_cases.MAXCAP.items():
+            assert same(base[r], top[hostile_cases.with_cap(r, c)]), (n, r, c, base[r], top[hostile_cases.with_cap(r, c)])
+            assert c >= r[5]
+        if n == 16:                                       # (at n = 1 the 256-disparity row runs DISP at every cap)
+            for r, c in hostile_cases.MAXCAP.items():
+                if c < 63:
+                    assert not same(base[r], over[hostile_cases.with_cap(r, c + 1)]), (r, c + 1, over[hostile_cases.with_cap(r, c + 1)])
+
+
+@pytest.mark.parametrize("n,row,lpp", hostile_cases.LONG_STRIPS + hostile_cases.LONG_STRIPS_64_9_4)
+def test_long_strip_batches_walk_more_than_two_rebase_intervals(exe, n, row, lpp):
+    # what tests/test_gpu_search_hostile.py and tests/test_gpu_ring_pair.py rest on: at these batch sizes the model cuts a frame
+    # into strips that walk (output rows + w - 1) more rows than two rebase intervals, so both prefix rings of a workgroup
+    # are rebased at least twice at the worst-case growth.  (One compute_device call per handle: the tuner keeps the model.)
+    lanes, count, rs, rebase_rows = strips(exe, n, row)
+    W, H, D, w, minD, cap = row[:6]
+    assert lanes == lpp
+    assert rebase_rows == hostile_cases.ring_rebase_trips(D, w, lpp, cap) * hostile_cases.ring_trip(D, w, lpp) > 0
+    assert count * rs >= H - (w - 1) > (count - 1) * rs
+    assert rs + w - 1 > 2 * rebase_rows, (rs, w, rebase_rows)
+    assert n * H * W * 2 <= 45e6 or (D, w, lpp) == (64, 9, 4)      # device input of the new batches: about 40 MB at most
+
+
+def test_border_forms_of_the_hostile_border_rows(exe):
+    rows = [hostile_cases.BORDER_ROWS_ROW, hostile_cases.BORDER_DISP_ROW]
+    one, many = plans(exe, 1, rows=rows), plans(exe, 16, rows=rows)
+    r, d = rows
+    assert (one[r]["border"], one[r]["place"], one[r]["variant"]) == ("ROWS", "FUSED", "fast_ring4_qsad"), one[r]
+    assert (many[r]["border"], many[r]["place"]) == ("ROWS", "SIDE"), many[r]
+    assert 64 * r[3] * 2 * r[5] <= 65535 < 64 * r[3] * 2 * (r[5] + 1)
+    assert (one[d]["border"], one[d]["place"], one[d]["variant"]) == ("DISP", "FUSED", "fast_qsad"), one[d]
+    assert (many[d]["border"], many[d]["place"]) == ("DISP", "SIDE"), many[d]
+    assert 2 * d[5] * d[3] ** 2 <= 32766 < 2 * (d[5] + 1) * d[3] ** 2
+
+
+@pytest.mark.parametrize("n,row,lpp", hostile_cases.NO_REBASE_STRIPS)
+def test_forms_that_do_not_rebase_get_strips_of_the_full_allowed_length(exe, n, row, lpp):
+    # every form of the ring table whose trip is longer than ring_rows_cap at cap 63, and no other
+    lanes, count, rs, rebase_rows = strips(exe, n, row)
+    W, H, D, w, minD, cap = row[:6]
+    assert lanes == lpp and rebase_rows == 0 == hostile_cases.ring_rebase_trips(D, w, lpp, cap)
+    assert count == 3 and rs == hostile_cases.ring_rows_cap(w, cap) and H - (w - 1) == 3 * rs
+    assert n * H * W * 2 <= 45e6
+
+
+def test_the_forms_that_do_not_rebase_are_all_listed():
+    from test_gpu_fuzz import RING_TABLE
+    none = {(D, w, lpp) for D, w, lpp in RING_TABLE for cap in (31, 63) if hostile_cases.ring_rebase_trips(D, w, lpp, cap) == 0}
+    assert none == {(r[2], r[3], lpp) for _, r, lpp in hostile_cases.NO_REBASE_STRIPS}
+    assert all(hostile_cases.ring_rebase_trips(D, w, lpp, 31) > 0 for D, w, lpp in RING_TABLE)
