@@ -307,6 +307,33 @@ int rtdm_bm_compute_depth(rtdm_bm* bm, const uint8_t* left, size_t left_pitch, c
 int rtdm_depth_stats_device(int device, const int16_t* d_disp, size_t disp_pitch, int width, int height, const double* Q,
                             const uint8_t* d_mask, size_t mask_pitch, const rtdm_region* regions, int nregions,
                             double calibration_unit, double* mean_cm, int* counts, void* hip_stream);
+/* rtdm_depth_objects_device: the same reduction for n frames whose object lists lie in device memory as
+ *                          rtdm_objects_detect_device leaves them (rules D1-D6).  Frame f has total_f =
+ *                          sum over c of max(d_counts[f * nclasses + c], 0) objects, the first min(total_f, capacity) of them at
+ *                          d_objects + f * capacity; object i is measured over its box (intersected with the frame) where mask
+ *                          plane f * nclasses + cls (at d_masks + plane * mask_plane_stride) is non-zero, against disparity map
+ *                          f (at d_disp + f * disp_frame_stride bytes) and that map's own minimum.  d_mean_cm[f * capacity + i]
+ *                          and d_npix[f * capacity + i] receive the result; entries at or beyond min(total_f, capacity) are
+ *                          left untouched.  There is no limit on the number of objects.  An object whose cls lies outside
+ *                          [0, nclasses) or whose clipped box is empty gets npix 0 and mean 0.0; no list content makes the
+ *                          kernels read outside the maps, planes and lists.  Bit-identical run to run and independent of n,
+ *                          of the frame's position, of capacity and of the other objects.  Enqueued on hip_stream: the call
+ *                          never synchronises, allocates or copies to the host; Q is read before it returns.  d_workspace: at
+ *                          least rtdm_depth_objects_workspace_bytes(n, capacity, height) bytes of device memory, the call's own
+ *                          until its work has finished (that function needs no device and grows with each argument).
+ *                          n = 0 is RTDM_OK.  Refusals, before any device use: RTDM_ERR_NULL (d_disp, Q, d_masks, d_counts,
+ *                          d_mean_cm, d_npix, d_workspace; d_objects with capacity > 0), RTDM_ERR_BAD_SIZE (n < 0, capacity < 0,
+ *                          width or height <= 0, an odd disp_pitch or disp_frame_stride, disp_pitch < 2 * width, mask_pitch <
+ *                          width, a frame stride below disp_pitch * height or a plane stride below mask_pitch * height where
+ *                          a second frame or plane follows), RTDM_ERR_BAD_PARAM (nclasses outside 1 .. RTDM_MAX_CLASSES),
+ *                          RTDM_ERR_BAD_SIZE (workspace_bytes too small). */
+struct rtdm_object;
+size_t rtdm_depth_objects_workspace_bytes(int n, int capacity, int height);
+int rtdm_depth_objects_device(int device, int n, const int16_t* d_disp, size_t disp_pitch, size_t disp_frame_stride,
+                              int width, int height, const double* Q, const uint8_t* d_masks, size_t mask_pitch,
+                              size_t mask_plane_stride, int nclasses, const struct rtdm_object* d_objects, int capacity,
+                              const int* d_counts, double calibration_unit, double* d_mean_cm, int* d_npix,
+                              void* d_workspace, size_t workspace_bytes, void* hip_stream);
 
 /* ---- the step in front of the matcher, on the device --------------
  * rtdm_rectify_create  <- the maps the reference builds once (main.cpp:95-96, initUndistortRectifyMap(..., CV_16SC2,
@@ -467,6 +494,51 @@ int rtdm_estimate_frame_classes(rtdm_bm* bm, rtdm_rectify* rc, rtdm_objects* ob,
                                 const int* range_class, int nranges, int nclasses, int min_area, int zero_border,
                                 double calibration_unit, rtdm_object* objects, double* mean_cm, int* counts, int max_objects,
                                 int* nobjects, int16_t* disp, size_t disp_pitch);
+
+/* ---- the whole loop body on frame batches -------------------------------------------------------
+ * rtdm_estimator_create: a handle for rtdm_estimate_batch.  It BORROWS the three handles: they must outlive it, live on one
+ *                        device and fit together as rtdm_estimate_frame_classes asks (detector and matcher serve the
+ *                        rectifier's crop).  It owns the raw frames, the rectified gray pairs and the colour crops of one
+ *                        chunk, the object lists and results of a chunk, the depth workspace and page-locked read-back space.
+ *                        A chunk is min(max_batch, the matcher's max_batch, the detector's max_batch) frames; capacity: the
+ *                        objects of a frame that are stored and measured.  Refusals: RTDM_ERR_NULL (out), RTDM_ERR_BAD_SIZE
+ *                        (max_batch < 1, capacity < 1), RTDM_ERR_NULL (a handle), RTDM_ERR_BAD_PARAM (handles of different
+ *                        devices), RTDM_ERR_BAD_SIZE (a detector of another size than the crop, a matcher too small for it).
+ * rtdm_estimate_batch:   rtdm_estimate_frame_classes for n frame pairs (frame f at rgb + f * frame_stride; n may exceed the
+ *                        chunk).  Per chunk: one batched rectification, one detector launch set, ONE read-back of the chunk's
+ *                        counts and union boxes, the matcher (consecutive frames with equal union boxes share a launch set
+ *                        under that ROI1, every other frame runs under its own), one rtdm_depth_objects_device launch set and
+ *                        one download.  objects: frame f's list at objects + f * capacity (the first min(total, capacity)
+ *                        entries, every one of them measured: there is no RTDM_MAX_REGIONS limit here); counts[f * nclasses +
+ *                        c]: kept objects of class c, never clipped; mean_cm / npix[f * capacity + i]: object i of frame f;
+ *                        disp (may be NULL): frame f's x16 map at disp + f * disp_frame_stride bytes.  A frame without objects
+ *                        skips the matcher: its counts are 0 and its disp frame and mean_cm / npix entries are left
+ *                        untouched, as are the entries past the stored ones, as rtdm_estimate_frame leaves them.  ROI1 of the
+ *                        matcher is left at the last frame that had objects, as a loop of single calls leaves it.  Objects,
+ *                        counts, npix and maps are those of rtdm_estimate_frame_classes on each frame alone; the means are
+ *                        the same sums in another fixed order (rule D3).  Refusals, in the order of
+ *                        rtdm_estimate_frame_classes: RTDM_ERR_NULL (frames, Q, outputs), the ranges' and classes' refusals
+ *                        of rtdm_objects_detect_device, RTDM_ERR_BAD_SIZE (n < 0), RTDM_ERR_NULL (the handle),
+ *                        RTDM_ERR_BAD_PARAM (nclasses above the detector's max_classes), RTDM_ERR_BAD_SIZE (a pitch below 3 *
+ *                        width, disp_pitch below 2 * crop width or odd, an odd disp_frame_stride, with n > 1 a frame stride
+ *                        below pitch * height).  n = 0 is RTDM_OK.
+ * rtdm_estimate_batch_device: the same with device frames and device outputs, enqueued on hip_stream, which is synchronised
+ *                        ONCE PER CHUNK (the read-back that decides the matcher's ROI1); the results are complete on the stream
+ *                        when the call returns, not synchronised.  Calls that share handles must be ordered on one stream. */
+typedef struct rtdm_estimator rtdm_estimator;
+int rtdm_estimator_create(rtdm_bm* bm, rtdm_rectify* rc, rtdm_objects* ob, int max_batch, int capacity, rtdm_estimator** out);
+void rtdm_estimator_destroy(rtdm_estimator* est);
+int rtdm_estimate_batch(rtdm_estimator* est, int n, const uint8_t* rgb_left, size_t left_pitch, size_t left_frame_stride,
+                        const uint8_t* rgb_right, size_t right_pitch, size_t right_frame_stride, const double* Q,
+                        const rtdm_hsv_range* ranges, const int* range_class, int nranges, int nclasses, int min_area,
+                        int zero_border, double calibration_unit, rtdm_object* objects, int* counts, double* mean_cm, int* npix,
+                        int16_t* disp, size_t disp_pitch, size_t disp_frame_stride);
+int rtdm_estimate_batch_device(rtdm_estimator* est, int n, const uint8_t* d_rgb_left, size_t left_pitch,
+                               size_t left_frame_stride, const uint8_t* d_rgb_right, size_t right_pitch,
+                               size_t right_frame_stride, const double* Q, const rtdm_hsv_range* ranges, const int* range_class,
+                               int nranges, int nclasses, int min_area, int zero_border, double calibration_unit,
+                               rtdm_object* d_objects, int* d_counts, double* d_mean_cm, int* d_npix, int16_t* d_disp,
+                               size_t disp_pitch, size_t disp_frame_stride, void* hip_stream);
 
 /* ---- the step after the matcher that the reference keeps switched off: the disparity WLS post-filter -------------------
  * ENABLE_POST_FILTER (estimator.cpp:57-70, 106-109; include/estimator.h:32,116) -- cv::ximgproc's createRightMatcher,

@@ -188,6 +188,16 @@ def lib():
         "rtdm_estimate_frame_classes": (C.c_int, [vp, vp, vp, u8p, sz, u8p, sz, C.POINTER(C.c_double), C.POINTER(HsvRange),
                                                   C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, vp,
                                                   C.POINTER(C.c_double), C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), i16p, sz]),
+        "rtdm_depth_objects_workspace_bytes": (sz, [C.c_int, C.c_int, C.c_int]),
+        "rtdm_depth_objects_device": (C.c_int, [C.c_int, C.c_int, i16p, sz, sz, C.c_int, C.c_int, C.POINTER(C.c_double), u8p, sz, sz,
+                                                C.c_int, vp, C.c_int, vp, C.c_double, vp, vp, vp, sz, vp]),
+        "rtdm_estimator_create": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.POINTER(vp)]),
+        "rtdm_estimator_destroy": (None, [vp]),
+        "rtdm_estimate_batch": (C.c_int, [vp, C.c_int, u8p, sz, sz, u8p, sz, sz, C.POINTER(C.c_double), C.POINTER(HsvRange),
+                                          C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, vp, vp, vp, vp, i16p, sz, sz]),
+        "rtdm_estimate_batch_device": (C.c_int, [vp, C.c_int, u8p, sz, sz, u8p, sz, sz, C.POINTER(C.c_double), C.POINTER(HsvRange),
+                                                 C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, vp, vp, vp, vp, i16p,
+                                                 sz, sz, vp]),
         "rtdm_wls_params_for_bm": (C.c_int, [C.POINTER(BMParams), C.POINTER(WLSParams)]),
         "rtdm_wls_params_for_sgm": (C.c_int, [C.POINTER(SGMParams), C.POINTER(WLSParams)]),
         "rtdm_bm_right_params": (C.c_int, [C.POINTER(BMParams), C.POINTER(BMParams)]),
@@ -250,7 +260,9 @@ EXPORTS = ("rtdm_strerror rtdm_last_hip_error rtdm_abi_version rtdm_device_count
            "rtdm_bm_compute_mjpeg rtdm_mjpeg_set_split rtdm_mjpeg_get_split rtdm_mjpeg_get_split_stats rtdm_calib_load rtdm_stereo_rectify rtdm_undistort_rectify_map "
            "rtdm_undistort_rectify_map_device rtdm_rectify_create_calib rtdm_morph_make_element rtdm_morph_set_op rtdm_morph_get_op "
            "rtdm_objects_set_morph rtdm_objects_get_morph rtdm_debug_morph_general rtdm_objects_create_batch "
-           "rtdm_objects_detect_device rtdm_objects_detect_batch rtdm_estimate_frame_classes").split()
+           "rtdm_objects_detect_device rtdm_objects_detect_batch rtdm_estimate_frame_classes "
+           "rtdm_depth_objects_workspace_bytes rtdm_depth_objects_device rtdm_estimator_create rtdm_estimator_destroy "
+           "rtdm_estimate_batch rtdm_estimate_batch_device").split()
 
 
 def check(status, where):

@@ -132,6 +132,21 @@ struct rtdm_mjpeg {
     rtdm::AllocList mem;
 };
 
+struct rtdm_estimator {
+    rtdm_bm* bm; rtdm_rectify* rc; rtdm_objects* ob;      // borrowed
+    int device, chunk, cap;        // frames of one chunk; objects of a frame that are stored and measured
+    size_t cpitch;                 // row pitch of the colour crops (objects_rgb_pitch)
+    uint8_t* dRgb[2];              // host form: the raw frames of a chunk, [chunk] x H x W x 3 each
+    uint8_t* dGray[2];             // rectified gray pairs [chunk][rh][gpitch]
+    uint8_t* dCrop;                // left colour crops    [chunk][rh][cpitch]
+    rtdm::CcObject* dObj; int* dCounts; double* dMean; int* dNpix;      // host form: [chunk] x cap, [chunk] x RTDM_MAX_CLASSES
+    int* dRois;                    // [chunk] x 4
+    void* dWork; size_t workBytes; // rtdm_depth_objects_device's workspace for a chunk
+    // page-locked: the read-back in front of the matcher, then what the host form brings back and takes in
+    int *hCounts, *hRois, *hNpix; rtdm::CcObject* hObj; double* hMean; int16_t* hDisp; uint8_t* hRgb[2];
+    rtdm::AllocList mem;
+};
+
 namespace rtdm {
 
 // api_bm.hip.  bm_run_chunk: one chunk (n <= maxB) of device-resident frames, enqueued on s.  bm_download_disp: the internal

@@ -253,6 +253,21 @@ void launch_depth_stats(const int16_t* disp, size_t pitch_e, int W, int H, const
                         const int* h_regions, int n, int maxH, double unit, void* scratch, double* h_mean, int* h_counts,
                         hipStream_t stream, bool reuse_min = false);
 
+// The same statistics for n frames whose object lists lie on the device (k_depth_objects.hip, rules D1-D6 in DESIGN.md section
+// 4.16).  Travels BY VALUE in the kernel arguments.  disp: frame f at disp + f * dframe_e (elements); mask: plane f * K + c at
+// mask + (f * K + c) * mplane (bytes); obj: frame f's list at obj + f * cap; counts: n * K.  nb is set by the launcher.
+struct CcObject;
+struct DepthObjects {
+    const int16_t* disp; size_t dpitch_e, dframe_e;
+    const uint8_t* mask; size_t mpitch, mplane;
+    const CcObject* obj; const int* counts;
+    int n, W, H, K, cap, nb;
+};
+size_t depth_objects_bytes(int n, int cap, int H);
+// mean / npix: n * cap entries on the device, written for the stored objects only.  Three kernels and one memset on `stream`,
+// nothing else: no allocation, no synchronisation, no copy.
+void launch_depth_objects(DepthObjects a, const DepthQ& q, double unit, void* workspace, double* mean, int* npix, hipStream_t stream);
+
 // Rectification in front of the matcher (estimator.cpp:29-39).  RectifySrc: n RGB frames, pitch/frame in bytes.
 struct RectifySrc { const uint8_t* base; size_t pitch, frame; };
 void launch_rectify_gray(RectifySrc L, RectifySrc R, const int16_t* map1L, const uint16_t* map2L, const int16_t* map1R,

@@ -108,7 +108,25 @@ HIPObjectsCore::HIPObjectsCore(int cols, int rows, int device, int maxBatch, int
     status_ = rtdm_objects_create_batch(cols, rows, maxBatch, maxClasses, device, &ob_);
     if (status_ != RTDM_OK) std::fprintf(stderr, "HIPObjects: %s\n", rtdm_strerror(status_));
 }
-HIPObjectsCore::~HIPObjectsCore() { rtdm_objects_destroy(ob_); }
+HIPObjectsCore::~HIPObjectsCore() { rtdm_estimator_destroy(est_); rtdm_objects_destroy(ob_); }
+int HIPObjectsCore::estimateBatch(HIPMatcherCore& matcher, HIPRectifierCore& rectifier, int maxBatch, int capacity, int n,
+                                  const uint8_t* rgbLeft, size_t leftStep, size_t leftFrameStride, const uint8_t* rgbRight,
+                                  size_t rightStep, size_t rightFrameStride, const double* Q, int minObjSize, bool zeroBorder,
+                                  double calibrationUnit, rtdm_object* objects, int* counts, double* meanCm, int* npix, int16_t* disp,
+                                  size_t dispStep, size_t dispFrameStride)
+{
+    if (!ob_ || !matcher.handle() || !rectifier.handle()) return status_ != RTDM_OK ? status_ : RTDM_ERR_NO_DEVICE;
+    if (!est_ || estBm_ != matcher.handle() || estRc_ != rectifier.handle() || estBatch_ != maxBatch || estCap_ != capacity) {
+        rtdm_estimator_destroy(est_);
+        est_ = nullptr;
+        status_ = rtdm_estimator_create(matcher.handle(), rectifier.handle(), ob_, maxBatch, capacity, &est_);
+        if (status_ != RTDM_OK) return status_;
+        estBm_ = matcher.handle(); estRc_ = rectifier.handle(); estBatch_ = maxBatch; estCap_ = capacity;
+    }
+    return status_ = rtdm_estimate_batch(est_, n, rgbLeft, leftStep, leftFrameStride, rgbRight, rightStep, rightFrameStride, Q, ranges_,
+                                         cls_, nranges_, nclasses_, minObjSize, zeroBorder ? 1 : 0, calibrationUnit, objects, counts,
+                                         meanCm, npix, disp, dispStep, dispFrameStride);
+}
 int HIPObjectsCore::setRanges(const rtdm_hsv_range* ranges, const int* cls, int nranges, int nclasses)
 {
     if (!ranges || !cls) return RTDM_ERR_NULL;

@@ -260,10 +260,24 @@ public:
                              const uint8_t* rgbRight, size_t rightStep, const double* Q, int minObjSize, bool zeroBorder,
                              double calibrationUnit, rtdm_object* objects, double* meanCm, int* counts, int maxObjects,
                              int16_t* disp = nullptr, size_t dispStep = 0);
+    // estimateFrameClasses for n frame pairs per call (rtdm_estimate_batch): frame f at rgb + f * frameStride, its objects at
+    // objects + f * capacity (every stored one is measured: meanCm / npix[f * capacity + i]), counts[f * classes() + c], its map
+    // at disp + f * dispFrameStride bytes (disp may be null).  Frames without objects keep what the arrays held.  The estimator
+    // handle is made by the first call and made anew when the matcher, the rectifier, maxBatch or capacity differ from the
+    // call before; matcher and rectifier must live as long as this object uses them.  Returns a status.
+    int estimateBatch(HIPMatcherCore& matcher, HIPRectifierCore& rectifier, int maxBatch, int capacity, int n,
+                      const uint8_t* rgbLeft, size_t leftStep, size_t leftFrameStride, const uint8_t* rgbRight, size_t rightStep,
+                      size_t rightFrameStride, const double* Q, int minObjSize, bool zeroBorder, double calibrationUnit,
+                      rtdm_object* objects, int* counts, double* meanCm, int* npix, int16_t* disp = nullptr, size_t dispStep = 0,
+                      size_t dispFrameStride = 0);
     int status() const { return status_; }
 
 private:
     rtdm_objects* ob_ = nullptr;
+    rtdm_estimator* est_ = nullptr;                          // estimateBatch: the handle and what it was made for
+    rtdm_bm* estBm_ = nullptr;
+    rtdm_rectify* estRc_ = nullptr;
+    int estBatch_ = 0, estCap_ = 0;
     rtdm_hsv_range range_;
     rtdm_hsv_range ranges_[RTDM_MAX_HSV_RANGES];
     int cls_[RTDM_MAX_HSV_RANGES];

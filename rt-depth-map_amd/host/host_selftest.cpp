@@ -33,8 +33,29 @@ int main(int argc, char** argv)
         rtdm::HIPRectifierCore rect(map1.data(), map2.data(), map1.data(), map2.data(), RH, RW, full);
         const int rs = rect.rectifyGray(rgb.data(), RW * 3, rgb.data(), RW * 3, gl.data(), RW, gr.data(), RW);
         std::printf("rectifier_status=%d rectify_status=%d\n", rect.status(), rs);
+        // the batched loop body: three gray 128x96 frame pairs (identity maps) hold nothing red, so the matcher is skipped
+        const int EW = 128, EH = 96, EN = 3, ECAP = 8;
+        std::vector<int16_t> emap1((size_t)EW * EH * 2);
+        std::vector<uint16_t> emap2((size_t)EW * EH, 0);
+        for (int y = 0; y < EH; ++y)
+            for (int x = 0; x < EW; ++x) { emap1[((size_t)y * EW + x) * 2] = (int16_t)x; emap1[((size_t)y * EW + x) * 2 + 1] = (int16_t)y; }
+        rtdm::Rect efull; efull.width = EW; efull.height = EH;
+        rtdm::HIPRectifierCore erect(emap1.data(), emap2.data(), emap1.data(), emap2.data(), EH, EW, efull);
+        rtdm::HIPObjectsCore objs(EW, EH, 0, 2, 1);
+        const rtdm_hsv_range red = {{0, 150, 0}, {9, 255, 255}};
+        const int cls0 = 0;
+        objs.setRanges(&red, &cls0, 1, 1);
+        std::vector<uint8_t> frames((size_t)EN * EW * EH * 3, 90);
+        std::vector<rtdm_object> eobj((size_t)EN * ECAP);
+        std::vector<double> emean((size_t)EN * ECAP, -1.0);
+        std::vector<int> enpix((size_t)EN * ECAP, -1), ecnt(EN, -1);
+        const double Qid[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 0, 1, 0, 0, 1, 0};
+        const int es = objs.estimateBatch(m, erect, 2, ECAP, EN, frames.data(), (size_t)EW * 3, (size_t)EW * EH * 3, frames.data(), (size_t)EW * 3,
+                                          (size_t)EW * EH * 3, Qid, 100, true, 25.0, eobj.data(), ecnt.data(), emean.data(), enpix.data());
+        std::printf("estimate_batch_status=%d counts=%d,%d,%d\n", es, ecnt[0], ecnt[1], ecnt[2]);
         if (ndev == 0)
-            return (m.status() == RTDM_ERR_NO_DEVICE && c == RTDM_ERR_NO_DEVICE && rs == RTDM_ERR_NO_DEVICE) ? 0 : 1;
+            return (m.status() == RTDM_ERR_NO_DEVICE && c == RTDM_ERR_NO_DEVICE && rs == RTDM_ERR_NO_DEVICE && es == RTDM_ERR_NO_DEVICE) ? 0 : 1;
+        if (es != RTDM_OK || ecnt[0] || ecnt[1] || ecnt[2] || emean[0] != -1.0 || enpix[0] != -1) return 1;
         bool same = rs == RTDM_OK;
         for (int y = 0; y < RH && same; ++y)
             for (int x = 0; x < RW; ++x) same = same && gl[(size_t)y * RW + x] == (uint8_t)(x * 9 + y) && gr[(size_t)y * RW + x] == gl[(size_t)y * RW + x];
