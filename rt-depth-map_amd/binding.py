@@ -96,6 +96,136 @@ class MorphElement(C.Structure):        # rtdm_morph_element
     _fields_ = [(n, C.c_int) for n in ("width", "height", "anchor_x", "anchor_y")] + [("mask", C.c_uint8 * (MORPH_MAX_SIZE * MORPH_MAX_SIZE))]
 
 
+vp, u8p, i16p, u16p, sz = C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t
+SIGNATURES = {          # every entry point of include/rtdm.h: (restype, argtypes)
+    "rtdm_strerror": (C.c_char_p, [C.c_int]),
+    "rtdm_last_hip_error": (C.c_char_p, []),
+    "rtdm_abi_version": (C.c_int, []),
+    "rtdm_device_count": (C.c_int, [C.POINTER(C.c_int)]),
+    "rtdm_bm_default_params": (None, [C.POINTER(BMParams), C.c_int]),
+    "rtdm_bm_create": (C.c_int, [C.POINTER(BMParams), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]),
+    "rtdm_bm_destroy": (None, [vp]),
+    "rtdm_bm_set_roi": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "rtdm_bm_get_params": (C.c_int, [vp, C.POINTER(BMParams)]),
+    "rtdm_bm_set_prefilter": (C.c_int, [vp, C.c_int, C.c_int]),
+    "rtdm_bm_get_prefilter": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "rtdm_bm_compute": (C.c_int, [vp, u8p, sz, u8p, sz, C.c_int, C.c_int, i16p, sz]),
+    "rtdm_bm_compute_device": (C.c_int, [vp, C.c_int, u8p, u8p, sz, sz, C.c_int, C.c_int, i16p, sz, sz, vp]),
+    "rtdm_bm_compute_batch": (C.c_int, [vp, C.c_int, u8p, u8p, sz, sz, C.c_int, C.c_int, i16p, sz, sz]),
+    "rtdm_bm_synchronize": (C.c_int, [vp]),
+    "rtdm_bm_set_profiling": (C.c_int, [vp, C.c_int]),
+    "rtdm_bm_get_stage_time": (C.c_int, [vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_long), C.POINTER(C.c_long)]),
+    "rtdm_bm_reset_stage_times": (C.c_int, [vp]),
+    "rtdm_bm_search_variant": (C.c_char_p, [vp]),
+    "rtdm_bm_get_tuner_stats": (C.c_int, [vp, C.POINTER(C.c_long), C.POINTER(C.c_long)]),
+    "rtdm_debug_search_kernel": (None, [C.c_int]),
+    "rtdm_debug_disparity_slice": (None, [C.c_int]),
+    "rtdm_morph_make_element": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(MorphElement)]),
+    "rtdm_morph_set_op": (C.c_int, [vp, C.c_int, C.c_int, C.POINTER(MorphElement)]),
+    "rtdm_morph_get_op": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(MorphElement)]),
+    "rtdm_objects_set_morph": (C.c_int, [vp, C.c_int, C.c_int, C.POINTER(MorphElement)]),
+    "rtdm_objects_get_morph": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(MorphElement)]),
+    "rtdm_debug_morph_general": (None, [C.c_int]),
+    "rtdm_morph_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]),
+    "rtdm_morph_destroy": (None, [vp]),
+    "rtdm_morph_in_buffer": (vp, [vp]),
+    "rtdm_morph_out_buffer": (vp, [vp]),
+    "rtdm_morph_run": (C.c_int, [vp, u8p, sz, u8p, sz, C.c_int, C.c_int]),
+    "rtdm_morph_run_device": (C.c_int, [vp, C.c_int, u8p, sz, sz, u8p, sz, sz, C.c_int, C.c_int, vp]),
+    "rtdm_sgm_default_params": (None, [C.POINTER(SGMParams), C.c_int, C.c_int]),
+    "rtdm_sgm_create": (C.c_int, [C.POINTER(SGMParams), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]),
+    "rtdm_sgm_destroy": (None, [vp]),
+    "rtdm_sgm_compute": (C.c_int, [vp, u8p, sz, u8p, sz, C.c_int, C.c_int, i16p, sz]),
+    "rtdm_sgm_compute_device": (C.c_int, [vp, C.c_int, u8p, u8p, sz, sz, C.c_int, C.c_int, i16p, sz, sz, vp]),
+    "rtdm_sgm_get_pass_stats": (C.c_int, [vp, C.POINTER(C.c_long), C.POINTER(C.c_int)]),
+    "rtdm_sgm_path_variant": (C.c_char_p, [vp]),
+    "rtdm_debug_sgm_wide_paths": (None, [C.c_int]),
+    "rtdm_sgm_set_prefilter_cap": (C.c_int, [vp, C.c_int]),
+    "rtdm_sgm_compute_cn": (C.c_int, [vp, C.c_int, u8p, sz, u8p, sz, C.c_int, C.c_int, i16p, sz]),
+    "rtdm_sgm_compute_device_cn": (C.c_int, [vp, C.c_int, C.c_int, u8p, u8p, sz, sz, C.c_int, C.c_int, i16p, sz, sz, vp]),
+    "rtdm_debug_sgm_cost16": (None, [C.c_int]),
+    "rtdm_bm_compute_depth": (C.c_int, [vp, u8p, sz, u8p, sz, C.c_int, C.c_int, C.POINTER(C.c_double), u8p, sz,
+                                        C.POINTER(Region), C.c_int, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_int), i16p, sz]),
+    "rtdm_depth_stats_device": (C.c_int, [C.c_int, i16p, sz, C.c_int, C.c_int, C.POINTER(C.c_double), u8p, sz,
+                                          C.POINTER(Region), C.c_int, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_int), vp]),
+    "rtdm_rectify_create": (C.c_int, [i16p, u16p, i16p, u16p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                      C.c_int, C.c_int, C.POINTER(vp)]),
+    "rtdm_rectify_destroy": (None, [vp]),
+    "rtdm_rectify_gray": (C.c_int, [vp, u8p, sz, u8p, sz, u8p, sz, u8p, sz]),
+    "rtdm_rectify_rgb": (C.c_int, [vp, C.c_int, u8p, sz, u8p, sz]),
+    "rtdm_rectify_gray_device": (C.c_int, [vp, C.c_int, u8p, u8p, u8p, u8p, vp]),
+    "rtdm_bm_compute_rgb": (C.c_int, [vp, vp, u8p, sz, u8p, sz, i16p, sz]),
+    "rtdm_bm_compute_rgb_device": (C.c_int, [vp, vp, C.c_int, u8p, u8p, i16p, vp]),
+    "rtdm_calib_load": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(Calib), C.POINTER(Rectification), C.POINTER(C.c_uint)]),
+    "rtdm_stereo_rectify": (C.c_int, [C.POINTER(Calib), C.c_int, C.c_double, C.c_int, C.c_int, C.POINTER(Rectification)]),
+    "rtdm_undistort_rectify_map": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, i16p, u16p]),
+    "rtdm_undistort_rectify_map_device": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, i16p, u16p, vp]),
+    "rtdm_rectify_create_calib": (C.c_int, [C.POINTER(Calib), C.POINTER(Rectification), C.c_int, C.c_int, C.c_int, C.c_int,
+                                            C.c_int, C.c_int, C.POINTER(vp)]),
+    "rtdm_objects_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(vp)]),
+    "rtdm_objects_destroy": (None, [vp]),
+    "rtdm_objects_detect": (C.c_int, [vp, u8p, sz, C.POINTER(HsvRange), C.c_int, C.c_int, u8p, sz, C.POINTER(Region), C.c_int,
+                                      C.POINTER(C.c_int), C.POINTER(Region)]),
+    "rtdm_estimate_frame": (C.c_int, [vp, vp, vp, u8p, sz, u8p, sz, C.POINTER(C.c_double), C.POINTER(HsvRange), C.c_int, C.c_int,
+                                      C.c_double, C.POINTER(Region), C.POINTER(C.c_double), C.POINTER(C.c_int), C.c_int,
+                                      C.POINTER(C.c_int), i16p, sz]),
+    "rtdm_objects_create_batch": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]),
+    "rtdm_objects_detect_device": (C.c_int, [vp, C.c_int, u8p, sz, sz, C.POINTER(HsvRange), C.POINTER(C.c_int), C.c_int, C.c_int,
+                                             C.c_int, C.c_int, u8p, sz, sz, vp, C.c_int, vp, vp, vp]),
+    "rtdm_objects_detect_batch": (C.c_int, [vp, C.c_int, u8p, sz, sz, C.POINTER(HsvRange), C.POINTER(C.c_int), C.c_int, C.c_int,
+                                            C.c_int, C.c_int, u8p, sz, sz, vp, C.c_int, vp, vp]),
+    "rtdm_estimate_frame_classes": (C.c_int, [vp, vp, vp, u8p, sz, u8p, sz, C.POINTER(C.c_double), C.POINTER(HsvRange),
+                                              C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, vp,
+                                              C.POINTER(C.c_double), C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), i16p, sz]),
+    "rtdm_depth_objects_workspace_bytes": (sz, [C.c_int, C.c_int, C.c_int]),
+    "rtdm_depth_objects_device": (C.c_int, [C.c_int, C.c_int, i16p, sz, sz, C.c_int, C.c_int, C.POINTER(C.c_double), u8p, sz, sz,
+                                            C.c_int, vp, C.c_int, vp, C.c_double, vp, vp, vp, sz, vp]),
+    "rtdm_estimator_create": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.POINTER(vp)]),
+    "rtdm_estimator_destroy": (None, [vp]),
+    "rtdm_estimate_batch": (C.c_int, [vp, C.c_int, u8p, sz, sz, u8p, sz, sz, C.POINTER(C.c_double), C.POINTER(HsvRange),
+                                      C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, vp, vp, vp, vp, i16p, sz, sz]),
+    "rtdm_estimate_batch_device": (C.c_int, [vp, C.c_int, u8p, sz, sz, u8p, sz, sz, C.POINTER(C.c_double), C.POINTER(HsvRange),
+                                             C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, vp, vp, vp, vp, i16p,
+                                             sz, sz, vp]),
+    "rtdm_wls_params_for_bm": (C.c_int, [C.POINTER(BMParams), C.POINTER(WLSParams)]),
+    "rtdm_wls_params_for_sgm": (C.c_int, [C.POINTER(SGMParams), C.POINTER(WLSParams)]),
+    "rtdm_bm_right_params": (C.c_int, [C.POINTER(BMParams), C.POINTER(BMParams)]),
+    "rtdm_sgm_right_params": (C.c_int, [C.POINTER(SGMParams), C.POINTER(SGMParams)]),
+    "rtdm_wls_create": (C.c_int, [C.POINTER(WLSParams), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]),
+    "rtdm_wls_destroy": (None, [vp]),
+    "rtdm_wls_set_params": (C.c_int, [vp, C.POINTER(WLSParams)]),
+    "rtdm_wls_get_params": (C.c_int, [vp, C.POINTER(WLSParams)]),
+    "rtdm_wls_filter": (C.c_int, [vp, i16p, sz, i16p, sz, u8p, sz, C.c_int, C.c_int, C.c_int, i16p, sz, vp, sz, vp, sz]),
+    "rtdm_wls_filter_device": (C.c_int, [vp, C.c_int, i16p, sz, sz, i16p, sz, sz, u8p, sz, sz, C.c_int, C.c_int, C.c_int,
+                                         i16p, sz, sz, vp, sz, sz, vp, sz, sz, vp]),
+    "rtdm_bm_compute_filtered": (C.c_int, [vp, vp, vp, u8p, sz, u8p, sz, C.c_int, C.c_int, i16p, sz, i16p, sz]),
+    "rtdm_xyz_default_params": (None, [C.POINTER(XYZParams), C.POINTER(C.c_double), C.c_int]),
+    "rtdm_xyz_create": (C.c_int, [C.POINTER(XYZParams), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]),
+    "rtdm_xyz_destroy": (None, [vp]),
+    "rtdm_xyz_set_params": (C.c_int, [vp, C.POINTER(XYZParams)]),
+    "rtdm_xyz_get_params": (C.c_int, [vp, C.POINTER(XYZParams)]),
+    "rtdm_xyz_map": (C.c_int, [vp, i16p, sz, C.c_int, C.c_int, vp, sz, vp, sz]),
+    "rtdm_xyz_map_device": (C.c_int, [vp, C.c_int, i16p, sz, sz, C.c_int, C.c_int, vp, sz, sz, vp, sz, sz, vp]),
+    "rtdm_xyz_cloud": (C.c_int, [vp, i16p, sz, u8p, sz, C.c_int, u8p, sz, C.c_int, C.c_int, vp, C.c_int, C.POINTER(C.c_int)]),
+    "rtdm_xyz_cloud_device": (C.c_int, [vp, C.c_int, i16p, sz, sz, u8p, sz, sz, C.c_int, u8p, sz, sz, C.c_int, C.c_int,
+                                        vp, sz, C.c_int, vp, vp]),
+    "rtdm_bm_compute_cloud": (C.c_int, [vp, vp, u8p, sz, u8p, sz, C.c_int, C.c_int, u8p, sz, C.c_int, u8p, sz, vp, C.c_int,
+                                        C.POINTER(C.c_int), i16p, sz]),
+    "rtdm_mjpeg_probe": (C.c_int, [u8p, sz, C.POINTER(MJPEGInfo)]),
+    "rtdm_mjpeg_create": (C.c_int, [C.c_int, C.c_int, C.c_int, sz, C.c_int, C.POINTER(vp)]),
+    "rtdm_mjpeg_destroy": (None, [vp]),
+    "rtdm_mjpeg_decode": (C.c_int, [vp, u8p, sz, C.c_int, C.c_int, u8p, sz]),
+    "rtdm_mjpeg_decode_batch_device": (C.c_int, [vp, C.c_int, C.POINTER(C.c_void_p), C.POINTER(sz), C.c_int, C.c_int, u8p,
+                                                 sz, sz, vp, vp]),
+    "rtdm_bm_compute_mjpeg": (C.c_int, [vp, vp, vp, u8p, sz, u8p, sz, C.c_int, C.c_int, i16p, sz]),
+    "rtdm_mjpeg_set_split": (C.c_int, [vp, C.c_int]),
+    "rtdm_mjpeg_get_split": (C.c_int, [vp, C.POINTER(C.c_int)]),
+    "rtdm_mjpeg_get_split_stats": (C.c_int, [vp, C.POINTER(C.c_long), C.POINTER(C.c_long), C.POINTER(C.c_int)]),
+    "rtdm_synth_pairs_device": (C.c_int, [C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, u8p, u8p,
+                                          sz, sz, C.c_int, vp]),
+}
+EXPORTS = tuple(SIGNATURES)
+
 _lib = None
 
 
@@ -107,162 +237,11 @@ def lib():
         raise RuntimeError("HIP extension %s is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                            "(there is no CPU fallback)" % LIB_PATH)
     L = C.CDLL(LIB_PATH)
-    vp, u8p, i16p, u16p, sz = C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t
-    sig = {
-        "rtdm_strerror": (C.c_char_p, [C.c_int]),
-        "rtdm_last_hip_error": (C.c_char_p, []),
-        "rtdm_abi_version": (C.c_int, []),
-        "rtdm_device_count": (C.c_int, [C.POINTER(C.c_int)]),
-        "rtdm_bm_default_params": (None, [C.POINTER(BMParams), C.c_int]),
-        "rtdm_bm_create": (C.c_int, [C.POINTER(BMParams), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]),
-        "rtdm_bm_destroy": (None, [vp]),
-        "rtdm_bm_set_roi": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
-        "rtdm_bm_get_params": (C.c_int, [vp, C.POINTER(BMParams)]),
-        "rtdm_bm_set_prefilter": (C.c_int, [vp, C.c_int, C.c_int]),
-        "rtdm_bm_get_prefilter": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
-        "rtdm_bm_compute": (C.c_int, [vp, u8p, sz, u8p, sz, C.c_int, C.c_int, i16p, sz]),
-        "rtdm_bm_compute_device": (C.c_int, [vp, C.c_int, u8p, u8p, sz, sz, C.c_int, C.c_int, i16p, sz, sz, vp]),
-        "rtdm_bm_compute_batch": (C.c_int, [vp, C.c_int, u8p, u8p, sz, sz, C.c_int, C.c_int, i16p, sz, sz]),
-        "rtdm_bm_synchronize": (C.c_int, [vp]),
-        "rtdm_bm_set_profiling": (C.c_int, [vp, C.c_int]),
-        "rtdm_bm_get_stage_time": (C.c_int, [vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_long), C.POINTER(C.c_long)]),
-        "rtdm_bm_reset_stage_times": (C.c_int, [vp]),
-        "rtdm_bm_search_variant": (C.c_char_p, [vp]),
-        "rtdm_bm_get_tuner_stats": (C.c_int, [vp, C.POINTER(C.c_long), C.POINTER(C.c_long)]),
-        "rtdm_debug_search_kernel": (None, [C.c_int]),
-        "rtdm_debug_disparity_slice": (None, [C.c_int]),
-        "rtdm_morph_make_element": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(MorphElement)]),
-        "rtdm_morph_set_op": (C.c_int, [vp, C.c_int, C.c_int, C.POINTER(MorphElement)]),
-        "rtdm_morph_get_op": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(MorphElement)]),
-        "rtdm_objects_set_morph": (C.c_int, [vp, C.c_int, C.c_int, C.POINTER(MorphElement)]),
-        "rtdm_objects_get_morph": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(MorphElement)]),
-        "rtdm_debug_morph_general": (None, [C.c_int]),
-        "rtdm_morph_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]),
-        "rtdm_morph_destroy": (None, [vp]),
-        "rtdm_morph_in_buffer": (vp, [vp]),
-        "rtdm_morph_out_buffer": (vp, [vp]),
-        "rtdm_morph_run": (C.c_int, [vp, u8p, sz, u8p, sz, C.c_int, C.c_int]),
-        "rtdm_morph_run_device": (C.c_int, [vp, C.c_int, u8p, sz, sz, u8p, sz, sz, C.c_int, C.c_int, vp]),
-        "rtdm_sgm_default_params": (None, [C.POINTER(SGMParams), C.c_int, C.c_int]),
-        "rtdm_sgm_create": (C.c_int, [C.POINTER(SGMParams), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]),
-        "rtdm_sgm_destroy": (None, [vp]),
-        "rtdm_sgm_compute": (C.c_int, [vp, u8p, sz, u8p, sz, C.c_int, C.c_int, i16p, sz]),
-        "rtdm_sgm_compute_device": (C.c_int, [vp, C.c_int, u8p, u8p, sz, sz, C.c_int, C.c_int, i16p, sz, sz, vp]),
-        "rtdm_sgm_get_pass_stats": (C.c_int, [vp, C.POINTER(C.c_long), C.POINTER(C.c_int)]),
-        "rtdm_sgm_path_variant": (C.c_char_p, [vp]),
-        "rtdm_debug_sgm_wide_paths": (None, [C.c_int]),
-        "rtdm_sgm_set_prefilter_cap": (C.c_int, [vp, C.c_int]),
-        "rtdm_sgm_compute_cn": (C.c_int, [vp, C.c_int, u8p, sz, u8p, sz, C.c_int, C.c_int, i16p, sz]),
-        "rtdm_sgm_compute_device_cn": (C.c_int, [vp, C.c_int, C.c_int, u8p, u8p, sz, sz, C.c_int, C.c_int, i16p, sz, sz, vp]),
-        "rtdm_debug_sgm_cost16": (None, [C.c_int]),
-        "rtdm_bm_compute_depth": (C.c_int, [vp, u8p, sz, u8p, sz, C.c_int, C.c_int, C.POINTER(C.c_double), u8p, sz,
-                                            C.POINTER(Region), C.c_int, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_int), i16p, sz]),
-        "rtdm_depth_stats_device": (C.c_int, [C.c_int, i16p, sz, C.c_int, C.c_int, C.POINTER(C.c_double), u8p, sz,
-                                              C.POINTER(Region), C.c_int, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_int), vp]),
-        "rtdm_rectify_create": (C.c_int, [i16p, u16p, i16p, u16p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                                          C.c_int, C.c_int, C.POINTER(vp)]),
-        "rtdm_rectify_destroy": (None, [vp]),
-        "rtdm_rectify_gray": (C.c_int, [vp, u8p, sz, u8p, sz, u8p, sz, u8p, sz]),
-        "rtdm_rectify_rgb": (C.c_int, [vp, C.c_int, u8p, sz, u8p, sz]),
-        "rtdm_rectify_gray_device": (C.c_int, [vp, C.c_int, u8p, u8p, u8p, u8p, vp]),
-        "rtdm_bm_compute_rgb": (C.c_int, [vp, vp, u8p, sz, u8p, sz, i16p, sz]),
-        "rtdm_bm_compute_rgb_device": (C.c_int, [vp, vp, C.c_int, u8p, u8p, i16p, vp]),
-        "rtdm_calib_load": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(Calib), C.POINTER(Rectification), C.POINTER(C.c_uint)]),
-        "rtdm_stereo_rectify": (C.c_int, [C.POINTER(Calib), C.c_int, C.c_double, C.c_int, C.c_int, C.POINTER(Rectification)]),
-        "rtdm_undistort_rectify_map": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, i16p, u16p]),
-        "rtdm_undistort_rectify_map_device": (C.c_int, [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, i16p, u16p, vp]),
-        "rtdm_rectify_create_calib": (C.c_int, [C.POINTER(Calib), C.POINTER(Rectification), C.c_int, C.c_int, C.c_int, C.c_int,
-                                                C.c_int, C.c_int, C.POINTER(vp)]),
-        "rtdm_objects_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(vp)]),
-        "rtdm_objects_destroy": (None, [vp]),
-        "rtdm_objects_detect": (C.c_int, [vp, u8p, sz, C.POINTER(HsvRange), C.c_int, C.c_int, u8p, sz, C.POINTER(Region), C.c_int,
-                                          C.POINTER(C.c_int), C.POINTER(Region)]),
-        "rtdm_estimate_frame": (C.c_int, [vp, vp, vp, u8p, sz, u8p, sz, C.POINTER(C.c_double), C.POINTER(HsvRange), C.c_int, C.c_int,
-                                          C.c_double, C.POINTER(Region), C.POINTER(C.c_double), C.POINTER(C.c_int), C.c_int,
-                                          C.POINTER(C.c_int), i16p, sz]),
-        "rtdm_objects_create_batch": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]),
-        "rtdm_objects_detect_device": (C.c_int, [vp, C.c_int, u8p, sz, sz, C.POINTER(HsvRange), C.POINTER(C.c_int), C.c_int, C.c_int,
-                                                 C.c_int, C.c_int, u8p, sz, sz, vp, C.c_int, vp, vp, vp]),
-        "rtdm_objects_detect_batch": (C.c_int, [vp, C.c_int, u8p, sz, sz, C.POINTER(HsvRange), C.POINTER(C.c_int), C.c_int, C.c_int,
-                                                C.c_int, C.c_int, u8p, sz, sz, vp, C.c_int, vp, vp]),
-        "rtdm_estimate_frame_classes": (C.c_int, [vp, vp, vp, u8p, sz, u8p, sz, C.POINTER(C.c_double), C.POINTER(HsvRange),
-                                                  C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, vp,
-                                                  C.POINTER(C.c_double), C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), i16p, sz]),
-        "rtdm_depth_objects_workspace_bytes": (sz, [C.c_int, C.c_int, C.c_int]),
-        "rtdm_depth_objects_device": (C.c_int, [C.c_int, C.c_int, i16p, sz, sz, C.c_int, C.c_int, C.POINTER(C.c_double), u8p, sz, sz,
-                                                C.c_int, vp, C.c_int, vp, C.c_double, vp, vp, vp, sz, vp]),
-        "rtdm_estimator_create": (C.c_int, [vp, vp, vp, C.c_int, C.c_int, C.POINTER(vp)]),
-        "rtdm_estimator_destroy": (None, [vp]),
-        "rtdm_estimate_batch": (C.c_int, [vp, C.c_int, u8p, sz, sz, u8p, sz, sz, C.POINTER(C.c_double), C.POINTER(HsvRange),
-                                          C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, vp, vp, vp, vp, i16p, sz, sz]),
-        "rtdm_estimate_batch_device": (C.c_int, [vp, C.c_int, u8p, sz, sz, u8p, sz, sz, C.POINTER(C.c_double), C.POINTER(HsvRange),
-                                                 C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, vp, vp, vp, vp, i16p,
-                                                 sz, sz, vp]),
-        "rtdm_wls_params_for_bm": (C.c_int, [C.POINTER(BMParams), C.POINTER(WLSParams)]),
-        "rtdm_wls_params_for_sgm": (C.c_int, [C.POINTER(SGMParams), C.POINTER(WLSParams)]),
-        "rtdm_bm_right_params": (C.c_int, [C.POINTER(BMParams), C.POINTER(BMParams)]),
-        "rtdm_sgm_right_params": (C.c_int, [C.POINTER(SGMParams), C.POINTER(SGMParams)]),
-        "rtdm_wls_create": (C.c_int, [C.POINTER(WLSParams), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]),
-        "rtdm_wls_destroy": (None, [vp]),
-        "rtdm_wls_set_params": (C.c_int, [vp, C.POINTER(WLSParams)]),
-        "rtdm_wls_get_params": (C.c_int, [vp, C.POINTER(WLSParams)]),
-        "rtdm_wls_filter": (C.c_int, [vp, i16p, sz, i16p, sz, u8p, sz, C.c_int, C.c_int, C.c_int, i16p, sz, vp, sz, vp, sz]),
-        "rtdm_wls_filter_device": (C.c_int, [vp, C.c_int, i16p, sz, sz, i16p, sz, sz, u8p, sz, sz, C.c_int, C.c_int, C.c_int,
-                                             i16p, sz, sz, vp, sz, sz, vp, sz, sz, vp]),
-        "rtdm_bm_compute_filtered": (C.c_int, [vp, vp, vp, u8p, sz, u8p, sz, C.c_int, C.c_int, i16p, sz, i16p, sz]),
-        "rtdm_xyz_default_params": (None, [C.POINTER(XYZParams), C.POINTER(C.c_double), C.c_int]),
-        "rtdm_xyz_create": (C.c_int, [C.POINTER(XYZParams), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]),
-        "rtdm_xyz_destroy": (None, [vp]),
-        "rtdm_xyz_set_params": (C.c_int, [vp, C.POINTER(XYZParams)]),
-        "rtdm_xyz_get_params": (C.c_int, [vp, C.POINTER(XYZParams)]),
-        "rtdm_xyz_map": (C.c_int, [vp, i16p, sz, C.c_int, C.c_int, vp, sz, vp, sz]),
-        "rtdm_xyz_map_device": (C.c_int, [vp, C.c_int, i16p, sz, sz, C.c_int, C.c_int, vp, sz, sz, vp, sz, sz, vp]),
-        "rtdm_xyz_cloud": (C.c_int, [vp, i16p, sz, u8p, sz, C.c_int, u8p, sz, C.c_int, C.c_int, vp, C.c_int, C.POINTER(C.c_int)]),
-        "rtdm_xyz_cloud_device": (C.c_int, [vp, C.c_int, i16p, sz, sz, u8p, sz, sz, C.c_int, u8p, sz, sz, C.c_int, C.c_int,
-                                            vp, sz, C.c_int, vp, vp]),
-        "rtdm_bm_compute_cloud": (C.c_int, [vp, vp, u8p, sz, u8p, sz, C.c_int, C.c_int, u8p, sz, C.c_int, u8p, sz, vp, C.c_int,
-                                            C.POINTER(C.c_int), i16p, sz]),
-        "rtdm_mjpeg_probe": (C.c_int, [u8p, sz, C.POINTER(MJPEGInfo)]),
-        "rtdm_mjpeg_create": (C.c_int, [C.c_int, C.c_int, C.c_int, sz, C.c_int, C.POINTER(vp)]),
-        "rtdm_mjpeg_destroy": (None, [vp]),
-        "rtdm_mjpeg_decode": (C.c_int, [vp, u8p, sz, C.c_int, C.c_int, u8p, sz]),
-        "rtdm_mjpeg_decode_batch_device": (C.c_int, [vp, C.c_int, C.POINTER(C.c_void_p), C.POINTER(sz), C.c_int, C.c_int, u8p,
-                                                     sz, sz, vp, vp]),
-        "rtdm_bm_compute_mjpeg": (C.c_int, [vp, vp, vp, u8p, sz, u8p, sz, C.c_int, C.c_int, i16p, sz]),
-        "rtdm_mjpeg_set_split": (C.c_int, [vp, C.c_int]),
-        "rtdm_mjpeg_get_split": (C.c_int, [vp, C.POINTER(C.c_int)]),
-        "rtdm_mjpeg_get_split_stats": (C.c_int, [vp, C.POINTER(C.c_long), C.POINTER(C.c_long), C.POINTER(C.c_int)]),
-        "rtdm_synth_pairs_device": (C.c_int, [C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, u8p, u8p,
-                                              sz, sz, C.c_int, vp]),
-    }
-    for name, (res, args) in sig.items():
+    for name, (res, args) in SIGNATURES.items():
         fn = getattr(L, name)
         fn.restype, fn.argtypes = res, args
     _lib = L
     return L
-
-
-EXPORTS = ("rtdm_strerror rtdm_last_hip_error rtdm_abi_version rtdm_device_count rtdm_bm_default_params "
-           "rtdm_bm_create rtdm_bm_destroy rtdm_bm_set_roi rtdm_bm_get_params rtdm_bm_set_prefilter rtdm_bm_get_prefilter rtdm_bm_compute "
-           "rtdm_bm_compute_device rtdm_bm_compute_batch rtdm_bm_synchronize rtdm_bm_set_profiling "
-           "rtdm_bm_get_stage_time rtdm_bm_reset_stage_times rtdm_bm_search_variant rtdm_bm_get_tuner_stats rtdm_debug_search_kernel rtdm_debug_disparity_slice rtdm_morph_create "
-           "rtdm_morph_destroy rtdm_morph_in_buffer rtdm_morph_out_buffer rtdm_morph_run "
-           "rtdm_morph_run_device rtdm_synth_pairs_device rtdm_sgm_default_params rtdm_sgm_create rtdm_sgm_destroy "
-           "rtdm_sgm_compute rtdm_sgm_compute_device rtdm_sgm_get_pass_stats rtdm_sgm_path_variant rtdm_debug_sgm_wide_paths "
-           "rtdm_sgm_set_prefilter_cap rtdm_sgm_compute_cn rtdm_sgm_compute_device_cn rtdm_debug_sgm_cost16 rtdm_bm_compute_depth rtdm_depth_stats_device "
-           "rtdm_rectify_create rtdm_rectify_destroy rtdm_rectify_gray rtdm_rectify_rgb rtdm_rectify_gray_device "
-           "rtdm_bm_compute_rgb rtdm_bm_compute_rgb_device rtdm_objects_create rtdm_objects_destroy rtdm_objects_detect "
-           "rtdm_estimate_frame rtdm_wls_params_for_bm rtdm_wls_params_for_sgm rtdm_bm_right_params rtdm_sgm_right_params "
-           "rtdm_wls_create rtdm_wls_destroy rtdm_wls_set_params rtdm_wls_get_params rtdm_wls_filter rtdm_wls_filter_device "
-           "rtdm_bm_compute_filtered rtdm_xyz_default_params rtdm_xyz_create rtdm_xyz_destroy rtdm_xyz_set_params "
-           "rtdm_xyz_get_params rtdm_xyz_map rtdm_xyz_map_device rtdm_xyz_cloud rtdm_xyz_cloud_device rtdm_bm_compute_cloud "
-           "rtdm_mjpeg_probe rtdm_mjpeg_create rtdm_mjpeg_destroy rtdm_mjpeg_decode rtdm_mjpeg_decode_batch_device "
-           "rtdm_bm_compute_mjpeg rtdm_mjpeg_set_split rtdm_mjpeg_get_split rtdm_mjpeg_get_split_stats rtdm_calib_load rtdm_stereo_rectify rtdm_undistort_rectify_map "
-           "rtdm_undistort_rectify_map_device rtdm_rectify_create_calib rtdm_morph_make_element rtdm_morph_set_op rtdm_morph_get_op "
-           "rtdm_objects_set_morph rtdm_objects_get_morph rtdm_debug_morph_general rtdm_objects_create_batch "
-           "rtdm_objects_detect_device rtdm_objects_detect_batch rtdm_estimate_frame_classes "
-           "rtdm_depth_objects_workspace_bytes rtdm_depth_objects_device rtdm_estimator_create rtdm_estimator_destroy "
-           "rtdm_estimate_batch rtdm_estimate_batch_device").split()
 
 
 def check(status, where):

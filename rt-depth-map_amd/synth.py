@@ -16,6 +16,8 @@ Stamps      : one flat patch (texture rejection), one 8-px-period stripe patch (
 """
 import numpy as np
 
+from . import binding as B
+
 STREAM_SEED = 0x5EED0000
 _M = np.uint64(0xFFFFFFFFFFFFFFFF)
 _K = [np.uint64(k) for k in (0x9E3779B97F4A7C15, 0xBF58476D1CE4E5B9, 0x94D049BB133111EB,
@@ -129,3 +131,11 @@ def make_stream(first_frame, n, W, H, D, seed=STREAM_SEED):
     for i in range(n):
         L[i], R[i] = make_pair(seed + first_frame + i, W, H, D)
     return L, R
+
+
+def synth_pairs_device(d_left, d_right, first_frame, numDisparities, seed=None, device=0, stream=None):
+    """Fill torch uint8 [n,H,W] tensors with frames [first_frame, first_frame+n) of the stream."""
+    n, H, W = d_left.shape
+    B.check(B.lib().rtdm_synth_pairs_device(STREAM_SEED if seed is None else seed, first_frame, n, W, H,
+                                            numDisparities, d_left.data_ptr(), d_right.data_ptr(), W, W * H,
+                                            device, stream), "rtdm_synth_pairs_device")

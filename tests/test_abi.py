@@ -64,6 +64,43 @@ def test_no_device_means_loud_failure():
         pkg.HIPMorphologicalFilter(64, 48)
 
 
+PUBLIC_NAMES = """binding synth MORPH_BLACKHAT MORPH_CLOSE MORPH_CROSS MORPH_DILATE MORPH_ELLIPSE MORPH_ERODE MORPH_GRADIENT
+    MORPH_OPEN MORPH_OPEN_CLOSE MORPH_RECT MORPH_TOPHAT OBJECT_DTYPE POINT_DTYPE PREFILTER_NORMALIZED_RESPONSE PREFILTER_XSOBEL
+    XYZ_FIXED16 XYZ_ROUNDED HIPDisparityWLSFilter HIPEstimator HIPMatcher HIPMJPEGDecoder HIPMorphologicalFilter HIPObjectDetector
+    HIPReprojector HIPRectifier HIPSemiGlobalMatcher create_disparity_wls_filter create_right_matcher depth_objects_device
+    depth_objects_workspace_bytes depth_stats_device estimate_frame estimate_frame_classes get_structuring_element
+    init_undistort_rectify_map load_calibration mjpeg_probe stereo_rectify synth_pairs_device wls_params_for""".split()
+HANDLE_API = {
+    "HIPMatcher": """close setPreFilterType setPreFilterSize getPreFilterType getPreFilterSize setROI1 setROI2 filtered compute
+                     compute_depth compute_batch compute_device synchronize set_profiling reset_stage_times stage_times
+                     search_variant tuner_stats""",
+    "HIPSemiGlobalMatcher": """close MODE_SGBM MODE_HH MODE_SGBM_3WAY MODE_HH4 setPreFilterCap setROI1 setROI2 filtered mode compute
+                               pass_stats path_variant compute_device""",
+    "HIPDisparityWLSFilter": """close setLambda getLambda setSigmaColor getSigmaColor setLRCthresh getLRCthresh
+                                setDepthDiscontinuityRadius getDepthDiscontinuityRadius getConfidenceMap getROI invalid filter
+                                filter_device compute_filtered""",
+    "HIPReprojector": "close set_params reprojectImageTo3D depth cloud compute map_device cloud_device",
+    "HIPMorphologicalFilter": "close getFrameSize getVideoInBuffer getVideoOutBuffer set_op get_op run run_device",
+    "HIPRectifier": "close from_calibration gray rgb gray_device compute compute_device",
+    "HIPMJPEGDecoder": "close split split_stats decode decode_batch compute",
+    "HIPObjectDetector": "close set_op get_op detect detect_classes detect_device",
+    "HIPEstimator": "close estimate estimate_device",
+}
+
+
+def test_public_surface_and_the_one_handle_base():
+    # the package's exports and the nine handle classes' public names, as they were when the layer was one module
+    pkg = load()
+    Handle = load("_marshal").Handle
+    assert [n for n in PUBLIC_NAMES if not hasattr(pkg, n)] == []
+    assert Handle.__del__ is Handle.close
+    for cname, names in HANDLE_API.items():
+        cls = getattr(pkg, cname)
+        assert [n for n in names.split() if not hasattr(cls, n)] == [], cname
+        assert issubclass(cls, Handle) and cls._destroy in pkg.binding.EXPORTS, cname
+        assert "close" not in vars(cls) and "__del__" not in vars(cls), cname
+
+
 def test_product_package_never_touches_the_oracle():
     pkgdir = os.path.join(ROOT, "rt-depth-map_amd")
     for dp, _, fs in os.walk(pkgdir):

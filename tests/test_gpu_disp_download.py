@@ -64,7 +64,7 @@ def _cycle(pkg, frames, streams):
         out["mjpeg"] = got + (rect.compute(bm, dl, dr),)
         # last: the call leaves ROI 1 of the matcher set to the union of its boxes
         boxes, n = (B.Region * 64)(), C.c_int()
-        rng = B.HsvRange((C.c_int * 3)(*pkg.matcher.HSV_LOW), (C.c_int * 3)(*pkg.matcher.HSV_HIGH))
+        rng = B.HsvRange((C.c_int * 3)(*pkg.objects.HSV_LOW), (C.c_int * 3)(*pkg.objects.HSV_HIGH))
         got = pitched(lambda p: B.check(lib.rtdm_estimate_frame(
             bm._h, rect._h, det._h, left.ctypes.data, left.strides[0], right.ctypes.data, right.strides[0], qp, C.byref(rng), 40, 1,
             25.0, boxes, mean, cnt, 64, C.byref(n), p, PITCH), "rtdm_estimate_frame"))

@@ -369,7 +369,7 @@ def test_chain_with_one_class_is_estimate_frame(pkg, synth, chain):
     left, right = ru.red_scene(synth, 1, c["W"], c["H"], 32)
     det = pkg.HIPObjectDetector(c["roi"][2], c["roi"][3])
     boxes, mean, cnt, disp = pkg.estimate_frame(m, rect, det, left, right, c["Q"], min_area=40, want_disp=True)
-    objs, mean2, cnt2, disp2 = pkg.estimate_frame_classes(m, rect, det, left, right, c["Q"], [(pkg.matcher.HSV_LOW, pkg.matcher.HSV_HIGH)],
+    objs, mean2, cnt2, disp2 = pkg.estimate_frame_classes(m, rect, det, left, right, c["Q"], [(pkg.objects.HSV_LOW, pkg.objects.HSV_HIGH)],
                                                           min_area=40, want_disp=True)
     assert len(boxes) >= 2 and objs == [b + (0,) for b in boxes]
     assert np.array_equal(cnt, cnt2) and cnt.sum() > 0 and np.array_equal(mean, mean2) and np.array_equal(disp, disp2)

@@ -182,7 +182,7 @@ def test_make_element_refusals_and_abi_version(B):
 
 def test_python_argument_checks_raise():
     pkg = load()
-    M = load("matcher")
+    M = load("morph")
     with pytest.raises(ValueError):
         M._morph_element(np.zeros((0, 3)), None)
     with pytest.raises(ValueError):

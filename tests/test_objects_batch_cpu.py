@@ -130,7 +130,7 @@ def test_python_layer_raises_for_wrong_arguments():
         pkg.HIPObjectDetector(64, 48, max_classes=9)
     assert e.value.status == BAD_PARAM
     from importlib import import_module
-    m = import_module(pkg.__name__ + ".matcher")
+    m = import_module(pkg.__name__ + ".objects")
     with pytest.raises(ValueError):
         m._hsv_classes([ref.R_RED, ref.R_BLUE], [0])
     rng, cls, nr, K = m._hsv_classes([ref.R_RED, ref.R_BLUE, ref.R_GREEN], None)
