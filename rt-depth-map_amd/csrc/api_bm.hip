@@ -217,18 +217,20 @@ static int chunk_back(rtdm_bm* bm, int n, int W, int H, Plane16W disp, const BMG
     StageEvent ev;
     const bool speckle = p.speckleRange >= 0 && p.speckleWindowSize > 0;
     const bool lr = p.disp12MaxDiff >= 0;
-    int compact_rows = 0;                // > 0: k_lrcheck_vec wrote per-chunk head records and merged blocks of that many rows
+    const SpkBuffers wk = speckle ? SpkBuffers{bm->dLabel, bm->dSize, bm->dRuns, bm->dRowCnt, bm->dHead} : SpkBuffers{};
+    SpkHeads heads = SpkHeads::NONE;     // what the check leaves for the filter; off: the filter initialises its rows itself
+    int block_rows = 1;
     if (lr) {
         stage_begin(bm, RTDM_STAGE_LRCHECK, n, s, &ev);
-        if (speckle) compact_rows = launch_lrcheck(disp, bm->dCost, g, p.disp12MaxDiff, n, s, bm->dLabel, bm->dSize, bm->dRuns, bm->dRowCnt, bm->dHead,
-                                                   p.speckleRange);
-        else         launch_lrcheck(disp, bm->dCost, g, p.disp12MaxDiff, n, s);
+        const LrPlan lp = plan_lrcheck(g, p.disp12MaxDiff, speckle ? p.speckleRange : 0, n, speckle, rows_aligned(disp, bm->dCost, wk.headmap, W));
+        launch_lrcheck(lp, disp, bm->dCost, g, wk, s);
+        heads = lp.heads; block_rows = lp.block_rows;
         stage_end(bm, s, &ev);
     }
     if (speckle) {
         stage_begin(bm, RTDM_STAGE_SPECKLE, n, s, &ev);
-        launch_speckle(disp, bm->dLabel, bm->dSize, bm->dRuns, bm->dRowCnt, bm->dHead, W, g.Ws, H, n, g.filtered, p.speckleWindowSize,
-                       p.speckleRange, lr, std::max(compact_rows, 1), g.vy0, g.vy1, s, compact_rows > 0);
+        const SpkPlan sp = plan_speckle(W, g.Ws, H, n, heads, block_rows, g.vy0, g.vy1, rows_aligned(disp, nullptr, nullptr, W));
+        launch_speckle(sp, disp, wk, g.filtered, p.speckleWindowSize, p.speckleRange, s);
         stage_end(bm, s, &ev);
     }
     HIPC(hipGetLastError());

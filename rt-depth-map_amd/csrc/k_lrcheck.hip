@@ -1,11 +1,9 @@
 // k_lrcheck.hip -- K3, the left-right check of the block matcher for gfx950, in three forms (scalar, eight columns per
-// thread, packed) with the speckle filter's per-row init fused in, and their launch policy.
-// Semantics: SURVEY.md Appendix A.4; oracle: oracle/bm_oracle.c.
+// thread, packed) with the speckle filter's per-row init fused in, and the entry that launches the form plan_lrcheck
+// (k_rows.hip) has chosen.  Semantics: SURVEY.md Appendix A.4; oracle: oracle/bm_oracle.c.
 #include "rtdm_kernels.h"
 #include "rtdm_device.h"
 #include "rtdm_pk16.h"
-
-#include <cstdlib>
 
 namespace rtdm {
 
@@ -312,15 +310,12 @@ __global__ __launch_bounds__(512) void k_lrcheck_vec(Plane16W disp, const uint16
 // validity of the final row, the connected-to-the-left flags) is extracted -- eight flags at a time with two v_perm and two
 // v_dot4_u32_u8.  Measured: 354 instead of 509 VALU instructions on the always-taken path, but packed ops and v_perm issue at
 // 4.4 cycles where most of k_lrcheck_vec's v_and / v_or / v_add / v_sub issue at 2.6: 1.39 -> 1.32 ms per 1024 720p pairs,
-// 0.527 -> 0.487 at 640x480.  NIT > 1 (thread constants formed once for NIT row pairs; measured and retired, only NIT = 1 is launched) is SLOWER, with or
-// without the next trip's rows requested a trip ahead (1.51-1.77 ms): 74+ VGPRs instead of 44, and what bounds the kernel is
-// how many short barrier-chained workgroups a CU holds, not its instruction count (also with barriers that do not wait
-// for global memory: 1.79 ms).  Timing-only ablations (profiles/r03_lrcheck_ablation.txt): loading the two planes and
+// 0.527 -> 0.487 at 640x480.  Timing-only ablations (profiles/r03_lrcheck_ablation.txt): loading the two planes and
 // resetting the keys alone takes 0.59 ms -- 3.8 GB at 6.4 TB/s, the HBM floor; the speckle init costs 0.25 ms, the votes 0.09.  Key slots: key[W] takes the votes nobody may see, key[W + 1] is never written
 // ("no vote").  Needs: costs < 32768 (a slot's cost half is negative only in the empty slot), minD .. minD + D inside
 // int16 / 16, the workgroup's LDS below 64 KB.  Same bytes as k_lrcheck_vec.
 // ---------------------------------------------------------------------------------------------
-template <bool SPK, int NIT>
+template <bool SPK>
 __global__ __launch_bounds__(512) void k_lrcheck_pk(Plane16W disp, const uint16_t* cost, BMGeom g, int maxDiff16,
                                                     int32_t* label, int32_t* size, uint32_t* runs, int32_t* rowcnt,
                                                     int16_t* headmap, int spkDiff)
@@ -360,10 +355,13 @@ __global__ __launch_bounds__(512) void k_lrcheck_pk(Plane16W disp, const uint16_
     const uint32_t Mpk = (uint32_t)maxDiff16 * 0x00010001u;
     const uint32_t Spk = (uint32_t)spkDiff * 0x00010001u, S2pk = Spk + Spk;
     if (chunk == 0) { key[Wp] = ~0u; key[Wp + 1] = ~0u; }            // (W == Wp: the two slots lie behind the chunks)
+    // One trip.  The loop statement is what is left of the retired form that walked several row pairs.  It stays: as straight-line
+    // code the same body compiles to 45 VGPRs / 838 instructions instead of 46 / 830, with two s_waitcnt vmcnt(0) behind the row's
+    // write-back -- the wait lr_lds_barrier() exists to avoid -- and the stage is 1.8 % slower (profiles/basic_split_resources.txt,
+    // profiles/rows_plan_resources.txt).
 #pragma unroll 1
-    for (int it = 0; it < NIT; ++it) {
-        const int ypair = 2 * ((int)blockIdx.y * NIT + it);           // first row of this trip, from vy0
-        if (NIT > 1 && g.vy0 + ypair >= g.vy1) break;                 // (uniform)
+    for (int it = 0; it < 1; ++it) {
+        const int ypair = 2 * (int)blockIdx.y;                        // first row of the pair, from vy0
         const int y0 = g.vy0 + ypair, y = y0 + half;                  // (row addresses: wave-uniform part + the half's row step)
         const bool active = x0 < W && y < g.vy1;
         int16_t* row = disp.base + ((size_t)f * disp.frame_e + (size_t)y0 * disp.pitch_e) + (half ? (uint32_t)disp.pitch_e : 0u);
@@ -434,7 +432,7 @@ __global__ __launch_bounds__(512) void k_lrcheck_pk(Plane16W disp, const uint16_
             if (chg) *(uint4*)(row + x0) = make_uint4(D[0], D[1], D[2], D[3]);
             if (SPK) *(uint4*)(fin + x0) = make_uint4(D[0], D[1], D[2], D[3]);
         }
-        if (!SPK) { if (NIT > 1) { lr_lds_barrier(); continue; } else return; }
+        if (!SPK) return;
         lr_lds_barrier();
         // ---- speckle init of the finished row (as in k_lrcheck_vec) ----
         unsigned im = 0, cb = 0;
@@ -460,91 +458,32 @@ __global__ __launch_bounds__(512) void k_lrcheck_pk(Plane16W disp, const uint16_
         lr_lds_barrier();
         const int run = spk_agg_carry(t, hl, wsum[half], wv);
         if (active) spk_register_runs(run, hm, lm, 0u, x0, chunk, W, g.Ws, f * g.H + y, label, size, runs, rowcnt, headmap);
-        // (no barrier here: the next trip's first writes to the keys, the row and wsum lie behind barriers every thread only
-        //  passes after its reads of this trip)
     }
 }
 
-static bool two_ok_for_pk(const BMGeom& g, int md, int spkDiff)
+// The plan's form -> its kernel; SPK: the speckle init runs in the same pass (plan.heads != NONE).
+template <bool SPK>
+static void lr_issue(const LrPlan& p, Plane16W disp, const void* cost, const BMGeom& g, const SpkBuffers& wk, hipStream_t stream)
 {
-    return 2L * g.cap * g.w * g.w < 32768 && md >= 0 && md <= 8192 && spkDiff >= 0 && spkDiff <= 4096 &&
-           g.minD >= -1024 && g.minD + g.D <= 1024 && g.W + 2 < 16384;
+    const auto go = [&](auto kernel, auto* c) {
+        hipLaunchKernelGGL(kernel, dim3(1, p.gy, p.n), dim3(p.threads), p.lds, stream, disp, c, g, p.maxDiff16, wk.label, wk.size,
+                           wk.runs, wk.rowcnt, wk.headmap, p.spkDiff);
+    };
+    const uint16_t* c16 = (const uint16_t*)cost;
+    switch (p.form) {
+        case LrForm::SCALAR_U16: go(k_lrcheck<SPK, uint16_t, uint32_t>, c16); break;
+        case LrForm::SCALAR_I32: go(k_lrcheck<SPK, int32_t, unsigned long long>, (const int32_t*)cost); break;
+        case LrForm::VEC_WAVE:   go(k_lrcheck_vec<SPK, false, 1>, c16); break;
+        case LrForm::VEC_HALF:   go(k_lrcheck_vec<SPK, true, 1>, c16); break;
+        case LrForm::VEC_HALF2:  go(k_lrcheck_vec<true, true, 2>, c16); break;   // (planned with the speckle init only)
+        case LrForm::PACKED:     go(k_lrcheck_pk<SPK>, c16); break;
+    }
 }
 
-// Returns 0 if the head map was written per pixel (int16 head columns, nodes = head positions), else (k_lrcheck_vec: one
-// record per chunk, nodes = run indices) the number of consecutive rows, counted from g.vy0, whose pairs the kernel has
-// already merged (1: none).
-int launch_lrcheck(Plane16W disp, const void* cost, const BMGeom& g, int disp12MaxDiff, int n,
-                   hipStream_t stream, int32_t* label, int32_t* size, uint32_t* runs, int32_t* rowcnt,
-                   int16_t* headmap, int spkDiff)
+void launch_lrcheck(const LrPlan& plan, Plane16W disp, const void* cost, const BMGeom& g, const SpkBuffers& wk, hipStream_t stream)
 {
-    const int md = disp12MaxDiff * 16;
-    const int nrows = g.vy1 - g.vy0;
-    dim3 block(256);
-    const bool k32 = g.cost16 && g.W < 65536;
-    const size_t kb = k32 ? 4 : 8;
-#define RTDM_LR(SPK, CT, KT)                                                                                          \
-    hipLaunchKernelGGL((k_lrcheck<SPK, CT, KT>), dim3(1, nrows, n), block, (size_t)g.W * (kb + 2 + (SPK ? 2 : 0)), stream, \
-                       disp, (const CT*)cost, g, md, label, size, runs, rowcnt, headmap, spkDiff)
-    const int Wp = (g.W + 7) & ~7;                      // a ragged last chunk is masked in registers; it needs padding columns
-    const bool vec = k32 && (g.Ws & 7) == 0 && g.W <= 4096 && disp.pitch_e >= (size_t)Wp &&   // that belong to the plane
-                     (((size_t)disp.base | (disp.pitch_e * 2) | (disp.frame_e * 2) | (size_t)cost | (size_t)headmap) & 15) == 0;
-    if (vec) {
-        const int chunks = Wp >> 3;
-        const auto per_half = [&](int nb) { return (size_t)Wp * 4 + 16 + (size_t)nb * Wp * 2; };
-        // row pairs a workgroup walks and merges (1: none -- every pair is left to k_spk_merge_strip, round 3's first form)
-        // Two row pairs per workgroup with the vertical contacts inside the block found right here (k_lrcheck_vec<.., NIT = 2> +
-        // k_spk_merge_rec): a frame's contacts are chains of dependent L2 round trips, and with half of them settled from the head
-        // records the merge of one 720p frame takes 12 us instead of 29 (the whole frame 82 -> 66 us of kernels).  Measured against
-        // the packed one-pair form (k_lrcheck_pk + k_spk_merge_strip<4>) over batch sizes (profiles/r03_lr_pairs_ab.txt): frames
-        // up to 1024 wide -- faster or level at every batch size (640x480: -32 % at 12 pairs, -5 % at 128, level at 512); 1280
-        // wide -- faster up to ~16 pairs per call (-9 % for one frame, -23 % at 4), 2-5 % slower beyond, where k_lrcheck_pk
-        // streams and the merge is HBM bound.  RTDM_LR_PAIRS=1 / 2 (test hook) fixes the choice.
-        static const int pairs_raw = env_int("RTDM_LR_PAIRS", 0);
-        const int pairs = (pairs_raw == 1 || pairs_raw == 2) ? pairs_raw : ((g.W <= 1024 || (long)n * nrows <= 11520) ? 2 : 1);
-        // two rows per workgroup (one per half-wave) where that fits 512 threads: it never takes more lanes than the whole-wave form
-        const int waves1 = (chunks + 63) / 64, waves2 = (chunks + 31) / 32;
-        const bool two = waves2 <= 8 && nrows >= 2;
-        // packed form (k_lrcheck_pk): costs below 32768, every quantity of the consistency / closeness tests inside int16,
-        // LDS byte addresses inside 16 bits.  RTDM_LR_PACKED=0 (test hook): k_lrcheck_vec, the form wherever these fail.
-        static const int pk_env = env_int("RTDM_LR_PACKED", 1);
-        const bool pk_ok = pk_env && two_ok_for_pk(g, md, spkDiff) && 2 * per_half(1) + 1024 < 65536;
-        const bool contacts_here = two && label && nrows >= 4 && pairs > 1;   // k_lrcheck_vec<.., NIT = 2> below
-        if (two && pk_ok && !contacts_here) {
-            const dim3 vblock((unsigned)(waves2 * 64));
-#define RTDM_LRP(SPK) hipLaunchKernelGGL((k_lrcheck_pk<SPK, 1>), dim3(1, (nrows + 1) / 2, n), vblock, 2 * per_half(1), stream, disp, \
-                                 (const uint16_t*)cost, g, md, label, size, runs, rowcnt, headmap, spkDiff)
-            if (label) RTDM_LRP(true); else RTDM_LRP(false);
-#undef RTDM_LRP
-            return label ? 1 : 0;
-        }
-        if (two) {
-            const dim3 vblock((unsigned)(waves2 * 64));
-            const int nit = (label && nrows >= 4) ? pairs : 1;
-#define RTDM_LRV(SPK, NIT) hipLaunchKernelGGL((k_lrcheck_vec<SPK, true, NIT>), dim3(1, (nrows + 2 * NIT - 1) / (2 * NIT), n), vblock, \
-                               2 * per_half(NIT > 1 ? 2 : 1), stream, disp, (const uint16_t*)cost, g, md, label, size, runs, rowcnt, headmap, spkDiff)
-            if (!label) RTDM_LRV(false, 1);
-            else if (nit == 2) RTDM_LRV(true, 2);
-            else RTDM_LRV(true, 1);
-#undef RTDM_LRV
-            return label ? (nit > 1 ? 2 * nit : 1) : 0;
-        }
-        const dim3 vblock((unsigned)(waves1 * 64));
-        const size_t lds = per_half(1);
-        if (label) hipLaunchKernelGGL((k_lrcheck_vec<true, false, 1>), dim3(1, nrows, n), vblock, lds, stream, disp, (const uint16_t*)cost, g, md, label, size, runs, rowcnt, headmap, spkDiff);
-        else       hipLaunchKernelGGL((k_lrcheck_vec<false, false, 1>), dim3(1, nrows, n), vblock, lds, stream, disp, (const uint16_t*)cost, g, md, label, size, runs, rowcnt, headmap, spkDiff);
-        return label ? 1 : 0;
-    } else if (label) {
-        if (k32) RTDM_LR(true, uint16_t, uint32_t);
-        else if (g.cost16) RTDM_LR(true, uint16_t, unsigned long long);
-        else RTDM_LR(true, int32_t, unsigned long long);
-    } else {
-        if (k32) RTDM_LR(false, uint16_t, uint32_t);
-        else if (g.cost16) RTDM_LR(false, uint16_t, unsigned long long);
-        else RTDM_LR(false, int32_t, unsigned long long);
-    }
-#undef RTDM_LR
-    return 0;
+    if (plan.heads != SpkHeads::NONE) lr_issue<true>(plan, disp, cost, g, wk, stream);
+    else lr_issue<false>(plan, disp, cost, g, wk, stream);
 }
 
 }  // namespace rtdm

@@ -105,8 +105,9 @@ static void sgm_finish(Plane16W disp, const SGMGeom& g, const SGMBuffers& b, int
     if (speckle) {
         hipLaunchKernelGGL((k_sgm_median<true>), dim3(1, g.H, n), blk, mlds, stream, tmp, disp, g.W, g.H, INV, b.label, b.size, b.runs,
                            b.rowcnt, b.headmap, 16 * speckleRange);
-        launch_speckle(disp, b.label, b.size, b.runs, b.rowcnt, b.headmap, g.W, g.W, g.H, n, INV, speckleWindowSize,
-                       16 * speckleRange, true, 1, 0, g.H, stream);
+        // k_sgm_median has initialised every row with per-pixel heads (workspace rows of W elements) and merged nothing
+        const SpkPlan sp = plan_speckle(g.W, g.W, g.H, n, SpkHeads::PIXEL, 1, 0, g.H, rows_aligned(disp, nullptr, nullptr, g.W));
+        launch_speckle(sp, disp, SpkBuffers{b.label, b.size, b.runs, b.rowcnt, b.headmap}, INV, speckleWindowSize, 16 * speckleRange, stream);
     } else {
         hipLaunchKernelGGL((k_sgm_median<false>), dim3(1, g.H, n), blk, mlds, stream, tmp, disp, g.W, g.H, INV, b.label, b.size, b.runs,
                            b.rowcnt, b.headmap, 0);

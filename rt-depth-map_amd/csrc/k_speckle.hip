@@ -1,10 +1,8 @@
-// k_speckle.hip -- K4, the speckle filter of the block matcher for gfx950: init, the merge kernels, count, apply and their
-// launch policy.  Semantics: SURVEY.md Appendix A.5; oracle: oracle/bm_oracle.c.
+// k_speckle.hip -- K4, the speckle filter of the block matcher for gfx950: init, the merge kernels, count, apply and the entry
+// that launches what plan_speckle (k_rows.hip) has chosen.  Semantics: SURVEY.md Appendix A.5; oracle: oracle/bm_oracle.c.
 #include "rtdm_kernels.h"
 #include "rtdm_device.h"
 #include "rtdm_pk16.h"
-
-#include <cstdlib>
 
 namespace rtdm {
 
@@ -112,9 +110,7 @@ __device__ __forceinline__ void spk_queue_drain(const int2* queue, const int& qn
     for (int i = threadIdx.x; i < total; i += 256) uf_union_contact(label, size, queue[i].x, queue[i].y, maxSize);
 }
 
-// The contacts k_lrcheck_vec<.., NIT > 1> has found: row pairs (y - 1, y) inside its blocks of `blk` rows, `nrows` rows counted
-// from vy0, `nch` chunks per row; `blocks` workgroups of 256 items cover them.
-struct MergeRecArgs { int blocks, vy0, nrows, blk, nch; };
+// The contacts k_lrcheck_vec<.., NIT > 1> has found (MergeRecArgs, rtdm_kernels.h).
 // Item idx = one chunk of a row y of frame f: all it reads is the row's head records -- most have cand == 0 -- and, for the
 // others, the record of the chunk above; every contact goes to the queue.
 __device__ __forceinline__ void spk_rec_collect(int2* queue, int& qn, int32_t* label, const uint32_t* heads, int Ws, int H,
@@ -391,72 +387,39 @@ __global__ __launch_bounds__(256) void k_spk_apply(Plane16W disp, const int32_t*
     }
 }
 
-// label/size/runs/headmap: n*W*H elements each; rowcnt: n*H.  If init_done, the rows [y_lo, y_hi) were
-// initialised by k_lrcheck<true> (rowcnt was zeroed before it) and no other row holds a valid pixel.
-void launch_speckle(Plane16W disp, int32_t* label, int32_t* size, uint32_t* runs, int32_t* rowcnt, int16_t* headmap,
-                    int W, int Ws, int H, int n, int newVal, int maxSize, int maxDiff, bool init_done, int premerged_rows,
-                    int y_lo, int y_hi, hipStream_t stream, bool compact_heads)
+void launch_speckle(const SpkPlan& p, Plane16W disp, const SpkBuffers& wk, int newVal, int maxSize, int maxDiff, hipStream_t stream)
 {
-    dim3 block(256);
-    if (!init_done) {
-        y_lo = 0; y_hi = H; premerged_rows = 1;
-        hipLaunchKernelGGL(k_spk_init, dim3(1, H, n), block, (size_t)W * 6, stream, disp, label, size, runs, rowcnt, headmap,
-                           W, Ws, H, newVal, maxDiff);
+    const dim3 block(256);
+    if (p.init_lds)
+        hipLaunchKernelGGL(k_spk_init, dim3(1, p.H, p.n), block, p.init_lds, stream, disp, wk.label, wk.size, wk.runs, wk.rowcnt,
+                           wk.headmap, p.W, p.Ws, p.H, newVal, maxDiff);
+    if (p.rec_own.blocks)
+        hipLaunchKernelGGL(k_spk_merge_rec, dim3(p.rec_own.blocks, p.n), block, 0, stream, wk.label, (const uint32_t*)wk.headmap, p.Ws,
+                           p.H, p.rec_own, wk.size, maxSize);
+    const auto strip = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(p.merge_gx, p.n), block, 0, stream, disp, wk.label, wk.headmap, p.W, p.Ws, p.H, p.first, p.npairs,
+                           newVal, maxDiff, wk.size, maxSize, p.ystep, p.rec_fused, wk.runs);
+    };
+    switch (p.merge) {
+        case SpkMerge::NONE: break;
+        case SpkMerge::ROWS:
+            hipLaunchKernelGGL(k_spk_merge, dim3(p.merge_gx, p.n), block, 0, stream, disp, wk.label, wk.headmap, p.W, p.Ws, p.H, p.first,
+                               p.npairs, newVal, maxDiff);
+            break;
+        case SpkMerge::STRIP4_PIXEL:     strip(k_spk_merge_strip<4, false, false>); break;
+        case SpkMerge::STRIP1_CHUNK:     strip(k_spk_merge_strip<1, true, false>); break;
+        case SpkMerge::STRIP2_CHUNK:     strip(k_spk_merge_strip<2, true, false>); break;
+        case SpkMerge::STRIP4_CHUNK:     strip(k_spk_merge_strip<4, true, false>); break;
+        case SpkMerge::STRIP1_CHUNK_REC: strip(k_spk_merge_strip<1, true, true>); break;
     }
-    // row pairs still to merge: (y, y+1), y = first + k*step.  The init pass may already have merged the pairs
-    // inside blocks of premerged_rows rows (k_lrcheck_vec<.., NIT = 2>, compact heads); then only the pairs across blocks remain.
-    const int step = premerged_rows > 1 ? premerged_rows : 1;
-    const int first = y_lo + step - 1;
-    const int last = min(y_hi, H) - 2;               // last y with y+1 initialised
-    const int npairs = last >= first ? (last - first) / step + 1 : 0;
-    MergeRecArgs rec{};
-    // RTDM_MERGE_REC_FUSED=0 (test hook): k_spk_merge_rec as a launch of its own, as where no pair is left across blocks
-    static const int fuse_rec = env_int("RTDM_MERGE_REC_FUSED", 1);
-    if (compact_heads && step > 1) {               // the contacts inside blocks of `step` rows are in the head records (k_lrcheck_vec<.., NIT > 1>)
-        const int nr = min(y_hi, H) - y_lo, inside = (nr / step) * (step - 1) + max(nr % step - 1, 0), nxb = (W + 7) / 8;
-        if (inside > 0) {
-            const MergeRecArgs ra{(inside * nxb + 255) / 256, y_lo, nr, step, nxb};
-            if (fuse_rec && npairs > 0) rec = ra;      // rides in k_spk_merge_strip<1, true, true> below
-            else hipLaunchKernelGGL(k_spk_merge_rec, dim3(ra.blocks, n), block, 0, stream, label, (const uint32_t*)headmap, Ws, H, ra, size, maxSize);
-        }
-    }
-    if (npairs > 0) {
-        const int nxb = (W + 7) / 8;
-        const bool vec = (((size_t)disp.base | (disp.pitch_e * 2) | (disp.frame_e * 2)) & 15) == 0 && (Ws & 7) == 0 &&
-                         disp.pitch_e >= (size_t)((W + 7) & ~7);   // a ragged last chunk reads (never writes) padding columns
-        // strips of RS row pairs, the first at `first`; strips of one pair lie ystep rows apart
-#define RTDM_STRIP(RS, COMPACT, REC, nblocks, ystep)                                                                                  \
-    hipLaunchKernelGGL((k_spk_merge_strip<RS, COMPACT, REC>), dim3((nxb * ((npairs + RS - 1) / RS) + 255) / 256 + (nblocks), n), block, 0, \
-                       stream, disp, label, headmap, W, Ws, H, first, npairs, newVal, maxDiff, size, maxSize, ystep, rec, runs)
-        if (compact_heads && step > 1) {           // k_lrcheck_vec<.., NIT > 1> has found the contacts inside blocks of `step` rows
-            if (rec.blocks) RTDM_STRIP(1, true, true, rec.blocks, step);
-            else RTDM_STRIP(1, true, false, 0, step);
-        } else
-        if (compact_heads) {                       // written by k_lrcheck_vec, whose alignment conditions imply `vec`
-            // Strips of four row pairs read every row 1.25 times instead of twice -- what a batch wants (the kernel streams the
-            // plane) -- but a single frame is 111 workgroups whose threads each work through up to four queued unions, chains of
-            // dependent L2 round trips: 32 us, more than the frame's search.  Small launches take shorter strips: more workgroups,
-            // one union per thread.
-            int rsc = 4;
-            while (rsc > 1 && (long)((nxb * ((npairs + rsc - 1) / rsc) + 255) / 256) * n < 1024) rsc >>= 1;
-            if (rsc == 4)      RTDM_STRIP(4, true, false, 0, 1);
-            else if (rsc == 2) RTDM_STRIP(2, true, false, 0, 1);
-            else               RTDM_STRIP(1, true, false, 0, 1);
-        } else if (vec) {                          // (step == 1: without compact heads nothing was merged in blocks)
-            RTDM_STRIP(4, false, false, 0, 1);
-        } else {
-            hipLaunchKernelGGL(k_spk_merge, dim3((nxb * npairs + 255) / 256, n), block, 0, stream, disp, label, headmap, W, Ws, H, first, npairs, newVal, maxDiff);
-        }
-#undef RTDM_STRIP
-    }
-    const int nrows = n * H;
-    // DENSE (compact heads, k_lrcheck_vec): nodes are run indices
-#define RTDM_COUNT_APPLY(DENSE) do {                                                                                                  \
-        hipLaunchKernelGGL(k_spk_count<DENSE>, dim3((nrows + 15) / 16), block, 0, stream, label, size, runs, rowcnt, Ws, nrows, maxSize); \
-        hipLaunchKernelGGL(k_spk_apply<DENSE>, dim3((nrows + 15) / 16), block, 0, stream, disp, label, size, runs, rowcnt, Ws, H, nrows, newVal, maxSize); \
-    } while (0)
-    if (compact_heads) RTDM_COUNT_APPLY(true); else RTDM_COUNT_APPLY(false);
-#undef RTDM_COUNT_APPLY
+    const int nrows = p.n * p.H;
+    const auto count_apply = [&](auto count, auto apply) {   // DENSE (chunk records): nodes are run indices
+        hipLaunchKernelGGL(count, dim3(p.rows_gx), block, 0, stream, wk.label, wk.size, wk.runs, wk.rowcnt, p.Ws, nrows, maxSize);
+        hipLaunchKernelGGL(apply, dim3(p.rows_gx), block, 0, stream, disp, wk.label, wk.size, wk.runs, wk.rowcnt, p.Ws, p.H, nrows, newVal, maxSize);
+    };
+    if (p.heads == SpkHeads::CHUNK) count_apply(k_spk_count<true>, k_spk_apply<true>);
+    else count_apply(k_spk_count<false>, k_spk_apply<false>);
 }
 
 }  // namespace rtdm
+

@@ -132,24 +132,59 @@ hipError_t launch_search(const SearchPlan& plan, Plane8 Lp, Plane8 Rp, Plane16W 
 void ring_set_mode(int mode);      // rtdm_debug_search_kernel
 void dslice_set_width(int dt);     // rtdm_debug_disparity_slice
 
-// K3: row-local left-right consistency check (+ column masking to the valid rectangle).  With
-// label != nullptr the speckle filter's per-row init runs on the checked row in the same pass.
-// Returns 0 if the speckle head map was written per pixel; otherwise it was written as per-chunk records (compact_heads for
-// launch_speckle) and the value is the number of consecutive rows, from g.vy0, whose pairs the kernel has merged itself
-// (1: none; premerged_rows for launch_speckle).
-int launch_lrcheck(Plane16W disp, const void* cost, const BMGeom& g, int disp12MaxDiff, int n,
-                   hipStream_t stream, int32_t* label = nullptr, int32_t* size = nullptr,
-                   uint32_t* runs = nullptr, int32_t* rowcnt = nullptr, int16_t* headmap = nullptr, int spkDiff = 0);
-
-// K4: speckle filter (connected components under |a-b| <= maxDiff, size <= maxSize removed).
-// label/size/runs/headmap: n*W*H elements each, rowcnt: n*H.  init_done: rows [y_lo,y_hi) were
-// initialised by the caller's row kernel (rowcnt zeroed beforehand) and every other row is entirely
-// `newVal`; premerged_rows > 1 (compact_heads only): that kernel also merged the row pairs inside blocks of that many rows
-// (launch_lrcheck's return value).
-void launch_speckle(Plane16W disp, int32_t* label, int32_t* size, uint32_t* runs, int32_t* rowcnt, int16_t* headmap,
-                    int W, int Ws, int H, int n, int newVal, int maxSize, int maxDiff, bool init_done, int premerged_rows,
-                    int y_lo, int y_hi, hipStream_t stream, bool compact_heads = false);
-// Ws = row stride of label/size/runs/headmap (>= W)
+// K3 / K4: the row stages behind the search -- the row-local left-right consistency check (+ column masking to the valid
+// rectangle; k_lrcheck.hip) and the speckle filter (connected components under |a-b| <= maxDiff, size <= maxSize removed;
+// k_speckle.hip).  plan_lrcheck / plan_speckle (k_rows.hip) decide, once per call and without touching the runtime, what
+// launch_lrcheck / launch_speckle then issue.  The route table is in DESIGN.md ("K3 / K4: routes").
+// The speckle filter's workspace: label / size / runs / headmap n * Ws * H elements each, rowcnt n * H.
+struct SpkBuffers { int32_t *label, *size; uint32_t* runs; int32_t* rowcnt; int16_t* headmap; };
+// What a row kernel (k_lrcheck*, k_sgm_median) has left in that workspace for the filter: nothing; the rows initialised with
+// one int16 head column per pixel (union-find nodes = head positions); the rows initialised with one record per 8-column
+// chunk (nodes = run indices).
+enum class SpkHeads { NONE, PIXEL, CHUNK };
+// k_lrcheck<SPK, uint16_t, uint32_t> / <SPK, int32_t, unsigned long long>, k_lrcheck_vec<SPK, false, 1> / <SPK, true, 1> /
+// <true, true, 2>, k_lrcheck_pk<SPK>
+enum class LrForm { SCALAR_U16, SCALAR_I32, VEC_WAVE, VEC_HALF, VEC_HALF2, PACKED };
+struct LrPlan {
+    LrForm form;
+    unsigned threads, gy, n;               // block; grid (1, gy, n)
+    size_t lds;                            // dynamic LDS
+    int maxDiff16, spkDiff;                // kernel arguments: 16 disp12MaxDiff, speckleRange
+    SpkHeads heads;                        // what the launch leaves for the speckle filter (NONE: the SPK = false instantiation)
+    int block_rows;                        // CHUNK: the pairs inside blocks of that many rows, from g.vy0, are merged (1: none)
+};
+// The contacts k_lrcheck_vec<.., NIT > 1> has found: row pairs (y - 1, y) inside its blocks of `blk` rows, `nrows` rows counted
+// from vy0, `nch` chunks per row; `blocks` workgroups of 256 items cover them.
+struct MergeRecArgs { int blocks, vy0, nrows, blk, nch; };
+// k_spk_merge (rows that are not aligned); k_spk_merge_strip<4, false>, <1 | 2 | 4, true>, <1, true, true>
+enum class SpkMerge { NONE, ROWS, STRIP4_PIXEL, STRIP1_CHUNK, STRIP2_CHUNK, STRIP4_CHUNK, STRIP1_CHUNK_REC };
+struct SpkPlan {
+    int W, Ws, H, n;                       // Ws: row stride of label / size / runs / headmap (>= W)
+    size_t init_lds;                       // k_spk_init's dynamic LDS; 0: the caller's row kernel has initialised the rows
+    SpkHeads heads;                        // PIXEL or CHUNK (count / apply: DENSE)
+    MergeRecArgs rec_own, rec_fused;       // k_spk_merge_rec as a launch of its own / in the first workgroups of the strip form
+                                           // (blocks == 0: not there)
+    SpkMerge merge;
+    int merge_gx;                          // its grid (merge_gx, n)
+    int first, npairs, ystep;              // row pairs (y, y + 1), y = first + k * ystep, k < npairs
+    int rows_gx;                           // grid of count and apply
+};
+// The pointer-dependent conditions of the 128-bit row kernels, evaluated by the callers so that the plans stay pure: base,
+// pitch and frame stride of the plane 16-byte aligned, its rows at least W rounded up to 8 long (a ragged last chunk is
+// masked in registers; it needs padding columns that belong to the plane), and the cost plane and head map, where the kernel
+// at hand moves them in 128-bit accesses too (K3; the merge kernels of K4 pass null), 16-byte aligned.
+inline bool rows_aligned(Plane16W disp, const void* cost, const void* headmap, int W)
+{
+    return (((size_t)disp.base | (disp.pitch_e * 2) | (disp.frame_e * 2) | (size_t)cost | (size_t)headmap) & 15) == 0 &&
+           disp.pitch_e >= (size_t)((W + 7) & ~7);
+}
+// speckle: the speckle filter's per-row init runs on the checked row in the same pass (the launch needs the workspace).
+LrPlan plan_lrcheck(const BMGeom& g, int disp12MaxDiff, int spkDiff, int n, bool speckle, bool aligned);
+void launch_lrcheck(const LrPlan& plan, Plane16W disp, const void* cost, const BMGeom& g, const SpkBuffers& wk, hipStream_t stream);
+// heads != NONE: the rows [y_lo, y_hi) were initialised by the caller's row kernel (rowcnt zeroed beforehand), every other row
+// is entirely newVal, and (CHUNK) the pairs inside blocks of block_rows rows are merged.  NONE: k_spk_init does every row.
+SpkPlan plan_speckle(int W, int Ws, int H, int n, SpkHeads heads, int block_rows, int y_lo, int y_hi, bool aligned);
+void launch_speckle(const SpkPlan& plan, Plane16W disp, const SpkBuffers& wk, int newVal, int maxSize, int maxDiff, hipStream_t stream);
 // n frames of W x H int16: src -> dst (any pitches)
 void launch_copy16(Plane16W src, Plane16W dst, int W, int H, int n, hipStream_t stream);
 

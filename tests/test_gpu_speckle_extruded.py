@@ -34,11 +34,9 @@ def assert_same(got, want, what):
 
 # One string, run in a child process per setting (the hooks are read once per process).  Cases 1 - 4: every job of
 # extruded.single_frame_jobs at every one of its windows.  Case 5: device-resident batches of four distinct pairs, cycled.
-# launch_speckle's rsc loop starts at strips of 4 row pairs and halves while workgroups x frames < 1024.  640 wide is 80
-# chunks, 40 rows at blockSize 9 are 31 pairs: 4-pair strips are 8 strips = ceil(640 / 256) = 3 workgroups, 3 n >= 1024 from
-# n = 342 -> 352 frames run k_spk_merge_strip<4, true>; 2-pair strips are 16 strips = 5 workgroups, 5 n >= 1024 from n = 205
-# while 3 n < 1024 -> 208 frames run k_spk_merge_strip<2, true> (both under RTDM_LR_PAIRS=1; two pairs per workgroup leave
-# the rec form + k_spk_merge_strip<1, true, true> at any batch size).
+# The batch sizes pick the strip length of plan_speckle (k_rows.hip; rows x352 and x208 of tests/rows_cases.py pin it and
+# carry the arithmetic): at 640 x 40, blockSize 9, 352 frames run k_spk_merge_strip<4, true> and 208 frames k_spk_merge_strip<2, true>
+# (both under RTDM_LR_PAIRS=1; two pairs per workgroup leave the rec form + k_spk_merge_strip<1, true, true> at any batch size).
 _CASES = r'''
 import importlib, sys, zlib, numpy as np, torch
 sys.path.insert(0, %r); sys.path.insert(0, %r)
@@ -115,7 +113,7 @@ def test_every_merge_form_matches_the_oracle_on_extruded_pairs():
 
 def test_a_frame_wider_than_4096_is_refused(pkg):
     # both matchers keep whole rows in LDS and refuse such frames at creation, so no extruded input reaches the wide-frame
-    # selections of launch_lrcheck; the scalar k_lrcheck is reached by SAD sums past 16 bits instead (extruded.head_jobs)
+    # selections of plan_lrcheck; the scalar k_lrcheck is reached by SAD sums past 16 bits instead (extruded.head_jobs)
     B = load("binding")
     with pytest.raises(B.RtdmError):
         pkg.HIPMatcher(numOfDisparities=16, blockSize=9, width=4104, height=24)
