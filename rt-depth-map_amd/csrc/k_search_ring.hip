@@ -31,7 +31,7 @@
 // x_tile + phi + 4 p (PAIR: wave = half of the tile and one of two 2-byte phases, lane (p, h) = the columns x0, x0 + 1 with
 // x0 = x_tile + 32 (phi >> 1) + 2 (phi & 1) + 4 p).  The four waves never synchronise: each stages ITS byte-shifted copy
 // of the entering rows (64 or 128 dwords, padded) into its own LDS slice, two rows ahead of their use, and the LDS queue of
-// a wave is in order.  The texture sum is a prefix ring too (one dword per pixel and slot, in LDS).  Only columns whose window needs no border
+// a wave is in order.  The texture sum is a prefix ring too (16 bits per pixel and slot, in LDS; PAIR: RingTexture).  Only columns whose window needs no border
 // clamping are handled here; the border columns ride in front of the tiles or go to a launch of their own (k_search.hip).
 // Semantics: SURVEY.md Appendix A.3b; oracle: oracle/bm_oracle.c.
 //
@@ -111,7 +111,9 @@ struct RingCfg {
     static constexpr bool STATIC_SLOTS = ITEMS == 1 && TRIP % 4 == 0;
     static constexpr int NSLOT = STATIC_SLOTS ? 4 : 3;
     // dwords per wave: staged rows + the texture prefix ring [W1][PPW] + the window texture sums of a group's rows [RPG][PPW] (u16)
-    static constexpr int STG = (NSLOT * SLOT + (W1 + RPG) * PPW / 2 + 3) & ~3;
+    // (PAIR: the prefix ring is [PPW][TRIP], one entry per column and unrolled row step, + the row terms of a group [PPW][RPG])
+    static constexpr int TEXD = (PAIR ? (TRIP + RPG) : (W1 + RPG)) * PPW / 2;
+    static constexpr int STG = (NSLOT * SLOT + TEXD + 3) & ~3;
     // PAIR: the records of a pair's LPG owners lie one behind the other at the bare record size (D/2 + D/16 = 36 dwords: 4 banks
     // on per owner) and pair p starts 2 (p & 1) + 8 (p >> 1) dwords behind that.  An 8-byte LDS access serves 16 lanes per cycle
     // from 32 banks; the 16 lanes here are the 8 pairs x 2 lanes whose slices lie 4 dwords apart in the target record, so the
@@ -241,22 +243,16 @@ __device__ __forceinline__ uint64_t ring_add_halves(uint64_t a, uint64_t b)
 // quad-group: the shared pieces are summed once (sh, from 0), each column adds its one-byte piece (v_mqsad skips the zeroed
 // reference bytes) on top of its own prefix sum, and sh joins both with plain additions -- NP + 1 quad-SADs for the pair
 // instead of 2 NP.  No carry between the packed halves: e + sh IS the column's new prefix sum, which stays below 2^16
-// (ring_rows_cap, rebase).  tpk = the texture terms of the row (the caller adds them to its packed prefix sums): x0 in the
-// low half, x0 + 1 in the high half.
+// (ring_rows_cap, rebase).  The texture term is not formed here: eight lanes would repeat it for every row, and each owner needs
+// one per group -- RingTexture below.
 template <int D, int WS, int LPP, int K, int NRLc>
-__device__ __forceinline__ void ring_step_pair(RingState<D, WS, LPP>& st, const RowRegs<D, WS, LPP>& rw, uint32_t capb,
-                                               uint32_t& tpk, uint32_t (&S)[NRLc], uint32_t (&S2)[NRLc])
+__device__ __forceinline__ void ring_step_pair(RingState<D, WS, LPP>& st, const RowRegs<D, WS, LPP>& rw, uint32_t (&S)[NRLc], uint32_t (&S2)[NRLc])
 {
     using C = RingCfg<D, WS, LPP>;
     static_assert(C::PAIR && WS % 4 == 1, "the two windows share whole dwords only for w = 1 (mod 4)");
     constexpr int NP = C::NP, NGL = C::NGL, W1 = C::W1;
     constexpr int KP = (K + W1 - 1) % W1, KO = (K + 1) % W1;
     const uint32_t lf = rw.l[0] & 0xff000000u, ll = rw.l[NP] & 0x000000ffu;
-    uint32_t tsh = 0;
-#pragma unroll
-    for (int k = 1; k < NP; ++k) tsh = __builtin_amdgcn_sad_u8(rw.l[k], capb, tsh);
-    const uint32_t t1 = __builtin_amdgcn_msad_u8(capb, lf, tsh), t2 = __builtin_amdgcn_msad_u8(capb, ll, tsh);   // (zero reference bytes are skipped)
-    tpk = t1 | (t2 << 16);
     uint64_t sh[NGL], e1[NGL], e2[NGL];
     // issue order = window index (the LDS returns the windows in order)
 #pragma unroll
@@ -290,6 +286,86 @@ __device__ __forceinline__ void pin(uint32_t (&v)[N])
 #pragma unroll
     for (int i = 0; i < N; ++i) asm volatile("" : "+v"(v[i]));
 }
+
+template <typename T>
+__device__ __forceinline__ __attribute__((address_space(3))) T* lds_as(uint32_t a) { return (__attribute__((address_space(3))) T*)(uintptr_t)a; }
+
+// The texture window sums of the PAIRED layout: one row term per OWNER and row group instead of one per lane and row.
+// Slots are static and a trip is a multiple of four rows, so row R of every group sits in staging slot R; step U + R commits
+// row U + R + 2 at its end.  Between the commits of steps U + 1 and U + 2 all four rows of the group are therefore resident,
+// and the owner (p, h) of column x0 + j, row k (j = h & 1, k = h >> 1) reads ITS row's left bytes at lane-constant addresses:
+// the two shared dwords and one edge byte (ds_read_u8 delivers it zero-extended; v_msad skips the three zero bytes).
+//   term():   inside step U + 2, before its commit: the row term, as u16, to terms[column][k]
+//   prefix(): behind that commit: the four terms of the column in one 8-byte read; own prefix = the carried prefix (replicated
+//             in the column's four owners) + the terms of the rows <= k (two v_dot2_u32_u16 with lane-constant 0/1 weights), to
+//             ring[column][U + k]; the carried prefix moves on by all four
+//   back():   the prefix w rows back, ring[column][(U + k - w) mod TRIP] -- base + immediate, but for the one group where the
+//             wrap falls between the group's rows (U = w - 1: row -1 for k = 0), which has a lane-constant address of its own
+// Everything is taken modulo 2^16 (window sums are < 2^16); the ring is zeroed in the prologue: rows above the strip read 0.
+// (The four owners of a column read their rows from four slots 64 dwords apart -- the same banks.  Slots of 72 dwords take
+//  those conflicts away and cost seven address additions, the offsets no longer fit ds_read2: measured, no gain, not kept.)
+template <typename C>
+struct RingTexture {
+    static constexpr int TRIP = C::TRIP, RPG = C::RPG, WS = C::W1 - 1;
+    static_assert(RPG == 4 && TRIP % RPG == 0 && TRIP >= WS + RPG && (WS - 1) % RPG == 0, "one straddling group, at U = w - 1");
+    static constexpr int RING_BYTES = C::PPW * TRIP * 2;      // u16 [PPW][TRIP]; behind it the terms, u16 [PPW][RPG]
+    uint32_t a_row, a_edge;       // the owned row's shared dwords / edge byte in the staging slots
+    uint32_t a_term, a_col;       // terms[column][k], terms[column][0]
+    uint32_t a_ring, a_wrap;      // ring[column][k], ring[column][(k + TRIP - 1) % TRIP]
+    uint32_t w_lo, w_hi;          // packed 0/1 weights of the rows (0, 1) and (2, 3): rows <= k
+    uint32_t carry;               // prefix sum of the column up to the last row of the previous group
+
+    __device__ __forceinline__ void init(uint32_t stg_addr, uint32_t tex_addr, int p, int h)
+    {
+        const int k = h >> 1, j = h & 1, colw = 2 * p + j;
+        a_row = stg_addr + (uint32_t)(k * C::SLOT + p + 1) * 4;
+        a_edge = stg_addr + (uint32_t)(k * C::SLOT + p) * 4 + (j ? 12u : 3u);
+        a_col = tex_addr + RING_BYTES + (uint32_t)colw * (RPG * 2);
+        a_term = a_col + 2 * k;
+        a_ring = tex_addr + (uint32_t)(colw * TRIP + k) * 2;
+        a_wrap = tex_addr + (uint32_t)(colw * TRIP + (k + TRIP - 1) % TRIP) * 2;
+        w_lo = k >= 1 ? 0x00010001u : 0x00000001u;
+        w_hi = k >= 3 ? 0x00010001u : k == 2 ? 0x00000001u : 0u;
+        carry = 0;
+        // (laundered: every access below is one lane-constant register + an immediate)
+        asm volatile("" : "+v"(a_row), "+v"(a_edge), "+v"(a_term), "+v"(a_col), "+v"(a_ring), "+v"(a_wrap), "+v"(w_lo), "+v"(w_hi));
+    }
+    template <int U>
+    __device__ __forceinline__ uint32_t back() const
+    {
+        constexpr int lo = U - WS;                                    // the group's first row looks back to row `lo` of the trip
+        if constexpr (lo < 0 && lo + RPG - 1 >= 0) {
+            static_assert(lo == -1, "a_wrap is the address for U = w - 1");
+            return *lds_as<const uint16_t>(a_wrap);
+        } else {
+            constexpr int idx = (lo + TRIP) % TRIP;
+            static_assert(idx + RPG - 1 < TRIP, "no wrap inside the group");
+            return *lds_as<const uint16_t>(a_ring + idx * 2);
+        }
+    }
+    __device__ __forceinline__ void term(uint32_t capb) const
+    {
+        const uint32_t l1 = *lds_as<const uint32_t>(a_row), l2 = *lds_as<const uint32_t>(a_row + 4);
+        const uint32_t e = *lds_as<const uint8_t>(a_edge);
+        uint32_t t = __builtin_amdgcn_sad_u8(l1, capb, 0u);
+        t = __builtin_amdgcn_sad_u8(l2, capb, t);
+        t = __builtin_amdgcn_msad_u8(capb, e, t);                     // (zero reference bytes are skipped)
+        *lds_as<uint16_t>(a_term) = (uint16_t)t;
+    }
+    template <int U>
+    __device__ __forceinline__ uint32_t prefix()
+    {
+        const uint64_t q = *lds_as<const uint64_t>(a_col);
+        const sel_us2 lo = __builtin_bit_cast(sel_us2, (uint32_t)q), hi = __builtin_bit_cast(sel_us2, (uint32_t)(q >> 32));
+        const sel_us2 ones = __builtin_bit_cast(sel_us2, 0x00010001u);
+        uint32_t own = __builtin_amdgcn_udot2(lo, __builtin_bit_cast(sel_us2, w_lo), carry, false);
+        own = __builtin_amdgcn_udot2(hi, __builtin_bit_cast(sel_us2, w_hi), own, false);
+        carry = __builtin_amdgcn_udot2(lo, ones, carry, false);
+        carry = __builtin_amdgcn_udot2(hi, ones, carry, false);
+        *lds_as<uint16_t>(a_ring + U * 2) = (uint16_t)own;
+        return own;
+    }
+};
 
 // compile-time loops: over the row groups of one trip of the row loop (f returns false to stop) and over a group's rows
 template <typename F, int... U>
@@ -365,11 +441,12 @@ __global__ __launch_bounds__(256, (RingBounds<D, WS, LPP, FUSE>::WAVES)) void k_
     // the window texture sum of row R of a group goes to ptw[R][p] (every lane of the pixel writes the same 16 bits) and the
     // row's owner reads its own at the end of the group: no per-row select in registers
     unsigned short* ptw = ptr + W1 * PPW;
-    // (PAIR: a pair's two 16-bit entries are one dword, x0 in the low half -- written and read as such by the row step)
-    uint32_t* const ptr2 = (uint32_t*)ptr;
-    uint32_t* const ptw2 = (uint32_t*)ptw;
     const bool owner = PAIR || RPG == LPP || h < RPG;   // this lane owns row h of every group
-    const unsigned short* ptw_own = ptw + (owner ? hrow : 0) * PPW + (PAIR ? 2 * p + (h & 1) : p);
+    const unsigned short* ptw_own = ptw + (owner ? hrow : 0) * PPW + p;
+    // (PAIR: neither of the two -- a prefix ring per column and the row terms of a group in their place, RingTexture)
+    struct None {};
+    [[maybe_unused]] std::conditional_t<PAIR, RingTexture<C>, None> tex;
+    static_assert(!PAIR || ((C::NSLOT * SLOT) % 2 == 0 && C::WAVE_LDS % 2 == 0), "the row terms of a column are read as 8 bytes");
     // this lane's selection record (lanes that own nothing: never used); rec0: the record of the lane group's first owner
     uint32_t* scr = stg + C::STG + (PAIR ? C::pair_rec(p, h) : (owner ? lane : 0) * RECD);
     uint32_t* const rec0 = stg + C::STG + (PAIR ? C::pair_rec(p, 0) : p * RECD);
@@ -432,12 +509,17 @@ __global__ __launch_bounds__(256, (RingBounds<D, WS, LPP, FUSE>::WAVES)) void k_
             st.P[k][i] = 0;
             if constexpr (PAIR) st.P2[k][i] = 0;
         }
+    if constexpr (PAIR) {
+        constexpr int RINGD = RingTexture<C>::RING_BYTES / 4;
 #pragma unroll
-    for (int k = 0; k < W1; ++k) {
-        if constexpr (PAIR) ptr2[k * GPW + p] = 0;
-        else ptr[k * PPW + p] = 0;
+        for (int i = 0; i < (RINGD + 63) / 64; ++i)
+            if (i * 64 + 63 < RINGD || lane + i * 64 < RINGD) stg[C::NSLOT * SLOT + lane + i * 64] = 0;
+        tex.init(lds_addr(stg), lds_addr(stg + C::NSLOT * SLOT), p, h);
+    } else {
+#pragma unroll
+        for (int k = 0; k < W1; ++k) ptr[k * PPW + p] = 0;
     }
-    uint32_t pt = 0;                                // texture prefix sum of the rows so far (PAIR: both columns', packed)
+    uint32_t pt = 0;                                // texture prefix sum of the rows so far
 
     const int nsteps = (ys1 - ys0) + WS - 1;
     const int nstepsg = (nsteps + RPG - 1) / RPG * RPG;   // rows go in groups of RPG; padded last rows are computed and dropped
@@ -487,7 +569,8 @@ __global__ __launch_bounds__(256, (RingBounds<D, WS, LPP, FUSE>::WAVES)) void k_
         }
     };
     // Sr / Sr2: the window sums of the row (PAIR: of column x0 / x0 + 1; Sr2 is not written otherwise)
-    auto step = [&](auto Kc, auto SLc, auto Rc, const RowRegs<D, WS, LPP>& rw, uint32_t (&Sr)[NRL], uint32_t (&Sr2)[NRL]) {
+    [[maybe_unused]] uint32_t tback = 0, tpre = 0;  // PAIR: the owned row's texture prefix sum and the one w rows back
+    auto step = [&](auto Kc, auto SLc, auto Rc, auto Uc, const RowRegs<D, WS, LPP>& rw, uint32_t (&Sr)[NRL], uint32_t (&Sr2)[NRL]) {
         constexpr int K = decltype(Kc)::value;            // ring slot of row t: a compile-time register set
         using SetIn = std::integral_constant<int, (K + 1) & 1>;    // row t+3 goes where row t+1 was (W1 is even: K and t have the same parity)
         using SetOut = std::integral_constant<int, K & 1>;         // row t+2
@@ -495,11 +578,11 @@ __global__ __launch_bounds__(256, (RingBounds<D, WS, LPP, FUSE>::WAVES)) void k_
         uint32_t tnew = 0;
         constexpr int KO = (K + 1) % W1;
         if constexpr (PAIR) {
-            ring_step_pair<D, WS, LPP, K>(st, rw, capb, tnew, Sr, Sr2);
-            pt = __builtin_bit_cast(uint32_t, __builtin_bit_cast(sel_us2, pt) + __builtin_bit_cast(sel_us2, tnew));
-            const uint32_t told = ptr2[KO * GPW + p];
-            ptr2[K * GPW + p] = pt;
-            ptw2[decltype(Rc)::value * GPW + p] = __builtin_bit_cast(uint32_t, __builtin_bit_cast(sel_us2, pt) - __builtin_bit_cast(sel_us2, told));
+            constexpr int R = decltype(Rc)::value, U = decltype(Uc)::value;
+            // the group's four rows are resident from the commit of step 1 to the commit of this step's end (RingTexture)
+            if constexpr (R == 2) { tback = tex.template back<U>(); tex.term(capb); }
+            if constexpr (R == 3) tpre = tex.template prefix<U>();
+            ring_step_pair<D, WS, LPP, K>(st, rw, Sr, Sr2);
             pin(Sr2);
         } else {
             ring_step<D, WS, LPP, K>(st, rw, rg.lastmask, capb, tnew, Sr);
@@ -557,7 +640,7 @@ __global__ __launch_bounds__(256, (RingBounds<D, WS, LPP, FUSE>::WAVES)) void k_
                 using SL = std::integral_constant<int, (U + R) % 4>;    // (static slots: TRIP % 4 == 0, so t % 4 == (U + R) % 4)
                 lds_row(SL{}, rw);
                 uint32_t S2[NRL] = {};                                  // (PAIR only: column x0 + 1)
-                step(std::integral_constant<int, (U + R) % W1>{}, SL{}, Rc, rw, S[R], S2);
+                step(std::integral_constant<int, (U + R) % W1>{}, SL{}, Rc, std::integral_constant<int, U>{}, rw, S[R], S2);
                 // the row's slice and the minima of its groups go to its owner's record at once: S[R] is dead after this
                 // (also while the window fills: no branch around it)
                 if constexpr (PAIR) {
@@ -573,7 +656,9 @@ __global__ __launch_bounds__(256, (RingBounds<D, WS, LPP, FUSE>::WAVES)) void k_
             dofs += dstep; cofs += cstep;
             // Selection is skipped for a wave none of whose pixels can produce a disparity here (untextured, outside the
             // tile, masked): exact, such a pixel is FILTERED and writes no cost whatever its SADs are.
-            const int tsum = *ptw_own;                               // the texture sum of the row this lane owns
+            int tsum;                                                // the texture sum of the row this lane owns
+            if constexpr (PAIR) tsum = (int)((tpre - tback) & 0xffffu);
+            else tsum = *ptw_own;
             // (bitwise: one lane mask for the vote, no branch around the texture read)
             const bool dead = !active | !row_ok | masked_col | (tsum < g.tex);
             if (__builtin_amdgcn_ballot_w64(!dead) == 0) {
