@@ -495,6 +495,56 @@ int rtdm_estimate_frame_classes(rtdm_bm* bm, rtdm_rectify* rc, rtdm_objects* ob,
                                 double calibration_unit, rtdm_object* objects, double* mean_cm, int* counts, int max_objects,
                                 int* nobjects, int16_t* disp, size_t disp_pitch);
 
+/* ---- which pixels belong to which object: label planes, pixel moments, own-pixel depth (rules L1-L8) ----
+ * rtdm_objects_detect_labels_device: rtdm_objects_detect_device with two more outputs, each optional.
+ *                        d_labels: one int32 plane per (frame, class), plane f * nclasses + c at d_labels + plane *
+ *                        label_plane_stride bytes, rows of label_pitch bytes.  A pixel holds 1 + i where i is the index, in frame
+ *                        f's stored list, of the kept object whose component (8-connected foreground of the filtered class
+ *                        plane) contains it; every other pixel holds 0: background, the outermost rows and columns under
+ *                        zero_border, components that are enclosed, below min_area or beyond capacity.  Only width ints of a
+ *                        row are written.
+ *                        d_stats[f * capacity + i]: the raw moments of exactly the pixels that carry object i's label (x, y in
+ *                        frame coordinates, exact integers); its centroid is (m10 / m00, m01 / m00).  Entries at or beyond
+ *                        min(total_f, capacity) are left untouched.
+ *                        Labels and stats are bit-identical from run to run and independent of n, of the frame's position, of
+ *                        max_batch and of the chunking.  With both absent the call enqueues what rtdm_objects_detect_device
+ *                        enqueues and writes the same bytes.  Refusals: those of rtdm_objects_detect_device in its order, then
+ *                        RTDM_ERR_BAD_SIZE (label_pitch < 4 * width or no multiple of 4; a label_plane_stride that is no
+ *                        multiple of 4, or below label_pitch * height where a second plane follows; a d_labels that is not
+ *                        4-byte aligned; a d_stats that is not 8-byte aligned), then RTDM_ERR_UNSUPPORTED (a handle whose
+ *                        width * height * max(width, height)^2 does not fit int64: none that can be created today).
+ * rtdm_objects_detect_labels_batch: the same with host pointers; synchronous.
+ * rtdm_depth_objects_labels_device: rtdm_depth_objects_device with label planes in place of mask planes: object i of frame f
+ *                        is measured over its clipped box where label == i + 1 on plane f * nclasses + cls, so same-class
+ *                        pixels of OTHER objects inside its box stay out of its mean.  Everything else is that call's: the
+ *                        summation order (an object whose box holds no foreign foreground of its class gets the same bits
+ *                        from both), the untouched entries, the workspace (rtdm_depth_objects_workspace_bytes serves both).
+ *                        A label is only ever compared, never used as an index: no plane content makes the kernels read
+ *                        or write outside.  Refusals: that call's with "mask" read as "label": label_pitch < 4 * width or no
+ *                        multiple of 4, a stride that is no multiple of 4, d_labels not 4-byte aligned.
+ * rtdm_estimator_set_own_pixels: on != 0: rtdm_estimate_batch and rtdm_estimate_batch_device run the labels form of the
+ *                        detector and of the depth call, so every object is measured over its own pixels; objects, counts,
+ *                        ROIs and maps are unaffected.  The chunk's label planes (4 bytes per pixel and class plane of the
+ *                        detector) are allocated by this call, not per estimate, and freed when it is switched off.  The
+ *                        default is 0: nothing changes, allocations included.  Waits for the device. */
+typedef struct rtdm_object_stats { int64_t m00, m10, m01, m20, m11, m02; } rtdm_object_stats;
+int rtdm_objects_detect_labels_device(rtdm_objects* ob, int n, const uint8_t* d_rgb, size_t pitch, size_t frame_stride,
+                                      const rtdm_hsv_range* ranges, const int* range_class, int nranges, int nclasses,
+                                      int min_area, int zero_border, uint8_t* d_masks, size_t mask_pitch,
+                                      size_t mask_plane_stride, rtdm_object* d_objects, int capacity, int* d_counts,
+                                      rtdm_region* d_rois, int32_t* d_labels, size_t label_pitch, size_t label_plane_stride,
+                                      rtdm_object_stats* d_stats, void* hip_stream);
+int rtdm_objects_detect_labels_batch(rtdm_objects* ob, int n, const uint8_t* rgb, size_t pitch, size_t frame_stride,
+                                     const rtdm_hsv_range* ranges, const int* range_class, int nranges, int nclasses,
+                                     int min_area, int zero_border, uint8_t* masks, size_t mask_pitch, size_t mask_plane_stride,
+                                     rtdm_object* objects, int capacity, int* counts, rtdm_region* rois, int32_t* labels,
+                                     size_t label_pitch, size_t label_plane_stride, rtdm_object_stats* stats);
+int rtdm_depth_objects_labels_device(int device, int n, const int16_t* d_disp, size_t disp_pitch, size_t disp_frame_stride,
+                                     int width, int height, const double* Q, const int32_t* d_labels, size_t label_pitch,
+                                     size_t label_plane_stride, int nclasses, const rtdm_object* d_objects, int capacity,
+                                     const int* d_counts, double calibration_unit, double* d_mean_cm, int* d_npix,
+                                     void* d_workspace, size_t workspace_bytes, void* hip_stream);
+
 /* ---- the whole loop body on frame batches -------------------------------------------------------
  * rtdm_estimator_create: a handle for rtdm_estimate_batch.  It BORROWS the three handles: they must outlive it, live on one
  *                        device and fit together as rtdm_estimate_frame_classes asks (detector and matcher serve the
@@ -528,6 +578,8 @@ int rtdm_estimate_frame_classes(rtdm_bm* bm, rtdm_rectify* rc, rtdm_objects* ob,
 typedef struct rtdm_estimator rtdm_estimator;
 int rtdm_estimator_create(rtdm_bm* bm, rtdm_rectify* rc, rtdm_objects* ob, int max_batch, int capacity, rtdm_estimator** out);
 void rtdm_estimator_destroy(rtdm_estimator* est);
+int rtdm_estimator_set_own_pixels(rtdm_estimator* est, int on);
+int rtdm_estimator_get_own_pixels(const rtdm_estimator* est, int* on);
 int rtdm_estimate_batch(rtdm_estimator* est, int n, const uint8_t* rgb_left, size_t left_pitch, size_t left_frame_stride,
                         const uint8_t* rgb_right, size_t right_pitch, size_t right_frame_stride, const double* Q,
                         const rtdm_hsv_range* ranges, const int* range_class, int nranges, int nclasses, int min_area,

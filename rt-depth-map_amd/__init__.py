@@ -15,13 +15,13 @@ The C++ adapter that actually plugs into the reference is rt-depth-map_amd/host/
 are thin shells over the same C ABI (include/rtdm.h).
 """
 from . import binding, synth  # noqa: F401
-from .chain import (HIPEstimator, depth_objects_device, depth_objects_workspace_bytes, depth_stats_device, estimate_frame,  # noqa: F401
-                    estimate_frame_classes)
+from .chain import (HIPEstimator, depth_objects_device, depth_objects_labels_device, depth_objects_workspace_bytes,  # noqa: F401
+                    depth_stats_device, estimate_frame, estimate_frame_classes)
 from .matcher import PREFILTER_NORMALIZED_RESPONSE, PREFILTER_XSOBEL, HIPMatcher, HIPSemiGlobalMatcher, create_right_matcher  # noqa: F401
 from .mjpeg import HIPMJPEGDecoder, mjpeg_probe  # noqa: F401
 from .morph import (MORPH_BLACKHAT, MORPH_CLOSE, MORPH_CROSS, MORPH_DILATE, MORPH_ELLIPSE, MORPH_ERODE, MORPH_GRADIENT,  # noqa: F401
                     MORPH_OPEN, MORPH_OPEN_CLOSE, MORPH_RECT, MORPH_TOPHAT, HIPMorphologicalFilter, get_structuring_element)
-from .objects import OBJECT_DTYPE, HIPObjectDetector  # noqa: F401
+from .objects import OBJECT_DTYPE, STATS_DTYPE, HIPObjectDetector, centroids  # noqa: F401
 from .rectify import HIPRectifier, init_undistort_rectify_map, load_calibration, stereo_rectify  # noqa: F401
 from .synth import synth_pairs_device  # noqa: F401
 from .wls import HIPDisparityWLSFilter, create_disparity_wls_filter, wls_params_for  # noqa: F401

@@ -95,3 +95,22 @@ def mask_planes(d_masks, n, K, H, W):
     if st[3] != 1 or st[2] < W or st[1] < st[2] * H or (n > 1 and st[0] != K * st[1]):
         raise ValueError("d_masks: contiguous rows and one stride from plane to plane; got strides %s" % (tuple(st),))
     return d_masks.data_ptr(), st[2], st[1]
+
+
+def label_planes(d_labels, n, K, H, W):
+    """(pointer, row pitch, plane stride) in bytes of the int32 [n, K, H, W] device label planes (row pitch and plane stride free)"""
+    import torch
+    if d_labels.dtype != torch.int32 or tuple(d_labels.shape) != (n, K, H, W):
+        raise ValueError("d_labels must be int32 n x nclasses x H x W; got %s %s" % (d_labels.dtype, tuple(d_labels.shape)))
+    st = d_labels.stride()
+    if st[3] != 1 or st[2] < W or st[1] < st[2] * H or (n > 1 and st[0] != K * st[1]):
+        raise ValueError("d_labels: contiguous rows and one stride from plane to plane; got strides %s" % (tuple(st),))
+    return d_labels.data_ptr(), st[2] * 4, st[1] * 4
+
+
+def stats_lists(d_stats, n, capacity):
+    """the device moments: uint8 [n, capacity * 48] (view a host copy as STATS_DTYPE)"""
+    import torch
+    if d_stats.dtype != torch.uint8 or tuple(d_stats.shape) != (n, capacity * 48) or not d_stats.is_contiguous():
+        raise ValueError("d_stats must be a contiguous uint8 tensor n x capacity * 48; got %s %s" % (d_stats.dtype, tuple(d_stats.shape)))
+    return d_stats.data_ptr()

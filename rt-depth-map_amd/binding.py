@@ -35,6 +35,10 @@ class Object(C.Structure):              # rtdm_object, 32 bytes
     _fields_ = [(n, C.c_int) for n in ("x", "y", "width", "height", "cls", "first_pixel")] + [("reserved", C.c_int * 2)]
 
 
+class ObjectStats(C.Structure):         # rtdm_object_stats, 48 bytes
+    _fields_ = [(n, C.c_int64) for n in ("m00", "m10", "m01", "m20", "m11", "m02")]
+
+
 MAX_HSV_RANGES, MAX_CLASSES = 16, 8      # RTDM_MAX_HSV_RANGES, RTDM_MAX_CLASSES
 MAX_REGIONS = 64                         # RTDM_MAX_REGIONS: objects of a frame that get a depth
 
@@ -177,6 +181,14 @@ SIGNATURES = {          # every entry point of include/rtdm.h: (restype, argtype
     "rtdm_estimate_frame_classes": (C.c_int, [vp, vp, vp, u8p, sz, u8p, sz, C.POINTER(C.c_double), C.POINTER(HsvRange),
                                               C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, vp,
                                               C.POINTER(C.c_double), C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int), i16p, sz]),
+    "rtdm_objects_detect_labels_device": (C.c_int, [vp, C.c_int, u8p, sz, sz, C.POINTER(HsvRange), C.POINTER(C.c_int), C.c_int, C.c_int,
+                                                    C.c_int, C.c_int, u8p, sz, sz, vp, C.c_int, vp, vp, vp, sz, sz, vp, vp]),
+    "rtdm_objects_detect_labels_batch": (C.c_int, [vp, C.c_int, u8p, sz, sz, C.POINTER(HsvRange), C.POINTER(C.c_int), C.c_int, C.c_int,
+                                                   C.c_int, C.c_int, u8p, sz, sz, vp, C.c_int, vp, vp, vp, sz, sz, vp]),
+    "rtdm_depth_objects_labels_device": (C.c_int, [C.c_int, C.c_int, i16p, sz, sz, C.c_int, C.c_int, C.POINTER(C.c_double), vp, sz, sz,
+                                                   C.c_int, vp, C.c_int, vp, C.c_double, vp, vp, vp, sz, vp]),
+    "rtdm_estimator_set_own_pixels": (C.c_int, [vp, C.c_int]),
+    "rtdm_estimator_get_own_pixels": (C.c_int, [vp, C.POINTER(C.c_int)]),
     "rtdm_depth_objects_workspace_bytes": (sz, [C.c_int, C.c_int, C.c_int]),
     "rtdm_depth_objects_device": (C.c_int, [C.c_int, C.c_int, i16p, sz, sz, C.c_int, C.c_int, C.POINTER(C.c_double), u8p, sz, sz,
                                             C.c_int, vp, C.c_int, vp, C.c_double, vp, vp, vp, sz, vp]),

@@ -4,7 +4,7 @@ import ctypes as C
 import numpy as np
 
 from . import binding as B
-from ._marshal import Handle, device_plane, mask_planes, object_lists, object_tuples, q16, regions_array, rgb_batch
+from ._marshal import Handle, device_plane, label_planes, mask_planes, object_lists, object_tuples, q16, regions_array, rgb_batch
 from .objects import HSV_HIGH, HSV_LOW, OBJECT_DTYPE, _hsv_classes, _hsv_range
 
 
@@ -77,11 +77,27 @@ def depth_objects_device(d_disp, Q, d_masks, d_objects, d_counts, d_mean_cm, d_n
     tensor of at least depth_objects_workspace_bytes(n, capacity, H) bytes (None: one is allocated through torch and returned;
     keep it until the work has finished).  Enqueued on `stream` (a raw hipStream_t value; None = the null stream), not
     synchronised.  -> the workspace tensor."""
+    return _depth_objects(False, d_disp, Q, d_masks, d_objects, d_counts, d_mean_cm, d_npix, calibration_unit, capacity, d_workspace,
+                          device, stream)
+
+
+def depth_objects_labels_device(d_disp, Q, d_labels, d_objects, d_counts, d_mean_cm, d_npix, calibration_unit=25.0, capacity=None,
+                                d_workspace=None, device=0, stream=None):
+    """depth_objects_device over every object's OWN pixels (rtdm_depth_objects_labels_device, rule L5): d_labels int32
+    [n, nclasses, H, W] as HIPObjectDetector.detect_labels_device leaves them (row pitch and plane stride free) in place of the
+    class masks; everything else as depth_objects_device.  -> the workspace tensor."""
+    return _depth_objects(True, d_disp, Q, d_labels, d_objects, d_counts, d_mean_cm, d_npix, calibration_unit, capacity, d_workspace,
+                          device, stream)
+
+
+def _depth_objects(labels, d_disp, Q, d_masks, d_objects, d_counts, d_mean_cm, d_npix, calibration_unit, capacity, d_workspace, device,
+                   stream):
+    """Both forms of the call: the planes are the class masks (uint8) or the detector's label planes (int32)."""
     import torch
     dp, dpitch, dframe = device_plane(d_disp, "d_disp", torch.int16)
     n, H, W = d_disp.shape
     K = d_masks.shape[1] if d_masks.dim() == 4 else 0          # the class count is the masks'; any other rank is refused below
-    mp, mpitch, mplane = mask_planes(d_masks, n, K, H, W)
+    mp, mpitch, mplane = (label_planes if labels else mask_planes)(d_masks, n, K, H, W)
     capacity = object_lists(d_objects, d_counts, n, K, capacity)
     if d_mean_cm.dtype != torch.float64 or tuple(d_mean_cm.shape) != (n, capacity) or not d_mean_cm.is_contiguous():
         raise ValueError("d_mean_cm must be a contiguous float64 tensor n x capacity")
@@ -90,10 +106,11 @@ def depth_objects_device(d_disp, Q, d_masks, d_objects, d_counts, d_mean_cm, d_n
     need = depth_objects_workspace_bytes(n, capacity, H)
     if d_workspace is None:
         d_workspace = torch.empty(need, dtype=torch.uint8, device=d_disp.device)
-    B.check(B.lib().rtdm_depth_objects_device(device, n, dp, dpitch, dframe, W, H, q16(Q),
-                                              mp, mpitch, mplane, K, d_objects.data_ptr(), capacity, d_counts.data_ptr(),
-                                              calibration_unit, d_mean_cm.data_ptr(), d_npix.data_ptr(), d_workspace.data_ptr(),
-                                              d_workspace.numel(), stream), "rtdm_depth_objects_device")
+    name = "rtdm_depth_objects_labels_device" if labels else "rtdm_depth_objects_device"
+    B.check(getattr(B.lib(), name)(device, n, dp, dpitch, dframe, W, H, q16(Q),
+                                   mp, mpitch, mplane, K, d_objects.data_ptr(), capacity, d_counts.data_ptr(),
+                                   calibration_unit, d_mean_cm.data_ptr(), d_npix.data_ptr(), d_workspace.data_ptr(),
+                                   d_workspace.numel(), stream), name)
     return d_workspace
 
 
@@ -103,12 +120,25 @@ class HIPEstimator(Handle):
     detector's max_batch) frames, `capacity` objects of a frame are stored and measured."""
     _destroy = "rtdm_estimator_destroy"
 
-    def __init__(self, matcher, rectifier, detector, max_batch=1, capacity=256):
+    def __init__(self, matcher, rectifier, detector, max_batch=1, capacity=256, own_pixels=False):
         self.matcher, self.rectifier, self.detector = matcher, rectifier, detector
         self.max_batch, self.capacity = int(max_batch), int(capacity)
         self._h = C.c_void_p()
         B.check(B.lib().rtdm_estimator_create(matcher._h, rectifier._h, detector._h, self.max_batch, self.capacity, C.byref(self._h)),
                 "rtdm_estimator_create")
+        if own_pixels:
+            self.own_pixels = True
+
+    @property
+    def own_pixels(self):
+        """True: every object is measured over its own pixels (its label), not over its class's mask inside its box (rule L7)."""
+        on = C.c_int()
+        B.check(B.lib().rtdm_estimator_get_own_pixels(self._h, C.byref(on)), "rtdm_estimator_get_own_pixels")
+        return bool(on.value)
+
+    @own_pixels.setter
+    def own_pixels(self, on):
+        B.check(B.lib().rtdm_estimator_set_own_pixels(self._h, int(bool(on))), "rtdm_estimator_set_own_pixels")
 
     def estimate(self, rgb_left, rgb_right, Q, ranges, classes=None, min_area=100, zero_border=True, calibration_unit=25.0,
                  want_disp=False, disp=None):

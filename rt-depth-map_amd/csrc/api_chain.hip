@@ -182,7 +182,29 @@ void rtdm_estimator_destroy(rtdm_estimator* E)
     (void)hipSetDevice(E->device);
     (void)hipDeviceSynchronize();                       // its buffers may be in use on any stream; the borrowed handles are not touched
     E->mem.release();
+    if (E->dLabels) (void)hipFree(E->dLabels);
     delete E;
+}
+
+// L7.  The label planes of a chunk live from the call that switches own pixels on to the one that switches them off.
+int rtdm_estimator_set_own_pixels(rtdm_estimator* E, int on)
+{
+    if (!E) return RTDM_ERR_NULL;
+    if ((on != 0) == (E->dLabels != nullptr)) return RTDM_OK;
+    HIPC(hipSetDevice(E->device));
+    HIPC(hipDeviceSynchronize());                       // (the planes may be in use on any stream)
+    if (!on) { HIPC(hipFree(E->dLabels)); E->dLabels = nullptr; return RTDM_OK; }
+    const size_t bytes = (size_t)E->chunk * E->ob->maxC * E->rc->rw * E->rc->rh * sizeof(int32_t);
+    const hipError_t e = hipMalloc(&E->dLabels, bytes);
+    if (e != hipSuccess) { E->dLabels = nullptr; return create_failed("rtdm_estimator_set_own_pixels", e); }
+    return RTDM_OK;
+}
+
+int rtdm_estimator_get_own_pixels(const rtdm_estimator* E, int* on)
+{
+    if (!E || !on) return RTDM_ERR_NULL;
+    *on = E->dLabels != nullptr;
+    return RTDM_OK;
 }
 
 int rtdm_estimator_create(rtdm_bm* bm, rtdm_rectify* rc, rtdm_objects* ob, int max_batch, int capacity, rtdm_estimator** out)
@@ -298,7 +320,9 @@ static int est_run(rtdm_estimator* E, int n, const EstIo& io, const double* Q, c
         int* dCounts = io.device ? io.counts + (size_t)i0 * K : E->dCounts;
         double* dMean = io.device ? io.mean + (size_t)i0 * cap : E->dMean;
         int* dNpix = io.device ? io.npix + (size_t)i0 * cap : E->dNpix;
-        int st = objects_run_chunk(ob, m, E->dCrop, E->cpitch, cframe, C, min_area, zero_border, nullptr, 0, 0, dObj, cap, dCounts, E->dRois, s);
+        const size_t lpitch = (size_t)W * sizeof(int32_t), lplane = lpitch * H;       // own pixels (L7): the chunk's label planes
+        int st = objects_run_chunk(ob, m, E->dCrop, E->cpitch, cframe, C, min_area, zero_border, nullptr, 0, 0, dObj, cap, dCounts, E->dRois, s,
+                                   CcLabelsOut{E->dLabels, lpitch, lplane, nullptr});
         if (st) return st;
         // 3. the one read-back in front of the matcher: per-class counts and union boxes
         HIPC(hipMemcpyAsync(E->hCounts, dCounts, (size_t)m * K * sizeof(int), hipMemcpyDeviceToHost, s));
@@ -327,8 +351,10 @@ static int est_run(rtdm_estimator* E, int n, const EstIo& io, const double* Q, c
             j = j1;
         }
         // 5. every object of the chunk under its own class's mask, against its own frame's plane of the matcher
-        const DepthObjects a{bm->dOut, O.pitch_e, O.frame_e, ob->dMaskOut, ob->mpitch, ob->mpitch * H, dObj, dCounts, m, W, H, K, cap, 0};
-        launch_depth_objects(a, q, unit, E->dWork, dMean, dNpix, s);
+        // (with own pixels: under its own label on its class's label plane)
+        const DepthObjects a{bm->dOut, O.pitch_e, O.frame_e, E->dLabels ? (const uint8_t*)E->dLabels : ob->dMaskOut,
+                             E->dLabels ? lpitch : ob->mpitch, E->dLabels ? lplane : ob->mpitch * H, dObj, dCounts, m, W, H, K, cap, 0};
+        launch_depth_objects(a, q, unit, E->dWork, dMean, dNpix, s, E->dLabels != nullptr);
         HIPC(hipGetLastError());
         // 6. the results; frames without objects keep what the caller's arrays held
         for (int j = 0; io.disp && j < m; ++j) {

@@ -13,6 +13,8 @@ void rtdm_objects_destroy(rtdm_objects* ob)
     if (ob->stream) (void)hipStreamSynchronize(ob->stream);
     ob->mem.release();
     if (ob->dObj) (void)hipFree(ob->dObj);
+    if (ob->dLab) (void)hipFree(ob->dLab);
+    if (ob->dStats) (void)hipFree(ob->dStats);
     if (ob->stream) (void)hipStreamDestroy(ob->stream);
     delete ob;
 }
@@ -20,6 +22,7 @@ void rtdm_objects_destroy(rtdm_objects* ob)
 int rtdm_objects_create_batch(int width, int height, int max_batch, int max_classes, int device, rtdm_objects** out)
 {
     static_assert(sizeof(rtdm_object) == 32 && sizeof(CcObject) == sizeof(rtdm_object), "one record layout");
+    static_assert(sizeof(rtdm_object_stats) == 48 && sizeof(CcStats) == sizeof(rtdm_object_stats), "one moments layout");
     static_assert(HSV_MAX_RANGES == RTDM_MAX_HSV_RANGES && HSV_MAX_CLASSES == RTDM_MAX_CLASSES, "one limit");
     if (!out) return RTDM_ERR_NULL;
     *out = nullptr;
@@ -173,11 +176,28 @@ static int objects_batch_check(const rtdm_objects* ob, int n, const void* rgb, s
     return RTDM_OK;
 }
 
+// L8: what the labels form of a call refuses on top, in the order include/rtdm.h gives.  W, H: the handle's (L2: the largest
+// moment, below W * H * max(W, H)^2, must fit int64).  planes: how many label planes the call writes or reads.
+static int labels_check(const void* labels, size_t label_pitch, size_t label_plane_stride, const void* stats, int W, int H, size_t planes)
+{
+    if (labels) {
+        if (label_pitch < (size_t)W * 4 || label_pitch % 4) return RTDM_ERR_BAD_SIZE;
+        if (label_plane_stride % 4 || (planes > 1 && label_plane_stride < label_pitch * H)) return RTDM_ERR_BAD_SIZE;
+        if ((size_t)labels % 4) return RTDM_ERR_BAD_SIZE;
+    }
+    if (stats && (size_t)stats % 8) return RTDM_ERR_BAD_SIZE;
+    if (labels || stats) {
+        const unsigned __int128 side = (unsigned)std::max(W, H), top = (unsigned __int128)W * H * side * side;
+        if (top > (unsigned __int128)INT64_MAX) return RTDM_ERR_UNSUPPORTED;
+    }
+    return RTDM_OK;
+}
+
 // One chunk (m <= maxB frames) on s: class masks -> filter -> labelling -> selection.  d_masks == null: the filtered planes
-// stay in the handle (dMaskOut, rows of ob->mpitch).
+// stay in the handle (dMaskOut, rows of ob->mpitch).  lab: the chunk's label planes and moments, each may be null.
 int rtdm::objects_run_chunk(rtdm_objects* ob, int m, const uint8_t* d_rgb, size_t pitch, size_t frame_stride, const HsvClasses& C,
                             int min_area, int zero_border, uint8_t* d_masks, size_t mask_pitch, size_t mask_plane_stride,
-                            CcObject* d_objects, int capacity, int* d_counts, int* d_rois, hipStream_t s)
+                            CcObject* d_objects, int capacity, int* d_counts, int* d_rois, hipStream_t s, const CcLabelsOut& lab)
 {
     const int W = ob->W, H = ob->H, planes = m * C.nclasses;
     const size_t ip = ob->mpitch, iplane = ip * H;
@@ -186,19 +206,23 @@ int rtdm::objects_run_chunk(rtdm_objects* ob, int m, const uint8_t* d_rgb, size_
     const int rc = morph_run(ob->morph, Plane8{ob->dMaskIn, ip, iplane}, out, ob->dT0, ob->dT1, W, H, planes, s);
     if (rc) return rc;
     launch_cc_objects(out.base, out.pitch, out.frame, m, C.nclasses, W, H, zero_border, min_area, ob->dScratch, ob->maxRec, d_objects,
-                      capacity, d_counts, d_rois, s);
+                      capacity, d_counts, d_rois, s, lab);
     HIPC(hipGetLastError());
     return RTDM_OK;
 }
 
-int rtdm_objects_detect_device(rtdm_objects* ob, int n, const uint8_t* d_rgb, size_t pitch, size_t frame_stride,
-                               const rtdm_hsv_range* ranges, const int* range_class, int nranges, int nclasses, int min_area,
-                               int zero_border, uint8_t* d_masks, size_t mask_pitch, size_t mask_plane_stride,
-                               rtdm_object* d_objects, int capacity, int* d_counts, rtdm_region* d_rois, void* hip_stream)
+int rtdm_objects_detect_labels_device(rtdm_objects* ob, int n, const uint8_t* d_rgb, size_t pitch, size_t frame_stride,
+                                      const rtdm_hsv_range* ranges, const int* range_class, int nranges, int nclasses,
+                                      int min_area, int zero_border, uint8_t* d_masks, size_t mask_pitch,
+                                      size_t mask_plane_stride, rtdm_object* d_objects, int capacity, int* d_counts,
+                                      rtdm_region* d_rois, int32_t* d_labels, size_t label_pitch, size_t label_plane_stride,
+                                      rtdm_object_stats* d_stats, void* hip_stream)
 {
     HsvClasses C;
-    const int rc = objects_batch_check(ob, n, d_rgb, pitch, frame_stride, ranges, range_class, nranges, nclasses, d_masks, mask_pitch,
-                                       mask_plane_stride, d_objects, capacity, d_counts, d_rois, &C);
+    int rc = objects_batch_check(ob, n, d_rgb, pitch, frame_stride, ranges, range_class, nranges, nclasses, d_masks, mask_pitch,
+                                 mask_plane_stride, d_objects, capacity, d_counts, d_rois, &C);
+    if (rc) return rc;
+    rc = labels_check(d_labels, label_pitch, label_plane_stride, d_stats, ob->W, ob->H, (size_t)n * nclasses);
     if (rc) return rc;
     if (n == 0) return RTDM_OK;
     HIPC(hipSetDevice(ob->device));
@@ -208,10 +232,22 @@ int rtdm_objects_detect_device(rtdm_objects* ob, int n, const uint8_t* d_rgb, si
         const int st = objects_run_chunk(ob, m, d_rgb + (size_t)i0 * frame_stride, pitch, frame_stride, C, min_area, zero_border,
                                          d_masks ? d_masks + (size_t)i0 * nclasses * mask_plane_stride : nullptr, mask_pitch,
                                          mask_plane_stride, (CcObject*)d_objects + (size_t)i0 * capacity, capacity,
-                                         d_counts + (size_t)i0 * nclasses, (int*)(d_rois + i0), s);
+                                         d_counts + (size_t)i0 * nclasses, (int*)(d_rois + i0), s,
+                                         CcLabelsOut{d_labels ? (int32_t*)((uint8_t*)d_labels + (size_t)i0 * nclasses * label_plane_stride) : nullptr,
+                                                     label_pitch, label_plane_stride, d_stats ? (CcStats*)d_stats + (size_t)i0 * capacity : nullptr});
         if (st) return st;
     }
     return RTDM_OK;
+}
+
+int rtdm_objects_detect_device(rtdm_objects* ob, int n, const uint8_t* d_rgb, size_t pitch, size_t frame_stride,
+                               const rtdm_hsv_range* ranges, const int* range_class, int nranges, int nclasses, int min_area,
+                               int zero_border, uint8_t* d_masks, size_t mask_pitch, size_t mask_plane_stride,
+                               rtdm_object* d_objects, int capacity, int* d_counts, rtdm_region* d_rois, void* hip_stream)
+{
+    return rtdm_objects_detect_labels_device(ob, n, d_rgb, pitch, frame_stride, ranges, range_class, nranges, nclasses, min_area, zero_border,
+                                             d_masks, mask_pitch, mask_plane_stride, d_objects, capacity, d_counts, d_rois, nullptr, 0, 0,
+                                             nullptr, hip_stream);
 }
 
 // room for `entries` records in the handle's device staging of the host entry points
@@ -225,14 +261,35 @@ int rtdm::objects_stage(rtdm_objects* ob, size_t entries)
     return RTDM_OK;
 }
 
-int rtdm_objects_detect_batch(rtdm_objects* ob, int n, const uint8_t* rgb, size_t pitch, size_t frame_stride,
-                              const rtdm_hsv_range* ranges, const int* range_class, int nranges, int nclasses, int min_area,
-                              int zero_border, uint8_t* masks, size_t mask_pitch, size_t mask_plane_stride,
-                              rtdm_object* objects, int capacity, int* counts, rtdm_region* rois)
+// room for a chunk's label planes / moments in the handle's device staging of the host entry point
+static int objects_stage_labels(rtdm_objects* ob, size_t label_bytes, size_t stat_entries)
+{
+    if (label_bytes > ob->labBytes) {
+        if (ob->dLab) { HIPC(hipStreamSynchronize(ob->stream)); HIPC(hipFree(ob->dLab)); }
+        ob->dLab = nullptr; ob->labBytes = 0;
+        HIPC(hipMalloc(&ob->dLab, label_bytes));
+        ob->labBytes = label_bytes;
+    }
+    if (stat_entries > ob->statCap) {
+        if (ob->dStats) { HIPC(hipStreamSynchronize(ob->stream)); HIPC(hipFree(ob->dStats)); }
+        ob->dStats = nullptr; ob->statCap = 0;
+        HIPC(hipMalloc(&ob->dStats, stat_entries * sizeof(CcStats)));
+        ob->statCap = stat_entries;
+    }
+    return RTDM_OK;
+}
+
+int rtdm_objects_detect_labels_batch(rtdm_objects* ob, int n, const uint8_t* rgb, size_t pitch, size_t frame_stride,
+                                     const rtdm_hsv_range* ranges, const int* range_class, int nranges, int nclasses,
+                                     int min_area, int zero_border, uint8_t* masks, size_t mask_pitch, size_t mask_plane_stride,
+                                     rtdm_object* objects, int capacity, int* counts, rtdm_region* rois, int32_t* labels,
+                                     size_t label_pitch, size_t label_plane_stride, rtdm_object_stats* stats)
 {
     HsvClasses C;
     int rc = objects_batch_check(ob, n, rgb, pitch, frame_stride, ranges, range_class, nranges, nclasses, masks, mask_pitch,
                                  mask_plane_stride, objects, capacity, counts, rois, &C);
+    if (rc) return rc;
+    rc = labels_check(labels, label_pitch, label_plane_stride, stats, ob->W, ob->H, (size_t)n * nclasses);
     if (rc) return rc;
     if (n == 0) return RTDM_OK;
     HIPC(hipSetDevice(ob->device));
@@ -244,13 +301,17 @@ int rtdm_objects_detect_batch(rtdm_objects* ob, int n, const uint8_t* rgb, size_
     const int cap = (int)std::min((size_t)capacity, (size_t)K * ob->maxRec);
     rc = objects_stage(ob, (size_t)std::min(ob->maxB, n) * cap);
     if (rc) return rc;
+    const size_t lp = (size_t)W * 4, lplane = lp * H;                        // the staged label planes: dense rows
+    rc = objects_stage_labels(ob, labels ? (size_t)std::min(ob->maxB, n) * K * lplane : 0, stats ? (size_t)std::min(ob->maxB, n) * cap : 0);
+    if (rc) return rc;
     int* dCounts = ob->dMeta;
     int* dRois = ob->dMeta + (size_t)ob->maxB * ob->maxC;
     for (int i0 = 0; i0 < n; i0 += ob->maxB) {
         const int m = std::min(ob->maxB, n - i0);
         for (int j = 0; j < m; ++j)
             HIPC(hipMemcpy2DAsync(ob->dRgb + j * rf, rp, rgb + (size_t)(i0 + j) * frame_stride, pitch, (size_t)W * 3, H, hipMemcpyHostToDevice, s));
-        rc = objects_run_chunk(ob, m, ob->dRgb, rp, rf, C, min_area, zero_border, nullptr, 0, 0, ob->dObj, cap, dCounts, dRois, s);
+        rc = objects_run_chunk(ob, m, ob->dRgb, rp, rf, C, min_area, zero_border, nullptr, 0, 0, ob->dObj, cap, dCounts, dRois, s,
+                               CcLabelsOut{labels ? ob->dLab : nullptr, lp, lplane, stats ? ob->dStats : nullptr});
         if (rc) return rc;
         int* hCounts = ob->hRec;
         int* hRois = ob->hRec + m * K;
@@ -264,6 +325,11 @@ int rtdm_objects_detect_batch(rtdm_objects* ob, int n, const uint8_t* rgb, size_
             const size_t stored = (size_t)std::min<long>(total, cap);                  // O4: the rest of the caller's array stays as it is
             if (stored) HIPC(hipMemcpyAsync(objects + (size_t)(i0 + j) * capacity, ob->dObj + (size_t)j * cap, stored * sizeof(rtdm_object),
                                             hipMemcpyDeviceToHost, s));
+            if (stored && stats) HIPC(hipMemcpyAsync(stats + (size_t)(i0 + j) * capacity, ob->dStats + (size_t)j * cap,
+                                                     stored * sizeof(rtdm_object_stats), hipMemcpyDeviceToHost, s));
+            for (int c = 0; labels && c < K; ++c)
+                HIPC(hipMemcpy2DAsync((uint8_t*)labels + ((size_t)(i0 + j) * K + c) * label_plane_stride, label_pitch,
+                                      (uint8_t*)ob->dLab + ((size_t)j * K + c) * lplane, lp, lp, H, hipMemcpyDeviceToHost, s));
             for (int c = 0; masks && c < K; ++c)
                 HIPC(hipMemcpy2DAsync(masks + ((size_t)(i0 + j) * K + c) * mask_plane_stride, mask_pitch,
                                       ob->dMaskOut + ((size_t)j * K + c) * iplane, ip, (size_t)W, H, hipMemcpyDeviceToHost, s));
@@ -272,4 +338,13 @@ int rtdm_objects_detect_batch(rtdm_objects* ob, int n, const uint8_t* rgb, size_
     }
     drain.armed = false;
     return RTDM_OK;
+}
+
+int rtdm_objects_detect_batch(rtdm_objects* ob, int n, const uint8_t* rgb, size_t pitch, size_t frame_stride,
+                              const rtdm_hsv_range* ranges, const int* range_class, int nranges, int nclasses, int min_area,
+                              int zero_border, uint8_t* masks, size_t mask_pitch, size_t mask_plane_stride,
+                              rtdm_object* objects, int capacity, int* counts, rtdm_region* rois)
+{
+    return rtdm_objects_detect_labels_batch(ob, n, rgb, pitch, frame_stride, ranges, range_class, nranges, nclasses, min_area, zero_border,
+                                            masks, mask_pitch, mask_plane_stride, objects, capacity, counts, rois, nullptr, 0, 0, nullptr);
 }

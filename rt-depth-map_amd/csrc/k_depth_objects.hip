@@ -51,7 +51,10 @@ __global__ __launch_bounds__(256) void k_dobj_min(const int16_t* disp, size_t pi
     if (threadIdx.x == 0) atomicMin(minval + blockIdx.y, min(min(red[0], red[1]), min(red[2], red[3])));
 }
 
-// one wave = one band of one object slot; the waves stride over all n * cap * nb of them
+// one wave = one band of one object slot; the waves stride over all n * cap * nb of them.  LABELS (rule L5): the planes are
+// the detector's int32 label planes and slot i counts the pixels that carry i + 1 -- the value is compared, never used
+// (L6); the walk and the reduction tree are the same code for both predicates.
+template <bool LABELS>
 __global__ __launch_bounds__(256) void k_dobj_bands(DepthObjects a, DepthQ q, const int* minval, double* psum, int* pcnt)
 {
     const int lane = threadIdx.x & 63;
@@ -82,7 +85,8 @@ __global__ __launch_bounds__(256) void k_dobj_bands(DepthObjects a, DepthQ q, co
                 float z = (float)(Zh / Wh);
                 if (d == mind) z = 10000.0f;
                 const double zd = (double)z;
-                if (fabs(zd - 10000.0) < 1.1920928955078125e-07 || fabs(zd) > 10000.0 || mp[(size_t)y * a.mpitch + x] == 0) continue;
+                if (fabs(zd - 10000.0) < 1.1920928955078125e-07 || fabs(zd) > 10000.0) continue;
+                if (LABELS ? *(const int32_t*)(mp + (size_t)y * a.mpitch + (size_t)x * 4) != i + 1 : mp[(size_t)y * a.mpitch + x] == 0) continue;
                 s += zd; ++c;
             }
         }
@@ -116,7 +120,8 @@ size_t depth_objects_bytes(int n, int cap, int H)
     return 64 + dobj_min_bytes(n) + (size_t)std::max(n, 0) * std::max(cap, 0) * dobj_bands(H) * (sizeof(double) + sizeof(int));
 }
 
-void launch_depth_objects(DepthObjects a, const DepthQ& q, double unit, void* workspace, double* mean, int* npix, hipStream_t stream)
+void launch_depth_objects(DepthObjects a, const DepthQ& q, double unit, void* workspace, double* mean, int* npix, hipStream_t stream,
+                          bool labels)
 {
     if (a.n <= 0) return;
     a.nb = (int)dobj_bands(a.H);
@@ -131,7 +136,8 @@ void launch_depth_objects(DepthObjects a, const DepthQ& q, double unit, void* wo
                            a.disp + (size_t)f0 * a.dframe_e, a.dpitch_e, a.dframe_e, a.W, a.H, minval + f0);
     if (a.cap <= 0) return;
     const size_t blocks = std::min<size_t>((parts + 3) / 4, (size_t)1 << 16);
-    hipLaunchKernelGGL(k_dobj_bands, dim3((unsigned)blocks), dim3(256), 0, stream, a, q, minval, psum, pcnt);
+    if (labels) hipLaunchKernelGGL(k_dobj_bands<true>, dim3((unsigned)blocks), dim3(256), 0, stream, a, q, minval, psum, pcnt);
+    else hipLaunchKernelGGL(k_dobj_bands<false>, dim3((unsigned)blocks), dim3(256), 0, stream, a, q, minval, psum, pcnt);
     const size_t slots = (size_t)a.n * a.cap;
     hipLaunchKernelGGL(k_dobj_final, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, stream, a, psum, pcnt, unit, mean, npix);
 }

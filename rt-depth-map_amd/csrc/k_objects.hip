@@ -9,6 +9,8 @@
 // Frame batches and several colour classes per call: k_hsv_classes writes one mask plane per class,
 // the labelling kernels take their plane from blockIdx.y, and k_cc_count / k_cc_scan / k_cc_scatter select and order the boxes
 // on the device, where the single-frame path collects records in arbitrary order (k_cc_collect) for a host sort.
+// Which pixels belong to which stored object: k_cc_scatter<true> leaves every root its object's id,
+// k_cc_labels writes the label planes from them, run by run, and adds up the raw moments of every object's pixels.
 #include <mutex>
 #include "rtdm_kernels.h"
 #include "rtdm_device.h"
@@ -286,13 +288,20 @@ __global__ __launch_bounds__(256) void k_cc_scan(CcPlanes P, CcSelect S, int* co
     if (threadIdx.x == 0) { roi[4 * f] = 1000000; roi[4 * f + 1] = 1000000; roi[4 * f + 2] = -1000000; roi[4 * f + 3] = -1000000; }
 }
 
-__global__ __launch_bounds__(256) void k_cc_scatter(CcPlanes P, CcSelect S, CcObject* objects, int capacity, int* roi)
+// IDS (labels or stats are wanted, rule L1): every foreground root also gets its object's id in the first word of its own box
+// entry, written by the lane that has just read that entry -- 1 + position for a stored object, 0 for a root that is not kept
+// or lies beyond the capacity -- and a stored object's moments start at zero.  k_cc_labels reads the id from there.
+template <bool IDS>
+__global__ __launch_bounds__(256) void k_cc_scatter(CcPlanes P, CcSelect S, CcObject* objects, int capacity, int* roi, CcStats* stats)
 {
     __shared__ int wsum[4];
     const int plane = blockIdx.y, f = plane / S.nclasses, cls = plane - f * S.nclasses, wave = threadIdx.x >> 6;
     const int p = blockIdx.x * 256 + threadIdx.x;
     int4 b = make_int4(0, 0, 0, 0);
     const bool keep = cc_keep(P, S, p, &b);
+    if (IDS && !keep && p < S.W * S.H && cc_fg(cc_mask(P), P.mpitch, S.W, S.H, p % S.W, p / S.W, S.zero_border) &&
+        ld_relaxed(&cc_label(P)[p]) == p)
+        cc_box(P)[p].x = 0;
     const unsigned long long bal = __ballot(keep);
     if ((threadIdx.x & 63) == 0) wsum[wave] = __popcll(bal);
     __syncthreads();
@@ -307,6 +316,11 @@ __global__ __launch_bounds__(256) void k_cc_scatter(CcPlanes P, CcSelect S, CcOb
         o->x = b.x; o->y = b.y; o->w = b.z - b.x + 1; o->h = b.w - b.y + 1;
         o->cls = cls; o->first_pixel = p; o->reserved[0] = 0; o->reserved[1] = 0;
     }
+    if (IDS && keep) {
+        const bool stored = pos < capacity;
+        cc_box(P)[p].x = stored ? pos + 1 : 0;
+        if (stored && stats) stats[(size_t)f * capacity + pos] = CcStats{0, 0, 0, 0, 0, 0};
+    }
     int x0 = keep ? b.x : 1000000, y0 = keep ? b.y : 1000000, x1 = keep ? b.z + 1 : -1000000, y1 = keep ? b.w + 1 : -1000000;
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
@@ -316,6 +330,82 @@ __global__ __launch_bounds__(256) void k_cc_scatter(CcPlanes P, CcSelect S, CcOb
     if ((threadIdx.x & 63) == 0) {
         atomicMin(roi + 4 * f, x0); atomicMin(roi + 4 * f + 1, y0); atomicMax(roi + 4 * f + 2, x1); atomicMax(roi + 4 * f + 3, y1);
     }
+}
+
+// L1 / L2: one workgroup per row of a plane, run-based like k_cc_rows.  The max-scan gives every pixel the start of its run;
+// the LAST pixel of a foreground run [a, x] finds the root from a, reads the id k_cc_scatter left there and leaves it at
+// sc[a], where no other run reads or writes.  Then the row goes out from LDS, lane after lane: whole waves of neighbouring
+// dwords, or of 16-byte quads where base, pitch and plane stride allow (vec4).  No atomic decides a label.
+// Moments: a run's closed-form sums (n, sum x, sum x^2; the other three follow from the row's y) are first combined per id
+// inside the row, in a table of CC_ROW_IDS entries in LDS (open addressing, CC_ROW_PROBES tries), and one lane per used entry
+// adds the row's share to the object's six words with 64-bit integer atomics -- the same sum in any order.  A run that
+// finds no entry adds its own share directly.  (Per-run atomics on the words of one object cost 4.5 ms on a 934x404 frame
+// of 60 % noise, whose largest component has some 60000 runs: profiles/objects_labels_time.txt.)
+#define CC_ROW_IDS 64
+#define CC_ROW_PROBES 8
+__device__ __forceinline__ void cc_add_moments(CcStats* s, long long y, unsigned long long n, unsigned long long sx, unsigned long long sxx)
+{
+    unsigned long long* m = (unsigned long long*)s;
+    atomicAdd(m + 0, n); atomicAdd(m + 1, sx); atomicAdd(m + 2, n * y);
+    atomicAdd(m + 3, sxx); atomicAdd(m + 4, sx * y); atomicAdd(m + 5, n * y * y);
+}
+
+__global__ __launch_bounds__(256) void k_cc_labels(CcPlanes P, int W, int H, int zero_border, int nclasses, int capacity, CcLabelsOut O,
+                                                   int vec4)
+{
+    extern __shared__ int sc[];
+    __shared__ int wsum[4];
+    __shared__ int row_id[CC_ROW_IDS];
+    __shared__ unsigned long long row_sum[CC_ROW_IDS][3];
+    const uint8_t* mask = cc_mask(P);
+    const size_t mpitch = P.mpitch;
+    const int y = blockIdx.x;
+    CcStats* stats = O.stats ? O.stats + (size_t)(blockIdx.y / nclasses) * capacity : nullptr;
+    if (threadIdx.x < CC_ROW_IDS) {
+        row_id[threadIdx.x] = 0;
+        row_sum[threadIdx.x][0] = 0; row_sum[threadIdx.x][1] = 0; row_sum[threadIdx.x][2] = 0;
+    }
+    for (int x = threadIdx.x; x < W; x += 256) {
+        const bool v = cc_fg(mask, mpitch, W, H, x, y, zero_border);
+        const bool start = x == 0 || cc_fg(mask, mpitch, W, H, x - 1, y, zero_border) != v;
+        sc[x] = start ? x + 1 : 0;
+    }
+    __syncthreads();
+    row_scan<OpMax>(sc, W, wsum);
+    for (int x = threadIdx.x; x < W; x += 256) {
+        if (!cc_fg(mask, mpitch, W, H, x, y, zero_border)) continue;
+        if (x != W - 1 && cc_fg(mask, mpitch, W, H, x + 1, y, zero_border)) continue;
+        const int a = sc[x] - 1;
+        const int id = cc_box(P)[uf_find(cc_label(P), y * W + a)].x;
+        sc[a] = id;
+        if (!stats || id <= 0 || id > capacity) continue;
+        const long long n = x - a + 1, sx = (long long)(a + x) * n / 2;
+        const long long lo = a - 1, hi = x, sxx = hi * (hi + 1) * (2 * hi + 1) / 6 - lo * (lo + 1) * (2 * lo + 1) / 6;
+        bool placed = false;
+        for (int k = 0; k < CC_ROW_PROBES && !placed; ++k) {
+            const int e = (id + k) & (CC_ROW_IDS - 1);
+            const int old = atomicCAS(&row_id[e], 0, id);
+            if (old != 0 && old != id) continue;
+            atomicAdd(&row_sum[e][0], (unsigned long long)n); atomicAdd(&row_sum[e][1], (unsigned long long)sx);
+            atomicAdd(&row_sum[e][2], (unsigned long long)sxx);
+            placed = true;
+        }
+        if (!placed) cc_add_moments(stats + (id - 1), y, n, sx, sxx);
+    }
+    __syncthreads();
+    if (stats && threadIdx.x < CC_ROW_IDS && row_id[threadIdx.x] != 0)
+        cc_add_moments(stats + (row_id[threadIdx.x] - 1), y, row_sum[threadIdx.x][0], row_sum[threadIdx.x][1], row_sum[threadIdx.x][2]);
+    if (!O.labels) return;
+    int32_t* row = (int32_t*)((uint8_t*)O.labels + (size_t)blockIdx.y * O.lplane + (size_t)y * O.lpitch);
+    const auto id_at = [&](int x) {
+        if (!cc_fg(mask, mpitch, W, H, x, y, zero_border)) return 0;
+        const int t = sc[x];                              // a run's first pixel holds the id, the others the run's start + 1
+        return (x == 0 || !cc_fg(mask, mpitch, W, H, x - 1, y, zero_border)) ? t : sc[t - 1];
+    };
+    const int quads = vec4 ? W / 4 : 0;
+    for (int q = threadIdx.x; q < quads; q += 256)
+        ((int4*)row)[q] = make_int4(id_at(4 * q), id_at(4 * q + 1), id_at(4 * q + 2), id_at(4 * q + 3));
+    for (int x = 4 * quads + threadIdx.x; x < W; x += 256) row[x] = id_at(x);
 }
 
 __global__ void k_cc_roi(int* roi, int n)
@@ -400,7 +490,7 @@ size_t cc_plane_bytes(int W, int H, int max_records) { return (cc_scratch_bytes(
 // where launch_cc_boxes keeps its records: (chunks + 2) ints, less than the 24 bytes per possible record there.
 void launch_cc_objects(const uint8_t* mask, size_t mpitch, size_t mplane, int n, int nclasses, int W, int H, int zero_border,
                        int min_area, void* scratch, int max_records, CcObject* objects, int capacity, int* counts, int* rois,
-                       hipStream_t stream)
+                       hipStream_t stream, const CcLabelsOut& out)
 {
     const int N = W * H, planes = n * nclasses;
     const CcLayout L = cc_layout(W, H, max_records);
@@ -412,8 +502,14 @@ void launch_cc_objects(const uint8_t* mask, size_t mpitch, size_t mplane, int n,
     hipLaunchKernelGGL(k_cc_bbox, grid, block, 0, stream, P, W, H, zero_border);
     hipLaunchKernelGGL(k_cc_count, chunks, block, 0, stream, P, S);
     hipLaunchKernelGGL(k_cc_scan, dim3(n), block, 0, stream, P, S, counts, rois);
-    hipLaunchKernelGGL(k_cc_scatter, chunks, block, 0, stream, P, S, objects, capacity, rois);
+    const bool ids = out.labels || out.stats;
+    if (ids) hipLaunchKernelGGL(k_cc_scatter<true>, chunks, block, 0, stream, P, S, objects, capacity, rois, out.stats);
+    else hipLaunchKernelGGL(k_cc_scatter<false>, chunks, block, 0, stream, P, S, objects, capacity, rois, (CcStats*)nullptr);
     hipLaunchKernelGGL(k_cc_roi, dim3((n + 63) / 64), dim3(64), 0, stream, rois, n);
+    if (!ids) return;
+    const int vec4 = ((size_t)out.labels | out.lpitch | out.lplane) % 16 == 0;
+    hipLaunchKernelGGL(k_cc_labels, dim3(H, planes), block, (size_t)W * sizeof(int), stream, P, W, H, zero_border, nclasses, capacity,
+                       out, vec4);
 }
 
 }  // namespace rtdm

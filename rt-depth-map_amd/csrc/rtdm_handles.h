@@ -77,6 +77,8 @@ struct rtdm_objects {
     int* dMeta;                   // host entry points: [maxB * maxC] counts, then [maxB] union boxes
     rtdm::CcObject* dObj;         // host entry points: object lists, grown on demand (objCap entries; not in `mem`)
     size_t objCap;
+    int32_t* dLab; size_t labBytes;       // rtdm_objects_detect_labels_batch: a chunk's label planes and moments, grown on
+    rtdm::CcStats* dStats; size_t statCap;   // demand like dObj (not in `mem`)
     int* hRec;                    // pinned: [0] = count, then the first HEAD records (the batched calls: counts, union boxes)
     std::vector<int> all;         // host copy of every record when there are more than HEAD
     rtdm::AllocList mem;
@@ -142,6 +144,7 @@ struct rtdm_estimator {
     rtdm::CcObject* dObj; int* dCounts; double* dMean; int* dNpix;      // host form: [chunk] x cap, [chunk] x RTDM_MAX_CLASSES
     int* dRois;                    // [chunk] x 4
     void* dWork; size_t workBytes; // rtdm_depth_objects_device's workspace for a chunk
+    int32_t* dLabels;              // rtdm_estimator_set_own_pixels: [chunk] x [detector's max_classes] planes of rh x rw ints, or null
     // page-locked: the read-back in front of the matcher, then what the host form brings back and takes in
     int *hCounts, *hRois, *hNpix; rtdm::CcObject* hObj; double* hMean; int16_t* hDisp; uint8_t* hRgb[2];
     rtdm::AllocList mem;
@@ -179,7 +182,8 @@ size_t objects_rgb_pitch(const rtdm_objects* ob);
 int objects_classes_check(const rtdm_hsv_range* ranges, const int* range_class, int nranges, int nclasses, HsvClasses* C);
 int objects_run_chunk(rtdm_objects* ob, int m, const uint8_t* d_rgb, size_t pitch, size_t frame_stride, const HsvClasses& C,
                       int min_area, int zero_border, uint8_t* d_masks, size_t mask_pitch, size_t mask_plane_stride,
-                      CcObject* d_objects, int capacity, int* d_counts, int* d_rois, hipStream_t s);
+                      CcObject* d_objects, int capacity, int* d_counts, int* d_rois, hipStream_t s,
+                      const CcLabelsOut& lab = CcLabelsOut{nullptr, 0, 0, nullptr});
 int objects_stage(rtdm_objects* ob, size_t entries);
 int wls_check(const rtdm_wls* h, int channels, int W, int H);
 int wls_chunk(rtdm_wls* h, int n, WlsDisp dl, WlsDisp dr, WlsGuide G, WlsOut o, int W, int H, hipStream_t s);

@@ -300,8 +300,10 @@ struct DepthObjects {
 };
 size_t depth_objects_bytes(int n, int cap, int H);
 // mean / npix: n * cap entries on the device, written for the stored objects only.  Three kernels and one memset on `stream`,
-// nothing else: no allocation, no synchronisation, no copy.
-void launch_depth_objects(DepthObjects a, const DepthQ& q, double unit, void* workspace, double* mean, int* npix, hipStream_t stream);
+// nothing else: no allocation, no synchronisation, no copy.  labels (rule L5): `mask` holds the detector's int32 label planes
+// (mpitch / mplane in bytes, multiples of 4) and object i counts the pixels whose label is i + 1; the walk and the sums are the same.
+void launch_depth_objects(DepthObjects a, const DepthQ& q, double unit, void* workspace, double* mean, int* npix, hipStream_t stream,
+                          bool labels = false);
 
 // Rectification in front of the matcher (estimator.cpp:29-39).  RectifySrc: n RGB frames, pitch/frame in bytes.
 struct RectifySrc { const uint8_t* base; size_t pitch, frame; };
@@ -340,9 +342,14 @@ size_t cc_plane_bytes(int W, int H, int max_records);                        // 
 // Labels the n * nclasses planes (scratch: cc_plane_bytes each) and selects on the device: frame f's kept boxes, class
 // ascending and first pixel descending inside a class, at objects + f * capacity (positions >= capacity are not written);
 // counts[f * nclasses + c]: kept boxes of the plane; rois: 4 ints per frame, the union box (x, y, w, h) of all of them.
+// out (rules L1-L4), both parts optional: labels -- plane f * nclasses + c at labels + plane * lplane
+// bytes, rows of lpitch bytes (multiples of 4), 1 + list index on the pixels of the stored objects and 0 elsewhere; stats -- the
+// raw moments of those pixels at stats + f * capacity.  With neither the launches are the ones without `out`.
+struct CcStats { long long m00, m10, m01, m20, m11, m02; };                  // rtdm_object_stats
+struct CcLabelsOut { int32_t* labels; size_t lpitch, lplane; CcStats* stats; };
 void launch_cc_objects(const uint8_t* mask, size_t mpitch, size_t mplane, int n, int nclasses, int W, int H, int zero_border,
                        int min_area, void* scratch, int max_records, CcObject* objects, int capacity, int* counts, int* rois,
-                       hipStream_t stream);
+                       hipStream_t stream, const CcLabelsOut& out = CcLabelsOut{nullptr, 0, 0, nullptr});
 
 // Disparity WLS post-filter (k_wls.hip, rules W1-W8 in DESIGN.md section 4.9).  Internal planes (F, weights, confidence,
 // window statistics) share one layout: element (f, y, x) at f * frame + y * pitch + x.

@@ -123,6 +123,8 @@ int HIPObjectsCore::estimateBatch(HIPMatcherCore& matcher, HIPRectifierCore& rec
         if (status_ != RTDM_OK) return status_;
         estBm_ = matcher.handle(); estRc_ = rectifier.handle(); estBatch_ = maxBatch; estCap_ = capacity;
     }
+    status_ = rtdm_estimator_set_own_pixels(est_, ownPixels_ ? 1 : 0);          // (nothing happens unless the setting changed)
+    if (status_ != RTDM_OK) return status_;
     return status_ = rtdm_estimate_batch(est_, n, rgbLeft, leftStep, leftFrameStride, rgbRight, rightStep, rightFrameStride, Q, ranges_,
                                          cls_, nranges_, nclasses_, minObjSize, zeroBorder ? 1 : 0, calibrationUnit, objects, counts,
                                          meanCm, npix, disp, dispStep, dispFrameStride);
@@ -143,6 +145,18 @@ int HIPObjectsCore::detectDevice(int n, const uint8_t* dRgb, size_t step, size_t
     return status_ = rtdm_objects_detect_device(ob_, n, dRgb, step, frameStride, ranges_, cls_, nranges_, nclasses_, minObjSize,
                                                 zeroBorder ? 1 : 0, dMasks, maskStep, maskPlaneStride, dObjects, capacity, dCounts,
                                                 reinterpret_cast<rtdm_region*>(dRois), hipStream);
+}
+void HIPObjectsCore::setOwnPixels(bool on) { ownPixels_ = on; }
+int HIPObjectsCore::detectLabelsDevice(int n, const uint8_t* dRgb, size_t step, size_t frameStride, int minObjSize, bool zeroBorder,
+                                       uint8_t* dMasks, size_t maskStep, size_t maskPlaneStride, rtdm_object* dObjects, int capacity,
+                                       int* dCounts, Rect* dRois, int32_t* dLabels, size_t labelStep, size_t labelPlaneStride,
+                                       rtdm_object_stats* dStats, void* hipStream)
+{
+    if (!ob_) return status_ != RTDM_OK ? status_ : RTDM_ERR_NO_DEVICE;
+    return status_ = rtdm_objects_detect_labels_device(ob_, n, dRgb, step, frameStride, ranges_, cls_, nranges_, nclasses_, minObjSize,
+                                                       zeroBorder ? 1 : 0, dMasks, maskStep, maskPlaneStride, dObjects, capacity,
+                                                       dCounts, reinterpret_cast<rtdm_region*>(dRois), dLabels, labelStep,
+                                                       labelPlaneStride, dStats, hipStream);
 }
 int HIPObjectsCore::estimateFrameClasses(HIPMatcherCore& matcher, HIPRectifierCore& rectifier, const uint8_t* rgbLeft, size_t leftStep,
                                          const uint8_t* rgbRight, size_t rightStep, const double* Q, int minObjSize, bool zeroBorder,

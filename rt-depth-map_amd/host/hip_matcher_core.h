@@ -254,6 +254,17 @@ public:
     int detectDevice(int n, const uint8_t* dRgb, size_t step, size_t frameStride, int minObjSize, bool zeroBorder, uint8_t* dMasks,
                      size_t maskStep, size_t maskPlaneStride, rtdm_object* dObjects, int capacity, int* dCounts, Rect* dRois,
                      void* hipStream);
+    // detectDevice with the pixels of every object (include/rtdm.h, rules L1-L4): dLabels -- one int32 plane per (frame, class),
+    // 1 + the object's index in its frame's list on the pixels of its component, 0 elsewhere -- and dStats -- the raw moments of
+    // those pixels at dStats + f * capacity -- may each be null.  Returns a status.
+    int detectLabelsDevice(int n, const uint8_t* dRgb, size_t step, size_t frameStride, int minObjSize, bool zeroBorder,
+                           uint8_t* dMasks, size_t maskStep, size_t maskPlaneStride, rtdm_object* dObjects, int capacity, int* dCounts,
+                           Rect* dRois, int32_t* dLabels, size_t labelStep, size_t labelPlaneStride, rtdm_object_stats* dStats,
+                           void* hipStream);
+    // estimateBatch measures every object over its own pixels instead of its class's mask inside its box (rule L7); kept
+    // across the estimator handles this object makes.
+    void setOwnPixels(bool on);
+    bool ownPixels() const { return ownPixels_; }
     // estimateFrame for the classes of setRanges: every object with its class, measured under its class's mask.  Returns the
     // number of objects (only maxObjects are stored) or a negative status.
     int estimateFrameClasses(HIPMatcherCore& matcher, HIPRectifierCore& rectifier, const uint8_t* rgbLeft, size_t leftStep,
@@ -278,6 +289,7 @@ private:
     rtdm_bm* estBm_ = nullptr;
     rtdm_rectify* estRc_ = nullptr;
     int estBatch_ = 0, estCap_ = 0;
+    bool ownPixels_ = false;
     rtdm_hsv_range range_;
     rtdm_hsv_range ranges_[RTDM_MAX_HSV_RANGES];
     int cls_[RTDM_MAX_HSV_RANGES];

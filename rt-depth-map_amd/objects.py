@@ -4,7 +4,7 @@ import ctypes as C
 import numpy as np
 
 from . import binding as B
-from ._marshal import Handle, device_plane, mask_planes, object_lists, object_tuples, rgb_batch
+from ._marshal import Handle, device_plane, label_planes, mask_planes, object_lists, object_tuples, rgb_batch, stats_lists
 from .morph import _get_morph, _morph_element
 
 HSV_LOW, HSV_HIGH = (0, 150, 0), (9, 255, 255)          # the reference's red filter, estimator.cpp:110-115
@@ -15,6 +15,22 @@ def _hsv_range(low, high):
 
 
 OBJECT_DTYPE = np.dtype([(n, "<i4") for n in ("x", "y", "width", "height", "cls", "first_pixel")] + [("reserved", "<i4", (2,))])   # rtdm_object
+
+
+STATS_DTYPE = np.dtype([(n, "<i8") for n in ("m00", "m10", "m01", "m20", "m11", "m02")])   # rtdm_object_stats
+
+
+def centroids(stats):
+    """STATS_DTYPE records of any shape -> float64 [..., 2]: (m10 / m00, m01 / m00), NaN where m00 is 0."""
+    stats = np.asarray(stats)
+    if stats.dtype != STATS_DTYPE:
+        raise ValueError("stats must be STATS_DTYPE records; got %s" % stats.dtype)
+    m00 = stats["m00"].astype(np.float64)
+    out = np.full(stats.shape + (2,), np.nan)
+    ok = m00 != 0
+    out[..., 0][ok] = stats["m10"][ok] / m00[ok]
+    out[..., 1][ok] = stats["m01"][ok] / m00[ok]
+    return out
 
 
 def _hsv_classes(ranges, classes):
@@ -98,3 +114,53 @@ class HIPObjectDetector(Handle):
         B.check(B.lib().rtdm_objects_detect_device(self._h, n, rp, rpitch, rframe, rng, cls, nr, K, int(min_area), int(zero_border),
                                                    mp, mpitch, mplane, d_objects.data_ptr(), capacity, d_counts.data_ptr(),
                                                    d_rois.data_ptr(), stream), "rtdm_objects_detect_device")
+
+    def detect_labels(self, rgbs, ranges, classes=None, min_area=100, zero_border=True, capacity=256, want_masks=True,
+                      want_labels=True, want_stats=True):
+        """detect_classes with the pixels of every object (rules L1-L4) -> (objects, rois, counts, masks, labels, stats).
+        labels: int32 n x nclasses x H x W, 1 + the index in the frame's stored list on the pixels of that object's component
+        and 0 everywhere else; stats: per frame the STATS_DTYPE records (raw moments over exactly the labelled pixels) of its
+        stored objects -- centroids(stats[f]) gives (x, y).  masks / labels / stats are None when not wanted."""
+        rgbs = rgb_batch(np.asarray(rgbs), self.height, self.width, "rgbs")
+        rng, cls, nr, K = _hsv_classes(ranges, classes)
+        n, H, W = rgbs.shape[0], self.height, self.width
+        capacity = int(capacity)
+        if capacity < 0:
+            raise ValueError("capacity must not be negative; got %d" % capacity)
+        objs = np.zeros((n, capacity), OBJECT_DTYPE)
+        counts = np.zeros((n, max(K, 1)), np.int32); rois = np.zeros((n, 4), np.int32)
+        masks = np.empty((n, max(K, 1), H, W), np.uint8) if want_masks else None
+        labels = np.zeros((n, max(K, 1), H, W), np.int32) if want_labels else None
+        stats = np.zeros((n, capacity), STATS_DTYPE) if want_stats else None
+        B.check(B.lib().rtdm_objects_detect_labels_batch(self._h, n, rgbs.ctypes.data, rgbs.strides[1], rgbs.strides[0], rng, cls, nr, K,
+                                                         int(min_area), int(zero_border), masks.ctypes.data if want_masks else None,
+                                                         W, W * H, objs.ctypes.data, capacity, counts.ctypes.data, rois.ctypes.data,
+                                                         labels.ctypes.data if want_labels else None, 4 * W, 4 * W * H,
+                                                         stats.ctypes.data if want_stats else None),
+                "rtdm_objects_detect_labels_batch")
+        stored = [min(int(counts[f].sum()), capacity) for f in range(n)]
+        out = [object_tuples(objs[f, :stored[f]]) for f in range(n)]
+        return (out, [tuple(int(v) for v in r) for r in rois], counts, masks, labels,
+                [stats[f, :stored[f]].copy() for f in range(n)] if want_stats else None)
+
+    def detect_labels_device(self, d_rgb, ranges, classes, d_objects, d_counts, d_rois, d_masks=None, d_labels=None, d_stats=None,
+                             min_area=100, zero_border=True, capacity=None, stream=None):
+        """detect_device with two more optional outputs (rules L1-L4): d_labels int32 [n, nclasses, H, W] (row pitch and plane
+        stride free) and d_stats uint8 [n, capacity * 48] (frame i's moments in row i; view a host copy as STATS_DTYPE; written
+        for the stored objects only).  Enqueued on `stream`, not synchronised."""
+        import torch
+        rng, cls, nr, K = _hsv_classes(ranges, classes)
+        if d_rgb.dtype != torch.uint8 or d_rgb.dim() != 4 or tuple(d_rgb.shape[1:]) != (self.height, self.width, 3):
+            raise ValueError("d_rgb must be uint8 n x %d x %d x 3; got %s %s" % (self.height, self.width, d_rgb.dtype, tuple(d_rgb.shape)))
+        rp, rpitch, rframe = device_plane(d_rgb, "d_rgb", torch.uint8)
+        n, H, W = d_rgb.shape[0], self.height, self.width
+        capacity = object_lists(d_objects, d_counts, n, K, capacity)
+        if d_rois.dtype != torch.int32 or tuple(d_rois.shape) != (n, 4) or not d_rois.is_contiguous():
+            raise ValueError("d_rois must be a contiguous int32 tensor n x 4")
+        mp, mpitch, mplane = mask_planes(d_masks, n, K, H, W) if d_masks is not None else (None, 0, 0)
+        lp, lpitch, lplane = label_planes(d_labels, n, K, H, W) if d_labels is not None else (None, 0, 0)
+        sp = stats_lists(d_stats, n, capacity) if d_stats is not None else None
+        B.check(B.lib().rtdm_objects_detect_labels_device(self._h, n, rp, rpitch, rframe, rng, cls, nr, K, int(min_area),
+                                                          int(zero_border), mp, mpitch, mplane, d_objects.data_ptr(), capacity,
+                                                          d_counts.data_ptr(), d_rois.data_ptr(), lp, lpitch, lplane, sp, stream),
+                "rtdm_objects_detect_labels_device")
