@@ -16,7 +16,8 @@ struct rtdm_sgm {
                                    // wrap the library's 16-bit path costs (sgm_cost_limit)
     int32_t* hOvf;                 // page-locked copy of b.ovf
     uint32_t sweep_epoch;          // launches of k_sgm_sweep (tags of its edge ring)
-    int sweep_cap[36];             // workgroups the device holds at once, per instantiation (0 = not asked yet)
+    SgmLimits lim;                 // cap: workgroups the device holds at once per sweep form, asked by the first call (caps_asked)
+    bool caps_asked;
     bool sweep_reported;           // a give-up of the sweep has been returned to the caller
     const char* path_variant;      // the path-pass form of the last call (launch_sgm), "" before the first
     AllocList mem;                 // every device and page-locked buffer above, the colour buffers from their first call on
@@ -133,7 +134,7 @@ int rtdm_sgm_create(const rtdm_sgm_params* params, int max_width, int max_height
     // S2 is optional: without it the horizontal passes run one after the other)
     if (e == hipSuccess && !wide && !m.dev(&sg->b.S2, vol * 2)) { (void)hipGetLastError(); e = hipSuccess; }
     if (e == hipSuccess) *sg->b.abortf = 0;
-    sg->b.epoch = &sg->sweep_epoch; sg->b.sweep_cap = sg->sweep_cap;
+    sg->b.epoch = &sg->sweep_epoch;
     if (e == hipSuccess) e = hipEventCreateWithFlags((hipEvent_t*)&sg->b.ev_in, hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventCreateWithFlags((hipEvent_t*)&sg->b.ev_out, hipEventDisableTiming);
     if (e != hipSuccess) { const hipError_t first = e; rtdm_sgm_destroy(sg); return create_failed("rtdm_sgm_create", first); }
@@ -161,8 +162,14 @@ static int sgm_chunk(rtdm_sgm* sg, int n, int cn, Plane8 L, Plane8 R, int W, int
     g.x0 = std::max(g.minD + g.D, 0);
     g.W1 = (W + std::min(g.minD, 0)) - g.x0;
     if (g.W1 <= 0) { launch_fill16(disp, 0, W, 0, H, n, (g.minD - 1) * 16, s); return RTDM_OK; }
-    sg->path_variant = launch_sgm(L, R, disp, g, sg->b, p.blockSize, p.P1, p.P2, p.uniquenessRatio, p.disp12MaxDiff,
-                                  p.speckleWindowSize, p.speckleRange, p.paths, n, s, sg->cost_limit, cn, sgm_ftzero(sg));
+    const SGMBuffers& b = sg->b;
+    if (!sg->caps_asked) { sgm_sweep_caps(g.D, p.paths, b.S2 != nullptr, sg->lim.cap); sg->caps_asked = true; }
+    sg->lim.sweep = b.ring && b.ev_in && b.ev_out && b.abortf && *b.abortf == 0;
+    sg->lim.s2 = b.S2 != nullptr;
+    sg->lim.ring_words = b.ring_words;
+    sg->path_variant = launch_sgm(L, R, disp, g, b, sg->lim, p.paths, n, s,
+                                  SgmParams{p.blockSize, p.P1, p.P2, p.uniquenessRatio, p.disp12MaxDiff, p.speckleWindowSize,
+                                            p.speckleRange, sg->cost_limit, cn, sgm_ftzero(sg)});
     HIPC(hipGetLastError());
     return RTDM_OK;
 }

@@ -8,13 +8,12 @@
 //   k_sgm_cost.hip   the two frames -> the block costs C (launch_sgm_cost)
 //   k_sgm_paths.hip  the path passes over lines of at most 256 disparities: C -> S, the last pass -> the winners
 //   k_sgm_wide.hip   the path pass for wider lines
-//   here             the schedule of the passes (launch_sgm) and what follows the winners:
+//   here             the schedule of the passes (plan_sgm / launch_sgm) and what follows the winners:
 //
 //   k_sgm_lrfinal one workgroup per row: the votes of the integer winners (LDS, right-most voter wins ties: R7) and the
 //                always-on left-right check (R9)
 //   k_sgm_median 3x3 median with clamped coordinates (R10) + the speckle filter's per-row init
-#include "rtdm_kernels.h"
-#include "rtdm_device.h"
+#include "rtdm_sgm.h"
 
 namespace rtdm {
 
@@ -114,78 +113,140 @@ static void sgm_finish(Plane16W disp, const SGMGeom& g, const SGMBuffers& b, int
     }
 }
 
-const char* launch_sgm(Plane8 L, Plane8 R, Plane16W disp, const SGMGeom& g, const SGMBuffers& b, int blockSize, int P1, int P2,
-                       int uniq, int disp12MaxDiff, int speckleWindowSize, int speckleRange, int paths, int n, hipStream_t stream,
-                       int cost_limit, int cn, int ftz)
+// Whether a sweep of the form (LAST, ADD2) fits, and in which shape: the narrowest strips whose workgroups all fit the device at
+// once -- 8 columns (one per half-wave), 16, 32: a frame's rows are a serial chain, so the pass is latency bound until every
+// SIMD holds several waves, and the fewer lines a wave carries the shorter its row; wider strips pay the per-row overhead
+// (barrier, edges, addresses) less often -- and whose edges fit the ring.  cols == 0: none does.
+struct SweepFit { int cols, strips, items, grid; };
+static SweepFit sweep_fit(const SGMGeom& g, int n, const SgmLimits& lim, bool last, bool add2)
 {
-    launch_sgm_cost(L, R, g, b, blockSize, cost_limit, cn, ftz, n, stream);
+    // RTDM_SGM_SWEEP_COLS=1 / 2 / 4 (test hook): fixes the first width tried, as a capacity miss does
+    static const int cols_env = env_int("RTDM_SGM_SWEEP_COLS", 0);
+    const auto cap = [&](int c) { return lim.cap[last][c == 4 ? 2 : c - 1][add2]; };
+    const int pick = cols_env ? cols_env : (n * ((g.W1 + 7) / 8) <= cap(1) ? 1 : (n * ((g.W1 + 15) / 16) <= cap(2) ? 2 : 4));
+    for (int c = pick == 1 || pick == 2 ? pick : 4; c <= 4; c *= 2) {
+        const int strips = (g.W1 + 8 * c - 1) / (8 * c), items = n * strips;
+        if (cap(c) >= strips && (size_t)items * 2 * SWEEP_RING * 32 * sgm_np2(g.D) <= lim.ring_words)
+            return SweepFit{c, strips, items, items <= cap(c) ? items : cap(c) / strips * strips};   // the strips of a frame run in the same round
+    }
+    return SweepFit{0, 0, 0, 0};
+}
+
+SgmPlan plan_sgm(const SGMGeom& g, int paths, int n, const SgmLimits& lim, SgmDone done)
+{
     static const int dirs[8][2] = {{1, 0}, {-1, 0}, {0, 1}, {0, -1}, {1, 1}, {-1, 1}, {1, -1}, {-1, -1}};
     const int last_dir = paths == 4 ? 3 : (paths == 5 ? 5 : 7);   // MODE_HH4 (R4'): the first four directions and no others
-    SgmWin* win = (SgmWin*)b.gr;                     // the right image's bounds are dead once the pixel costs exist: 8 bytes per pixel
+    SgmPlan plan{};
+    const auto add = [&](SgmStep step, int k, bool s2) -> SgmPass& {
+        SgmPass& p = plan.pass[plan.npasses++];
+        p = SgmPass{step, k, k < 0 ? 0 : dirs[k][0], k < 0 ? 0 : dirs[k][1], k == 0, k == last_dir, s2, 0, 0, 0, 0, 0};
+        return p;
+    };
     // D > 256 (or rtdm_debug_sgm_wide_paths): one wide pass per direction (k_sgm_wide.hip), the last one deciding the winners;
-    // none of the forms below -- they hold at most 256 disparities per line
-    if (g.D > 256 || sgm_wide_mode()) {
-        for (int k = 0; k <= last_dir; ++k) {
-            if (paths == 5 && dirs[k][1] < 0) continue;
-            launch_sgm_wide(g, b.C, b.S, dirs[k][0], dirs[k][1], P1, P2, k == 0 ? 1 : 0, k == last_dir, n, win, uniq, stream);
-        }
-        sgm_finish(disp, g, b, disp12MaxDiff, speckleWindowSize, speckleRange, n, stream, win);
-        return sgm_wide_waves(g.D) == 1 ? "wide_w1" : "wide_w4";
+    // none of the forms below -- they hold at most 256 disparities per line -- and none of their hooks
+    const int wide = sgm_wide_mode();
+    if (g.D > 256 || wide) {
+        const int waves = wide == 4 || g.D > 1024 ? 4 : 1;
+        for (int k = 0; k <= last_dir; ++k)
+            if (paths != 5 || dirs[k][1] >= 0) add(SgmStep::WIDE, k, false).waves = waves;
+        plan.variant = waves == 1 ? "wide_w1" : "wide_w4";
+        return plan;
     }
-    // (C, S and S2 are whole allocations: 16-byte aligned, as the packed loads and stores of the path passes need)
-    // RTDM_SGM_SWEEP=0 (test hook): one pass per direction for the six that advance a row per step as well -- what runs after
-    // a sweep gave up or did not fit
+    // RTDM_SGM_SWEEP=0 (test hook): one k_sgm_path_h pass per direction for those that advance a row per step as well -- what
+    // runs after a sweep gave up or did not fit, and what k_sgm_vert is timed against
     static const int sweep_env = env_int("RTDM_SGM_SWEEP", 1);
-    bool sweep = sweep_env && b.ring && b.abortf && *b.abortf == 0;
-    bool swept_down = false, swept_up = false;
     // RTDM_SGM_DUAL=0 (test hook): the two horizontal directions one after the other (the second adds to S) instead of side by
     // side -- what runs without S2
     static const int dual_env = env_int("RTDM_SGM_DUAL", 1);
-    if (paths == 4) {
+    if (paths == 4 && sweep_env) {
         // MODE_HH4: -> and <- (side by side into S and S2 where there is an S2), then the two vertical directions on the
-        // column-parallel pass, the upward one deciding the winners -- no sweep, no ring, no epoch, no sweep stream.
-        // RTDM_SGM_SWEEP=0: one k_sgm_path_h pass per direction instead (what k_sgm_vert is timed against)
-        if (!sweep_env) {
-            for (int k = 0; k < 4; ++k) launch_path_h(g, b, dirs[k][0], dirs[k][1], P1, P2, k == 0, k == 3, n, win, uniq, stream);
-            sgm_finish(disp, g, b, disp12MaxDiff, speckleWindowSize, speckleRange, n, stream, win);
-            return "half";
-        }
-        const bool dual = dual_env && b.S2;
-        launch_path_h(g, b, 1, 0, P1, P2, 1, false, n, win, uniq, stream, dual ? b.S2 : nullptr);
-        if (!dual) launch_path_h(g, b, -1, 0, P1, P2, 0, false, n, win, uniq, stream);
-        launch_vert(g, b, 1, P1, P2, false, n, win, uniq, stream, dual ? b.S2 : nullptr);
-        launch_vert(g, b, -1, P1, P2, true, n, win, uniq, stream, nullptr);
-        sgm_finish(disp, g, b, disp12MaxDiff, speckleWindowSize, speckleRange, n, stream, win);
-        return "vert";
+        // column-parallel pass, the upward one deciding the winners -- no sweep, no ring, no epoch, no sweep stream
+        const bool dual = dual_env && lim.s2;
+        add(SgmStep::PATH_H, 0, dual);
+        if (!dual) add(SgmStep::PATH_H, 1, false);
+        add(SgmStep::VERT, 2, dual);
+        add(SgmStep::VERT, 3, false);
+        plan.variant = "vert";
+        return plan;
     }
-    bool s2_pending = false;                         // S2 holds the (-1, 0) direction's L_r and has not been added to S yet
-    bool swept = false;                              // a row-synchronous sweep ran (the variant this call reports)
-    for (int k = 0; k < 8; ++k) {
-        const int dx = dirs[k][0], dy = dirs[k][1];
-        if (paths == 5 && dy < 0) continue;          // MODE_SGBM's five directions: nothing runs upwards
-        if (k == 0 && sweep && dual_env && b.S2 &&
-            launch_sweep(paths == 5, g, b, 1, P1, P2, n, win, uniq, stream, nullptr, true)) {
-            // both horizontal directions in one launch: (1, 0) -> S, (-1, 0) -> S2; the downward sweep adds the two up
-            launch_path_h(g, b, 1, 0, P1, P2, 1, false, n, win, uniq, stream, b.S2);
-            s2_pending = true;
+    bool sweeping = sweep_env && lim.sweep;
+    for (int k = 0; k <= last_dir; ++k) {
+        if ((done.dirs >> k & 1) || (paths == 5 && dirs[k][1] < 0)) continue;   // MODE_SGBM's five directions: nothing runs upwards
+        if (k == 0) {
+            // both horizontal directions in one launch, (1, 0) -> S and (-1, 0) -> S2, where the downward sweep will add the two up
+            done.s2_pending = sweeping && dual_env && lim.s2 && sweep_fit(g, n, lim, paths == 5, true).cols;
+            add(SgmStep::PATH_H, 0, done.s2_pending);
+            if (done.s2_pending) done.dirs |= 1u << 1;
             continue;
         }
-        if (k == 1 && s2_pending) continue;
-        if (dy != 0) {
-            // (0, dy), (+1, dy), (-1, dy) in one row-synchronous pass: -> <- down [up]; the last sweep decides the winners
-            bool& done = dy > 0 ? swept_down : swept_up;
-            if (done) continue;
-            if (sweep && (k == 2 || k == 3)) {
-                const bool last_sweep = paths == 5 || dy < 0;
-                if (launch_sweep(last_sweep, g, b, dy, P1, P2, n, win, uniq, stream, s2_pending ? b.S2 : nullptr)) { done = true; s2_pending = false; swept = true; continue; }
-                sweep = false;                       // not launched: this and the remaining directions run as passes of their own
+        if (k == 2 || k == 3) {
+            // (0, dy), (+1, dy), (-1, dy) in one row-synchronous pass: -> <- down [up]; the last sweep decides the winners.  One
+            // that does not fit: this and the remaining directions run as passes of their own
+            const bool last = paths == 5 || k == 3;
+            const SweepFit f = sweeping ? sweep_fit(g, n, lim, last, done.s2_pending) : SweepFit{0, 0, 0, 0};
+            sweeping = f.cols != 0;
+            if (sweeping) {
+                SgmPass& p = add(SgmStep::SWEEP, k, done.s2_pending);
+                p.last = last; p.cols = f.cols; p.strips = f.strips; p.items = f.items; p.grid = f.grid;
+                done.dirs |= k == 2 ? 0x30u : 0xc0u;   // the two diagonals of that dy are covered
+                done.s2_pending = false; done.swept = true;
+                continue;
             }
-            if (s2_pending) { launch_sgm_add_s2(g, b, n, stream); s2_pending = false; }   // (the sweep that was to add S2 could not be launched)
         }
-        launch_path_h(g, b, dx, dy, P1, P2, k == 0, k == last_dir, n, win, uniq, stream);
+        if (done.s2_pending) { add(SgmStep::ADD_S2, -1, false); done.s2_pending = false; }   // (no sweep adds S2 after all)
+        add(SgmStep::PATH_H, k, false);
     }
-    sgm_finish(disp, g, b, disp12MaxDiff, speckleWindowSize, speckleRange, n, stream, win);
-    return swept ? "sweep" : "half";
+    plan.variant = done.swept ? "sweep" : "half";
+    return plan;
+}
+
+// What is done once the first `count` passes of a plan have been issued
+static SgmDone sgm_done(const SgmPlan& plan, int count)
+{
+    SgmDone d{0, false, false};
+    for (int i = 0; i < count; ++i) {
+        const SgmPass& p = plan.pass[i];
+        if (p.dir >= 0) d.dirs |= 1u << p.dir;
+        if (p.step == SgmStep::PATH_H && p.s2) { d.dirs |= 1u << 1; d.s2_pending = true; }
+        if (p.step == SgmStep::SWEEP) { d.dirs |= p.dy > 0 ? 0x30u : 0xc0u; d.swept = true; }
+        if (p.step == SgmStep::SWEEP || p.step == SgmStep::ADD_S2) d.s2_pending = false;
+    }
+    return d;
+}
+
+// Issues the passes in order; returns how many were issued: less than all where the next one is a sweep the runtime refused
+static int sgm_issue(const SgmPlan& plan, const SgmCall& c)
+{
+    for (int i = 0; i < plan.npasses; ++i) {
+        const SgmPass& p = plan.pass[i];
+        switch (p.step) {
+            case SgmStep::WIDE: launch_sgm_wide(p, c); break;
+            case SgmStep::PATH_H: launch_path_h(p, c); break;
+            case SgmStep::VERT: launch_vert(p, c); break;
+            case SgmStep::ADD_S2: launch_sgm_add_s2(c); break;
+            case SgmStep::SWEEP: if (!launch_sweep(p, c)) return i; break;
+        }
+    }
+    return plan.npasses;
+}
+
+const char* launch_sgm(Plane8 L, Plane8 R, Plane16W disp, const SGMGeom& g, const SGMBuffers& b, const SgmLimits& lim, int paths,
+                       int n, hipStream_t stream, SgmParams p)
+{
+    launch_sgm_cost(L, R, g, b, p.blockSize, p.cost_limit, p.cn, p.ftz, n, stream);
+    // (the right image's bounds are dead once the pixel costs exist: 8 bytes per pixel for the winners; C, S and S2 are whole
+    // allocations: 16-byte aligned, as the packed loads and stores of the path passes need)
+    const SgmCall c{g, b, p.P1, p.P2, p.uniq, n, (SgmWin*)b.gr, stream};
+    SgmPlan plan = plan_sgm(g, paths, n, lim);
+    const int issued = sgm_issue(plan, c);
+    if (issued < plan.npasses) {                     // a refused sweep: the remainder without sweeps, which nothing can refuse
+        SgmLimits rest = lim;
+        rest.sweep = false;
+        plan = plan_sgm(g, paths, n, rest, sgm_done(plan, issued));
+        sgm_issue(plan, c);
+    }
+    sgm_finish(disp, g, b, p.disp12MaxDiff, p.speckleWindowSize, p.speckleRange, n, stream, c.win);
+    return plan.variant;
 }
 
 }  // namespace rtdm

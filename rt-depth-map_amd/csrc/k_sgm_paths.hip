@@ -149,10 +149,9 @@ __global__ __launch_bounds__(256) void k_sgm_path_h(const uint16_t* C, uint16_t*
 // the low half: single-copy atomic, so a word that shows the expected tag is the expected data -- no fence, no L2 write-back).
 // Every strip needs its neighbours' edge of the PREVIOUS row, which they publish at the start of that row: the strips of a
 // frame advance in lockstep within a row of each other, and a wait is normally already satisfied.  All workgroups of the
-// launch must be resident at once (grid <= what the device holds, one sweep at a time per process: launch_sweep_c); as a second
+// launch must be resident at once (grid <= what the device holds, one sweep at a time per process: launch_sweep); as a second
 // line of defence a wait gives up after ~1 s, sets *abortf and the pass runs to its end without waiting (the host then
 // reports the call as failed and the handle falls back to one pass per direction).
-static constexpr int SWEEP_RING = 4;                      // rows of edge data kept per (strip, side)
 __device__ __forceinline__ unsigned long long ld_u64_relaxed(const unsigned long long* p)
 { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void st_u64_relaxed(unsigned long long* p, unsigned long long v)
@@ -398,27 +397,58 @@ __global__ __launch_bounds__(256) void k_sgm_add_s2(uint32_t* S, const uint32_t*
     if (i < npairs) S[i] = pk_min_u(pk_add(S[i], S2[i]), 0x7fff7fffu);
 }
 
-static inline int sgm_np2(int D) { return D <= 64 ? 1 : (D <= 128 ? 2 : 4); }
 size_t sgm_ring_words(int maxW, int D, int max_batch)                  // sized for the narrowest strips (8 columns)
 { return (size_t)max_batch * ((size_t)(maxW + 7) / 8) * 2 * SWEEP_RING * 32 * sgm_np2(D); }
 
-// One row-synchronous pass over (0, dy), (+1, dy), (-1, dy).  false = not launched (the caller runs the three passes).
-template <int NP2, bool LAST, int CPH, bool ADD2>
-static int sweep_capacity(const SGMBuffers& b)
+// The k_sgm_sweep instantiation of a form: the one table the capacities and the launch go through.  (ADD2, the instantiation
+// that also adds S2 -- the first sweep after the side-by-side horizontal directions -- holds one more volume's row in
+// registers: a template parameter, so that the other sweep keeps its occupancy.)
+using SweepKernel = decltype(&k_sgm_sweep<1, false, 1, false>);
+template <int NP2, bool LAST>
+static SweepKernel sweep_kernel_t(int cols, bool add2)
 {
-    int& cap = b.sweep_cap[(((NP2 == 1 ? 0 : (NP2 == 2 ? 1 : 2)) * 2 + (LAST ? 1 : 0)) * 3 + (CPH == 4 ? 2 : CPH - 1)) * 2 + (ADD2 ? 1 : 0)];
-    if (cap == 0) {
-        int dev = 0, cus = 0, per_cu = 0;
-        cap = -1;
-        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess &&
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_sgm_sweep<NP2, LAST, CPH, ADD2>, 256, 0) == hipSuccess && per_cu > 0)
-            cap = per_cu * cus;
-        (void)hipGetLastError();
+    switch (cols * 2 + (add2 ? 1 : 0)) {
+        case 2: return k_sgm_sweep<NP2, LAST, 1, false>;
+        case 3: return k_sgm_sweep<NP2, LAST, 1, true>;
+        case 4: return k_sgm_sweep<NP2, LAST, 2, false>;
+        case 5: return k_sgm_sweep<NP2, LAST, 2, true>;
+        case 8: return k_sgm_sweep<NP2, LAST, 4, false>;
+        default: return k_sgm_sweep<NP2, LAST, 4, true>;
     }
+}
+static SweepKernel sweep_kernel(int np2, bool last, int cols, bool add2)
+{
+    switch (np2 * 2 + (last ? 1 : 0)) {
+        case 2: return sweep_kernel_t<1, false>(cols, add2);
+        case 3: return sweep_kernel_t<1, true>(cols, add2);
+        case 4: return sweep_kernel_t<2, false>(cols, add2);
+        case 5: return sweep_kernel_t<2, true>(cols, add2);
+        case 8: return sweep_kernel_t<4, false>(cols, add2);
+        default: return sweep_kernel_t<4, true>(cols, add2);
+    }
+}
+static int sweep_capacity(SweepKernel k)
+{
+    int dev = 0, cus = 0, per_cu = 0, cap = -1;
+    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess &&
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, 256, 0) == hipSuccess && per_cu > 0)
+        cap = per_cu * cus;
+    (void)hipGetLastError();
     return cap;
 }
+// The capacities of every sweep form a handle of this mode can launch, three column widths each: the down form (LAST in
+// MODE_SGBM) without ADD2 and, where there is an S2, with it; MODE_HH's up form.  MODE_HH4 and wide lines: none (all 0).
+void sgm_sweep_caps(int D, int paths, bool s2, int cap[2][3][2])
+{
+    for (int i = 0; i < 12; ++i) (&cap[0][0][0])[i] = 0;
+    if (paths == 4 || D > 256) return;
+    for (int c = 0; c < 3; ++c) {
+        for (int add2 = 0; add2 <= (s2 ? 1 : 0); ++add2) cap[paths == 5][c][add2] = sweep_capacity(sweep_kernel(sgm_np2(D), paths == 5, 1 << c, add2));
+        if (paths == 8) cap[1][c][0] = sweep_capacity(sweep_kernel(sgm_np2(D), true, 1 << c, false));
+    }
+}
 // The workgroups of a sweep wait for each other, so all of them must be resident at once: the grid is no larger than what the
-// device holds, and the sweeps of ONE PROCESS never run side by side -- they all go through one stream per device (two sweeps
+// device holds (plan_sgm), and the sweeps of ONE PROCESS never run side by side -- they all go through one stream per device (two sweeps
 // half resident each would wait for workgroups that cannot start).  The caller's stream and the sweep stream are tied
 // together by the handle's two events; kernels of other streams may share the device with a sweep (they do not wait for it,
 // so they finish and make room).  (hipLaunchCooperativeKernel would promise the residency, but a process that has used it
@@ -426,100 +456,65 @@ static int sweep_capacity(const SGMBuffers& b)
 struct SweepLane { std::mutex mu; hipStream_t s = nullptr; };
 static SweepLane& sweep_lane(int dev) { static SweepLane lanes[64]; return lanes[dev & 63]; }
 
-template <int NP2, bool LAST, int CPH, bool ADD2>
-static bool launch_sweep_c(const SGMGeom& g, const SGMBuffers& b, int dy, int P1, int P2, int n, SgmWin* win, int uniq, hipStream_t stream, const uint16_t* S2in, bool probe)
+// One row-synchronous pass over (0, dy), (+1, dy), (-1, dy).
+bool launch_sweep(const SgmPass& p, const SgmCall& c)
 {
-    const int cap = sweep_capacity<NP2, LAST, CPH, ADD2>(b);
-    const int strips = (g.W1 + 8 * CPH - 1) / (8 * CPH);
-    if (cap < strips || !b.ev_in || !b.ev_out) return false;
-    const int items = n * strips;
-    if ((size_t)items * 2 * SWEEP_RING * 32 * NP2 > b.ring_words) return false;
-    if (probe) return true;                                              // (would be launched: the caller plans its passes on that)
-    const int grid = items <= cap ? items : cap / strips * strips;       // the strips of a frame run in the same round
+    const SGMBuffers& b = c.b;
     const uint32_t epoch = (*b.epoch + 1) & 0xffffu;
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return false; }
     SweepLane& lane = sweep_lane(dev);
     std::lock_guard<std::mutex> lk(lane.mu);
     if (!lane.s && hipStreamCreateWithFlags(&lane.s, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); lane.s = nullptr; return false; }
-    if (hipEventRecord((hipEvent_t)b.ev_in, stream) != hipSuccess || hipStreamWaitEvent(lane.s, (hipEvent_t)b.ev_in, 0) != hipSuccess) { (void)hipGetLastError(); return false; }
+    if (hipEventRecord((hipEvent_t)b.ev_in, c.stream) != hipSuccess || hipStreamWaitEvent(lane.s, (hipEvent_t)b.ev_in, 0) != hipSuccess) { (void)hipGetLastError(); return false; }
     // RTDM_SGM_SWEEP_TEST_GIVEUP=1 (tests only): strip 0 never publishes its edge, so its neighbour's wait must run into its bound
     static const int mute = env_int("RTDM_SGM_SWEEP_TEST_GIVEUP", 0) ? 0 : -1;
-    hipLaunchKernelGGL((k_sgm_sweep<NP2, LAST, CPH, ADD2>), dim3(grid), dim3(256), 0, lane.s, b.C, b.S, g, dy, P1, P2, strips, items, b.ring, b.abortf, epoch, win, uniq, mute, S2in);
+    const SweepKernel kernel = sweep_kernel(sgm_np2(c.g.D), p.last, p.cols, p.s2);
+    hipLaunchKernelGGL(kernel, dim3(p.grid), dim3(256), 0, lane.s, b.C, b.S, c.g, p.dy, c.P1, c.P2, p.strips, p.items, b.ring, b.abortf,
+                       epoch, c.win, c.uniq, mute, p.s2 ? (const uint16_t*)b.S2 : nullptr);
     // (from here on the caller's stream has to wait for the sweep stream whatever happens, or it would run ahead of it)
     (void)hipEventRecord((hipEvent_t)b.ev_out, lane.s);
-    (void)hipStreamWaitEvent(stream, (hipEvent_t)b.ev_out, 0);
+    (void)hipStreamWaitEvent(c.stream, (hipEvent_t)b.ev_out, 0);
     ++*b.epoch;
     return true;
 }
-template <int NP2, bool LAST>
-static bool launch_sweep_t(const SGMGeom& g, const SGMBuffers& b, int dy, int P1, int P2, int n, SgmWin* win, int uniq, hipStream_t stream, const uint16_t* S2in, bool probe)
-{
-    // the narrowest strips whose workgroups all fit the device at once: 8 columns (one per half-wave), 16, 32 -- a frame's rows
-    // are a serial chain, so the pass is latency bound until every SIMD holds several waves, and the fewer lines a wave carries
-    // the shorter its row; wider strips pay the per-row overhead (barrier, edges, addresses) less often
-    // (RTDM_SGM_SWEEP_COLS=1 / 2 / 4, test hook: fixes the choice, as a capacity miss does)
-    static const int cols_env = env_int("RTDM_SGM_SWEEP_COLS", 0);
-    // (the instantiation that also adds S2 -- the first sweep after the side-by-side horizontal directions -- holds one more
-    // volume's row in registers: a template parameter, so that the other sweep keeps its occupancy)
-    const bool add2 = S2in != nullptr || (probe && b.S2 != nullptr);
-    const int cap1 = add2 ? sweep_capacity<NP2, LAST, 1, true>(b) : sweep_capacity<NP2, LAST, 1, false>(b);
-    const int cap2 = add2 ? sweep_capacity<NP2, LAST, 2, true>(b) : sweep_capacity<NP2, LAST, 2, false>(b);
-    const int pick = cols_env ? cols_env : (n * ((g.W1 + 7) / 8) <= cap1 ? 1 : (n * ((g.W1 + 15) / 16) <= cap2 ? 2 : 4));
-#define RTDM_SWC(CC) (add2 ? launch_sweep_c<NP2, LAST, CC, true>(g, b, dy, P1, P2, n, win, uniq, stream, S2in, probe) \
-                           : launch_sweep_c<NP2, LAST, CC, false>(g, b, dy, P1, P2, n, win, uniq, stream, S2in, probe))
-    if (pick == 1 && RTDM_SWC(1)) return true;
-    if (pick <= 2 && RTDM_SWC(2)) return true;
-    return RTDM_SWC(4);
-#undef RTDM_SWC
-}
-bool launch_sweep(bool last, const SGMGeom& g, const SGMBuffers& b, int dy, int P1, int P2, int n, SgmWin* win, int uniq, hipStream_t stream,
-                         const uint16_t* S2in, bool probe)
-{
-    switch (sgm_np2(g.D) * 2 + (last ? 1 : 0)) {
-        case 2: return launch_sweep_t<1, false>(g, b, dy, P1, P2, n, win, uniq, stream, S2in, probe);
-        case 3: return launch_sweep_t<1, true>(g, b, dy, P1, P2, n, win, uniq, stream, S2in, probe);
-        case 4: return launch_sweep_t<2, false>(g, b, dy, P1, P2, n, win, uniq, stream, S2in, probe);
-        case 5: return launch_sweep_t<2, true>(g, b, dy, P1, P2, n, win, uniq, stream, S2in, probe);
-        case 8: return launch_sweep_t<4, false>(g, b, dy, P1, P2, n, win, uniq, stream, S2in, probe);
-        default: return launch_sweep_t<4, true>(g, b, dy, P1, P2, n, win, uniq, stream, S2in, probe);
-    }
-}
 
-// One k_sgm_path_h launch: half-wave lines, packed arithmetic, eight lines per workgroup.  S2 != null: the two horizontal
-// directions side by side, (dx, 0) -> S and (-dx, 0) -> S2 (first = 1).
-void launch_path_h(const SGMGeom& g, const SGMBuffers& b, int dx, int dy, int P1, int P2, int first, bool last, int n, SgmWin* win,
-                          int uniq, hipStream_t stream, uint16_t* S2)
+// One k_sgm_path_h launch: half-wave lines, packed arithmetic, eight lines per workgroup.  p.s2: the two horizontal
+// directions side by side, (dx, 0) -> S and (-dx, 0) -> S2 (first).
+void launch_path_h(const SgmPass& p, const SgmCall& c)
 {
-    const int lines = sgm_line_count(g, dx, dy);
-    const dim3 hgrid(((S2 ? 2 : 1) * lines + 7) / 8, n), blk(256);
-#define RTDM_PATHH(N) do { if (last) hipLaunchKernelGGL((k_sgm_path_h<N, 8, true>), hgrid, blk, 0, stream, b.C, b.S, g, dx, dy, P1, P2, first, lines, win, uniq, S2); \
-                           else hipLaunchKernelGGL((k_sgm_path_h<N, 8, false>), hgrid, blk, 0, stream, b.C, b.S, g, dx, dy, P1, P2, first, lines, win, uniq, S2); } while (0)
+    const SGMGeom& g = c.g;
+    uint16_t* S2 = p.s2 ? c.b.S2 : nullptr;
+    const int lines = sgm_line_count(g, p.dx, p.dy), first = p.first;
+    const dim3 hgrid(((S2 ? 2 : 1) * lines + 7) / 8, c.n), blk(256);
+#define RTDM_PATHH(N) do { if (p.last) hipLaunchKernelGGL((k_sgm_path_h<N, 8, true>), hgrid, blk, 0, c.stream, c.b.C, c.b.S, g, p.dx, p.dy, c.P1, c.P2, first, lines, c.win, c.uniq, S2); \
+                           else hipLaunchKernelGGL((k_sgm_path_h<N, 8, false>), hgrid, blk, 0, c.stream, c.b.C, c.b.S, g, p.dx, p.dy, c.P1, c.P2, first, lines, c.win, c.uniq, S2); } while (0)
     switch (sgm_np2(g.D)) { case 1: RTDM_PATHH(1); break; case 2: RTDM_PATHH(2); break; default: RTDM_PATHH(4); break; }
 #undef RTDM_PATHH
 }
 
-// One k_sgm_vert launch over (0, dy).  last: the winners instead of S; S2 != null (never with last): S2 is added to S on the way.
-void launch_vert(const SGMGeom& g, const SGMBuffers& b, int dy, int P1, int P2, bool last, int n, SgmWin* win, int uniq,
-                        hipStream_t stream, const uint16_t* S2)
+// One k_sgm_vert launch over (0, dy).  p.last: the winners instead of S; p.s2 (never with last): S2 is added to S on the way.
+void launch_vert(const SgmPass& p, const SgmCall& c)
 {
     // columns per workgroup and rows of prefetch, by measurement (profiles/sgm_hh4_time.txt: 720p, D = 128, 1 / 4 / 16 pairs per
     // call): 2 columns -- one wave per workgroup, so that a lone pair's 576 waves spread over all compute units -- and 8 rows
     // (2 / 4 / 16 rows: 14 % / 6 % / 3 % slower at one pair per call; 4 or 8 columns: 2 % to 15 % slower there; all within 4 %
     // of each other at 16 pairs); D = 64 and D = 256 agree
     constexpr int cols = 2, PF = 8;
-    const dim3 vgrid((g.W1 + cols - 1) / cols, n), blk(32 * cols);
-#define RTDM_VERT(N) do { if (last) hipLaunchKernelGGL((k_sgm_vert<N, true, false, PF>), vgrid, blk, 0, stream, b.C, b.S, S2, g, dy, P1, P2, win, uniq); \
-                          else if (S2) hipLaunchKernelGGL((k_sgm_vert<N, false, true, PF>), vgrid, blk, 0, stream, b.C, b.S, S2, g, dy, P1, P2, win, uniq); \
-                          else hipLaunchKernelGGL((k_sgm_vert<N, false, false, PF>), vgrid, blk, 0, stream, b.C, b.S, S2, g, dy, P1, P2, win, uniq); } while (0)
+    const SGMGeom& g = c.g;
+    const uint16_t* S2 = p.s2 ? c.b.S2 : nullptr;
+    const dim3 vgrid((g.W1 + cols - 1) / cols, c.n), blk(32 * cols);
+#define RTDM_VERT(N) do { if (p.last) hipLaunchKernelGGL((k_sgm_vert<N, true, false, PF>), vgrid, blk, 0, c.stream, c.b.C, c.b.S, S2, g, p.dy, c.P1, c.P2, c.win, c.uniq); \
+                          else if (S2) hipLaunchKernelGGL((k_sgm_vert<N, false, true, PF>), vgrid, blk, 0, c.stream, c.b.C, c.b.S, S2, g, p.dy, c.P1, c.P2, c.win, c.uniq); \
+                          else hipLaunchKernelGGL((k_sgm_vert<N, false, false, PF>), vgrid, blk, 0, c.stream, c.b.C, c.b.S, S2, g, p.dy, c.P1, c.P2, c.win, c.uniq); } while (0)
     switch (sgm_np2(g.D)) { case 1: RTDM_VERT(1); break; case 2: RTDM_VERT(2); break; default: RTDM_VERT(4); break; }
 #undef RTDM_VERT
 }
 
-void launch_sgm_add_s2(const SGMGeom& g, const SGMBuffers& b, int n, hipStream_t stream)
+void launch_sgm_add_s2(const SgmCall& c)
 {
-    const size_t npairs = (size_t)n * g.H * g.W1 * g.D / 2;
-    hipLaunchKernelGGL(k_sgm_add_s2, dim3((unsigned)((npairs + 255) / 256)), dim3(256), 0, stream, (uint32_t*)b.S, (const uint32_t*)b.S2, npairs);
+    const size_t npairs = (size_t)c.n * c.g.H * c.g.W1 * c.g.D / 2;
+    hipLaunchKernelGGL(k_sgm_add_s2, dim3((unsigned)((npairs + 255) / 256)), dim3(256), 0, c.stream, (uint32_t*)c.b.S, (const uint32_t*)c.b.S2, npairs);
 }
 
 }  // namespace rtdm

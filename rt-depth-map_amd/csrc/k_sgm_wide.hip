@@ -185,21 +185,14 @@ static void launch_wide_t(const SGMGeom& g, const uint16_t* C, uint16_t* S, int 
     else      hipLaunchKernelGGL((k_sgm_wide<NP2, NW, PF, false>), grid, dim3(256), 0, stream, C, S, g, dx, dy, P1, P2, first, lines, win, uniq);
 }
 
-int sgm_wide_waves(int D)
+void launch_sgm_wide(const SgmPass& p, const SgmCall& c)
 {
-    const int m = sgm_wide_mode();
-    return m == 4 || D > 1024 ? 4 : 1;
-}
-
-void launch_sgm_wide(const SGMGeom& g, const uint16_t* C, uint16_t* S, int dx, int dy, int P1, int P2, int first, bool last, int n,
-                     SgmWin* win, int uniq, hipStream_t stream)
-{
-    const int nw = sgm_wide_waves(g.D);
+    const SGMGeom& g = c.g;
     int np2 = 1;
-    while (nw * 128 * np2 < g.D) np2 *= 2;                        // D <= 4080 < 4 * 128 * 8
-    const int lines = sgm_line_count(g, dx, dy);
-#define RTDM_WIDE(N, W) launch_wide_t<N, W>(g, C, S, dx, dy, P1, P2, first, last, lines, n, win, uniq, stream)
-    if (nw == 1) {
+    while (p.waves * 128 * np2 < g.D) np2 *= 2;                   // D <= 4080 < 4 * 128 * 8
+    const int lines = sgm_line_count(g, p.dx, p.dy);
+#define RTDM_WIDE(N, W) launch_wide_t<N, W>(g, c.b.C, c.b.S, p.dx, p.dy, c.P1, c.P2, p.first, p.last, lines, c.n, c.win, c.uniq, c.stream)
+    if (p.waves == 1) {
         switch (np2) { case 1: RTDM_WIDE(1, 1); break; case 2: RTDM_WIDE(2, 1); break; case 4: RTDM_WIDE(4, 1); break; default: RTDM_WIDE(8, 1); break; }
     } else {
         switch (np2) { case 1: RTDM_WIDE(1, 4); break; case 2: RTDM_WIDE(2, 4); break; case 4: RTDM_WIDE(4, 4); break; default: RTDM_WIDE(8, 4); break; }

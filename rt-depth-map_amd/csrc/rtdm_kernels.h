@@ -235,46 +235,59 @@ struct SGMBuffers {
     int32_t *label, *size, *rowcnt; uint32_t* runs; int16_t* headmap;   // speckle filter workspace
     int32_t* ovf;            // set to 1 by the block-cost kernel where a block cost + P2 passes 32767 (windows > 17 only)
     // row-synchronous sweep (k_sgm_sweep): edge ring between neighbouring strips, give-up flag (page-locked, host readable),
-    // the handle's launch counter (tags of the ring words), how many workgroups the device holds at once per instantiation
+    // the handle's launch counter (tags of the ring words)
     unsigned long long* ring; size_t ring_words;
     int32_t* abortf; uint32_t* epoch;
-    int* sweep_cap;          // [36], 0 = not asked yet, < 0 = unusable
     void *ev_in, *ev_out;    // hipEvent_t: the caller's stream -> the process's sweep stream -> the caller's stream
 };
 size_t sgm_ring_words(int maxW, int D, int max_batch);
 // What the last path pass leaves per pixel for k_sgm_lrfinal: {x16 disparity or INV, integer winner + minD or minD - 1,
 // minimum cost, 0}
 struct SgmWin { int16_t d16, bd; uint16_t mins, pad; };
-// The path pass for wide lines (k_sgm_wide.hip): every D from 16 to 4080, one direction per launch, S (+)= L_r or (last) the
-// winners -> win.  sgm_wide_waves(D): waves per line it runs with (1 or 4).  sgm_wide_set_mode: rtdm_debug_sgm_wide_paths.
-void launch_sgm_wide(const SGMGeom& g, const uint16_t* C, uint16_t* S, int dx, int dy, int P1, int P2, int first, bool last, int n,
-                     SgmWin* win, int uniq, hipStream_t stream);
-int sgm_wide_waves(int D);
-void sgm_wide_set_mode(int m);
+void sgm_wide_set_mode(int m);     // rtdm_debug_sgm_wide_paths
 int sgm_wide_mode();
 // The cost stage (k_sgm_cost.hip): bounds, pixel cost and block sum of n pairs -> b.C; cost_limit, cn, ftz as for launch_sgm.
 void launch_sgm_cost(Plane8 L, Plane8 R, const SGMGeom& g, const SGMBuffers& b, int blockSize, int cost_limit, int cn, int ftz, int n,
                      hipStream_t stream);
-// The path passes for lines of at most 256 disparities (k_sgm_paths.hip).  launch_path_h: one direction per launch, or (S2 !=
-// null, first = 1) (dx, 0) -> S and (-dx, 0) -> S2 side by side.  launch_vert: (0, dy) column-parallel, S2 != null (never with
-// last) added to S on the way.  launch_sweep: (0, dy), (+1, dy), (-1, dy) in one row-synchronous pass, S2in != null added on
-// the way; false = not launched (the caller runs the three passes); probe: only say whether it would be launched.
-// launch_sgm_add_s2: S = min(S + S2, 32767).  last: the pass decides the winners -> win instead of writing S.
-void launch_path_h(const SGMGeom& g, const SGMBuffers& b, int dx, int dy, int P1, int P2, int first, bool last, int n, SgmWin* win,
-                   int uniq, hipStream_t stream, uint16_t* S2 = nullptr);
-void launch_vert(const SGMGeom& g, const SGMBuffers& b, int dy, int P1, int P2, bool last, int n, SgmWin* win, int uniq,
-                 hipStream_t stream, const uint16_t* S2);
-bool launch_sweep(bool last, const SGMGeom& g, const SGMBuffers& b, int dy, int P1, int P2, int n, SgmWin* win, int uniq,
-                  hipStream_t stream, const uint16_t* S2in = nullptr, bool probe = false);
-void launch_sgm_add_s2(const SGMGeom& g, const SGMBuffers& b, int n, hipStream_t stream);
+// The path passes between the cost stage and the winners' left-right check.  plan_sgm (k_sgm.hip) decides, once per call and
+// without touching the runtime, what launch_sgm then issues; the route table is in DESIGN.md ("SGM: routes").  Directions are
+// indexed 0..7 = (1,0) (-1,0) (0,1) (0,-1) (1,1) (-1,1) (1,-1) (-1,-1): paths 4 runs 0..3, paths 5 those with dy >= 0, paths 8 all.
+//   WIDE    k_sgm_wide, one direction, `waves` (1 / 4) waves per line: D > 256 or rtdm_debug_sgm_wide_paths
+//   PATH_H  k_sgm_path_h, one direction; s2: (dx, 0) -> S and (-dx, 0) -> S2 side by side
+//   VERT    k_sgm_vert over (0, dy); s2: S2 is added to S on the way
+//   SWEEP   k_sgm_sweep over (0, dy), (+1, dy), (-1, dy), `cols` (1 / 2 / 4) columns per half-wave, `strips` strips per frame,
+//           `items` = n strips on `grid` workgroups; s2: S2 is added to S on the way
+//   ADD_S2  k_sgm_add_s2: S = min(S + S2, 32767)
+// first: S is written, not added to; last: the pass decides the winners instead of writing S.
+enum class SgmStep { WIDE, PATH_H, VERT, SWEEP, ADD_S2 };
+struct SgmPass {
+    SgmStep step;
+    int dir, dx, dy;                       // direction index and vector (ADD_S2: -1, 0, 0)
+    bool first, last, s2;
+    int cols, strips, items, grid;         // SWEEP
+    int waves;                             // WIDE
+};
+struct SgmPlan {
+    SgmPass pass[8]; int npasses;
+    const char* variant;                   // "sweep", "half", "vert", "wide_w1", "wide_w4"
+};
+// What a plan may use of the handle and the device, filled by the caller: sweep -- the handle may run k_sgm_sweep (edge ring
+// and both events there, give-up flag clear); s2 -- S2 exists; cap -- the workgroups the device holds at once of the
+// k_sgm_sweep instantiations of the handle's numDisparities class, [LAST][columns 1 / 2 / 4][ADD2] (sgm_sweep_caps; <= 0: unusable).
+struct SgmLimits { bool sweep, s2; size_t ring_words; int cap[2][3][2]; };
+void sgm_sweep_caps(int D, int paths, bool s2, int cap[2][3][2]);   // asks the runtime: once per handle
+// What of a call has been issued already: bit k of dirs -- direction k is in S (or S2); s2_pending -- S2 holds (-1, 0) and has
+// not been added to S; swept -- a sweep ran.
+struct SgmDone { unsigned dirs; bool s2_pending, swept; };
+SgmPlan plan_sgm(const SGMGeom& g, int paths, int n, const SgmLimits& lim, SgmDone done = SgmDone{0, false, false});
 // cost_limit > 0: block costs above it set *b.ovf (the caller reads it back: api_sgm.hip).  cn: 1 (gray) or 3 (interleaved
 // colour, reads b.cl / b.cr); ftz: R1's ftzero = max(preFilterCap, 15) | 1, at most 127.  Where a pixel cost can pass 255
 // (sgm_cost16_needed: colour, ftz >= 97, or rtdm_debug_sgm_cost16) the cost stage runs on u16 pixel costs.
-// Returns the name of the path-pass form the call ran ("sweep", "half", "wide_w1", "wide_w4").  D > 256 (or a forced wide
-// mode) runs the wide pass for every direction.
-const char* launch_sgm(Plane8 L, Plane8 R, Plane16W disp, const SGMGeom& g, const SGMBuffers& b, int blockSize, int P1, int P2,
-                       int uniq, int disp12MaxDiff, int speckleWindowSize, int speckleRange, int paths, int n, hipStream_t stream,
-                       int cost_limit = 0, int cn = 1, int ftz = 15);
+struct SgmParams { int blockSize, P1, P2, uniq, disp12MaxDiff, speckleWindowSize, speckleRange, cost_limit, cn, ftz; };
+// Cost stage, the passes of plan_sgm, sgm_finish.  Returns the plan's variant.  A sweep that the runtime refuses before
+// anything was launched: the remainder runs as plan_sgm plans it without sweeps.
+const char* launch_sgm(Plane8 L, Plane8 R, Plane16W disp, const SGMGeom& g, const SGMBuffers& b, const SgmLimits& lim, int paths,
+                       int n, hipStream_t stream, SgmParams p);
 bool sgm_cost16_needed(int cn, int ftz);
 void sgm_cost16_set(int on);
 

@@ -169,4 +169,16 @@ __device__ __forceinline__ SgmWin sgm_win_record(int bd, int mins, int s_p, int 
     return w;
 }
 
+// Host side, between launch_sgm (k_sgm.hip) and the units that own the kernels: one launcher per step kind of a plan.  Each
+// issues the planned pass and decides nothing.
+static constexpr int SWEEP_RING = 4;                      // rows of edge data kept per (strip, side) of a k_sgm_sweep launch
+inline int sgm_np2(int D) { return D <= 64 ? 1 : (D <= 128 ? 2 : 4); }   // u16 pairs per lane of the half-wave forms
+struct SgmCall { const SGMGeom& g; const SGMBuffers& b; int P1, P2, uniq, n; SgmWin* win; hipStream_t stream; };
+void launch_sgm_wide(const SgmPass& p, const SgmCall& c);
+void launch_path_h(const SgmPass& p, const SgmCall& c);
+void launch_vert(const SgmPass& p, const SgmCall& c);
+// false: the runtime refused (device, sweep stream or event record) before anything was launched
+bool launch_sweep(const SgmPass& p, const SgmCall& c);
+void launch_sgm_add_s2(const SgmCall& c);
+
 }  // namespace rtdm
