@@ -592,6 +592,78 @@ int rtdm_estimate_batch_device(rtdm_estimator* est, int n, const uint8_t* d_rgb_
                                rtdm_object* d_objects, int* d_counts, double* d_mean_cm, int* d_npix, int16_t* d_disp,
                                size_t disp_pitch, size_t disp_frame_stride, void* hip_stream);
 
+/* ---- object measurements: Z quantiles, 3-D position and extent per object (rules G1-G10) -------------
+ * What calc_depth gives an object is one number: the mean of Z over its kept pixels, at integer disparity.  These calls
+ * reduce the same pixels of the same device lists to a record per object, in camera coordinates (Q's unit; distance_cm =
+ * value * calibration_unit / 10):
+ *   npix, nplane   kept pixels; pixels of the clipped box that pass the plane predicate
+ *   zq[k]          k < nquant: the Z of rank ((npix - 1) * permille[k]) / 1000 (64-bit integer arithmetic) among the kept Z in
+ *                  ascending order -- 0 the minimum, 1000 the maximum, 500 the lower median; nothing is interpolated, the float
+ *                  comes back bit for bit; duplicated and unsorted permille values are fine.  k >= nquant: +0.0.
+ *   lo[j], hi[j]   minimum / maximum of X, Y, Z (j = 0, 1, 2) over the kept pixels.  Exact.
+ *   mean[j]        sum of the component, widened to double, / npix: the centre.  The order of the sum is a function of the
+ *                  clipped box alone (rule D3's) and no atomic takes part, so the bits are the same run to run and independent
+ *                  of n, of the frame's position, of capacity and of the other objects.
+ * The order of floats is that of the key (sign bit set -> ~bits, else bits | 0x80000000), so -0.0 lies below +0.0.
+ * The point (X, Y, Z) of a pixel is exactly rtdm_xyz_map's for Q, disparity_mode and handle_missing_values = 1 (the minimum
+ * is the frame's, over the whole frame, in the key of the mode).  A pixel is kept iff it passes the plane predicate -- mask
+ * byte != 0, or with planes_are_labels the int32 label == i + 1 for object i (compared, never used as an index) -- and
+ * fabs((double)Z - 10000.0) >= FLT_EPSILON and fabs((double)Z) <= max_z (NaN fails): calc_depth's test with max_z a parameter.
+ * There is NO matcher-marker clause: a pixel whose disparity is the matcher's invalid value is kept unless it is the frame's
+ * minimum (which it is in a map that has any) or fails the Z tests.  An object with nothing kept, an empty clipped box or a
+ * cls outside [0, nclasses) gets npix 0 and +0.0 in zq, lo, hi and mean; nplane is what was counted (0 without a box).
+ * rtdm_objects_measure_device: addressing as rtdm_depth_objects_device: object i of frame f writes d_measures[f * capacity + i],
+ *                        entries at or beyond min(total_f, capacity) are left untouched; no list or plane content makes the
+ *                        kernels read or write outside.  Enqueued on hip_stream: the call never synchronises, allocates or
+ *                        copies to the host; Q and params are read before it returns; no kernel waits for another workgroup
+ *                        and every grid is sized from n, capacity, height and nquant.  d_workspace: at least
+ *                        rtdm_objects_measure_workspace_bytes(n, capacity, height, nquant) bytes, the call's own until its
+ *                        work has finished (that function needs no device, is never 0 and does not shrink when an argument
+ *                        grows).  n = 0 is RTDM_OK.  Refusals, before any device use: those of rtdm_depth_objects_device in
+ *                        its order up to nclasses, with "mask" read as "plane" (and rtdm_depth_objects_labels_device's pitch,
+ *                        stride and alignment rules with planes_are_labels), then RTDM_ERR_NULL (params, d_measures),
+ *                        RTDM_ERR_BAD_PARAM (disparity_mode other than 0 / 1, max_z not finite or <= 0, nquant outside 0 .. 8,
+ *                        a permille outside 0 .. 1000), RTDM_ERR_BAD_SIZE (d_measures not 8-byte aligned, workspace_bytes too
+ *                        small), RTDM_ERR_UNSUPPORTED (width * height >= 2^31).
+ * rtdm_estimate_batch_measured / _device: rtdm_estimate_batch / _device, which ARE these calls with mp = measures = NULL (the
+ *                        same launches, the same bytes).  With both given, every chunk's objects are also measured against
+ *                        the chunk's maps -- over their labels when own pixels are on, under their class masks otherwise --
+ *                        and the records travel with mean_cm / npix: measures[f * capacity + i], downloaded in the host form,
+ *                        complete on the stream in the device form; frames without objects and entries past the stored ones
+ *                        are left untouched.  mean_cm / npix mean what they always meant.  The measurement's workspace is
+ *                        allocated by the first measured call.  Refusals on top: RTDM_ERR_NULL first (one of mp / measures
+ *                        NULL and the other not), and after all of rtdm_estimate_batch's RTDM_ERR_BAD_PARAM (params, as
+ *                        above) and RTDM_ERR_BAD_SIZE (measures not 8-byte aligned). */
+typedef struct rtdm_measure_params {
+    int disparity_mode;         /* RTDM_XYZ_FIXED16 (0) | RTDM_XYZ_ROUNDED (1) */
+    double max_z;               /* finite, > 0; 1e4 (calc_depth's literal) */
+    int nquant;                 /* 0 .. 8 */
+    int permille[8];            /* 0 .. 1000 each */
+} rtdm_measure_params;
+typedef struct rtdm_object_measure {           /* 88 bytes, 8-byte aligned */
+    int32_t npix, nplane; float zq[8]; float lo[3], hi[3]; double mean[3];
+} rtdm_object_measure;
+void rtdm_measure_default_params(rtdm_measure_params* p);   /* ROUNDED, 1e4, nquant 3: 500, 250, 750 */
+size_t rtdm_objects_measure_workspace_bytes(int n, int capacity, int height, int nquant);
+int rtdm_objects_measure_device(int device, const rtdm_measure_params* params, int n, const int16_t* d_disp, size_t disp_pitch,
+                                size_t disp_frame_stride, int width, int height, const double* Q, const void* d_planes,
+                                size_t plane_pitch, size_t plane_stride, int planes_are_labels, int nclasses,
+                                const struct rtdm_object* d_objects, int capacity, const int* d_counts,
+                                rtdm_object_measure* d_measures, void* d_workspace, size_t workspace_bytes, void* hip_stream);
+int rtdm_estimate_batch_measured(rtdm_estimator* est, int n, const uint8_t* rgb_left, size_t left_pitch, size_t left_frame_stride,
+                                 const uint8_t* rgb_right, size_t right_pitch, size_t right_frame_stride, const double* Q,
+                                 const rtdm_hsv_range* ranges, const int* range_class, int nranges, int nclasses, int min_area,
+                                 int zero_border, double calibration_unit, rtdm_object* objects, int* counts, double* mean_cm,
+                                 int* npix, int16_t* disp, size_t disp_pitch, size_t disp_frame_stride,
+                                 const rtdm_measure_params* mp, rtdm_object_measure* measures);
+int rtdm_estimate_batch_measured_device(rtdm_estimator* est, int n, const uint8_t* d_rgb_left, size_t left_pitch,
+                                        size_t left_frame_stride, const uint8_t* d_rgb_right, size_t right_pitch,
+                                        size_t right_frame_stride, const double* Q, const rtdm_hsv_range* ranges,
+                                        const int* range_class, int nranges, int nclasses, int min_area, int zero_border,
+                                        double calibration_unit, rtdm_object* d_objects, int* d_counts, double* d_mean_cm,
+                                        int* d_npix, int16_t* d_disp, size_t disp_pitch, size_t disp_frame_stride,
+                                        void* hip_stream, const rtdm_measure_params* mp, rtdm_object_measure* d_measures);
+
 /* ---- the step after the matcher that the reference keeps switched off: the disparity WLS post-filter -------------------
  * ENABLE_POST_FILTER (estimator.cpp:57-70, 106-109; include/estimator.h:32,116) -- cv::ximgproc's createRightMatcher,
  * createDisparityWLSFilter, setLambda(8000), setSigmaColor(1.5) and filter(left_disp, left_rect, filtered, right_disp).

@@ -15,8 +15,9 @@ The C++ adapter that actually plugs into the reference is rt-depth-map_amd/host/
 are thin shells over the same C ABI (include/rtdm.h).
 """
 from . import binding, synth  # noqa: F401
-from .chain import (HIPEstimator, depth_objects_device, depth_objects_labels_device, depth_objects_workspace_bytes,  # noqa: F401
-                    depth_stats_device, estimate_frame, estimate_frame_classes)
+from .chain import (MEASURE_DTYPE, HIPEstimator, MeasureParams, depth_objects_device, depth_objects_labels_device,  # noqa: F401
+                    depth_objects_workspace_bytes, depth_stats_device, distance_cm, estimate_frame, estimate_frame_classes,
+                    objects_measure_device, objects_measure_workspace_bytes)
 from .matcher import PREFILTER_NORMALIZED_RESPONSE, PREFILTER_XSOBEL, HIPMatcher, HIPSemiGlobalMatcher, create_right_matcher  # noqa: F401
 from .mjpeg import HIPMJPEGDecoder, mjpeg_probe  # noqa: F401
 from .morph import (MORPH_BLACKHAT, MORPH_CLOSE, MORPH_CROSS, MORPH_DILATE, MORPH_ELLIPSE, MORPH_ERODE, MORPH_GRADIENT,  # noqa: F401

@@ -108,6 +108,29 @@ def label_planes(d_labels, n, K, H, W):
     return d_labels.data_ptr(), st[2] * 4, st[1] * 4
 
 
+def measure_params(disparity_mode, max_z, permille):
+    """rtdm_measure_params from checked values (rule G10's RTDM_ERR_BAD_PARAM, said here with the offending value)"""
+    if disparity_mode not in (B.XYZ_FIXED16, B.XYZ_ROUNDED):
+        raise ValueError("disparity_mode must be XYZ_FIXED16 (0) or XYZ_ROUNDED (1); got %r" % (disparity_mode,))
+    max_z = float(max_z)
+    if not np.isfinite(max_z) or max_z <= 0:
+        raise ValueError("max_z must be finite and positive; got %r" % (max_z,))
+    permille = [int(p) for p in permille]
+    if len(permille) > 8 or any(p < 0 or p > 1000 for p in permille):
+        raise ValueError("permille: at most 8 values in 0 .. 1000; got %r" % (permille,))
+    return B.MeasureParams(int(disparity_mode), max_z, len(permille), (C.c_int * 8)(*permille))
+
+
+def measure_lists(d_measures, n, capacity):
+    """the device records: uint8 [n, capacity * 88], 8-byte aligned (view a host copy as MEASURE_DTYPE)"""
+    import torch
+    if d_measures.dtype != torch.uint8 or tuple(d_measures.shape) != (n, capacity * 88) or not d_measures.is_contiguous():
+        raise ValueError("d_measures must be a contiguous uint8 tensor n x capacity * 88; got %s %s" % (d_measures.dtype, tuple(d_measures.shape)))
+    if d_measures.data_ptr() % 8:
+        raise ValueError("d_measures must be 8-byte aligned")
+    return d_measures.data_ptr()
+
+
 def stats_lists(d_stats, n, capacity):
     """the device moments: uint8 [n, capacity * 48] (view a host copy as STATS_DTYPE)"""
     import torch

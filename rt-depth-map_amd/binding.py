@@ -39,6 +39,15 @@ class ObjectStats(C.Structure):         # rtdm_object_stats, 48 bytes
     _fields_ = [(n, C.c_int64) for n in ("m00", "m10", "m01", "m20", "m11", "m02")]
 
 
+class MeasureParams(C.Structure):       # rtdm_measure_params
+    _fields_ = [("disparity_mode", C.c_int), ("max_z", C.c_double), ("nquant", C.c_int), ("permille", C.c_int * 8)]
+
+
+class ObjectMeasure(C.Structure):       # rtdm_object_measure, 88 bytes
+    _fields_ = [("npix", C.c_int32), ("nplane", C.c_int32), ("zq", C.c_float * 8), ("lo", C.c_float * 3), ("hi", C.c_float * 3),
+                ("mean", C.c_double * 3)]
+
+
 MAX_HSV_RANGES, MAX_CLASSES = 16, 8      # RTDM_MAX_HSV_RANGES, RTDM_MAX_CLASSES
 MAX_REGIONS = 64                         # RTDM_MAX_REGIONS: objects of a frame that get a depth
 
@@ -199,6 +208,16 @@ SIGNATURES = {          # every entry point of include/rtdm.h: (restype, argtype
     "rtdm_estimate_batch_device": (C.c_int, [vp, C.c_int, u8p, sz, sz, u8p, sz, sz, C.POINTER(C.c_double), C.POINTER(HsvRange),
                                              C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, vp, vp, vp, vp, i16p,
                                              sz, sz, vp]),
+    "rtdm_measure_default_params": (None, [C.POINTER(MeasureParams)]),
+    "rtdm_objects_measure_workspace_bytes": (sz, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "rtdm_objects_measure_device": (C.c_int, [C.c_int, C.POINTER(MeasureParams), C.c_int, i16p, sz, sz, C.c_int, C.c_int,
+                                              C.POINTER(C.c_double), vp, sz, sz, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, sz, vp]),
+    "rtdm_estimate_batch_measured": (C.c_int, [vp, C.c_int, u8p, sz, sz, u8p, sz, sz, C.POINTER(C.c_double), C.POINTER(HsvRange),
+                                               C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, vp, vp, vp, vp, i16p,
+                                               sz, sz, C.POINTER(MeasureParams), vp]),
+    "rtdm_estimate_batch_measured_device": (C.c_int, [vp, C.c_int, u8p, sz, sz, u8p, sz, sz, C.POINTER(C.c_double), C.POINTER(HsvRange),
+                                                      C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, vp, vp, vp, vp,
+                                                      i16p, sz, sz, vp, C.POINTER(MeasureParams), vp]),
     "rtdm_wls_params_for_bm": (C.c_int, [C.POINTER(BMParams), C.POINTER(WLSParams)]),
     "rtdm_wls_params_for_sgm": (C.c_int, [C.POINTER(SGMParams), C.POINTER(WLSParams)]),
     "rtdm_bm_right_params": (C.c_int, [C.POINTER(BMParams), C.POINTER(BMParams)]),

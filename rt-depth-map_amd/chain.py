@@ -4,7 +4,8 @@ import ctypes as C
 import numpy as np
 
 from . import binding as B
-from ._marshal import Handle, device_plane, label_planes, mask_planes, object_lists, object_tuples, q16, regions_array, rgb_batch
+from ._marshal import (Handle, device_plane, label_planes, mask_planes, measure_lists, measure_params, object_lists, object_tuples, q16,
+                       regions_array, rgb_batch)
 from .objects import HSV_HIGH, HSV_LOW, OBJECT_DTYPE, _hsv_classes, _hsv_range
 
 
@@ -114,6 +115,54 @@ def _depth_objects(labels, d_disp, Q, d_masks, d_objects, d_counts, d_mean_cm, d
     return d_workspace
 
 
+MEASURE_DTYPE = np.dtype([("npix", "<i4"), ("nplane", "<i4"), ("zq", "<f4", (8,)), ("lo", "<f4", (3,)), ("hi", "<f4", (3,)),
+                          ("mean", "<f8", (3,))])                          # rtdm_object_measure, 88 bytes
+
+
+class MeasureParams:
+    """What rtdm_objects_measure_device measures (rules G3-G5): the disparity mode of the points (XYZ_ROUNDED, the reference's,
+    or XYZ_FIXED16, sub-pixel), calc_depth's Z limit, and up to eight quantiles of Z in permille (0 the minimum, 500 the lower
+    median, 1000 the maximum; nothing is interpolated).  The defaults are rtdm_measure_default_params'."""
+
+    def __init__(self, disparity_mode=B.XYZ_ROUNDED, max_z=1e4, permille=(500, 250, 750)):
+        self.c = measure_params(disparity_mode, max_z, permille)
+        self.disparity_mode, self.max_z, self.permille = self.c.disparity_mode, self.c.max_z, tuple(self.c.permille[:self.c.nquant])
+
+
+def distance_cm(values, calibration_unit=25.0):
+    """camera coordinates (zq, lo, hi, mean of a measurement) -> centimetres, as mean_cm: value * calibration_unit / 10"""
+    return np.asarray(values, np.float64) * calibration_unit / 10.0
+
+
+def objects_measure_workspace_bytes(n, capacity, height, nquant=8):
+    return int(B.lib().rtdm_objects_measure_workspace_bytes(int(n), int(capacity), int(height), int(nquant)))
+
+
+def objects_measure_device(d_disp, Q, d_planes, d_objects, d_counts, d_measures, params=None, labels=False, capacity=None,
+                           d_workspace=None, device=0, stream=None):
+    """Z quantiles, extent and centre of every object of n frames from the detector's device lists
+    (rtdm_objects_measure_device, rules G1-G10).  torch device tensors: d_disp, d_objects, d_counts as depth_objects_device
+    takes them; d_planes the class masks (uint8 [n, nclasses, H, W]) or, with labels=True, the detector's label planes (int32);
+    d_measures uint8 [n, capacity * 88], written for the stored objects only (view a host copy as MEASURE_DTYPE).  params: a
+    MeasureParams (None: the defaults).  d_workspace: a uint8 tensor of at least objects_measure_workspace_bytes(n, capacity,
+    H, nquant) bytes (None: one is allocated through torch and returned; keep it until the work has finished).  Enqueued on
+    `stream` (a raw hipStream_t value; None = the null stream), not synchronised.  -> the workspace tensor."""
+    import torch
+    params = params or MeasureParams()
+    dp, dpitch, dframe = device_plane(d_disp, "d_disp", torch.int16)
+    n, H, W = d_disp.shape
+    K = d_planes.shape[1] if d_planes.dim() == 4 else 0
+    pp, ppitch, pplane = (label_planes if labels else mask_planes)(d_planes, n, K, H, W)
+    capacity = object_lists(d_objects, d_counts, n, K, capacity)
+    mp = measure_lists(d_measures, n, capacity)
+    if d_workspace is None:
+        d_workspace = torch.empty(objects_measure_workspace_bytes(n, capacity, H, params.c.nquant), dtype=torch.uint8, device=d_disp.device)
+    B.check(B.lib().rtdm_objects_measure_device(device, C.byref(params.c), n, dp, dpitch, dframe, W, H, q16(Q), pp, ppitch, pplane,
+                                                int(bool(labels)), K, d_objects.data_ptr(), capacity, d_counts.data_ptr(), mp,
+                                                d_workspace.data_ptr(), d_workspace.numel(), stream), "rtdm_objects_measure_device")
+    return d_workspace
+
+
 class HIPEstimator(Handle):
     """The loop body of Estimator::run (estimator.cpp:29-77) on frame batches: rtdm_estimate_batch.  Borrows a HIPMatcher, a
     HIPRectifier and a HIPObjectDetector (keep them alive; close this first); a chunk is min(max_batch, the matcher's, the
@@ -141,11 +190,13 @@ class HIPEstimator(Handle):
         B.check(B.lib().rtdm_estimator_set_own_pixels(self._h, int(bool(on))), "rtdm_estimator_set_own_pixels")
 
     def estimate(self, rgb_left, rgb_right, Q, ranges, classes=None, min_area=100, zero_border=True, calibration_unit=25.0,
-                 want_disp=False, disp=None):
+                 want_disp=False, disp=None, measure=None):
         """rgb_left / rgb_right: n x H x W x 3 uint8 (R first; row pitch and frame stride free) -> (objects, counts, mean_cm,
-        npix[, disp]): per frame the list of (x, y, w, h, cls) -- at most `capacity` --, counts n x nclasses (not clipped), and
-        per frame the arrays of its stored objects' mean depth [cm] and pixel count.  disp: n x crop H x crop W int16; frames
-        without objects keep what it held (zeros when it is allocated here)."""
+        npix[, disp][, measures]): per frame the list of (x, y, w, h, cls) -- at most `capacity` --, counts n x nclasses (not
+        clipped), and per frame the arrays of its stored objects' mean depth [cm] and pixel count.  disp: n x crop H x crop W
+        int16; frames without objects keep what it held (zeros when it is allocated here).  measure: a MeasureParams -- the
+        stored objects are also measured (rtdm_estimate_batch_measured) and the result ends with one more item, per frame the
+        MEASURE_DTYPE records of its stored objects."""
         rc = self.rectifier
         rgb_left, rgb_right = (rgb_batch(np.asarray(a), rc.height, rc.width, "frames") for a in (rgb_left, rgb_right))
         if rgb_right.shape[0] != rgb_left.shape[0]:
@@ -159,24 +210,34 @@ class HIPEstimator(Handle):
             disp = np.zeros((n, rh, rw), np.int16)
         if disp is not None and (disp.dtype != np.int16 or disp.shape != (n, rh, rw) or not disp.flags.c_contiguous):
             raise ValueError("disp must be a contiguous int16 array %s" % ((n, rh, rw),))
-        B.check(B.lib().rtdm_estimate_batch(self._h, n, rgb_left.ctypes.data, rgb_left.strides[1], rgb_left.strides[0],
-                                            rgb_right.ctypes.data, rgb_right.strides[1], rgb_right.strides[0],
-                                            q16(Q), rng, cls, nr, K, int(min_area), int(zero_border),
-                                            calibration_unit, objs.ctypes.data, counts.ctypes.data, mean.ctypes.data, npix.ctypes.data,
-                                            disp.ctypes.data if disp is not None else None, rw * 2, rw * rh * 2), "rtdm_estimate_batch")
-        out, means, pixels = [], [], []
+        args = (self._h, n, rgb_left.ctypes.data, rgb_left.strides[1], rgb_left.strides[0],
+                rgb_right.ctypes.data, rgb_right.strides[1], rgb_right.strides[0],
+                q16(Q), rng, cls, nr, K, int(min_area), int(zero_border),
+                calibration_unit, objs.ctypes.data, counts.ctypes.data, mean.ctypes.data, npix.ctypes.data,
+                disp.ctypes.data if disp is not None else None, rw * 2, rw * rh * 2)
+        if measure is None:
+            B.check(B.lib().rtdm_estimate_batch(*args), "rtdm_estimate_batch")
+        else:
+            meas = np.zeros((n, cap), MEASURE_DTYPE)
+            B.check(B.lib().rtdm_estimate_batch_measured(*(args + (C.byref(measure.c), meas.ctypes.data))), "rtdm_estimate_batch_measured")
+        out, means, pixels, records = [], [], [], []
         for f in range(n):
             k = min(int(counts[f].sum()), cap)
             out.append(object_tuples(objs[f, :k]))
             means.append(mean[f, :k].copy()); pixels.append(npix[f, :k].copy())
-        return (out, counts, means, pixels, disp) if disp is not None else (out, counts, means, pixels)
+            if measure is not None:
+                records.append(meas[f, :k].copy())
+        res = (out, counts, means, pixels) + ((disp,) if disp is not None else ())
+        return res + (records,) if measure is not None else res
 
     def estimate_device(self, d_rgb_left, d_rgb_right, Q, ranges, classes, d_objects, d_counts, d_mean_cm, d_npix, d_disp=None,
-                        min_area=100, zero_border=True, calibration_unit=25.0, stream=None):
+                        min_area=100, zero_border=True, calibration_unit=25.0, stream=None, d_measures=None, measure=None):
         """torch device tensors: uint8 [n,H,W,3] frames (row pitch and frame stride free); d_objects uint8 [n, capacity * 32],
         d_counts int32 [n, nclasses], d_mean_cm float64 [n, capacity], d_npix int32 [n, capacity], optional d_disp int16
         [n, crop H, crop W] (row pitch and frame stride free).  Enqueued on `stream` (a raw hipStream_t value; None = the null
-        stream), which is synchronised once per chunk; the results are complete on the stream, not synchronised."""
+        stream), which is synchronised once per chunk; the results are complete on the stream, not synchronised.  d_measures:
+        uint8 [n, capacity * 88] -- the stored objects are also measured (rtdm_estimate_batch_measured_device) with `measure`, a
+        MeasureParams (None: the defaults); view a host copy as MEASURE_DTYPE."""
         import torch
         rc, cap = self.rectifier, self.capacity
         rng, cls, nr, K = _hsv_classes(ranges, classes)
@@ -194,7 +255,14 @@ class HIPEstimator(Handle):
         if d_disp is not None:
             dp, dpitch, dframe = device_plane(d_disp, "d_disp", torch.int16, (n, rc.roi[3], rc.roi[2]))
         (lp, lpitch, lframe), (rp, rpitch, rframe) = ptr
-        B.check(B.lib().rtdm_estimate_batch_device(self._h, n, lp, lpitch, lframe, rp, rpitch, rframe, q16(Q),
-                                                   rng, cls, nr, K, int(min_area), int(zero_border), calibration_unit,
-                                                   d_objects.data_ptr(), d_counts.data_ptr(), d_mean_cm.data_ptr(), d_npix.data_ptr(),
-                                                   dp, dpitch, dframe, stream), "rtdm_estimate_batch_device")
+        args = (self._h, n, lp, lpitch, lframe, rp, rpitch, rframe, q16(Q), rng, cls, nr, K, int(min_area), int(zero_border),
+                calibration_unit, d_objects.data_ptr(), d_counts.data_ptr(), d_mean_cm.data_ptr(), d_npix.data_ptr(), dp, dpitch, dframe,
+                stream)
+        if d_measures is None:
+            if measure is not None:
+                raise ValueError("measure needs d_measures")
+            B.check(B.lib().rtdm_estimate_batch_device(*args), "rtdm_estimate_batch_device")
+        else:
+            measure = measure or MeasureParams()
+            B.check(B.lib().rtdm_estimate_batch_measured_device(*(args + (C.byref(measure.c), measure_lists(d_measures, n, cap)))),
+                    "rtdm_estimate_batch_measured_device")

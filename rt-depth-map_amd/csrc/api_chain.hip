@@ -183,6 +183,9 @@ void rtdm_estimator_destroy(rtdm_estimator* E)
     (void)hipDeviceSynchronize();                       // its buffers may be in use on any stream; the borrowed handles are not touched
     E->mem.release();
     if (E->dLabels) (void)hipFree(E->dLabels);
+    if (E->dMeasWork) (void)hipFree(E->dMeasWork);
+    if (E->dMeas) (void)hipFree(E->dMeas);
+    if (E->hMeas) (void)hipHostFree(E->hMeas);
     delete E;
 }
 
@@ -249,6 +252,7 @@ struct EstIo {
     const uint8_t* rgb[2]; size_t pitch[2], stride[2];
     rtdm_object* objects; int* counts; double* mean; int* npix;
     int16_t* disp; size_t disp_pitch, disp_stride;
+    const rtdm_measure_params* mp; rtdm_object_measure* measures;       // both or neither (rtdm_estimate_batch_measured)
 };
 
 // the refusals of both forms, in the order include/rtdm.h gives
@@ -256,6 +260,7 @@ static int est_check(const rtdm_estimator* E, int n, const EstIo& io, const doub
                      const int* range_class, int nranges, int nclasses, HsvClasses* C)
 {
     if (!io.rgb[0] || !io.rgb[1] || !Q || !io.objects || !io.counts || !io.mean || !io.npix) return RTDM_ERR_NULL;
+    if ((io.mp != nullptr) != (io.measures != nullptr)) return RTDM_ERR_NULL;
     int st = objects_classes_check(ranges, range_class, nranges, nclasses, C);
     if (st) return st;
     if (n < 0) return RTDM_ERR_BAD_SIZE;
@@ -268,7 +273,25 @@ static int est_check(const rtdm_estimator* E, int n, const EstIo& io, const doub
     if (n > 1 && (io.stride[0] < io.pitch[0] * rc->H || io.stride[1] < io.pitch[1] * rc->H ||
                   (io.disp && io.disp_stride < io.disp_pitch * rc->rh)))
         return RTDM_ERR_BAD_SIZE;
-    return bm_check_frame(E->bm, rc->rw, rc->rh);
+    st = bm_check_frame(E->bm, rc->rw, rc->rh);
+    if (st || !io.mp) return st;
+    st = measure_params_check(io.mp);
+    if (st) return st;
+    return (size_t)io.measures % 8 ? RTDM_ERR_BAD_SIZE : RTDM_OK;
+}
+
+// the first measured call makes the measurement's workspace for a chunk, the first measured host call the records' staging
+static int est_measure_stage(rtdm_estimator* E, bool host_form)
+{
+    const size_t slots = (size_t)E->chunk * E->cap;
+    if (!E->dMeasWork) {
+        const size_t bytes = measure_bytes(E->chunk, E->cap, E->rc->rh, 8);
+        HIPC(hipMalloc(&E->dMeasWork, bytes));
+        E->measWorkBytes = bytes;
+    }
+    if (host_form && !E->dMeas) HIPC(hipMalloc((void**)&E->dMeas, slots * sizeof(MeasRecord)));
+    if (host_form && !E->hMeas) HIPC(hipHostMalloc((void**)&E->hMeas, slots * sizeof(MeasRecord)));
+    return RTDM_OK;
 }
 
 // Gray pair and left colour crop of m frames.  k_rectify reads whole dwords up to RectifySrc::frame bytes from a frame's start:
@@ -298,6 +321,12 @@ static int est_run(rtdm_estimator* E, int n, const EstIo& io, const double* Q, c
     const size_t row = (size_t)rc->W * 3, fbytes = row * rc->H, gframe = rc->gpitch * H, cframe = E->cpitch * H;
     const Plane16W O = bm_internal_plane(bm, W, H);
     DepthQ q; std::copy(Q, Q + 16, q.q);
+    XyzParams mP; MeasQuant mQ;
+    if (io.mp) {
+        const int st = est_measure_stage(E, !io.device);
+        if (st) return st;
+        measure_params_kernel(io.mp, Q, &mP, &mQ);
+    }
     for (int i0 = 0; i0 < n; i0 += E->chunk) {
         const int m = std::min(E->chunk, n - i0);
         // 1. the chunk's frames -> gray pairs and colour crops
@@ -355,6 +384,8 @@ static int est_run(rtdm_estimator* E, int n, const EstIo& io, const double* Q, c
         const DepthObjects a{bm->dOut, O.pitch_e, O.frame_e, E->dLabels ? (const uint8_t*)E->dLabels : ob->dMaskOut,
                              E->dLabels ? lpitch : ob->mpitch, E->dLabels ? lplane : ob->mpitch * H, dObj, dCounts, m, W, H, K, cap, 0};
         launch_depth_objects(a, q, unit, E->dWork, dMean, dNpix, s, E->dLabels != nullptr);
+        MeasRecord* dMeas = io.mp ? (io.device ? (MeasRecord*)io.measures + (size_t)i0 * cap : E->dMeas) : nullptr;
+        if (io.mp) launch_measure(a, mP, mQ, E->dMeasWork, dMeas, s, E->dLabels != nullptr);     // ... and measured (G1-G10)
         HIPC(hipGetLastError());
         // 6. the results; frames without objects keep what the caller's arrays held
         for (int j = 0; io.disp && j < m; ++j) {
@@ -369,6 +400,7 @@ static int est_run(rtdm_estimator* E, int n, const EstIo& io, const double* Q, c
         HIPC(hipMemcpyAsync(E->hObj, dObj, slots * sizeof(CcObject), hipMemcpyDeviceToHost, s));
         HIPC(hipMemcpyAsync(E->hMean, dMean, slots * sizeof(double), hipMemcpyDeviceToHost, s));
         HIPC(hipMemcpyAsync(E->hNpix, dNpix, slots * sizeof(int), hipMemcpyDeviceToHost, s));
+        if (io.mp) HIPC(hipMemcpyAsync(E->hMeas, dMeas, slots * sizeof(MeasRecord), hipMemcpyDeviceToHost, s));
         HIPC(hipStreamSynchronize(s));
         for (int j = 0; j < m; ++j) {
             const size_t stored = (size_t)std::min<long>(total[j], cap), at = (size_t)(i0 + j) * cap, from = (size_t)j * cap;
@@ -376,6 +408,7 @@ static int est_run(rtdm_estimator* E, int n, const EstIo& io, const double* Q, c
             memcpy(io.objects + at, E->hObj + from, stored * sizeof(rtdm_object));
             std::copy(E->hMean + from, E->hMean + from + stored, io.mean + at);
             std::copy(E->hNpix + from, E->hNpix + from + stored, io.npix + at);
+            if (io.mp) memcpy(io.measures + at, E->hMeas + from, stored * sizeof(rtdm_object_measure));
             for (int y = 0; io.disp && y < H; ++y)
                 memcpy((uint8_t*)io.disp + (size_t)(i0 + j) * io.disp_stride + (size_t)y * io.disp_pitch, E->hDisp + ((size_t)j * H + y) * W, (size_t)W * 2);
         }
@@ -383,14 +416,15 @@ static int est_run(rtdm_estimator* E, int n, const EstIo& io, const double* Q, c
     return RTDM_OK;
 }
 
-int rtdm_estimate_batch(rtdm_estimator* E, int n, const uint8_t* rgb_left, size_t left_pitch, size_t left_frame_stride,
-                        const uint8_t* rgb_right, size_t right_pitch, size_t right_frame_stride, const double* Q,
-                        const rtdm_hsv_range* ranges, const int* range_class, int nranges, int nclasses, int min_area,
-                        int zero_border, double calibration_unit, rtdm_object* objects, int* counts, double* mean_cm, int* npix,
-                        int16_t* disp, size_t disp_pitch, size_t disp_frame_stride)
+int rtdm_estimate_batch_measured(rtdm_estimator* E, int n, const uint8_t* rgb_left, size_t left_pitch, size_t left_frame_stride,
+                                 const uint8_t* rgb_right, size_t right_pitch, size_t right_frame_stride, const double* Q,
+                                 const rtdm_hsv_range* ranges, const int* range_class, int nranges, int nclasses, int min_area,
+                                 int zero_border, double calibration_unit, rtdm_object* objects, int* counts, double* mean_cm,
+                                 int* npix, int16_t* disp, size_t disp_pitch, size_t disp_frame_stride,
+                                 const rtdm_measure_params* mp, rtdm_object_measure* measures)
 {
     const EstIo io{false, {rgb_left, rgb_right}, {left_pitch, right_pitch}, {left_frame_stride, right_frame_stride}, objects, counts,
-                   mean_cm, npix, disp, disp_pitch, disp_frame_stride};
+                   mean_cm, npix, disp, disp_pitch, disp_frame_stride, mp, measures};
     HsvClasses C;
     const int st = est_check(E, n, io, Q, ranges, range_class, nranges, nclasses, &C);
     if (st || n == 0) return st;
@@ -401,6 +435,34 @@ int rtdm_estimate_batch(rtdm_estimator* E, int n, const uint8_t* rgb_left, size_
     return rc;
 }
 
+int rtdm_estimate_batch(rtdm_estimator* E, int n, const uint8_t* rgb_left, size_t left_pitch, size_t left_frame_stride,
+                        const uint8_t* rgb_right, size_t right_pitch, size_t right_frame_stride, const double* Q,
+                        const rtdm_hsv_range* ranges, const int* range_class, int nranges, int nclasses, int min_area,
+                        int zero_border, double calibration_unit, rtdm_object* objects, int* counts, double* mean_cm, int* npix,
+                        int16_t* disp, size_t disp_pitch, size_t disp_frame_stride)
+{
+    return rtdm_estimate_batch_measured(E, n, rgb_left, left_pitch, left_frame_stride, rgb_right, right_pitch, right_frame_stride, Q, ranges,
+                                        range_class, nranges, nclasses, min_area, zero_border, calibration_unit, objects, counts, mean_cm,
+                                        npix, disp, disp_pitch, disp_frame_stride, nullptr, nullptr);
+}
+
+int rtdm_estimate_batch_measured_device(rtdm_estimator* E, int n, const uint8_t* d_rgb_left, size_t left_pitch,
+                                        size_t left_frame_stride, const uint8_t* d_rgb_right, size_t right_pitch,
+                                        size_t right_frame_stride, const double* Q, const rtdm_hsv_range* ranges,
+                                        const int* range_class, int nranges, int nclasses, int min_area, int zero_border,
+                                        double calibration_unit, rtdm_object* d_objects, int* d_counts, double* d_mean_cm,
+                                        int* d_npix, int16_t* d_disp, size_t disp_pitch, size_t disp_frame_stride,
+                                        void* hip_stream, const rtdm_measure_params* mp, rtdm_object_measure* d_measures)
+{
+    const EstIo io{true, {d_rgb_left, d_rgb_right}, {left_pitch, right_pitch}, {left_frame_stride, right_frame_stride}, d_objects, d_counts,
+                   d_mean_cm, d_npix, d_disp, disp_pitch, disp_frame_stride, mp, d_measures};
+    HsvClasses C;
+    const int st = est_check(E, n, io, Q, ranges, range_class, nranges, nclasses, &C);
+    if (st || n == 0) return st;
+    HIPC(hipSetDevice(E->device));
+    return est_run(E, n, io, Q, C, min_area, zero_border, calibration_unit, (hipStream_t)hip_stream);
+}
+
 int rtdm_estimate_batch_device(rtdm_estimator* E, int n, const uint8_t* d_rgb_left, size_t left_pitch,
                                size_t left_frame_stride, const uint8_t* d_rgb_right, size_t right_pitch,
                                size_t right_frame_stride, const double* Q, const rtdm_hsv_range* ranges, const int* range_class,
@@ -408,13 +470,10 @@ int rtdm_estimate_batch_device(rtdm_estimator* E, int n, const uint8_t* d_rgb_le
                                rtdm_object* d_objects, int* d_counts, double* d_mean_cm, int* d_npix, int16_t* d_disp,
                                size_t disp_pitch, size_t disp_frame_stride, void* hip_stream)
 {
-    const EstIo io{true, {d_rgb_left, d_rgb_right}, {left_pitch, right_pitch}, {left_frame_stride, right_frame_stride}, d_objects, d_counts,
-                   d_mean_cm, d_npix, d_disp, disp_pitch, disp_frame_stride};
-    HsvClasses C;
-    const int st = est_check(E, n, io, Q, ranges, range_class, nranges, nclasses, &C);
-    if (st || n == 0) return st;
-    HIPC(hipSetDevice(E->device));
-    return est_run(E, n, io, Q, C, min_area, zero_border, calibration_unit, (hipStream_t)hip_stream);
+    return rtdm_estimate_batch_measured_device(E, n, d_rgb_left, left_pitch, left_frame_stride, d_rgb_right, right_pitch, right_frame_stride,
+                                               Q, ranges, range_class, nranges, nclasses, min_area, zero_border, calibration_unit, d_objects,
+                                               d_counts, d_mean_cm, d_npix, d_disp, disp_pitch, disp_frame_stride, hip_stream, nullptr,
+                                               nullptr);
 }
 
 int rtdm_bm_compute_filtered(rtdm_bm* left_bm, rtdm_bm* right_bm, rtdm_wls* wls, const uint8_t* left, size_t left_pitch,

@@ -96,20 +96,31 @@ int rtdm_depth_stats_device(int device, const int16_t* d_disp, size_t disp_pitch
 // ---- ... for frame batches, from the detector's device lists (rules D1-D6) --------------------------------------------------
 size_t rtdm_depth_objects_workspace_bytes(int n, int capacity, int height) { return depth_objects_bytes(n, capacity, height); }
 
-// both forms: the planes are mask bytes (elem 1) or the detector's int32 labels (elem 4: rule L5, and L8 for the pitches)
-static int depth_objects_call(int device, int n, const int16_t* d_disp, size_t disp_pitch, size_t disp_frame_stride, int width,
-                              int height, const double* Q, const void* d_planes, size_t plane_pitch, size_t plane_stride, size_t elem,
-                              int nclasses, const rtdm_object* d_objects, int capacity, const int* d_counts, double calibration_unit,
-                              double* d_mean_cm, int* d_npix, void* d_workspace, size_t workspace_bytes, void* hip_stream)
+// D6 up to the class count, for both forms of the planes: mask bytes (elem 1) or the detector's int32 labels (elem 4: rule L5,
+// and L8 for the pitches).  outputs: the call's result pointers are all there.
+int rtdm::depth_objects_check(int n, const void* d_disp, size_t disp_pitch, size_t disp_frame_stride, int width, int height,
+                              const double* Q, const void* d_planes, size_t plane_pitch, size_t plane_stride, size_t elem, int nclasses,
+                              const void* d_objects, int capacity, const void* d_counts, bool outputs, const void* d_workspace)
 {
-    // D6, before any device use
-    if (!d_disp || !Q || !d_planes || !d_counts || !d_mean_cm || !d_npix || !d_workspace || (capacity > 0 && !d_objects)) return RTDM_ERR_NULL;
+    if (!d_disp || !Q || !d_planes || !d_counts || !outputs || !d_workspace || (capacity > 0 && !d_objects)) return RTDM_ERR_NULL;
     if (n < 0 || capacity < 0 || width <= 0 || height <= 0) return RTDM_ERR_BAD_SIZE;
     if ((disp_pitch & 1) || (disp_frame_stride & 1) || disp_pitch < (size_t)width * 2 || plane_pitch < (size_t)width * elem) return RTDM_ERR_BAD_SIZE;
     if (plane_pitch % elem || plane_stride % elem || (size_t)d_planes % elem) return RTDM_ERR_BAD_SIZE;
     if (n > 1 && disp_frame_stride < disp_pitch * height) return RTDM_ERR_BAD_SIZE;
     if (n > 0 && (long)n * nclasses > 1 && plane_stride < plane_pitch * height) return RTDM_ERR_BAD_SIZE;
     if (nclasses < 1 || nclasses > RTDM_MAX_CLASSES) return RTDM_ERR_BAD_PARAM;
+    return RTDM_OK;
+}
+
+static int depth_objects_call(int device, int n, const int16_t* d_disp, size_t disp_pitch, size_t disp_frame_stride, int width,
+                              int height, const double* Q, const void* d_planes, size_t plane_pitch, size_t plane_stride, size_t elem,
+                              int nclasses, const rtdm_object* d_objects, int capacity, const int* d_counts, double calibration_unit,
+                              double* d_mean_cm, int* d_npix, void* d_workspace, size_t workspace_bytes, void* hip_stream)
+{
+    // D6, before any device use
+    const int st = depth_objects_check(n, d_disp, disp_pitch, disp_frame_stride, width, height, Q, d_planes, plane_pitch, plane_stride, elem,
+                                       nclasses, d_objects, capacity, d_counts, d_mean_cm && d_npix, d_workspace);
+    if (st) return st;
     if (workspace_bytes < depth_objects_bytes(n, capacity, height)) return RTDM_ERR_BAD_SIZE;      // D5
     if (n == 0) return RTDM_OK;
     const int rc = use_device(device);

@@ -145,6 +145,10 @@ struct rtdm_estimator {
     int* dRois;                    // [chunk] x 4
     void* dWork; size_t workBytes; // rtdm_depth_objects_device's workspace for a chunk
     int32_t* dLabels;              // rtdm_estimator_set_own_pixels: [chunk] x [detector's max_classes] planes of rh x rw ints, or null
+    // rtdm_estimate_batch_measured: made by the first measured call -- the measurement's workspace for a chunk, and for the
+    // host form the chunk's records on the device and page-locked
+    void* dMeasWork; size_t measWorkBytes;
+    rtdm::MeasRecord *dMeas, *hMeas;
     // page-locked: the read-back in front of the matcher, then what the host form brings back and takes in
     int *hCounts, *hRois, *hNpix; rtdm::CcObject* hObj; double* hMean; int16_t* hDisp; uint8_t* hRgb[2];
     rtdm::AllocList mem;
@@ -162,6 +166,13 @@ void bm_scatter_disp(const rtdm_bm* bm, int W, int H, int16_t* disp, size_t disp
 inline size_t bm_ws(int W) { return (size_t)((W + 7) & ~7); }
 inline Plane16W bm_internal_plane(const rtdm_bm* bm, int W, int H) { return Plane16W{bm->dOut, bm_ws(W), bm_ws(W) * (size_t)H}; }
 int depth_check_regions(const rtdm_region* regions, int n, int W, int H, int* flat, int* maxh);   // (api_core.hip)
+// api_core.hip: rule D6 up to the class count (elem: bytes of a plane element, 1 or 4; outputs: all result pointers are there)
+int depth_objects_check(int n, const void* d_disp, size_t disp_pitch, size_t disp_frame_stride, int width, int height, const double* Q,
+                        const void* d_planes, size_t plane_pitch, size_t plane_stride, size_t elem, int nclasses, const void* d_objects,
+                        int capacity, const void* d_counts, bool outputs, const void* d_workspace);
+// api_measure.hip: rule G10's RTDM_ERR_BAD_PARAM (p non-null); the kernels' form of Q and the params
+int measure_params_check(const rtdm_measure_params* p);
+void measure_params_kernel(const rtdm_measure_params* p, const double* Q, XyzParams* P, MeasQuant* mq);
 // the other handles' files, by prefix
 // api_morph.hip.  morph_setting_check: the refusals of rtdm_morph_set_op, no device needed.  morph_run: THE routing of the
 // morphological filter -- the default setting with rtdm_debug_morph_general off runs launch_morph_open_close, everything

@@ -403,10 +403,23 @@ struct XyzCloudIn {
 };
 struct XyzRec { float x, y, z; uint32_t rgba; };                             // rtdm_point: r in the lowest byte
 int xyz_tiles(int W, int H);
+// X4: minkey[f] = the smallest key (xyz_key of `mode`) of frame f, f < n <= 65535
+void launch_xyz_min(XyzDisp D, int n, int W, int H, int mode, int* minkey, hipStream_t stream);
 void launch_xyz_map(XyzDisp D, int n, int W, int H, const XyzParams& P, int* minkey, XyzMap O, hipStream_t stream);
 // counts: n ints (device), the kept pixels of every frame; records at or beyond `capacity` are not written
 void launch_xyz_cloud(const XyzCloudIn& I, int n, int W, int H, const XyzParams& P, int* minkey, int* tile_cnt, XyzRec* points,
                       size_t points_frame_b, int capacity, int* counts, hipStream_t stream);
+
+// Per-object measurements (k_measure.hip, rules G1-G10 in DESIGN.md section 4.18): Z quantiles, extent and centre of every
+// stored object of the detector's device lists.  `a` as for launch_depth_objects (a.mask: mask bytes, or with `labels` the
+// int32 label planes); P: Q, max_z and mode are used, X4 is always on.  out: n * cap records, written for the stored objects
+// only.  One memset and the launches of launch_xyz_min, k_meas_bands, k_meas_final and -- with quantiles -- k_meas_select on
+// `stream`, nothing else: no allocation, no synchronisation, no copy, and every grid is sized from n, cap, H and nquant.
+struct MeasRecord { int32_t npix, nplane; float zq[8]; float lo[3], hi[3]; double mean[3]; };   // rtdm_object_measure
+struct MeasQuant { int nquant; int permille[8]; };
+size_t measure_bytes(int n, int cap, int H, int nquant);
+void launch_measure(DepthObjects a, const XyzParams& P, const MeasQuant& mq, void* workspace, MeasRecord* out, hipStream_t stream,
+                    bool labels);
 
 // Baseline MJPEG frames (k_mjpeg.hip, rules J1-J5 in DESIGN.md section 4.12): m frames of one geometry and sampling (`shape`:
 // any of their descriptors), descriptors, segment table and stream bytes on the device.  d_coef: m * blocks * 64 int16,

@@ -109,11 +109,7 @@ HIPObjectsCore::HIPObjectsCore(int cols, int rows, int device, int maxBatch, int
     if (status_ != RTDM_OK) std::fprintf(stderr, "HIPObjects: %s\n", rtdm_strerror(status_));
 }
 HIPObjectsCore::~HIPObjectsCore() { rtdm_estimator_destroy(est_); rtdm_objects_destroy(ob_); }
-int HIPObjectsCore::estimateBatch(HIPMatcherCore& matcher, HIPRectifierCore& rectifier, int maxBatch, int capacity, int n,
-                                  const uint8_t* rgbLeft, size_t leftStep, size_t leftFrameStride, const uint8_t* rgbRight,
-                                  size_t rightStep, size_t rightFrameStride, const double* Q, int minObjSize, bool zeroBorder,
-                                  double calibrationUnit, rtdm_object* objects, int* counts, double* meanCm, int* npix, int16_t* disp,
-                                  size_t dispStep, size_t dispFrameStride)
+int HIPObjectsCore::estimator(HIPMatcherCore& matcher, HIPRectifierCore& rectifier, int maxBatch, int capacity)
 {
     if (!ob_ || !matcher.handle() || !rectifier.handle()) return status_ != RTDM_OK ? status_ : RTDM_ERR_NO_DEVICE;
     if (!est_ || estBm_ != matcher.handle() || estRc_ != rectifier.handle() || estBatch_ != maxBatch || estCap_ != capacity) {
@@ -123,11 +119,32 @@ int HIPObjectsCore::estimateBatch(HIPMatcherCore& matcher, HIPRectifierCore& rec
         if (status_ != RTDM_OK) return status_;
         estBm_ = matcher.handle(); estRc_ = rectifier.handle(); estBatch_ = maxBatch; estCap_ = capacity;
     }
-    status_ = rtdm_estimator_set_own_pixels(est_, ownPixels_ ? 1 : 0);          // (nothing happens unless the setting changed)
-    if (status_ != RTDM_OK) return status_;
+    return status_ = rtdm_estimator_set_own_pixels(est_, ownPixels_ ? 1 : 0);   // (nothing happens unless the setting changed)
+}
+int HIPObjectsCore::estimateBatch(HIPMatcherCore& matcher, HIPRectifierCore& rectifier, int maxBatch, int capacity, int n,
+                                  const uint8_t* rgbLeft, size_t leftStep, size_t leftFrameStride, const uint8_t* rgbRight,
+                                  size_t rightStep, size_t rightFrameStride, const double* Q, int minObjSize, bool zeroBorder,
+                                  double calibrationUnit, rtdm_object* objects, int* counts, double* meanCm, int* npix, int16_t* disp,
+                                  size_t dispStep, size_t dispFrameStride)
+{
+    const int st = estimator(matcher, rectifier, maxBatch, capacity);
+    if (st != RTDM_OK) return st;
     return status_ = rtdm_estimate_batch(est_, n, rgbLeft, leftStep, leftFrameStride, rgbRight, rightStep, rightFrameStride, Q, ranges_,
                                          cls_, nranges_, nclasses_, minObjSize, zeroBorder ? 1 : 0, calibrationUnit, objects, counts,
                                          meanCm, npix, disp, dispStep, dispFrameStride);
+}
+int HIPObjectsCore::estimateBatchMeasured(HIPMatcherCore& matcher, HIPRectifierCore& rectifier, int maxBatch, int capacity, int n,
+                                          const uint8_t* rgbLeft, size_t leftStep, size_t leftFrameStride, const uint8_t* rgbRight,
+                                          size_t rightStep, size_t rightFrameStride, const double* Q, int minObjSize, bool zeroBorder,
+                                          double calibrationUnit, rtdm_object* objects, int* counts, double* meanCm, int* npix,
+                                          const rtdm_measure_params& params, rtdm_object_measure* measures, int16_t* disp,
+                                          size_t dispStep, size_t dispFrameStride)
+{
+    const int st = estimator(matcher, rectifier, maxBatch, capacity);
+    if (st != RTDM_OK) return st;
+    return status_ = rtdm_estimate_batch_measured(est_, n, rgbLeft, leftStep, leftFrameStride, rgbRight, rightStep, rightFrameStride, Q,
+                                                  ranges_, cls_, nranges_, nclasses_, minObjSize, zeroBorder ? 1 : 0, calibrationUnit,
+                                                  objects, counts, meanCm, npix, disp, dispStep, dispFrameStride, &params, measures);
 }
 int HIPObjectsCore::setRanges(const rtdm_hsv_range* ranges, const int* cls, int nranges, int nclasses)
 {

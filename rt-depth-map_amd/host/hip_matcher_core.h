@@ -281,9 +281,18 @@ public:
                       size_t rightFrameStride, const double* Q, int minObjSize, bool zeroBorder, double calibrationUnit,
                       rtdm_object* objects, int* counts, double* meanCm, int* npix, int16_t* disp = nullptr, size_t dispStep = 0,
                       size_t dispFrameStride = 0);
+    // estimateBatch that also measures every stored object (rtdm_estimate_batch_measured, rules G1-G10): Z quantiles, extent and
+    // centre in camera coordinates at measures[f * capacity + i]; over the object's own pixels when setOwnPixels is on.
+    int estimateBatchMeasured(HIPMatcherCore& matcher, HIPRectifierCore& rectifier, int maxBatch, int capacity, int n,
+                              const uint8_t* rgbLeft, size_t leftStep, size_t leftFrameStride, const uint8_t* rgbRight,
+                              size_t rightStep, size_t rightFrameStride, const double* Q, int minObjSize, bool zeroBorder,
+                              double calibrationUnit, rtdm_object* objects, int* counts, double* meanCm, int* npix,
+                              const rtdm_measure_params& params, rtdm_object_measure* measures, int16_t* disp = nullptr,
+                              size_t dispStep = 0, size_t dispFrameStride = 0);
     int status() const { return status_; }
 
 private:
+    int estimator(HIPMatcherCore& matcher, HIPRectifierCore& rectifier, int maxBatch, int capacity);   // est_ for these; a status
     rtdm_objects* ob_ = nullptr;
     rtdm_estimator* est_ = nullptr;                          // estimateBatch: the handle and what it was made for
     rtdm_bm* estBm_ = nullptr;
