@@ -53,7 +53,7 @@ int rtdm_objects_measure_device(int device, const rtdm_measure_params* params, i
     if (st) return st;
     if ((size_t)d_measures % 8) return RTDM_ERR_BAD_SIZE;
     if (workspace_bytes < measure_bytes(n, capacity, height, params->nquant)) return RTDM_ERR_BAD_SIZE;
-    if ((long long)width * height >= (1LL << 31)) return RTDM_ERR_UNSUPPORTED;     // (the frame minimum walks a 32-bit pixel index)
+    if ((long long)width * height >= (1LL << 31)) return RTDM_ERR_UNSUPPORTED;     // (rtdm_xyz's limit for the same points; G10 keeps it)
     if (n == 0) return RTDM_OK;
     st = use_device(device);
     if (st) return st;

@@ -1,10 +1,11 @@
 // k_measure.hip -- per-object measurements from the detector's device lists (rules G1-G10): for every
-// stored object the Z quantiles, the extent and the centre of its kept pixels in camera coordinates.  Where the objects lie and
-// which pixels they cover is k_depth_objects.hip's (rtdm_objslot.h), the point of a pixel is k_xyz.hip's (rtdm_xyz_point.h).
+// stored object the Z quantiles, the extent and the centre of its kept pixels in camera coordinates.  Where the objects lie,
+// which pixels they cover and the walk of a box are k_depth_objects.hip's too (rtdm_objslot.h); the point of a pixel, its Z and
+// the keep test are k_xyz.hip's too (rtdm_xyz_point.h).
 //
 //   launch_xyz_min   the frame's smallest disparity key (X4), either key mode
-//   k_meas_bands     one wave per (frame, slot, band of DOBJ_BAND rows): sums of X, Y, Z in D3's order, the two counts and the
-//                    six extreme keys of the band -> workspace.  No atomics.
+//   k_meas_bands     one wave per (frame, slot, band of DOBJ_BAND rows), rtdm_objslot.h's walk: sums of X, Y, Z in D3's order, the
+//                    two counts and the six extreme keys of the band -> workspace.  No atomics.
 //   k_meas_final     one lane per slot: the bands in ascending order -> every field of the record but the quantiles of a
 //                    non-empty object
 //   k_meas_select    one workgroup per slot: a most-significant-digit-first radix select (8-bit digits) over the Z keys that
@@ -13,8 +14,6 @@
 #include "rtdm_kernels.h"
 #include "rtdm_objslot.h"
 #include "rtdm_xyz_point.h"
-
-#include <cfloat>
 
 namespace rtdm {
 
@@ -28,88 +27,43 @@ __device__ __forceinline__ unsigned meas_key(float v)
 }
 __device__ __forceinline__ float meas_unkey(unsigned k) { return __uint_as_float((k & 0x80000000u) ? k ^ 0x80000000u : ~k); }
 
-// G2: the value is compared, never used (L6)
-template <bool LABELS>
-__device__ __forceinline__ bool meas_plane(const uint8_t* mp, size_t mpitch, int x, int y, int i)
-{
-    return LABELS ? *(const int32_t*)(mp + (size_t)y * mpitch + (size_t)x * 4) == i + 1 : mp[(size_t)y * mpitch + x] != 0;
-}
+struct MeasMin { __device__ __forceinline__ unsigned operator()(unsigned a, unsigned b) const { return min(a, b); } };
+struct MeasMax { __device__ __forceinline__ unsigned operator()(unsigned a, unsigned b) const { return max(a, b); } };
 
-// G3: Z of a pixel, k_xyz_map's statement (X3 + X4); *h3 for the other two components
-__device__ __forceinline__ float meas_z(const XyzParams& P, int key, int mk, double xd, double yd, double d, double* h3)
-{
-    *h3 = xyz_h(P, 3, xd, yd, d);
-    const float z = (float)(xyz_h(P, 2, xd, yd, d) / *h3);
-    return key == mk ? 10000.0f : z;
-}
-
-// G4 (NaN fails both tests)
-__device__ __forceinline__ bool meas_keep(const XyzParams& P, float z)
-{
-    const double zd = (double)z;
-    return fabs(zd - 10000.0) >= (double)FLT_EPSILON && fabs(zd) <= P.max_z;
-}
-
-// the lanes of a wave over a box of width cw, as k_dobj_bands lays them (D3): lw lanes per row, 64 / lw rows at once
-__device__ __forceinline__ int meas_row_lanes(int cw)
-{
-    int lw = 1;
-    while (lw < cw && lw < 64) lw <<= 1;
-    return lw;
-}
-
+// G2-G4 over rtdm_objslot.h's walk: the plane first (nplane counts what it passes), then Z and the keep test, then X and Y
 template <bool LABELS>
 __global__ __launch_bounds__(256) void k_meas_bands(DepthObjects a, XyzParams P, const int* minkey, MeasBand* part)
 {
-    const int lane = threadIdx.x & 63;
-    const long long items = (long long)a.n * a.cap * a.nb;
-    for (long long it = (long long)blockIdx.x * 4 + (threadIdx.x >> 6); it < items; it += (long long)gridDim.x * 4) {
-        const int band = (int)(it % a.nb);
-        const long long slot = it / a.nb;
-        const int i = (int)(slot % a.cap), f = (int)(slot / a.cap);
-        DobjBox b;
-        if (!dobj_slot(a, f, i, &b)) continue;
-        const int cw = b.x1 - b.x0, ch = b.y1 - b.y0, r0 = band * DOBJ_BAND;
-        if (r0 >= ch) continue;
-        const int r1 = min(r0 + DOBJ_BAND, ch);
-        const int lw = meas_row_lanes(cw);
-        const int col = lane & (lw - 1), rof = lane / lw, rstep = 64 / lw;
-        const int16_t* dp = a.disp + (size_t)f * a.dframe_e;
-        const uint8_t* mp = a.mask + ((size_t)f * a.K + b.cls) * a.mplane;
-        const int mk = minkey[f];
+    dobj_for_bands(a, [&](const DobjItem& t) {
+        const int mk = minkey[t.f];
         double s0 = 0.0, s1 = 0.0, s2 = 0.0;
         int c = 0, cp = 0;
         unsigned lo0 = ~0u, lo1 = ~0u, lo2 = ~0u, hi0 = 0u, hi1 = 0u, hi2 = 0u;
-        for (int r = r0 + rof; r < r1; r += rstep) {
-            const int y = b.y0 + r;
-            for (int x = b.x0 + col; x < b.x1; x += lw) {
-                if (!meas_plane<LABELS>(mp, a.mpitch, x, y, i)) continue;
-                ++cp;
-                const int key = xyz_key(dp[(size_t)y * a.dpitch_e + x], P.mode);
-                const double d = xyz_d(key, P.mode), xd = (double)x, yd = (double)y;
-                double h3;
-                const float Z = meas_z(P, key, mk, xd, yd, d, &h3);
-                if (!meas_keep(P, Z)) continue;
-                const float X = (float)(xyz_h(P, 0, xd, yd, d) / h3), Y = (float)(xyz_h(P, 1, xd, yd, d) / h3);
-                s0 += (double)X; s1 += (double)Y; s2 += (double)Z; ++c;
-                const unsigned k0 = meas_key(X), k1 = meas_key(Y), k2 = meas_key(Z);
-                lo0 = min(lo0, k0); lo1 = min(lo1, k1); lo2 = min(lo2, k2);
-                hi0 = max(hi0, k0); hi1 = max(hi1, k1); hi2 = max(hi2, k2);
-            }
-        }
-        for (int off = 32; off > 0; off >>= 1) {
-            s0 += __shfl_down(s0, off); s1 += __shfl_down(s1, off); s2 += __shfl_down(s2, off);
-            c += __shfl_down(c, off); cp += __shfl_down(cp, off);
-            lo0 = min(lo0, __shfl_down(lo0, off)); lo1 = min(lo1, __shfl_down(lo1, off)); lo2 = min(lo2, __shfl_down(lo2, off));
-            hi0 = max(hi0, __shfl_down(hi0, off)); hi1 = max(hi1, __shfl_down(hi1, off)); hi2 = max(hi2, __shfl_down(hi2, off));
-        }
-        if (lane == 0) {
-            MeasBand* o = part + (size_t)slot * a.nb + band;
+        dobj_for_pixels(t, [&](int x, int y) {
+            if (!dobj_plane<LABELS>(t.mp, a.mpitch, x, y, t.i)) return;
+            ++cp;
+            const int key = xyz_key(t.dp[(size_t)y * a.dpitch_e + x], P.mode);
+            const double d = xyz_d(key, P.mode), xd = (double)x, yd = (double)y;
+            double h3;
+            const float Z = xyz_z(P, key, true, mk, xd, yd, d, &h3);
+            if (!xyz_keep_z(P, Z)) return;
+            const float X = (float)(xyz_h(P, 0, xd, yd, d) / h3), Y = (float)(xyz_h(P, 1, xd, yd, d) / h3);
+            s0 += (double)X; s1 += (double)Y; s2 += (double)Z; ++c;
+            const unsigned k0 = meas_key(X), k1 = meas_key(Y), k2 = meas_key(Z);
+            lo0 = min(lo0, k0); lo1 = min(lo1, k1); lo2 = min(lo2, k2);
+            hi0 = max(hi0, k0); hi1 = max(hi1, k1); hi2 = max(hi2, k2);
+        });
+        s0 = dobj_fold(s0, DobjAdd()); s1 = dobj_fold(s1, DobjAdd()); s2 = dobj_fold(s2, DobjAdd());
+        c = dobj_fold(c, DobjAdd()); cp = dobj_fold(cp, DobjAdd());
+        lo0 = dobj_fold(lo0, MeasMin()); lo1 = dobj_fold(lo1, MeasMin()); lo2 = dobj_fold(lo2, MeasMin());
+        hi0 = dobj_fold(hi0, MeasMax()); hi1 = dobj_fold(hi1, MeasMax()); hi2 = dobj_fold(hi2, MeasMax());
+        if ((threadIdx.x & 63) == 0) {
+            MeasBand* o = part + (size_t)t.slot * a.nb + t.band;
             o->s[0] = s0; o->s[1] = s1; o->s[2] = s2;
             o->lo[0] = lo0; o->lo[1] = lo1; o->lo[2] = lo2; o->hi[0] = hi0; o->hi[1] = hi1; o->hi[2] = hi2;
             o->npix = c; o->nplane = cp;
         }
-    }
+    });
 }
 
 // one lane = one object slot: its bands in ascending order.  Writes G8's zeros, and the quantiles nobody asked for as zeros.
@@ -119,7 +73,7 @@ __global__ __launch_bounds__(256) void k_meas_final(DepthObjects a, int nquant, 
     if (slot >= (long long)a.n * a.cap) return;
     DobjBox b;
     if (!dobj_slot(a, (int)(slot / a.cap), (int)(slot % a.cap), &b)) return;
-    const int bands = (b.y1 - b.y0 + DOBJ_BAND - 1) / DOBJ_BAND;
+    const int bands = dobj_box_bands(b);
     double s0 = 0.0, s1 = 0.0, s2 = 0.0;
     int c = 0, cp = 0;
     unsigned lo0 = ~0u, lo1 = ~0u, lo2 = ~0u, hi0 = 0u, hi1 = 0u, hi2 = 0u;
@@ -169,8 +123,8 @@ __global__ __launch_bounds__(256) void k_meas_select(DepthObjects a, XyzParams P
         if (npix <= 0) continue;
         const unsigned klo = meas_key(o->lo[2]), diff = klo ^ meas_key(o->hi[2]);
         const int cw = b.x1 - b.x0, ch = b.y1 - b.y0;
-        const int lw = meas_row_lanes(cw);
-        const int col = lane & (lw - 1), rof = lane / lw, rstep = 64 / lw;
+        const DobjLanes L = dobj_lanes(cw, lane);
+        const int lw = L.lw, col = L.col, rof = L.rof, rstep = L.rstep;
         const int16_t* dp = a.disp + (size_t)f * a.dframe_e;
         const uint8_t* mp = a.mask + ((size_t)f * a.K + b.cls) * a.mplane;
         const int mk = minkey[f];
@@ -204,11 +158,11 @@ __global__ __launch_bounds__(256) void k_meas_select(DepthObjects a, XyzParams P
                     int bin = -1;
                     if (r < ch && xb + col < cw) {
                         const int x = b.x0 + xb + col, y = b.y0 + r;
-                        if (meas_plane<LABELS>(mp, a.mpitch, x, y, i)) {
+                        if (dobj_plane<LABELS>(mp, a.mpitch, x, y, i)) {
                             const int dkey = xyz_key(dp[(size_t)y * a.dpitch_e + x], P.mode);
                             double h3;
-                            const float Z = meas_z(P, dkey, mk, (double)x, (double)y, xyz_d(dkey, P.mode), &h3);
-                            if (meas_keep(P, Z)) {
+                            const float Z = xyz_z(P, dkey, true, mk, (double)x, (double)y, xyz_d(dkey, P.mode), &h3);
+                            if (xyz_keep_z(P, Z)) {
                                 const unsigned key = meas_key(Z);
 #pragma unroll
                                 for (int k = 0; k < 8; ++k)
@@ -259,16 +213,13 @@ __global__ __launch_bounds__(256) void k_meas_select(DepthObjects a, XyzParams P
     }
 }
 
-static size_t meas_bands(int H) { return (size_t)((std::max(H, 0) + DOBJ_BAND - 1) / DOBJ_BAND); }
-static size_t meas_min_bytes(int n) { return ((size_t)std::max(n, 0) * sizeof(int) + 63) & ~(size_t)63; }
-
 // workspace layout, from its address rounded up to 8 (the 64 bytes on top pay for that):
 // [n minimum keys, padded to 64 bytes | n * cap * bands(H) MeasBand].  The histograms of the selection live in LDS, so nquant
 // adds nothing.
 size_t measure_bytes(int n, int cap, int H, int nquant)
 {
     (void)nquant;
-    return 64 + meas_min_bytes(n) + (size_t)std::max(n, 0) * std::max(cap, 0) * meas_bands(H) * sizeof(MeasBand);
+    return 64 + dobj_min_bytes(n) + (size_t)std::max(n, 0) * std::max(cap, 0) * dobj_bands(H) * sizeof(MeasBand);
 }
 
 void launch_measure(DepthObjects a, const XyzParams& P, const MeasQuant& mq, void* workspace, MeasRecord* out, hipStream_t stream,
@@ -276,13 +227,11 @@ void launch_measure(DepthObjects a, const XyzParams& P, const MeasQuant& mq, voi
 {
     static_assert(sizeof(MeasBand) == 56 && sizeof(MeasRecord) == 88, "the layouts the workspace size and the ABI state");
     if (a.n <= 0) return;
-    a.nb = (int)meas_bands(a.H);
-    unsigned char* p = (unsigned char*)(((size_t)workspace + 7) & ~(size_t)7);
-    int* minkey = (int*)p; p += meas_min_bytes(a.n);
+    a.nb = (int)dobj_bands(a.H);
+    unsigned char* p;
+    int* minkey = dobj_carve_min(workspace, a.n, &p);
     MeasBand* part = (MeasBand*)p;
-    for (int f0 = 0; f0 < a.n; f0 += 32768)           // (the grid's second dimension ends at 65535)
-        launch_xyz_min(XyzDisp{a.disp + (size_t)f0 * a.dframe_e, a.dpitch_e, a.dframe_e}, std::min(a.n - f0, 32768), a.W, a.H, P.mode,
-                       minkey + f0, stream);
+    launch_xyz_min(XyzDisp{a.disp, a.dpitch_e, a.dframe_e}, a.n, a.W, a.H, P.mode, minkey, stream);
     if (a.cap <= 0) return;
     const size_t slots = (size_t)a.n * a.cap, parts = slots * a.nb;
     const unsigned blocks = (unsigned)std::min<size_t>((parts + 3) / 4, (size_t)1 << 16);

@@ -10,7 +10,10 @@
 // frame: exclusive scan of the tile counts, total = counts[f])  ->  k_xyz_scatter (the predicate again; rank inside a wave
 // from __ballot + v_mbcnt, wave offsets inside the tile through LDS, tile offset from the scan).  No atomic decides a
 // position.  With handle_missing_values the per-frame minimum is a pass of its own in front (k_xyz_min); its atomicMin
-// is an integer minimum, which is the same whatever order the tiles arrive in.
+// is an integer minimum, which is the same whatever order its workgroups (row groups, not tiles) arrive in.  It is the only
+// frame-minimum kernel: calc_depth (k_depth.hip), the per-object depth (k_depth_objects.hip) and the measurements
+// (k_measure.hip) call launch_xyz_min too.  Z (X3 + X4) and the Z part of the keep test (X6) are rtdm_xyz_point.h's, shared
+// with k_measure.hip.
 //
 // Floating point (X2, X3): every multiply and add of the homogeneous point is a double operation rounded on its own, in
 // the written order -- contraction is off inside xyz_h (rtdm_xyz_point.h) -- then one IEEE double division and one
@@ -18,17 +21,15 @@
 #include "rtdm_kernels.h"
 #include "rtdm_xyz_point.h"
 
-#include <cfloat>
-
 namespace rtdm {
 
 static const int XYZ_CHUNKS = XYZ_TILE / 256;
+static const int XYZ_MIN_GROUPS = 64;               // row groups of a frame in k_xyz_min: more of them meet at one atomicMin
 
 // X6
 __device__ __forceinline__ bool xyz_keep(const XyzParams& P, int disp, float z, int maskbyte)
 {
-    const double zd = (double)z;
-    return disp != P.invalid16 && fabs(zd - 10000.0) >= (double)FLT_EPSILON && fabs(zd) <= P.max_z && maskbyte != 0;
+    return disp != P.invalid16 && xyz_keep_z(P, z) && maskbyte != 0;
 }
 
 __device__ __forceinline__ int xyz_lane_rank(unsigned long long ballot)   // set bits below this lane
@@ -36,28 +37,20 @@ __device__ __forceinline__ int xyz_lane_rank(unsigned long long ballot)   // set
     return (int)__builtin_amdgcn_mbcnt_hi((unsigned)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)ballot, 0u));
 }
 
-// X4: minimum key of every frame.  minkey[f] starts above every key (launch_xyz_min sets it).
-__global__ __launch_bounds__(256) void k_xyz_min(XyzDisp D, int W, unsigned WH, int mode, int* minkey)
+// X4: minimum key of every frame.  minkey[f] starts above every key (launch_xyz_min sets it).  grid: (row groups, frames): a
+// workgroup walks the rows y = blockIdx.x, blockIdx.x + gridDim.x, ... of its frame, so no pixel index is formed and no
+// frame size is too large; a wave's minimum by shuffles, the workgroup's through four words of LDS, one atomicMin.
+__global__ __launch_bounds__(256) void k_xyz_min(XyzDisp D, int W, int H, int mode, int* minkey)
 {
-    __shared__ int red[256];
-    const int f = blockIdx.y;
-    const int16_t* disp = D.base + (size_t)f * D.frame_e;
+    __shared__ int red[4];
+    const int16_t* disp = D.base + (size_t)blockIdx.y * D.frame_e;
     int m = 0x7fffffff;
-#pragma unroll
-    for (int k = 0; k < XYZ_CHUNKS; ++k) {
-        const unsigned p = blockIdx.x * (unsigned)XYZ_TILE + k * 256 + threadIdx.x;
-        if (p < WH) {
-            const int y = (int)(p / (unsigned)W), x = (int)(p - (unsigned)y * (unsigned)W);
-            m = min(m, xyz_key(disp[(size_t)y * D.pitch_e + x], mode));
-        }
-    }
-    red[threadIdx.x] = m;
+    for (int y = blockIdx.x; y < H; y += gridDim.x)
+        for (int x = threadIdx.x; x < W; x += 256) m = min(m, xyz_key(disp[(size_t)y * D.pitch_e + x], mode));
+    for (int off = 32; off > 0; off >>= 1) m = min(m, __shfl_xor(m, off));
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
     __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (threadIdx.x < s) red[threadIdx.x] = min(red[threadIdx.x], red[threadIdx.x + s]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) atomicMin(minkey + f, red[0]);
+    if (threadIdx.x == 0) atomicMin(minkey + blockIdx.y, min(min(red[0], red[1]), min(red[2], red[3])));
 }
 
 // X5: the dense map.  xyz: 3 floats per pixel; zp: the Z plane; either may be null.
@@ -73,9 +66,8 @@ __global__ __launch_bounds__(256) void k_xyz_map(XyzDisp D, int W, unsigned WH, 
         const int y = (int)(p / (unsigned)W), x = (int)(p - (unsigned)y * (unsigned)W);
         const int key = xyz_key(disp[(size_t)y * D.pitch_e + x], P.mode);
         const double d = xyz_d(key, P.mode), xd = (double)x, yd = (double)y;
-        const double h3 = xyz_h(P, 3, xd, yd, d);
-        float z = (float)(xyz_h(P, 2, xd, yd, d) / h3);
-        if (P.hmv && key == mk) z = 10000.0f;
+        double h3;
+        const float z = xyz_z(P, key, P.hmv, mk, xd, yd, d, &h3);
         if (O.xyz) {
             float* o = O.xyz + (size_t)f * O.xyz_frame + (size_t)y * O.xyz_pitch + 3 * (size_t)x;
             o[0] = (float)(xyz_h(P, 0, xd, yd, d) / h3);
@@ -98,9 +90,7 @@ __device__ __forceinline__ XyzPix xyz_pixel(const XyzCloudIn& I, int f, int W, u
         const int disp = I.disp.base[(size_t)f * I.disp.frame_e + (size_t)px.y * I.disp.pitch_e + px.x];
         px.key = xyz_key(disp, P.mode);
         const double d = xyz_d(px.key, P.mode), xd = (double)px.x, yd = (double)px.y;
-        px.h3 = xyz_h(P, 3, xd, yd, d);
-        const float z = (float)(xyz_h(P, 2, xd, yd, d) / px.h3);
-        px.z = (P.hmv && px.key == mk) ? 10000.0f : z;                   // X3 + X4
+        px.z = xyz_z(P, px.key, P.hmv, mk, xd, yd, d, &px.h3);
         const int mb = I.mask ? I.mask[(size_t)f * I.mframe + (size_t)px.y * I.mpitch + px.x] : 1;
         px.keep = xyz_keep(P, disp, px.z, mb);
     }
@@ -200,11 +190,15 @@ __global__ __launch_bounds__(256) void k_xyz_scatter(XyzCloudIn I, int W, unsign
 
 int xyz_tiles(int W, int H) { return (int)(((unsigned)W * (unsigned)H + XYZ_TILE - 1) / XYZ_TILE); }
 
+// One memset and one kernel; one more kernel for every further 32768 frames (a grid's second dimension ends at 65535).
 void launch_xyz_min(XyzDisp D, int n, int W, int H, int mode, int* minkey, hipStream_t stream)
 {
-    // 0x7f7f7f7f is above every key (a key is at most an int16)
+    // the initial minimum is written on the device -- 0x7f7f7f7f is above every key (a key is at most an int16) --: an async
+    // copy from a stack local would only be safe if the runtime staged pageable sources at enqueue time
     (void)hipMemsetAsync(minkey, 0x7f, (size_t)n * sizeof(int), stream);
-    hipLaunchKernelGGL(k_xyz_min, dim3(xyz_tiles(W, H), n), dim3(256), 0, stream, D, W, (unsigned)W * (unsigned)H, mode, minkey);
+    for (int f0 = 0; f0 < n; f0 += 32768)
+        hipLaunchKernelGGL(k_xyz_min, dim3(std::min(H, XYZ_MIN_GROUPS), std::min(n - f0, 32768)), dim3(256), 0, stream,
+                           XyzDisp{D.base + (size_t)f0 * D.frame_e, D.pitch_e, D.frame_e}, W, H, mode, minkey + f0);
 }
 
 void launch_xyz_map(XyzDisp D, int n, int W, int H, const XyzParams& P, int* minkey, XyzMap O, hipStream_t stream)

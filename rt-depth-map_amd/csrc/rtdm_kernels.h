@@ -394,6 +394,7 @@ void launch_wls(const WlsLaunch& L, int n, hipStream_t stream);
 // xyz_tiles(W, H) ints per frame.  Strides are in elements unless the name says bytes.
 #define XYZ_TILE 1024
 struct XyzParams { double q[16]; double max_z; int mode, hmv, invalid16; };  // invalid16 = (min_disparity - 1) * 16
+#define XYZ_MODE_ROUNDED 1       // XyzParams::mode = RTDM_XYZ_ROUNDED: d is the rounded quotient, calc_depth's (0: RTDM_XYZ_FIXED16)
 struct XyzDisp { const int16_t* base; size_t pitch_e, frame_e; };
 struct XyzMap { float* xyz; size_t xyz_pitch, xyz_frame; float* z; size_t z_pitch, z_frame; };   // either may be null
 struct XyzCloudIn {
@@ -403,8 +404,11 @@ struct XyzCloudIn {
 };
 struct XyzRec { float x, y, z; uint32_t rgba; };                             // rtdm_point: r in the lowest byte
 int xyz_tiles(int W, int H);
-// X4: minkey[f] = the smallest key (xyz_key of `mode`) of frame f, f < n <= 65535
+// X4: minkey[f] = the smallest key (xyz_key of `mode`) of frame f, for any n and any frame size: one memset and one kernel
+// (one more for every further 32768 frames).  The one frame minimum: of the map and the cloud, of calc_depth and the
+// per-object depth (ROUNDED keys: the rounded disparity) and of the measurements.
 void launch_xyz_min(XyzDisp D, int n, int W, int H, int mode, int* minkey, hipStream_t stream);
+// (the map and the cloud: n <= 65535, W * H < 2^31)
 void launch_xyz_map(XyzDisp D, int n, int W, int H, const XyzParams& P, int* minkey, XyzMap O, hipStream_t stream);
 // counts: n ints (device), the kept pixels of every frame; records at or beyond `capacity` are not written
 void launch_xyz_cloud(const XyzCloudIn& I, int n, int W, int H, const XyzParams& P, int* minkey, int* tile_cnt, XyzRec* points,

@@ -6,6 +6,7 @@ reordering a double sum moves it by about 4e-11 relative).  Q is the 320x240 cal
 import numpy as np
 import pytest
 
+import d3_walk_model as d3
 import rectify_util as ru
 
 pytestmark = pytest.mark.gpu
@@ -57,8 +58,9 @@ def expect(oracle, disp, masks, lists, counts, cap):
     return mean, npix
 
 
-def run(pkg, disp, masks, lists, counts, cap, padded=False, two=False):
-    """One call (two: the same call twice on fresh outputs) -> (mean n x cap, npix n x cap) on the host."""
+def run(pkg, disp, masks, lists, counts, cap, padded=False, two=False, labels=False, q=Q):
+    """One call (two: the same call twice on fresh outputs; labels: `masks` are int32 label planes and the call is the labels
+    form) -> (mean n x cap, npix n x cap) on the host."""
     import torch
     n, h, w = disp.shape
     obj = np.full((n, cap * 32), OBJ0, np.uint8)
@@ -80,7 +82,8 @@ def run(pkg, disp, masks, lists, counts, cap, padded=False, two=False):
         d_mean = torch.full((n, cap), MEAN0, dtype=torch.float64, device="cuda")
         d_npix = torch.full((n, cap), NPIX0, dtype=torch.int32, device="cuda")
         torch.cuda.synchronize()
-        ws = pkg.depth_objects_device(d_disp, Q, d_masks, d_obj, d_cnt, d_mean, d_npix, capacity=cap)
+        fn = pkg.depth_objects_labels_device if labels else pkg.depth_objects_device
+        ws = fn(d_disp, q, d_masks, d_obj, d_cnt, d_mean, d_npix, capacity=cap)
         torch.cuda.synchronize()
         del ws
         out.append((d_mean.cpu().numpy(), d_npix.cpu().numpy()))
@@ -215,3 +218,19 @@ def test_against_the_single_frame_call(pkg, main_case):
                                         [lists[f][i][:4] for i in idx])
         assert np.array_equal(n1, npix[f, idx]) and n1.sum() > 0
         np.testing.assert_allclose(mean[f, idx], m1, rtol=1e-9, atol=0)
+
+
+@pytest.mark.parametrize("labels", [False, True])
+def test_the_walk_of_a_box_is_rule_d3(pkg, labels):
+    """D3 bit for bit: mean and npix of every box of tests/d3_walk_model.py's scene equal the model's lane-by-lane, band-by-band
+    float64 sums.  On that scene the order shows: tests/test_d3_walk_model_cpu.py holds that a row-major sum, another fold of the
+    lanes or the bands in descending order each change the bits of this mean in several boxes."""
+    disp, mask, planes, boxes = d3.scene()
+    plane = planes if labels else mask
+    k = len(boxes)
+    want_mean, want_npix = d3.depth_model(disp, plane[0], boxes, labels)
+    assert k == d3.CAP - 1 and (want_npix > 0).sum() >= k - 6 and (want_mean != 0).sum() == (want_npix > 0).sum()
+    mean, npix = run(pkg, disp[None], plane[None], [boxes], np.array([[k]], np.int32), d3.CAP, labels=labels, q=d3.Q)
+    assert npix[0, :k].tobytes() == want_npix.tobytes(), np.argwhere(npix[0, :k] != want_npix)[:8]
+    assert mean[0, :k].tobytes() == want_mean.tobytes(), np.argwhere(mean[0, :k] != want_mean)[:8]
+    assert (npix[0, k:] == NPIX0).all() and (mean[0, k:] == MEAN0).all()

@@ -11,6 +11,7 @@ import pytest
 
 import cc_cases as cc
 import cc_labels_ref as lr
+import d3_walk_model as d3
 import labels_scene as ls
 import measure_ref as mr
 import rectify_util as ru
@@ -388,3 +389,24 @@ def test_estimator_measures_what_the_call_measures(pkg, oracle, own):
     assert B.lib().rtdm_estimate_batch_measured(*(args + [None, buf.ctypes.data])) == -7
     for hnd in chain:
         hnd.close()
+
+
+@pytest.mark.parametrize("labels", [False, True])
+def test_the_walk_of_a_box_is_rule_d3(pkg, labels):
+    """D3 bit for bit, as tests/test_gpu_depth_objects.py holds the depth call to it: the three means, the extent and the two
+    counts of every box of tests/d3_walk_model.py's scene equal the model's lane-by-lane, band-by-band float64 sums, on values
+    whose sums depend on the order (tests/test_d3_walk_model_cpu.py)."""
+    import torch
+    disp, mask, planes, boxes = d3.scene()
+    plane = planes if labels else mask
+    k = len(boxes)
+    d_obj, d_cnt = device_lists(pkg, [boxes], [[k]], d3.CAP)
+    d_plane = torch.from_numpy(plane[None]).cuda()
+    for mode in MODES:
+        want = d3.measure_model(disp, plane[0], boxes, labels, mode)
+        assert k == d3.CAP - 1 and (want["npix"] > 0).sum() >= k - 6 and (want["nplane"] >= want["npix"]).all()
+        got = measure(pkg, disp[None], d3.Q, d_plane, d_obj, d_cnt, d3.CAP, labels, params_of(pkg, mode, permille=()))[0]
+        for name in ("npix", "nplane", "lo", "hi", "mean"):
+            a, b = np.ascontiguousarray(got[name][:k]), np.ascontiguousarray(want[name])
+            assert a.tobytes() == b.tobytes(), (mode, name, np.argwhere(a != b)[:8].tolist())
+        assert got[k:].tobytes() == bytes([SENTINEL]) * (88 * (d3.CAP - k))
