@@ -359,6 +359,32 @@ int rtdm_bm_compute_batch(rtdm_bm* bm, int n, const uint8_t* left, const uint8_t
     return RTDM_OK;
 }
 
+// The caller's Mats are pageable ROI views (estimator.cpp:33,36): the rows are gathered into the page-locked staging
+// area on the host and go over in linear async copies -- in two BANDS of rows per direction, so that the host gathers
+// band 1 while band 0 is on the bus, and scatters band 0 of the result while band 1 arrives.  720p pair, host to host:
+// 0.363 ms with one copy per plane and row-by-row gathers, 0.347 with one band, 0.325 with two, 0.375 with four (every
+// further async copy costs more in the runtime than its overlap hides).  Rows that are contiguous in the caller's plane
+// move as one memcpy.
+static int bm_band_rows(int height) { return height >= 256 ? (height + 1) / 2 : height; }
+
+int rtdm::bm_upload_gray(rtdm_bm* bm, const uint8_t* left, size_t left_pitch, const uint8_t* right, size_t right_pitch, int width, int height,
+                         hipStream_t s)
+{
+    const size_t dpitch = bm->ppitch, dframe = dpitch * (size_t)height;
+    const uint8_t* src[2] = {left, right};
+    const size_t spitch[2] = {left_pitch, right_pitch};
+    uint8_t* dIn[2] = {bm->dInL, bm->dInR};
+    for (int y0 = 0, bh = bm_band_rows(height); y0 < height; y0 += bh) {
+        const int rows = std::min(bh, height - y0);
+        for (int k = 0; k < 2; ++k) {
+            uint8_t* h = bm->hStage + k * dframe + (size_t)y0 * dpitch;
+            copy_rows(h, dpitch, src[k] + (size_t)y0 * spitch[k], spitch[k], (size_t)width, rows, RowPad::OURS);
+            HIPC(hipMemcpyAsync(dIn[k] + (size_t)y0 * dpitch, h, (size_t)rows * dpitch, hipMemcpyHostToDevice, s));
+        }
+    }
+    return RTDM_OK;
+}
+
 int rtdm_bm_compute(rtdm_bm* bm, const uint8_t* left, size_t left_pitch, const uint8_t* right,
                     size_t right_pitch, int width, int height, int16_t* disp, size_t disp_pitch)
 {
@@ -371,12 +397,6 @@ int rtdm_bm_compute(rtdm_bm* bm, const uint8_t* left, size_t left_pitch, const u
     hipStream_t s = bm->stream;
     DrainOnError drain{s};
     const size_t dpitch = bm->ppitch, dframe = bm->ppitch * (size_t)height;
-    // The caller's Mats are pageable ROI views (estimator.cpp:33,36): the rows are gathered into the page-locked staging
-    // area on the host and go over in linear async copies -- in two BANDS of rows per direction, so that the host gathers
-    // band 1 while band 0 is on the bus, and scatters band 0 of the result while band 1 arrives.  720p pair, host to host:
-    // 0.363 ms with one copy per plane and row-by-row gathers, 0.347 with one band, 0.325 with two, 0.375 with four (every
-    // further async copy costs more in the runtime than its overlap hides).  Rows that are contiguous in the caller's plane
-    // move as one memcpy.
     const Plane16W O = bm_internal_plane(bm, width, height);
     const size_t Ws = O.pitch_e;
     if (page_locked(left) && page_locked(right) && page_locked(disp)) {
@@ -391,40 +411,20 @@ int rtdm_bm_compute(rtdm_bm* bm, const uint8_t* left, size_t left_pitch, const u
         drain.armed = false;
         return RTDM_OK;
     }
-    uint8_t *hL = bm->hStage, *hR = hL + dframe;
-    int16_t* hD = bm->hD;
-    const int nb = height >= 256 ? 2 : 1, bh = (height + nb - 1) / nb;
-    const auto gather = [&](uint8_t* dst, const uint8_t* src, size_t spitch, int y0, int y1) {
-        if (spitch == dpitch) { memcpy(dst + (size_t)y0 * dpitch, src + (size_t)y0 * spitch, (size_t)(y1 - y0 - 1) * dpitch + (size_t)width); return; }
-        for (int y = y0; y < y1; ++y) memcpy(dst + (size_t)y * dpitch, src + (size_t)y * spitch, (size_t)width);
-    };
-    for (int b = 0; b < nb; ++b) {
-        const int y0 = b * bh, y1 = std::min(height, y0 + bh);
-        if (y0 >= y1) break;
-        gather(hL, left, left_pitch, y0, y1);
-        HIPC(hipMemcpyAsync(bm->dInL + (size_t)y0 * dpitch, hL + (size_t)y0 * dpitch, (size_t)(y1 - y0) * dpitch, hipMemcpyHostToDevice, s));
-        gather(hR, right, right_pitch, y0, y1);
-        HIPC(hipMemcpyAsync(bm->dInR + (size_t)y0 * dpitch, hR + (size_t)y0 * dpitch, (size_t)(y1 - y0) * dpitch, hipMemcpyHostToDevice, s));
-    }
+    rc = bm_upload_gray(bm, left, left_pitch, right, right_pitch, width, height, s);
+    if (rc) return rc;
     Plane8 L{bm->dInL, dpitch, dframe}, R{bm->dInR, dpitch, dframe};
     rc = bm_run_chunk(bm, 1, L, R, width, height, O, s);
     if (rc) return rc;
-    int nbo = 0;
-    for (int b = 0; b < nb; ++b, ++nbo) {
-        const int y0 = b * bh, y1 = std::min(height, y0 + bh);
-        if (y0 >= y1) break;
-        HIPC(hipMemcpyAsync(hD + (size_t)y0 * Ws, bm->dOut + (size_t)y0 * Ws, (size_t)(y1 - y0) * Ws * sizeof(int16_t), hipMemcpyDeviceToHost, s));
+    const int bh = bm_band_rows(height);                 // back in the same bands: band 0 is scattered while band 1 arrives
+    for (int y0 = 0, b = 0; y0 < height; y0 += bh, ++b) {
+        HIPC(hipMemcpyAsync(bm->hD + (size_t)y0 * Ws, bm->dOut + (size_t)y0 * Ws, (size_t)std::min(bh, height - y0) * Ws * sizeof(int16_t), hipMemcpyDeviceToHost, s));
         HIPC(hipEventRecord(bm->evBand[b], s));
     }
-    for (int b = 0; b < nbo; ++b) {
-        const int y0 = b * bh, y1 = std::min(height, y0 + bh);
+    for (int y0 = 0, b = 0; y0 < height; y0 += bh, ++b) {
         HIPC(hipEventSynchronize(bm->evBand[b]));
-        if ((size_t)width == Ws && disp_pitch == Ws * sizeof(int16_t)) {   // no pad columns between the rows: one copy per band
-            memcpy((uint8_t*)disp + (size_t)y0 * disp_pitch, hD + (size_t)y0 * Ws, (size_t)(y1 - y0 - 1) * disp_pitch + (size_t)width * sizeof(int16_t));
-        } else {
-            for (int y = y0; y < y1; ++y)
-                memcpy((uint8_t*)disp + (size_t)y * disp_pitch, hD + (size_t)y * Ws, (size_t)width * sizeof(int16_t));
-        }
+        copy_rows((uint8_t*)disp + (size_t)y0 * disp_pitch, disp_pitch, bm->hD + (size_t)y0 * Ws, Ws * sizeof(int16_t), (size_t)width * sizeof(int16_t),
+                  std::min(bh, height - y0), RowPad::KEEP);
     }
     drain.armed = false;
     return RTDM_OK;
@@ -509,16 +509,12 @@ int rtdm_bm_compute_depth(rtdm_bm* bm, const uint8_t* left, size_t left_pitch, c
     if (rc) return rc;
     HIPC(hipSetDevice(bm->device));
     hipStream_t s = bm->stream;
+    DrainOnError drain{s};
     const size_t dpitch = bm->ppitch, dframe = bm->ppitch * (size_t)height;
-    uint8_t *hL = bm->hStage, *hR = hL + dframe, *hM = bm->hM;
-    for (int y = 0; y < height; ++y) {
-        memcpy(hL + (size_t)y * dpitch, left + (size_t)y * left_pitch, (size_t)width);
-        memcpy(hR + (size_t)y * dpitch, right + (size_t)y * right_pitch, (size_t)width);
-        memcpy(hM + (size_t)y * width, mask + (size_t)y * mask_pitch, (size_t)width);
-    }
-    HIPC(hipMemcpyAsync(bm->dInL, hL, dframe, hipMemcpyHostToDevice, s));
-    HIPC(hipMemcpyAsync(bm->dInR, hR, dframe, hipMemcpyHostToDevice, s));
-    HIPC(hipMemcpyAsync(bm->dMask, hM, (size_t)width * height, hipMemcpyHostToDevice, s));
+    rc = bm_upload_gray(bm, left, left_pitch, right, right_pitch, width, height, s);
+    if (rc) return rc;
+    copy_rows(bm->hM, (size_t)width, mask, mask_pitch, (size_t)width, height, RowPad::OURS);
+    HIPC(hipMemcpyAsync(bm->dMask, bm->hM, (size_t)width * height, hipMemcpyHostToDevice, s));
     Plane8 L{bm->dInL, dpitch, dframe}, R{bm->dInR, dpitch, dframe};
     const Plane16W O = bm_internal_plane(bm, width, height);
     rc = bm_run_chunk(bm, 1, L, R, width, height, O, s);
@@ -529,6 +525,7 @@ int rtdm_bm_compute_depth(rtdm_bm* bm, const uint8_t* left, size_t left_pitch, c
     if (disp) { rc = bm_download_disp(bm, width, height, s); if (rc) return rc; }
     HIPC(hipGetLastError());
     HIPC(hipStreamSynchronize(s));
+    drain.armed = false;
     if (disp) bm_scatter_disp(bm, width, height, disp, disp_pitch);
     return RTDM_OK;
 }
@@ -542,5 +539,5 @@ int rtdm::bm_download_disp(rtdm_bm* bm, int W, int H, hipStream_t s)
 void rtdm::bm_scatter_disp(const rtdm_bm* bm, int W, int H, int16_t* disp, size_t disp_pitch)
 {
     const size_t Ws = bm_ws(W);
-    for (int y = 0; y < H; ++y) memcpy((uint8_t*)disp + (size_t)y * disp_pitch, bm->hD + (size_t)y * Ws, (size_t)W * sizeof(int16_t));
+    copy_rows(disp, disp_pitch, bm->hD, Ws * sizeof(int16_t), (size_t)W * sizeof(int16_t), H, RowPad::KEEP);
 }

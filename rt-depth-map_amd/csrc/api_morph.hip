@@ -177,11 +177,13 @@ int rtdm_morph_run(rtdm_morph* mf, const uint8_t* in, size_t in_pitch, uint8_t* 
     if (in_pitch < (size_t)width || out_pitch < (size_t)width) return RTDM_ERR_BAD_SIZE;
     HIPC(hipSetDevice(mf->device));
     hipStream_t s = mf->stream;
+    DrainOnError drain{s};
     HIPC(hipMemcpy2DAsync(mf->dIn, width, in, in_pitch, width, height, hipMemcpyHostToDevice, s));
     int rc = rtdm_morph_run_device(mf, 1, mf->dIn, width, (size_t)width * height, mf->dOut, width,
                                    (size_t)width * height, width, height, s);
     if (rc) return rc;
     HIPC(hipMemcpy2DAsync(out, out_pitch, mf->dOut, width, width, height, hipMemcpyDeviceToHost, s));
     HIPC(hipStreamSynchronize(s));
+    drain.armed = false;
     return RTDM_OK;
 }

@@ -124,16 +124,18 @@ int rtdm_objects_detect(rtdm_objects* ob, const uint8_t* rgb, size_t pitch, cons
     if (pitch < row || max_boxes < 0 || (mask_out && mask_pitch < (size_t)ob->W)) return RTDM_ERR_BAD_SIZE;
     HIPC(hipSetDevice(ob->device));
     hipStream_t s = ob->stream;
+    DrainOnError drain{s};
     uint8_t* h = (uint8_t*)(ob->hRec + 1 + 6 * OBJ_HEAD);
-    for (int y = 0; y < ob->H; ++y) memcpy(h + (size_t)y * row, rgb + (size_t)y * pitch, row);
+    copy_rows(h, row, rgb, pitch, row, ob->H, RowPad::OURS);
     HIPC(hipMemcpyAsync(ob->dRgb, h, row * ob->H, hipMemcpyHostToDevice, s));
     int st = objects_run(ob, range, min_area, zero_border, boxes, max_boxes, nboxes, roi, s);
     if (st) return st;
     if (mask_out) {                                     // through the page-locked area (the upload is long done)
         HIPC(hipMemcpyAsync(h, ob->dMaskOut, (size_t)ob->W * ob->H, hipMemcpyDeviceToHost, s));
         HIPC(hipStreamSynchronize(s));
-        for (int y = 0; y < ob->H; ++y) memcpy(mask_out + (size_t)y * mask_pitch, h + (size_t)y * ob->W, (size_t)ob->W);
+        copy_rows(mask_out, mask_pitch, h, (size_t)ob->W, (size_t)ob->W, ob->H, RowPad::KEEP);
     }
+    drain.armed = false;                                // (objects_run has synchronised)
     return RTDM_OK;
 }
 

@@ -67,10 +67,8 @@ int rtdm_rectify_create(const int16_t* map1_left, const uint16_t* map2_left, con
         const uint16_t* m2 = k ? map2_right : map2_left;
         int16_t* h1 = (int16_t*)rc->hStage;
         uint16_t* h2 = (uint16_t*)(rc->hStage + npx * 4);
-        for (int y = 0; y < roi_height; ++y) {
-            memcpy(h1 + (size_t)y * roi_width * 2, m1 + ((size_t)(roi_y + y) * width + roi_x) * 2, (size_t)roi_width * 4);
-            memcpy(h2 + (size_t)y * roi_width, m2 + (size_t)(roi_y + y) * width + roi_x, (size_t)roi_width * 2);
-        }
+        copy_rows(h1, (size_t)roi_width * 4, m1 + ((size_t)roi_y * width + roi_x) * 2, (size_t)width * 4, (size_t)roi_width * 4, roi_height, RowPad::OURS);
+        copy_rows(h2, (size_t)roi_width * 2, m2 + (size_t)roi_y * width + roi_x, (size_t)width * 2, (size_t)roi_width * 2, roi_height, RowPad::OURS);
         e = hipMemcpy(rc->dMap1[k], h1, npx * 4, hipMemcpyHostToDevice);
         if (e == hipSuccess) e = hipMemcpy(rc->dMap2[k], h2, npx * 2, hipMemcpyHostToDevice);
     }
@@ -216,8 +214,7 @@ int rtdm::rectify_upload(rtdm_rectify* rc, const uint8_t* a, size_t apitch, cons
     for (int k = 0; k < 2; ++k) {
         if (!src[k]) continue;
         uint8_t* h = rc->hStage + k * fbytes;
-        if (pit[k] == row) memcpy(h, src[k], fbytes);
-        else for (int y = 0; y < rc->H; ++y) memcpy(h + (size_t)y * row, src[k] + (size_t)y * pit[k], row);
+        copy_rows(h, row, src[k], pit[k], row, rc->H, RowPad::OURS);
         HIPC(hipMemcpyAsync(rc->dRgb[k], h, fbytes, hipMemcpyHostToDevice, s));
     }
     return RTDM_OK;
@@ -239,6 +236,7 @@ int rtdm_rectify_gray(rtdm_rectify* rc, const uint8_t* rgb_left, size_t left_pit
     if (left_pitch < row || right_pitch < row || left_rect_pitch < (size_t)rc->rw || right_rect_pitch < (size_t)rc->rw) return RTDM_ERR_BAD_SIZE;
     HIPC(hipSetDevice(rc->device));
     hipStream_t s = rc->stream;
+    DrainOnError drain{s};
     int st = rectify_upload(rc, rgb_left, left_pitch, rgb_right, right_pitch, s);
     if (st) return st;
     const size_t gframe = rc->gpitch * rc->rh;
@@ -250,10 +248,9 @@ int rtdm_rectify_gray(rtdm_rectify* rc, const uint8_t* rgb_left, size_t left_pit
     HIPC(hipMemcpyAsync(hl, rc->dGray[0], gframe, hipMemcpyDeviceToHost, s));
     HIPC(hipMemcpyAsync(hr, rc->dGray[1], gframe, hipMemcpyDeviceToHost, s));
     HIPC(hipStreamSynchronize(s));
-    for (int y = 0; y < rc->rh; ++y) {
-        memcpy(left_rect + (size_t)y * left_rect_pitch, hl + (size_t)y * rc->gpitch, (size_t)rc->rw);
-        memcpy(right_rect + (size_t)y * right_rect_pitch, hr + (size_t)y * rc->gpitch, (size_t)rc->rw);
-    }
+    drain.armed = false;
+    copy_rows(left_rect, left_rect_pitch, hl, rc->gpitch, (size_t)rc->rw, rc->rh, RowPad::KEEP);
+    copy_rows(right_rect, right_rect_pitch, hr, rc->gpitch, (size_t)rc->rw, rc->rh, RowPad::KEEP);
     return RTDM_OK;
 }
 
@@ -264,6 +261,7 @@ int rtdm_rectify_rgb(rtdm_rectify* rc, int which, const uint8_t* rgb, size_t pit
     if ((which != 0 && which != 1) || pitch < row || out_pitch < (size_t)rc->rw * 3) return RTDM_ERR_BAD_SIZE;
     HIPC(hipSetDevice(rc->device));
     hipStream_t s = rc->stream;
+    DrainOnError drain{s};
     int st = rectify_upload(rc, rgb, pitch, nullptr, 0, s);
     if (st) return st;
     launch_rectify_rgb(RectifySrc{rc->dRgb[0], row, fbytes}, rc->dMap1[which], rc->dMap2[which], rc->W, rc->H, rc->rw, rc->rh,
@@ -272,7 +270,8 @@ int rtdm_rectify_rgb(rtdm_rectify* rc, int which, const uint8_t* rgb, size_t pit
     uint8_t* ho = rc->hStage + 2 * fbytes;
     HIPC(hipMemcpyAsync(ho, rc->dOut, (size_t)rc->rw * 3 * rc->rh, hipMemcpyDeviceToHost, s));
     HIPC(hipStreamSynchronize(s));
-    for (int y = 0; y < rc->rh; ++y) memcpy(out + (size_t)y * out_pitch, ho + (size_t)y * rc->rw * 3, (size_t)rc->rw * 3);
+    drain.armed = false;
+    copy_rows(out, out_pitch, ho, (size_t)rc->rw * 3, (size_t)rc->rw * 3, rc->rh, RowPad::KEEP);
     return RTDM_OK;
 }
 

@@ -217,6 +217,7 @@ int rtdm_sgm_compute_cn(rtdm_sgm* sg, int channels, const uint8_t* left, size_t 
     if (channels == 3) { const int rc = sgm_colour_buffers(sg, true); if (rc) return rc; }
     sg->cost_limit = sgm_cost_limit(sg, channels);
     hipStream_t s = sg->stream;
+    DrainOnError drain{s};
     uint8_t* inL = channels == 3 ? sg->dInL3 : sg->dInL;
     uint8_t* inR = channels == 3 ? sg->dInR3 : sg->dInR;
     HIPC(hipMemcpy2DAsync(inL, row, left, left_pitch, row, height, hipMemcpyHostToDevice, s));
@@ -228,6 +229,7 @@ int rtdm_sgm_compute_cn(rtdm_sgm* sg, int channels, const uint8_t* left, size_t 
     HIPC(hipMemcpy2DAsync(disp, disp_pitch, sg->dOut, (size_t)width * 2, (size_t)width * 2, height, hipMemcpyDeviceToHost, s));
     HIPC(hipStreamSynchronize(s));
     rc = sgm_overflow_check(sg, s);
+    if (rc == RTDM_OK) drain.armed = false;
     return rc ? rc : sgm_sweep_check(sg);
 }
 

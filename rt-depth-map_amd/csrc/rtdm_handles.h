@@ -156,9 +156,12 @@ struct rtdm_estimator {
 
 namespace rtdm {
 
-// api_bm.hip.  bm_run_chunk: one chunk (n <= maxB) of device-resident frames, enqueued on s.  bm_download_disp: the internal
-// plane on its way to the staging area; bm_scatter_disp, after the caller's synchronise: its rows into the caller's plane.
+// api_bm.hip.  bm_run_chunk: one chunk (n <= maxB) of device-resident frames, enqueued on s.  bm_upload_gray: a pageable gray
+// pair through the staging area into dInL / dInR, in bands.  bm_download_disp: the internal plane on its way to the staging
+// area; bm_scatter_disp, after the caller's synchronise: its rows into the caller's plane.
 int bm_check_frame(const rtdm_bm* bm, int W, int H);
+int bm_upload_gray(rtdm_bm* bm, const uint8_t* left, size_t left_pitch, const uint8_t* right, size_t right_pitch, int width, int height,
+                   hipStream_t s);
 int bm_run_chunk(rtdm_bm* bm, int n, Plane8 L, Plane8 R, int W, int H, Plane16W out, hipStream_t s);
 int bm_download_disp(rtdm_bm* bm, int W, int H, hipStream_t s);
 void bm_scatter_disp(const rtdm_bm* bm, int W, int H, int16_t* disp, size_t disp_pitch);

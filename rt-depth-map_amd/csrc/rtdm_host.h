@@ -1,8 +1,9 @@
 // rtdm_host.h -- what the files of the C ABI layer (api_*.hip) share on the host side: the last-error string, the HIPC
-// macro, device selection, the drain guard of the host entry points, and the two helpers every create / destroy pair is
-// written with (AllocList, create_failed).  Host only and private to csrc/; needs nothing but the HIP runtime.
+// macro, device selection, the drain guard of the host entry points, the one host row copy (rtdm_rows.h: copy_rows), and the two
+// helpers every create / destroy pair is written with (AllocList, create_failed).  Host only and private to csrc/.
 #pragma once
 #include "../../include/rtdm.h"
+#include "rtdm_rows.h"
 #include <hip/hip_runtime.h>
 #include <string>
 #include <vector>
