@@ -110,6 +110,21 @@ int rtdm_bm_compute_device(rtdm_bm* bm, int n, const uint8_t* d_left, const uint
                            size_t pitch, size_t frame_stride, int width, int height,
                            int16_t* d_disp, size_t disp_pitch, size_t disp_frame_stride,
                            void* hip_stream);
+/* The same with one ROI1 PER FRAME, read from device memory (rules B1-B6): d_roi1 holds n x 4 ints
+ * (x, y, w, h).  Frame f's output plane holds, byte for byte, what rtdm_bm_set_roi(bm, 1, roi f) followed by
+ * rtdm_bm_compute_device on frame f alone writes -- except that a frame whose rectangle has w <= 0 or h <= 0 is SKIPPED: no
+ * byte of its plane is written (deliberately not rtdm_bm_set_roi's meaning of an empty rectangle, "no ROI").  ROI2 is the
+ * handle's; the handle's own ROI1 is neither read nor changed.  The rectangles are device data and untrusted: they become the
+ * frame's geometry on the device in 64-bit arithmetic, and whatever they hold, nothing is read or written outside the n
+ * frames and the handle's workspaces.  The work is enqueued on hip_stream; the call adds no synchronisation, allocation or
+ * host copy of its own, and its grids depend on n, width, height and the handle's parameters only.  What it shares with
+ * rtdm_bm_compute_device stays what it is there: the strip tuner's one measured (synchronising) call per work shape with 16
+ * pairs or more per chunk, the chunks of max_batch, rtdm_bm_search_variant, the stage times (the per-frame masks count as
+ * the left-right stage).  Refusals, before any device use: those of rtdm_bm_compute_device in its order, d_roi1 among the
+ * pointers of RTDM_ERR_NULL. */
+int rtdm_bm_compute_device_rois(rtdm_bm* bm, int n, const uint8_t* d_left, const uint8_t* d_right, size_t pitch,
+                                size_t frame_stride, int width, int height, const int* d_roi1 /* n x 4: x, y, w, h */,
+                                int16_t* d_disp, size_t disp_pitch, size_t disp_frame_stride, void* hip_stream);
 /* Host variant: frames in host memory, processed in chunks; returns when `disp` is complete.  If left, right and disp are
  * page-locked (hipHostMalloc / hipHostRegister) the copies are DMA on streams of their own: chunk k+1 comes in and chunk
  * k-1 goes out while chunk k is computed (needs max_batch >= 2).  Pageable memory is staged by the HIP runtime, chunk by
@@ -574,12 +589,22 @@ int rtdm_depth_objects_labels_device(int device, int n, const int16_t* d_disp, s
  *                        below pitch * height).  n = 0 is RTDM_OK.
  * rtdm_estimate_batch_device: the same with device frames and device outputs, enqueued on hip_stream, which is synchronised
  *                        ONCE PER CHUNK (the read-back that decides the matcher's ROI1); the results are complete on the stream
- *                        when the call returns, not synchronised.  Calls that share handles must be ordered on one stream. */
+ *                        when the call returns, not synchronised.  Calls that share handles must be ordered on one stream.
+ * rtdm_estimator_set_device_roi: on != 0: the matcher takes every frame's union box from device memory
+ *                        (rtdm_bm_compute_device_rois' route: one launch set per chunk, frames without objects skipped on the
+ *                        device), so the read-back in front of the matcher is gone.  The device forms then NEVER synchronise:
+ *                        the results are complete on the stream.  The host forms synchronise once per chunk, at its end.
+ *                        Every output is that of the default mode, byte for byte, and frames without objects still leave the
+ *                        caller's entries and maps untouched.  The one difference: the matcher's ROI1 is left as the caller
+ *                        set it, not at the last frame that had objects.  The default is 0: everything as before.  No
+ *                        allocation, no synchronisation. */
 typedef struct rtdm_estimator rtdm_estimator;
 int rtdm_estimator_create(rtdm_bm* bm, rtdm_rectify* rc, rtdm_objects* ob, int max_batch, int capacity, rtdm_estimator** out);
 void rtdm_estimator_destroy(rtdm_estimator* est);
 int rtdm_estimator_set_own_pixels(rtdm_estimator* est, int on);
 int rtdm_estimator_get_own_pixels(const rtdm_estimator* est, int* on);
+int rtdm_estimator_set_device_roi(rtdm_estimator* est, int on);
+int rtdm_estimator_get_device_roi(const rtdm_estimator* est, int* on);
 int rtdm_estimate_batch(rtdm_estimator* est, int n, const uint8_t* rgb_left, size_t left_pitch, size_t left_frame_stride,
                         const uint8_t* rgb_right, size_t right_pitch, size_t right_frame_stride, const double* Q,
                         const rtdm_hsv_range* ranges, const int* range_class, int nranges, int nclasses, int min_area,

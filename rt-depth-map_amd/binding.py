@@ -124,6 +124,7 @@ SIGNATURES = {          # every entry point of include/rtdm.h: (restype, argtype
     "rtdm_bm_get_prefilter": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "rtdm_bm_compute": (C.c_int, [vp, u8p, sz, u8p, sz, C.c_int, C.c_int, i16p, sz]),
     "rtdm_bm_compute_device": (C.c_int, [vp, C.c_int, u8p, u8p, sz, sz, C.c_int, C.c_int, i16p, sz, sz, vp]),
+    "rtdm_bm_compute_device_rois": (C.c_int, [vp, C.c_int, u8p, u8p, sz, sz, C.c_int, C.c_int, vp, i16p, sz, sz, vp]),
     "rtdm_bm_compute_batch": (C.c_int, [vp, C.c_int, u8p, u8p, sz, sz, C.c_int, C.c_int, i16p, sz, sz]),
     "rtdm_bm_synchronize": (C.c_int, [vp]),
     "rtdm_bm_set_profiling": (C.c_int, [vp, C.c_int]),
@@ -198,6 +199,8 @@ SIGNATURES = {          # every entry point of include/rtdm.h: (restype, argtype
                                                    C.c_int, vp, C.c_int, vp, C.c_double, vp, vp, vp, sz, vp]),
     "rtdm_estimator_set_own_pixels": (C.c_int, [vp, C.c_int]),
     "rtdm_estimator_get_own_pixels": (C.c_int, [vp, C.POINTER(C.c_int)]),
+    "rtdm_estimator_set_device_roi": (C.c_int, [vp, C.c_int]),
+    "rtdm_estimator_get_device_roi": (C.c_int, [vp, C.POINTER(C.c_int)]),
     "rtdm_depth_objects_workspace_bytes": (sz, [C.c_int, C.c_int, C.c_int]),
     "rtdm_depth_objects_device": (C.c_int, [C.c_int, C.c_int, i16p, sz, sz, C.c_int, C.c_int, C.POINTER(C.c_double), u8p, sz, sz,
                                             C.c_int, vp, C.c_int, vp, C.c_double, vp, vp, vp, sz, vp]),

@@ -169,7 +169,7 @@ class HIPEstimator(Handle):
     detector's max_batch) frames, `capacity` objects of a frame are stored and measured."""
     _destroy = "rtdm_estimator_destroy"
 
-    def __init__(self, matcher, rectifier, detector, max_batch=1, capacity=256, own_pixels=False):
+    def __init__(self, matcher, rectifier, detector, max_batch=1, capacity=256, own_pixels=False, device_roi=False):
         self.matcher, self.rectifier, self.detector = matcher, rectifier, detector
         self.max_batch, self.capacity = int(max_batch), int(capacity)
         self._h = C.c_void_p()
@@ -177,6 +177,20 @@ class HIPEstimator(Handle):
                 "rtdm_estimator_create")
         if own_pixels:
             self.own_pixels = True
+        if device_roi:
+            self.device_roi = True
+
+    @property
+    def device_roi(self):
+        """True: the matcher reads every frame's union box from device memory (rtdm_estimator_set_device_roi) -- no read-back in
+        front of it; estimate_device then never synchronises.  Same outputs; the matcher's ROI1 stays as the caller set it."""
+        on = C.c_int()
+        B.check(B.lib().rtdm_estimator_get_device_roi(self._h, C.byref(on)), "rtdm_estimator_get_device_roi")
+        return bool(on.value)
+
+    @device_roi.setter
+    def device_roi(self, on):
+        B.check(B.lib().rtdm_estimator_set_device_roi(self._h, int(bool(on))), "rtdm_estimator_set_device_roi")
 
     @property
     def own_pixels(self):
@@ -235,7 +249,8 @@ class HIPEstimator(Handle):
         """torch device tensors: uint8 [n,H,W,3] frames (row pitch and frame stride free); d_objects uint8 [n, capacity * 32],
         d_counts int32 [n, nclasses], d_mean_cm float64 [n, capacity], d_npix int32 [n, capacity], optional d_disp int16
         [n, crop H, crop W] (row pitch and frame stride free).  Enqueued on `stream` (a raw hipStream_t value; None = the null
-        stream), which is synchronised once per chunk; the results are complete on the stream, not synchronised.  d_measures:
+        stream), which is synchronised once per chunk (with device_roi: never); the results are complete on the stream, not
+        synchronised.  d_measures:
         uint8 [n, capacity * 88] -- the stored objects are also measured (rtdm_estimate_batch_measured_device) with `measure`, a
         MeasureParams (None: the defaults); view a host copy as MEASURE_DTYPE."""
         import torch

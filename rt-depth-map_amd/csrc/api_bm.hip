@@ -1,6 +1,7 @@
 // api_bm.hip -- rtdm_bm, the StereoBM counterpart: parameter validation (cv::StereoBM::compute's checks, SURVEY.md Appendix
 // A.1), geometry, staging copies and the launches  K1 prefilter -> K2 search -> K3 left-right check -> K4 speckle filter.
 #include "rtdm_handles.h"
+#include "rtdm_bm_geom.h"
 
 using namespace rtdm;
 
@@ -130,9 +131,18 @@ int rtdm_bm_get_prefilter(const rtdm_bm* bm, int* preFilterType, int* preFilterS
     return RTDM_OK;
 }
 
+// what the rectangles of a frame depend on besides ROI1 (rtdm_bm_geom.h)
+static BMRoiGeom roi_geom(const rtdm_bm* bm, int W, int H)
+{
+    const rtdm_bm_params& p = bm->p;
+    return BMRoiGeom{W, H, p.numDisparities, p.minDisparity, p.blockSize / 2, p.disp12MaxDiff >= 0,
+                     {bm->roi2[0], bm->roi2[1], bm->roi2[2], bm->roi2[3]}};
+}
+
 // offsets, valid rectangle (getValidDisparityROI, clipped to the image and
 // to rows that have a full window).  Returns false when the whole frame is FILTERED.
-static bool make_geom(const rtdm_bm* bm, int W, int H, BMGeom* g)
+// roi1: the handle's (bm->roi1).  envelope: the rectangle that holds every ROI1's, what rtdm_bm_compute_device_rois searches.
+static bool make_geom(const rtdm_bm* bm, int W, int H, BMGeom* g, const int* roi1, bool envelope = false)
 {
     const rtdm_bm_params& p = bm->p;
     g->W = W; g->H = H; g->Ws = (W + 7) & ~7; g->D = p.numDisparities; g->minD = p.minDisparity;
@@ -146,26 +156,11 @@ static bool make_geom(const rtdm_bm* bm, int W, int H, BMGeom* g)
     g->cost16 = 2L * p.preFilterCap * p.blockSize * p.blockSize < 65536;
     g->mask_cols = p.disp12MaxDiff < 0;
     g->legacy = p.legacy_right_clamp;
-    int r1[4] = {0, 0, W, H}, r2[4] = {0, 0, W, H};
-    if (bm->roi1[2] > 0 && bm->roi1[3] > 0) std::copy(bm->roi1, bm->roi1 + 4, r1);
-    if (bm->roi2[2] > 0 && bm->roi2[3] > 0) std::copy(bm->roi2, bm->roi2 + 4, r2);
-    const int maxD = g->minD + g->D - 1;
-    int xmin = std::max(r1[0], r2[0] + maxD) + g->r;
-    int xmax = std::min(r1[0] + r1[2], r2[0] + r2[2] - g->minD) - g->r;
-    int ymin = std::max(r1[1], r2[1]) + g->r;
-    int ymax = std::min(r1[1] + r1[3], r2[1] + r2[3]) - g->r;
-    xmin = std::max(xmin, 0); xmax = std::min(xmax, W);
-    ymin = std::max(ymin, g->r); ymax = std::min(ymax, H - g->r);
-    g->vx0 = xmin; g->vx1 = xmax; g->vy0 = ymin; g->vy1 = ymax;
-    // Columns worth searching (estimator.cpp:54 shrinks the rectangle every frame with setROI1):
-    // validateDisparity lets column x vote for x - round(d/16) in [x - maxD - 1, x - minD + 1] and
-    // reads the votes of x - floor/ceil(d/16), so a valid column depends on searched columns at
-    // most D + |minD| + 2 away.  Everything else is masked to FILTERED anyway.
-    const int reach = (p.disp12MaxDiff >= 0) ? g->D + std::abs(g->minD) + 2 : 0;
-    g->cx0 = std::max(g->lofs, xmin - reach);
-    g->cx1 = std::min(std::min(W, g->lofs + g->width1), xmax + reach);
-    if (g->lofs >= W || g->rofs >= W || g->width1 < 1) return false;
-    return xmax > xmin && ymax > ymin;
+    // the valid rectangle and the columns worth searching: rtdm_bm_geom.h, shared with the kernels of the per-frame ROIs
+    const BMRoiRect q = bm_roi_rect(roi_geom(bm, W, H), roi1, envelope);
+    g->vx0 = q.vx0; g->vx1 = q.vx1; g->vy0 = q.vy0; g->vy1 = q.vy1;
+    g->cx0 = q.cx0; g->cx1 = q.cx1;
+    return q.any != 0;
 }
 
 static void stage_begin(rtdm_bm* bm, int stage, int frames, hipStream_t s, StageEvent* ev)
@@ -183,13 +178,10 @@ static void stage_end(rtdm_bm* bm, hipStream_t s, StageEvent* ev)
 }
 
 // Fill + prefilter + SAD search of a chunk (VALU bound); *any = false: the whole frame is FILTERED, nothing follows.
-static int chunk_front(rtdm_bm* bm, int n, Plane8 L, Plane8 R, int W, int H, Plane16W disp, hipStream_t s, BMGeom* gout,
-                       bool* anyout)
+// g, any: make_geom's, under the handle's ROI1 or (rtdm_bm_compute_device_rois) the envelope of all of them.
+static int chunk_front(rtdm_bm* bm, int n, Plane8 L, Plane8 R, int W, int H, Plane16W disp, hipStream_t s, const BMGeom& g, bool any)
 {
     const rtdm_bm_params& p = bm->p;
-    BMGeom& g = *gout;
-    const bool any = make_geom(bm, W, H, &g);
-    *anyout = any;
     if (!any) { launch_fill16(disp, 0, W, 0, H, n, g.filtered, s); return RTDM_OK; }
     // the search kernels write columns [cx0, cx1) of the valid rows; everything else is FILTERED
     // (+ the speckle filter's run counts = 0); the fill rides in the prefilter's launch
@@ -251,11 +243,57 @@ int rtdm::bm_run_chunk(rtdm_bm* bm, int n, Plane8 L, Plane8 R, int W, int H, Pla
     const bool direct = internal || ((W & 7) == 0 && (((size_t)out.base | (out.pitch_e * 2) | (out.frame_e * 2)) & 15) == 0);
     const Plane16W disp = direct ? out : bm_internal_plane(bm, W, H);
     BMGeom g;
-    bool any = false;
-    int rc = chunk_front(bm, n, L, R, W, H, disp, s, &g, &any);
+    const bool any = make_geom(bm, W, H, &g, bm->roi1);
+    int rc = chunk_front(bm, n, L, R, W, H, disp, s, g, any);
     if (rc) return rc;
     if (any) { rc = chunk_back(bm, n, W, H, disp, g, s); if (rc) return rc; }
     if (!direct) launch_copy16(disp, out, W, H, n, s);
+    HIPC(hipGetLastError());
+    return RTDM_OK;
+}
+
+// bm_run_chunk with frame f under ROI1 = d_rois[f] (device memory; w <= 0 or h <= 0: the frame is skipped), rules B1-B4 of
+// DESIGN.md section 4.19.  The handle's ROI1 is not read.  Always on the handle's internal plane, where the results stay;
+// out.base != null: the planes of the frames that are not skipped are copied there.  The route:
+//   front    fill, prefilter and search ONCE for the chunk under the envelope of every ROI1 (make_geom): the search is per
+//            pixel, so further searched columns and rows change no searched value
+//   mask     SEARCHED: every frame gets the state its own restricted search leaves -- FILTERED outside its searched columns
+//            and valid rows, so that exactly the columns vote that vote there
+//   check    the left-right check with the envelope's valid rectangle, without the speckle init (its run heads would be stale
+//            after the next mask)
+//   mask     VALID: the frame's own valid rectangle (inside it the check has seen what the restricted path's sees)
+//   speckle  from SpkHeads::NONE, as where the check is off: FILTERED pixels join no component
+// With the check off the two masks are one (BOTH).  The masks' launches count as the left-right stage for the stage times.
+int rtdm::bm_run_chunk_rois(rtdm_bm* bm, int n, Plane8 L, Plane8 R, int W, int H, const int* d_rois, Plane16W out, hipStream_t s)
+{
+    const rtdm_bm_params& p = bm->p;
+    const Plane16W disp = bm_internal_plane(bm, W, H);
+    BMGeom g;
+    const bool any = make_geom(bm, W, H, &g, nullptr, true);
+    int rc = chunk_front(bm, n, L, R, W, H, disp, s, g, any);
+    if (rc) return rc;
+    if (any) {
+        const BMRoiGeom G = roi_geom(bm, W, H);
+        const bool speckle = p.speckleRange >= 0 && p.speckleWindowSize > 0;
+        const bool lr = p.disp12MaxDiff >= 0;
+        StageEvent ev;
+        stage_begin(bm, RTDM_STAGE_LRCHECK, n, s, &ev);
+        launch_roi_mask(lr ? RoiMask::SEARCHED : RoiMask::BOTH, disp, G, d_rois, n, g.filtered, s);
+        if (lr) {
+            const LrPlan lp = plan_lrcheck(g, p.disp12MaxDiff, 0, n, false, rows_aligned(disp, bm->dCost, nullptr, W));
+            launch_lrcheck(lp, disp, bm->dCost, g, SpkBuffers{}, s);
+            launch_roi_mask(RoiMask::VALID, disp, G, d_rois, n, g.filtered, s);
+        }
+        stage_end(bm, s, &ev);
+        if (speckle) {
+            const SpkBuffers wk{bm->dLabel, bm->dSize, bm->dRuns, bm->dRowCnt, bm->dHead};
+            stage_begin(bm, RTDM_STAGE_SPECKLE, n, s, &ev);
+            const SpkPlan sp = plan_speckle(W, g.Ws, H, n, SpkHeads::NONE, 1, g.vy0, g.vy1, rows_aligned(disp, nullptr, nullptr, W));
+            launch_speckle(sp, disp, wk, g.filtered, p.speckleWindowSize, p.speckleRange, s);
+            stage_end(bm, s, &ev);
+        }
+    }
+    if (out.base) launch_copy16_rois(disp, out, W, H, n, d_rois, s);
     HIPC(hipGetLastError());
     return RTDM_OK;
 }
@@ -285,6 +323,29 @@ int rtdm_bm_compute_device(rtdm_bm* bm, int n, const uint8_t* d_left, const uint
         Plane8 R{d_right + (size_t)i0 * frame_stride, pitch, frame_stride};
         Plane16W O{d_disp + (size_t)i0 * (disp_frame_stride / 2), disp_pitch / 2, disp_frame_stride / 2};
         rc = bm_run_chunk(bm, m, L, R, width, height, O, s);
+        if (rc) return rc;
+    }
+    return RTDM_OK;
+}
+
+int rtdm_bm_compute_device_rois(rtdm_bm* bm, int n, const uint8_t* d_left, const uint8_t* d_right, size_t pitch,
+                                size_t frame_stride, int width, int height, const int* d_roi1, int16_t* d_disp, size_t disp_pitch,
+                                size_t disp_frame_stride, void* hip_stream)
+{
+    if (!bm || !d_left || !d_right || !d_roi1 || !d_disp) return RTDM_ERR_NULL;
+    if (n <= 0) return RTDM_ERR_BAD_SIZE;
+    int rc = bm_check_frame(bm, width, height);
+    if (rc) return rc;
+    if (pitch < (size_t)width || disp_pitch < (size_t)width * 2 || (disp_pitch & 1) || (disp_frame_stride & 1))
+        return RTDM_ERR_BAD_SIZE;
+    HIPC(hipSetDevice(bm->device));
+    hipStream_t s = (hipStream_t)hip_stream;
+    for (int i0 = 0; i0 < n; i0 += bm->maxB) {
+        const int m = std::min(bm->maxB, n - i0);
+        Plane8 L{d_left + (size_t)i0 * frame_stride, pitch, frame_stride};
+        Plane8 R{d_right + (size_t)i0 * frame_stride, pitch, frame_stride};
+        Plane16W O{d_disp + (size_t)i0 * (disp_frame_stride / 2), disp_pitch / 2, disp_frame_stride / 2};
+        rc = bm_run_chunk_rois(bm, m, L, R, width, height, d_roi1 + 4 * (size_t)i0, O, s);
         if (rc) return rc;
     }
     return RTDM_OK;

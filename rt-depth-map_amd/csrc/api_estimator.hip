@@ -1,6 +1,8 @@
 // api_estimator.hip -- rtdm_estimator: the loop body on frame batches, host and device form.
 #include "rtdm_handles.h"
 
+#include <numeric>
+
 using namespace rtdm;
 
 void rtdm_estimator_destroy(rtdm_estimator* E)
@@ -34,6 +36,21 @@ int rtdm_estimator_get_own_pixels(const rtdm_estimator* E, int* on)
 {
     if (!E || !on) return RTDM_ERR_NULL;
     *on = E->dLabels != nullptr;
+    return RTDM_OK;
+}
+
+// B-rules of DESIGN.md section 4.19 for the estimator: a flag, nothing is allocated or waited for.
+int rtdm_estimator_set_device_roi(rtdm_estimator* E, int on)
+{
+    if (!E) return RTDM_ERR_NULL;
+    E->deviceRoi = on != 0;
+    return RTDM_OK;
+}
+
+int rtdm_estimator_get_device_roi(const rtdm_estimator* E, int* on)
+{
+    if (!E || !on) return RTDM_ERR_NULL;
+    *on = E->deviceRoi;
     return RTDM_OK;
 }
 
@@ -153,7 +170,8 @@ struct EstChunk {
     hipMemcpyKind kind;
 };
 
-// Steps 1 to 6 of a chunk of m frames, enqueued on s with one synchronisation in the middle; total[j]: the objects of frame j.
+// Steps 1 to 6 of a chunk of m frames, enqueued on s with one synchronisation in the middle (none with
+// rtdm_estimator_set_device_roi); total[j]: the objects of frame j (-1: not known on the host).
 static int est_chunk(rtdm_estimator* E, int m, const EstChunk& d, const EstIo& c, hipStream_t s, long* total)
 {
     rtdm_bm* bm = E->bm; rtdm_rectify* rc = E->rc; rtdm_objects* ob = E->ob;
@@ -168,6 +186,29 @@ static int est_chunk(rtdm_estimator* E, int m, const EstChunk& d, const EstIo& c
     int st = objects_run_chunk(ob, m, E->dCrop, E->cpitch, cframe, c.C, c.min_area, c.zero_border, nullptr, 0, 0, d.obj, cap, d.counts, E->dRois, s,
                                CcLabelsOut{E->dLabels, lpitch, lplane, nullptr});
     if (st) return st;
+    const DepthObjects a{bm->dOut, O.pitch_e, O.frame_e, E->dLabels ? (const uint8_t*)E->dLabels : ob->dMaskOut,
+                         E->dLabels ? lpitch : ob->mpitch, E->dLabels ? lplane : ob->mpitch * H, d.obj, d.counts, m, W, H, K, cap, 0};
+    if (E->deviceRoi) {
+        // 3 + 4 without the host (rtdm_estimator_set_device_roi): the matcher takes the union boxes where the detector left them --
+        // a frame without kept objects has a box of negative width there (k_cc_scan, k_cc_roi), which is that call's "skipped" --
+        // in one launch set for the chunk; total[] stays unknown here (-1), the host form counts after its one synchronisation
+        std::fill(total, total + m, -1L);
+        st = bm_run_chunk_rois(bm, m, Plane8{E->dGray[0], rc->gpitch, gframe}, Plane8{E->dGray[1], rc->gpitch, gframe}, W, H, E->dRois,
+                               Plane16W{nullptr, 0, 0}, s);
+        if (st) return st;
+        // 5 as below: a frame without objects has no object to measure
+        launch_depth_objects(a, c.q, c.unit, E->dWork, d.mean, d.npix, s, E->dLabels != nullptr);
+        if (d.meas) launch_measure(a, c.mP, c.mQ, E->dMeasWork, d.meas, s, E->dLabels != nullptr);
+        HIPC(hipGetLastError());
+        // 6. device form: the copy skips the frames without objects on the device; host form: every plane comes to the staging
+        // area in one copy (the internal planes are contiguous), and the caller of this function scatters those with objects
+        if (d.disp && d.kind == hipMemcpyDeviceToDevice)
+            launch_copy16_rois(O, Plane16W{(int16_t*)d.disp, d.disp_pitch / 2, d.disp_stride / 2}, W, H, m, E->dRois, s);
+        else if (d.disp)
+            HIPC(hipMemcpy2DAsync(d.disp, d.disp_pitch, O.base, O.pitch_e * 2, (size_t)W * 2, (size_t)H * m, d.kind, s));
+        HIPC(hipGetLastError());
+        return RTDM_OK;
+    }
     // 3. the one read-back in front of the matcher: per-class counts and union boxes
     HIPC(hipMemcpyAsync(E->hCounts, d.counts, (size_t)m * K * sizeof(int), hipMemcpyDeviceToHost, s));
     HIPC(hipMemcpyAsync(E->hRois, E->dRois, (size_t)m * 4 * sizeof(int), hipMemcpyDeviceToHost, s));
@@ -194,8 +235,6 @@ static int est_chunk(rtdm_estimator* E, int m, const EstChunk& d, const EstIo& c
     }
     // 5. every object of the chunk under its own class's mask, against its own frame's plane of the matcher
     // (with own pixels: under its own label on its class's label plane)
-    const DepthObjects a{bm->dOut, O.pitch_e, O.frame_e, E->dLabels ? (const uint8_t*)E->dLabels : ob->dMaskOut,
-                         E->dLabels ? lpitch : ob->mpitch, E->dLabels ? lplane : ob->mpitch * H, d.obj, d.counts, m, W, H, K, cap, 0};
     launch_depth_objects(a, c.q, c.unit, E->dWork, d.mean, d.npix, s, E->dLabels != nullptr);
     if (d.meas) launch_measure(a, c.mP, c.mQ, E->dMeasWork, d.meas, s, E->dLabels != nullptr);     // ... and measured (G1-G10)
     HIPC(hipGetLastError());
@@ -238,14 +277,22 @@ int rtdm_estimate_batch_measured(rtdm_estimator* E, int n, const uint8_t* rgb_le
         long total[64];                                   // (a detector serves at most 64 frames per launch)
         st = est_chunk(E, m, d, io, s, total);
         if (st) return st;
-        std::copy(E->hCounts, E->hCounts + (size_t)m * K, counts + (size_t)i0 * K);
-        if (std::count(total, total + m, 0L) == m) continue;
         const size_t slots = (size_t)m * cap;
+        if (E->deviceRoi)                                 // the counts come back with the results, behind everything else
+            HIPC(hipMemcpyAsync(E->hCounts, d.counts, (size_t)m * K * sizeof(int), hipMemcpyDeviceToHost, s));
+        else {
+            std::copy(E->hCounts, E->hCounts + (size_t)m * K, counts + (size_t)i0 * K);
+            if (std::count(total, total + m, 0L) == m) continue;
+        }
         HIPC(hipMemcpyAsync(E->hObj, d.obj, slots * sizeof(CcObject), hipMemcpyDeviceToHost, s));
         HIPC(hipMemcpyAsync(E->hMean, d.mean, slots * sizeof(double), hipMemcpyDeviceToHost, s));
         HIPC(hipMemcpyAsync(E->hNpix, d.npix, slots * sizeof(int), hipMemcpyDeviceToHost, s));
         if (mp) HIPC(hipMemcpyAsync(E->hMeas, d.meas, slots * sizeof(MeasRecord), hipMemcpyDeviceToHost, s));
         HIPC(hipStreamSynchronize(s));
+        if (E->deviceRoi) {                               // the chunk's one synchronisation lies behind: now the host counts
+            std::copy(E->hCounts, E->hCounts + (size_t)m * K, counts + (size_t)i0 * K);
+            for (int j = 0; j < m; ++j) total[j] = std::accumulate(E->hCounts + (size_t)j * K, E->hCounts + (size_t)(j + 1) * K, 0L);
+        }
         for (int j = 0; j < m; ++j) {
             const size_t stored = (size_t)std::min<long>(total[j], cap), at = (size_t)(i0 + j) * cap, from = (size_t)j * cap;
             if (!stored) continue;

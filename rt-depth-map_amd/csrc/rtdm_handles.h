@@ -144,6 +144,7 @@ struct rtdm_estimator {
     rtdm::CcObject* dObj; int* dCounts; double* dMean; int* dNpix;      // host form: [chunk] x cap, [chunk] x RTDM_MAX_CLASSES
     int* dRois;                    // [chunk] x 4
     void* dWork; size_t workBytes; // rtdm_depth_objects_device's workspace for a chunk
+    bool deviceRoi;                // rtdm_estimator_set_device_roi: the matcher reads dRois itself, no read-back in front of it
     int32_t* dLabels;              // rtdm_estimator_set_own_pixels: [chunk] x [detector's max_classes] planes of rh x rw ints, or null
     // rtdm_estimate_batch_measured: made by the first measured call -- the measurement's workspace for a chunk, and for the
     // host form the chunk's records on the device and page-locked
@@ -163,6 +164,9 @@ int bm_check_frame(const rtdm_bm* bm, int W, int H);
 int bm_upload_gray(rtdm_bm* bm, const uint8_t* left, size_t left_pitch, const uint8_t* right, size_t right_pitch, int width, int height,
                    hipStream_t s);
 int bm_run_chunk(rtdm_bm* bm, int n, Plane8 L, Plane8 R, int W, int H, Plane16W out, hipStream_t s);
+// ... with frame f under ROI1 = d_rois[f] from device memory (w <= 0 or h <= 0: skipped); the results stay on the internal
+// plane, and go to `out` as well where out.base is not null (rtdm_bm_compute_device_rois)
+int bm_run_chunk_rois(rtdm_bm* bm, int n, Plane8 L, Plane8 R, int W, int H, const int* d_rois, Plane16W out, hipStream_t s);
 int bm_download_disp(rtdm_bm* bm, int W, int H, hipStream_t s);
 void bm_scatter_disp(const rtdm_bm* bm, int W, int H, int16_t* disp, size_t disp_pitch);
 // the handle's internal disparity plane for W x H frames: rows of Ws = W rounded up to 8 elements (see bm_run_chunk)

@@ -188,6 +188,17 @@ void launch_speckle(const SpkPlan& plan, Plane16W disp, const SpkBuffers& wk, in
 // n frames of W x H int16: src -> dst (any pitches)
 void launch_copy16(Plane16W src, Plane16W dst, int W, int H, int n, hipStream_t stream);
 
+// The row stage under per-frame ROIs from device memory (k_bm_rois.hip, rules B1-B6 in DESIGN.md section 4.19).  d_rois: n x
+// (x, y, w, h) ints on the device; a frame with w <= 0 or h <= 0 is skipped: neither kernel touches it.  G: rtdm_bm_geom.h.
+// launch_roi_mask: every element of `disp` (the handle's internal plane: 16-byte aligned rows of W rounded up to 8 elements)
+// outside the frame's own rectangle becomes `filtered` -- SEARCHED: [cx0, cx1) x [vy0, vy1), what the frame's own restricted
+// search would have written; VALID: its valid rectangle; BOTH: their intersection (the left-right check is off).
+struct BMRoiGeom;
+enum class RoiMask { SEARCHED, VALID, BOTH };
+void launch_roi_mask(RoiMask what, Plane16W disp, const BMRoiGeom& G, const int* d_rois, int n, int filtered, hipStream_t stream);
+// launch_copy16 for the frames that are not skipped
+void launch_copy16_rois(Plane16W src, Plane16W dst, int W, int H, int n, const int* d_rois, hipStream_t stream);
+
 // K5: erode / dilate / dilate / erode with the 10x10 ellipse; tmp = n*W*H bytes scratch.
 void launch_morph_open_close(Plane8 in, Plane8W out, uint8_t* tmp0, uint8_t* tmp1, int W, int H,
                              int n, hipStream_t stream);

@@ -58,6 +58,16 @@ int HIPMatcherCore::computeBatch(int n, const uint8_t* left, const uint8_t* righ
     return status_;
 }
 
+int HIPMatcherCore::computeDeviceRois(int n, const uint8_t* dLeft, const uint8_t* dRight, size_t step, size_t frameStride, int rows,
+                                      int cols, const Rect* dRois, int16_t* dOut, size_t outStep, size_t outFrameStride, void* hipStream)
+{
+    if (!bm_) return status_ != RTDM_OK ? status_ : RTDM_ERR_NO_DEVICE;
+    static_assert(sizeof(Rect) == 4 * sizeof(int), "a Rect is the four ints of a device ROI");
+    status_ = rtdm_bm_compute_device_rois(bm_, n, dLeft, dRight, step, frameStride, cols, rows, reinterpret_cast<const int*>(dRois),
+                                          dOut, outStep, outFrameStride, hipStream);
+    return status_;
+}
+
 int HIPMatcherCore::computeDepth(const uint8_t* left, size_t leftStep, const uint8_t* right, size_t rightStep, int rows,
                                  int cols, const double* Q, const uint8_t* mask, size_t maskStep, const Rect* regions,
                                  int nregions, double calibrationUnit, double* meanCm, int* counts, int16_t* out, size_t outStep)
@@ -119,7 +129,9 @@ int HIPObjectsCore::estimator(HIPMatcherCore& matcher, HIPRectifierCore& rectifi
         if (status_ != RTDM_OK) return status_;
         estBm_ = matcher.handle(); estRc_ = rectifier.handle(); estBatch_ = maxBatch; estCap_ = capacity;
     }
-    return status_ = rtdm_estimator_set_own_pixels(est_, ownPixels_ ? 1 : 0);   // (nothing happens unless the setting changed)
+    status_ = rtdm_estimator_set_own_pixels(est_, ownPixels_ ? 1 : 0);          // (nothing happens unless the setting changed)
+    if (status_ != RTDM_OK) return status_;
+    return status_ = rtdm_estimator_set_device_roi(est_, deviceRoi_ ? 1 : 0);
 }
 int HIPObjectsCore::estimateBatch(HIPMatcherCore& matcher, HIPRectifierCore& rectifier, int maxBatch, int capacity, int n,
                                   const uint8_t* rgbLeft, size_t leftStep, size_t leftFrameStride, const uint8_t* rgbRight,
@@ -164,6 +176,7 @@ int HIPObjectsCore::detectDevice(int n, const uint8_t* dRgb, size_t step, size_t
                                                 reinterpret_cast<rtdm_region*>(dRois), hipStream);
 }
 void HIPObjectsCore::setOwnPixels(bool on) { ownPixels_ = on; }
+void HIPObjectsCore::setDeviceRoi(bool on) { deviceRoi_ = on; }
 int HIPObjectsCore::detectLabelsDevice(int n, const uint8_t* dRgb, size_t step, size_t frameStride, int minObjSize, bool zeroBorder,
                                        uint8_t* dMasks, size_t maskStep, size_t maskPlaneStride, rtdm_object* dObjects, int capacity,
                                        int* dCounts, Rect* dRois, int32_t* dLabels, size_t labelStep, size_t labelPlaneStride,

@@ -49,6 +49,13 @@ public:
     int computeBatch(int n, const uint8_t* left, const uint8_t* right, size_t step, size_t frameStride,
                      int rows, int cols, int16_t* out, size_t outStep, size_t outFrameStride);
 
+    // n device-resident frames, frame f under ROI1 = dRois[f] read from DEVICE memory (rtdm_bm_compute_device_rois, rules B1-B6 of
+    // DESIGN.md section 4.19): what setROI1(roi f) + a device compute of frame f alone writes, in one launch set for all of them;
+    // a frame whose rectangle has width <= 0 or height <= 0 is skipped.  Enqueued on hipStream, not synchronised; this
+    // object's own ROI1 is not touched.
+    int computeDeviceRois(int n, const uint8_t* dLeft, const uint8_t* dRight, size_t step, size_t frameStride, int rows, int cols,
+                          const Rect* dRois, int16_t* dOut, size_t outStep, size_t outFrameStride, void* hipStream);
+
     // The caller's next three lines in one call (estimator.cpp:75-77): left_disp /= 16., reprojectImageTo3D with
     // Q (row-major 4x4), calc_depth over `regions` under `mask`; the disparity stays on the device unless `out`
     // is given.  meanCm[i] = mean Z * calibrationUnit / 10, counts[i] = pixels that entered the mean.
@@ -265,6 +272,10 @@ public:
     // across the estimator handles this object makes.
     void setOwnPixels(bool on);
     bool ownPixels() const { return ownPixels_; }
+    // estimateBatch lets the matcher read every frame's union box from device memory (rtdm_estimator_set_device_roi): no
+    // read-back in front of the matcher, same outputs; the matcher's ROI1 stays as its owner set it.  Kept like setOwnPixels.
+    void setDeviceRoi(bool on);
+    bool deviceRoi() const { return deviceRoi_; }
     // estimateFrame for the classes of setRanges: every object with its class, measured under its class's mask.  Returns the
     // number of objects (only maxObjects are stored) or a negative status.
     int estimateFrameClasses(HIPMatcherCore& matcher, HIPRectifierCore& rectifier, const uint8_t* rgbLeft, size_t leftStep,
@@ -298,7 +309,7 @@ private:
     rtdm_bm* estBm_ = nullptr;
     rtdm_rectify* estRc_ = nullptr;
     int estBatch_ = 0, estCap_ = 0;
-    bool ownPixels_ = false;
+    bool ownPixels_ = false, deviceRoi_ = false;
     rtdm_hsv_range range_;
     rtdm_hsv_range ranges_[RTDM_MAX_HSV_RANGES];
     int cls_[RTDM_MAX_HSV_RANGES];

@@ -112,13 +112,25 @@ class HIPMatcher(Handle):
                                               disp.ctypes.data, disp.strides[1], disp.strides[0]), "rtdm_bm_compute_batch")
         return disp
 
-    def compute_device(self, d_left, d_right, d_disp, stream=None):
+    def compute_device(self, d_left, d_right, d_disp, stream=None, rois=None):
         """torch CUDA tensors: uint8 [n,H,W] x2, int16 [n,H,W]; enqueued on ``stream`` (a raw
-        hipStream_t value, e.g. torch.cuda.current_stream().cuda_stream), not synchronised."""
+        hipStream_t value, e.g. torch.cuda.current_stream().cuda_stream), not synchronised.
+        rois: a contiguous int32 [n, 4] device tensor (x, y, w, h) -- frame f runs under ROI1 = rois[f], read on the device
+        (rtdm_bm_compute_device_rois); a frame with w <= 0 or h <= 0 is skipped, its plane keeps what it held."""
         n, H, W = d_left.shape
         assert d_left.is_contiguous() and d_right.is_contiguous() and d_disp.is_contiguous()
-        B.check(B.lib().rtdm_bm_compute_device(self._h, n, d_left.data_ptr(), d_right.data_ptr(), W, W * H, W, H,
-                                               d_disp.data_ptr(), W * 2, W * H * 2, stream), "rtdm_bm_compute_device")
+        if rois is None:
+            B.check(B.lib().rtdm_bm_compute_device(self._h, n, d_left.data_ptr(), d_right.data_ptr(), W, W * H, W, H,
+                                                   d_disp.data_ptr(), W * 2, W * H * 2, stream), "rtdm_bm_compute_device")
+            return
+        import torch
+        if not isinstance(rois, torch.Tensor) or rois.dtype != torch.int32 or tuple(rois.shape) != (n, 4) or not rois.is_contiguous() \
+                or rois.device != d_left.device:
+            raise ValueError("rois must be a contiguous int32 tensor (%d, 4) on %s; got %s" % (
+                n, d_left.device, "%s %s on %s" % (rois.dtype, tuple(rois.shape), rois.device) if isinstance(rois, torch.Tensor)
+                else type(rois).__name__))
+        B.check(B.lib().rtdm_bm_compute_device_rois(self._h, n, d_left.data_ptr(), d_right.data_ptr(), W, W * H, W, H, rois.data_ptr(),
+                                                    d_disp.data_ptr(), W * 2, W * H * 2, stream), "rtdm_bm_compute_device_rois")
 
     def synchronize(self):
         B.check(B.lib().rtdm_bm_synchronize(self._h), "rtdm_bm_synchronize")

@@ -8,6 +8,13 @@ class; run on the GPU box), one JSON line per row:
         (b) rtdm_depth_objects_device on the 16 maps, masks and device lists of those frames (HIP events around `reps` calls,
         workspace made once) against rtdm_depth_stats_device on the same maps: one call per frame and class, host clock (that
         call allocates, synchronises and frees).
+        (c) rtdm_estimate_batch_device with n in {1, 4, 16} device frame pairs per call, default mode against
+        rtdm_estimator_set_device_roi on the same handles: host clock around `reps` calls and one
+        synchronisation of the stream (the default mode synchronises inside); the two alternate.
+        (d) the matcher alone on the 16 rectified gray pairs and their 16 different union boxes: one
+        rtdm_bm_compute_device_rois, the loop of rtdm_bm_set_roi + rtdm_bm_compute_device it replaces, and one ROI-free
+        rtdm_bm_compute_device of the 16 frames (the floor of the route: its search is the same launch); host clock as in (c).
+        A library without the new entry points (an older commit, for a comparison in one session) gets the rows it can run.
 Per row: the median and the range over `rounds` timings after 2 warm-up calls, in microseconds per frame.  The frames are
 tests/rectify_util.red_scene seeds 1 .. 16 with the objects of the right half turned blue."""
 import importlib, json, os, statistics, sys, time
@@ -126,3 +133,88 @@ print(json.dumps(dict(row="(b) rtdm_depth_objects_device, 16 frames per call, ag
                       objects_device_us_per_frame=stats(t_new), stats_device_us_per_frame=stats(t_old),
                       ratio_of_medians=round(statistics.median(t_new) / statistics.median(t_old), 3))))
 det.close(); rect.close()
+
+# (c) the device forms, and (d) the matcher alone
+HAVE_ROIS = "rtdm_bm_compute_device_rois" in pkg.binding.EXPORTS
+stream = torch.cuda.Stream()
+
+
+def host_timed(fn, frames):
+    stream.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        fn()
+    stream.synchronize()
+    return (time.perf_counter() - t0) * 1e6 / reps / frames
+
+
+def alternate(fns, frames):
+    for fn in fns:
+        for _ in range(2):
+            fn()
+    stream.synchronize()
+    t = [[] for _ in fns]
+    for _ in range(rounds):
+        for k, fn in enumerate(fns):
+            t[k].append(host_timed(fn, frames))
+    return t
+
+
+for n in (1, 4, 16):
+    rect = pkg.HIPRectifier(*maps, roi=c["roi"], max_batch=n)
+    m = pkg.HIPMatcher(numOfDisparities=D, blockSize=BLOCK, width=rw, height=rh, max_batch=n)
+    det = pkg.HIPObjectDetector(rw, rh, max_batch=n, max_classes=2)
+    est = pkg.HIPEstimator(m, rect, det, max_batch=n, capacity=CAP)
+    d_l, d_r = torch.from_numpy(lefts[:n]).cuda(), torch.from_numpy(rights[:n]).cuda()
+    outs = []
+    for _ in range(2):
+        outs.append((torch.zeros((n, CAP * 32), dtype=torch.uint8, device="cuda"), torch.zeros((n, 2), dtype=torch.int32, device="cuda"),
+                     torch.zeros((n, CAP), dtype=torch.float64, device="cuda"), torch.zeros((n, CAP), dtype=torch.int32, device="cuda"),
+                     torch.zeros((n, rh, rw), dtype=torch.int16, device="cuda")))
+
+    def call(mode, o):
+        if HAVE_ROIS:
+            est.device_roi = mode
+        est.estimate_device(d_l, d_r, c["Q"], RANGES, None, o[0], o[1], o[2], o[3], d_disp=o[4], min_area=MIN_AREA, stream=stream.cuda_stream)
+
+    fns = [lambda: call(False, outs[0])] + ([lambda: call(True, outs[1])] if HAVE_ROIS else [])
+    t = alternate(fns, n)
+    if HAVE_ROIS:
+        assert all(torch.equal(a, b) for a, b in zip(outs[0], outs[1])), "the two modes disagree"
+    row = dict(row="(c) rtdm_estimate_batch_device, default mode against rtdm_estimator_set_device_roi", n=n, crop=[rw, rh], reps=reps,
+               rounds=rounds, default_us_per_frame=stats(t[0]))
+    if HAVE_ROIS:
+        row.update(device_roi_us_per_frame=stats(t[1]), device_roi_over_default=round(statistics.median(t[1]) / statistics.median(t[0]), 3))
+    print(json.dumps(row), flush=True)
+    if n == NMAX:
+        d_gl = torch.zeros((n, rh, rw), dtype=torch.uint8, device="cuda"); d_gr = torch.zeros_like(d_gl)
+        rect.gray_device(d_l, d_r, d_gl, d_gr, stream=stream.cuda_stream)
+        boxes = [union(o) for o in last[0]]
+        rois = [(b[0], b[1], b[2] - b[0], b[3] - b[1]) for b in boxes]
+        assert len(set(rois)) == n
+        d_rois = torch.tensor(rois, dtype=torch.int32).cuda()
+        d_a, d_b, d_c = (torch.zeros((n, rh, rw), dtype=torch.int16, device="cuda") for _ in range(3))
+        L = pkg.binding.lib()
+
+        def loop():
+            for f in range(n):
+                m.setROI1(rois[f])
+                pkg.binding.check(L.rtdm_bm_compute_device(m._h, 1, d_gl[f].data_ptr(), d_gr[f].data_ptr(), rw, rw * rh, rw, rh, d_b[f].data_ptr(),
+                                                           rw * 2, rw * rh * 2, stream.cuda_stream), "rtdm_bm_compute_device")
+
+        def whole():
+            m.setROI1((0, 0, 0, 0))
+            m.compute_device(d_gl, d_gr, d_c, stream=stream.cuda_stream)
+
+        fns = [loop, whole] + ([lambda: m.compute_device(d_gl, d_gr, d_a, stream=stream.cuda_stream, rois=d_rois)] if HAVE_ROIS else [])
+        t = alternate(fns, n)
+        row = dict(row="(d) the matcher alone, 16 pairs with 16 different ROIs", crop=[rw, rh], reps=reps, rounds=rounds,
+                   loop_set_roi_compute_device_us_per_frame=stats(t[0]), roi_free_compute_device_us_per_frame=stats(t[1]),
+                   search_variant=m.search_variant)
+        if HAVE_ROIS:
+            assert torch.equal(d_a, d_b), "rtdm_bm_compute_device_rois and the loop disagree"
+            row.update(compute_device_rois_us_per_frame=stats(t[2]),
+                       rois_over_loop=round(statistics.median(t[2]) / statistics.median(t[0]), 3),
+                       rois_over_roi_free=round(statistics.median(t[2]) / statistics.median(t[1]), 3))
+        print(json.dumps(row), flush=True)
+    est.close(); det.close(); m.close(); rect.close()
