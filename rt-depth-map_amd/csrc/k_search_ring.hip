@@ -144,6 +144,19 @@ struct RingCfg {
     // LDS read addresses of a row: three registers that advance (3 VALU per row) or recomputed from the slot index (6 VALU,
     // no registers held) -- the latter for the two-lane configurations that sit at their three-wave register limit
     static constexpr bool ROW_PTRS = !(LPP == 2 && RING_REGS > 88 && WAVES == 3);
+    // PREFETCH: a step requests the NEXT row's pieces and windows from LDS before its own quad-SADs, into a second RowRegs
+    // set (NW * 2 + NL = 14 registers in the paired form, which has them to spare below its three-wave limit of 168), so
+    // the SADs of a step run on registers asked for a whole step earlier instead of a few instructions earlier, behind the
+    // previous step's record stores in the wave's in-order LDS queue.  Row t + 1 is resident all through step t (committed
+    // at the end of step t - 1), and the commit at the end of step t goes to another slot, that of row t + 2.
+    static constexpr bool PREFETCH = PAIR;
+    // LOAD_SETS: register sets of global loads in flight per wave.  Two: step t loads row t + 3 into the set that row t + 1
+    // left.  With the LDS read a step ahead a wave parks less on LDS, and what it parks on next is the load behind the
+    // commit (vmcnt): four sets -- row t + 5 is requested in step t, one more VGPR per set (ITEMS = 1) -- measured fastest of
+    // 2, 3, 4 and 6 (profiles/ring_prefetch_ab.txt).  The sets rotate by name (a queue, oldest first); the commit schedule,
+    // two rows ahead into four static slots, is what it was.
+    static constexpr int LOAD_SETS = PREFETCH ? 4 : 2;
+    static_assert(!PREFETCH || (STATIC_SLOTS && NSLOT == 4), "the slot of row t + 1 is a constant of the step, distinct from that of row t + 2");
 };
 
 // The form with the border-column workgroups in its grid (BORDER: single frames, batches < 16 -- a handful of scheduling rounds,
@@ -295,8 +308,8 @@ __device__ __forceinline__ __attribute__((address_space(3))) T* lds_as(uint32_t 
 // row U + R + 2 at its end.  Between the commits of steps U + 1 and U + 2 all four rows of the group are therefore resident,
 // and the owner (p, h) of column x0 + j, row k (j = h & 1, k = h >> 1) reads ITS row's left bytes at lane-constant addresses:
 // the two shared dwords and one edge byte (ds_read_u8 delivers it zero-extended; v_msad skips the three zero bytes).
-//   term():   inside step U + 2, before its commit: the row term, as u16, to terms[column][k]
-//   prefix(): behind that commit: the four terms of the column in one 8-byte read; own prefix = the carried prefix (replicated
+//   term():   inside step U + 2, before its commit: the row term, as u16, to terms[column][k]  (term_load + term)
+//   prefix(): (prefix_load + prefix) behind that commit: the four terms of the column in one 8-byte read; own prefix = the carried prefix (replicated
 //             in the column's four owners) + the terms of the rows <= k (two v_dot2_u32_u16 with lane-constant 0/1 weights), to
 //             ring[column][U + k]; the carried prefix moves on by all four
 //   back():   the prefix w rows back, ring[column][(U + k - w) mod TRIP] -- base + immediate, but for the one group where the
@@ -343,19 +356,23 @@ struct RingTexture {
             return *lds_as<const uint16_t>(a_ring + idx * 2);
         }
     }
-    __device__ __forceinline__ void term(uint32_t capb) const
+    // (term and prefix in two halves each: the reads go out at the top of their step, in FRONT of the step's read-ahead of
+    //  the next row, and are consumed behind the step's quad-SADs -- a wait for them in between would drain the read-ahead)
+    struct TermIn { uint32_t l1, l2, e; };
+    __device__ __forceinline__ TermIn term_load() const
+    { return TermIn{*lds_as<const uint32_t>(a_row), *lds_as<const uint32_t>(a_row + 4), *lds_as<const uint8_t>(a_edge)}; }
+    __device__ __forceinline__ void term(uint32_t capb, const TermIn& in) const
     {
-        const uint32_t l1 = *lds_as<const uint32_t>(a_row), l2 = *lds_as<const uint32_t>(a_row + 4);
-        const uint32_t e = *lds_as<const uint8_t>(a_edge);
+        const uint32_t l1 = in.l1, l2 = in.l2, e = in.e;
         uint32_t t = __builtin_amdgcn_sad_u8(l1, capb, 0u);
         t = __builtin_amdgcn_sad_u8(l2, capb, t);
         t = __builtin_amdgcn_msad_u8(capb, e, t);                     // (zero reference bytes are skipped)
         *lds_as<uint16_t>(a_term) = (uint16_t)t;
     }
+    __device__ __forceinline__ uint64_t prefix_load() const { return *lds_as<const uint64_t>(a_col); }
     template <int U>
-    __device__ __forceinline__ uint32_t prefix()
+    __device__ __forceinline__ uint32_t prefix(uint64_t q)
     {
-        const uint64_t q = *lds_as<const uint64_t>(a_col);
         const sel_us2 lo = __builtin_bit_cast(sel_us2, (uint32_t)q), hi = __builtin_bit_cast(sel_us2, (uint32_t)(q >> 32));
         const sel_us2 ones = __builtin_bit_cast(sel_us2, 0x00010001u);
         uint32_t own = __builtin_amdgcn_udot2(lo, __builtin_bit_cast(sel_us2, w_lo), carry, false);
@@ -459,7 +476,8 @@ __global__ __launch_bounds__(256, (RingBounds<D, WS, LPP, FUSE>::WAVES)) void k_
 
     // --- staging: item idx = one dword of the wave's copy; dword m holds copy bytes [4m, 4m+4) (biased planes) ---------
     // Unconditional loads: bytes past a row's end only ever reach lanes that are not `active`, and the prefiltered planes
-    // are allocated with 1 KB of slack behind the last row (api_bm.hip).  Two rows of loads are in flight (pre[0/1]).
+    // are allocated with 1 KB of slack behind the last row (api_bm.hip).  Two rows of loads are in flight (pre[0/1]; RingCfg::LOAD_SETS of
+    // them in the forms that queue more).
     const int row0 = ys0 - r;
     const int Hm1 = g.H - 1;
     // One load per staged dword: address = the left plane's row (wave-uniform: lives in SGPRs and advances on the scalar
@@ -479,7 +497,9 @@ __global__ __launch_bounds__(256, (RingBounds<D, WS, LPP, FUSE>::WAVES)) void k_
         loff[it] = (uint32_t)((isr ? Rbase : Lbase) + 4 * m) + (isr ? rg.rdelta : 0u);
     }
     int next_row = row0;
-    uint32_t pre[2][ITEMS];
+    constexpr int NPRE = C::LOAD_SETS;
+    constexpr bool QUEUED = NPRE > 2;               // pre[0] is the oldest row in flight, pre[NPRE - 1] the newest
+    uint32_t pre[NPRE][ITEMS];
     auto issue = [&](auto Sc) {                     // loads of the next row into register set Sc; rows past H-1 repeat H-1
         constexpr int SET = decltype(Sc)::value;
 #pragma unroll
@@ -526,6 +546,8 @@ __global__ __launch_bounds__(256, (RingBounds<D, WS, LPP, FUSE>::WAVES)) void k_
     issue(Set0{}); issue(Set1{});
     commit(Set0{}, 0); commit(Set1{}, 1);           // rows 0 and 1 -> slots 0 and 1
     issue(Set0{});                                  // row 2: committed at the end of step 0
+    if constexpr (QUEUED)                           // rows 3 .. NPRE
+        ring_for_rows(std::make_integer_sequence<int, NPRE - 2>{}, [&](auto Kc) { issue(std::integral_constant<int, decltype(Kc)::value + 1>{}); });
 
     // Output addresses: a wave-uniform frame base plus a 32-bit byte offset per lane that advances LPP rows per group
     // (the host checks that a frame's planes stay below 4 GB) -- no 64-bit multiply per store.
@@ -539,11 +561,14 @@ __global__ __launch_bounds__(256, (RingBounds<D, WS, LPP, FUSE>::WAVES)) void k_
     const bool masked_col = g.mask_cols && (col < g.vx0 || col >= g.vx1);
 
     uint32_t S[RPG][NRL];
-    // Row t is read from LDS slot t mod 3, where it was put two steps earlier.  Step t issues the global loads of row
-    // t+3 at its start and, at its end, writes row t+2 (issued one step earlier) to LDS -- BEHIND the step's quad-SADs
-    // (the empty asm on S pins that order: left alone the compiler sinks the SADs below the commit and every step then
+    // Row t is read from LDS slot t mod 3 (t mod 4 with static slots), where it was put two steps earlier.  Step t issues the
+    // global loads of row t+3 at its start and, at its end, writes row t+2 (issued one step earlier) to LDS -- BEHIND the step's
+    // quad-SADs (the empty asm on S pins that order: left alone the compiler sinks the SADs below the commit and every step then
     // waits for its loads).  Rows past the strip's last are loaded and staged too (clamped to the frame) and never read:
     // no branch in the step.
+    // The forms that queue their loads (LOAD_SETS > 2, the paired form): step t issues the loads of row t+LOAD_SETS+1 and its
+    // commit writes row t+2, issued LOAD_SETS-1 steps earlier; with PREFETCH the LDS reads of row t+1 go out at the top of
+    // step t as well, and the quad-SADs of step t run on what step t-1 requested.
     int sl_cur = 0;                                 // LDS slot of row t
     // this lane's read addresses in the slot of row t: three registers that move on by one slot per row (one v_add each
     // with a wave-uniform step; laundered so that every window offset folds into a ds_read immediate of ITS base)
@@ -570,21 +595,34 @@ __global__ __launch_bounds__(256, (RingBounds<D, WS, LPP, FUSE>::WAVES)) void k_
     };
     // Sr / Sr2: the window sums of the row (PAIR: of column x0 / x0 + 1; Sr2 is not written otherwise)
     [[maybe_unused]] uint32_t tback = 0, tpre = 0;  // PAIR: the owned row's texture prefix sum and the one w rows back
-    auto step = [&](auto Kc, auto SLc, auto Rc, auto Uc, const RowRegs<D, WS, LPP>& rw, uint32_t (&Sr)[NRL], uint32_t (&Sr2)[NRL]) {
+    // ahead(): the LDS reads of the NEXT row (PREFETCH; nothing otherwise), issued behind the step's own texture reads
+    auto step = [&](auto Kc, auto SLc, auto Rc, auto Uc, auto&& ahead, const RowRegs<D, WS, LPP>& rw, uint32_t (&Sr)[NRL], uint32_t (&Sr2)[NRL]) {
         constexpr int K = decltype(Kc)::value;            // ring slot of row t: a compile-time register set
+        // (two load sets, not queued:)
         using SetIn = std::integral_constant<int, (K + 1) & 1>;    // row t+3 goes where row t+1 was (W1 is even: K and t have the same parity)
         using SetOut = std::integral_constant<int, K & 1>;         // row t+2
-        issue(SetIn{});
+        if constexpr (QUEUED) issue(std::integral_constant<int, NPRE - 1>{});   // row t+NPRE+1, behind the queue
+        else issue(SetIn{});
         uint32_t tnew = 0;
         constexpr int KO = (K + 1) % W1;
         if constexpr (PAIR) {
             constexpr int R = decltype(Rc)::value, U = decltype(Uc)::value;
             // the group's four rows are resident from the commit of step 1 to the commit of this step's end (RingTexture)
-            if constexpr (R == 2) { tback = tex.template back<U>(); tex.term(capb); }
-            if constexpr (R == 3) tpre = tex.template prefix<U>();
+            [[maybe_unused]] typename RingTexture<C>::TermIn tin;
+            [[maybe_unused]] uint64_t tq;
+            if constexpr (R == 2) { tback = tex.template back<U>(); tin = tex.term_load(); }
+            if constexpr (R == 3) tq = tex.prefix_load();
+            ahead();
+            // nothing but scalar work, global loads and LDS stores crosses: the reads above stay in front of the step's first
+            // quad-SAD (left alone they sink to their first use, a step later) and the SADs stay behind them
+            if constexpr (C::PREFETCH) __builtin_amdgcn_sched_barrier(0x214);
             ring_step_pair<D, WS, LPP, K>(st, rw, Sr, Sr2);
             pin(Sr2);
+            // (the empty asm orders the use of what was read behind the quad-SADs: the wait for it is a counted one there)
+            if constexpr (R == 2) { asm volatile("" : "+v"(tin.l1), "+v"(tin.l2), "+v"(tin.e)); tex.term(capb, tin); }
+            if constexpr (R == 3) { asm volatile("" : "+v"(tq)); tpre = tex.template prefix<U>(tq); }
         } else {
+            ahead();
             ring_step<D, WS, LPP, K>(st, rw, rg.lastmask, capb, tnew, Sr);
             pt += tnew;
             const uint32_t told = ptr[KO * PPW + p];                  // prefix sum w rows back (0 while the window fills)
@@ -592,7 +630,15 @@ __global__ __launch_bounds__(256, (RingBounds<D, WS, LPP, FUSE>::WAVES)) void k_
             ptw[decltype(Rc)::value * PPW + p] = (unsigned short)(pt - told);   // (mod 2^16: the window sum itself is < 2^16)
         }
         pin(Sr);
-        if constexpr (C::STATIC_SLOTS) {
+        if constexpr (QUEUED) {
+            static_assert(C::STATIC_SLOTS, "the queued loads go with static slots");
+            commit(Set0{}, std::integral_constant<int, (decltype(SLc)::value + 2) % 4>{});   // row t+2, the head of the queue
+            // (the queue moves on: names only inside the unrolled trip, a few v_mov at its back edge)
+#pragma unroll
+            for (int it = 0; it < ITEMS; ++it)
+#pragma unroll
+                for (int k = 0; k + 1 < NPRE; ++k) pre[k][it] = pre[k + 1][it];
+        } else if constexpr (C::STATIC_SLOTS) {
             commit(SetOut{}, std::integral_constant<int, (decltype(SLc)::value + 2) % 4>{});   // row t+2
         } else {
             const int sl_new = sl_cur == 0 ? 2 : sl_cur - 1;        // slot of row t+2 = (t + 2) mod 3
@@ -603,6 +649,12 @@ __global__ __launch_bounds__(256, (RingBounds<D, WS, LPP, FUSE>::WAVES)) void k_
 
     // One trip of the outer loop = whole rounds of the ring AND whole row groups (TRIP rows), unrolled: every row step has
     // its ring slot -- its registers -- fixed at compile time.
+    // PREFETCH: two row register sets, alternating by the parity of the step (TRIP is even: a constant of every unrolled step,
+    // the same in every trip).  Row 0 is requested here, behind the commits of rows 0 and 1; step t requests row t + 1 into
+    // set (t + 1) & 1 and consumes set t & 1 -- across group, trip and rebase boundaries alike.  The last step's request goes
+    // to a slot that holds a staged row like any other (rows past the strip are staged clamped) and is never used.
+    [[maybe_unused]] RowRegs<D, WS, LPP> rwp[2];
+    if constexpr (C::PREFETCH) lds_row(std::integral_constant<int, 0>{}, rwp[0]);
     int trips_since_rebase = 0;
     for (int t0 = 0; t0 < nstepsg; t0 += C::TRIP) {
         // Rebase (round 3): a trip starts on ring slot 0, whose content P(t-w-1) is dead; slot 1 holds the oldest prefix sum
@@ -636,11 +688,21 @@ __global__ __launch_bounds__(256, (RingBounds<D, WS, LPP, FUSE>::WAVES)) void k_
             GSel gsel;
             ring_for_rows(std::make_integer_sequence<int, RPG>{}, [&](auto Rc) {
                 constexpr int R = decltype(Rc)::value;
-                RowRegs<D, WS, LPP> rw;
                 using SL = std::integral_constant<int, (U + R) % 4>;    // (static slots: TRIP % 4 == 0, so t % 4 == (U + R) % 4)
-                lds_row(SL{}, rw);
                 uint32_t S2[NRL] = {};                                  // (PAIR only: column x0 + 1)
-                step(std::integral_constant<int, (U + R) % W1>{}, SL{}, Rc, std::integral_constant<int, U>{}, rw, S[R], S2);
+                if constexpr (C::PREFETCH) {
+                    // The left pieces of THIS row, requested a step ago (the two oldest reads in the queue), are pinned here:
+                    // without it the byte masks of the pair's edge pieces and the quad-SADs that start from zero -- work that
+                    // depends on the row alone -- are lifted into the step that issued the reads, which then waits for them
+                    // at once.  The windows are not pinned: their waits are the compiler's, counted.
+                    pin(rwp[(U + R) & 1].l);
+                    const auto ahead = [&] { lds_row(std::integral_constant<int, (U + R + 1) % 4>{}, rwp[(U + R + 1) & 1]); };   // row t + 1
+                    step(std::integral_constant<int, (U + R) % W1>{}, SL{}, Rc, std::integral_constant<int, U>{}, ahead, rwp[(U + R) & 1], S[R], S2);
+                } else {
+                    RowRegs<D, WS, LPP> rw;
+                    lds_row(SL{}, rw);
+                    step(std::integral_constant<int, (U + R) % W1>{}, SL{}, Rc, std::integral_constant<int, U>{}, [] {}, rw, S[R], S2);
+                }
                 // the row's slice and the minima of its groups go to its owner's record at once: S[R] is dead after this
                 // (also while the window fills: no branch around it)
                 if constexpr (PAIR) {
