@@ -5,9 +5,14 @@
 //     rows_plan_host sgm { <W> <H> <n> }...
 // the hand-off of sgm_finish (per-pixel heads, nothing merged, every row, workspace rows of W elements, aligned plane);
 //     rows_plan_host sweep <D> <w> <cap>
-// the bm line for every W in 16..4096 that is a multiple of 8, n in {1, 16, 1024} and H in {w + 1, w + 3, 720}.
+// the bm line for every W in 16..4096 that is a multiple of 8, n in {1, 16, 1024} and H in {w + 1, w + 3, 720};
+//     rows_plan_host lr { <W> <H> <D> <w> <cap> <n> <disp12MaxDiff> <speckleWindowSize> <speckleRange> <minDisparity>
+//                         <roi1 x> <roi1 y> <roi1 w> <roi1 h> }...
+// the left-right check alone under any minDisparity, speckleRange and ROI1 (w or h <= 0: none), with the geometry of
+// api_bm.hip's make_geom (rtdm_bm_geom.h) and aligned rows.
 // Linked against librtdm_hip.so; touches no device (the plans make no runtime call).  tests/test_rows_plan_cpu.py.
 #include "rtdm_kernels.h"
+#include "rtdm_bm_geom.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -26,6 +31,34 @@ static BMGeom geom(int W, int H, int D, int w, int cap)
     g.filtered = -16; g.cost16 = 2L * cap * w * w < 65536;
     g.vx0 = std::min(D - 1 + g.r, W); g.vx1 = std::max(W - g.r, 0); g.vy0 = g.r; g.vy1 = H - g.r;
     return g;
+}
+
+// api_bm.hip's make_geom: any minDisparity, ROI1 as rtdm_bm_set_roi stores it, no ROI2; false: the whole frame is FILTERED
+static bool geom_roi(int W, int H, int D, int w, int cap, int minD, bool lr, const int* roi1, BMGeom* g)
+{
+    *g = BMGeom{};
+    g->W = W; g->H = H; g->Ws = (W + 7) & ~7; g->D = D; g->minD = minD; g->w = w; g->r = w / 2; g->cap = cap;
+    g->lofs = std::max(D - 1 + minD, 0); g->rofs = -std::min(D - 1 + minD, 0); g->width1 = W - g->rofs - D + 1;
+    g->filtered = (minD - 1) * 16; g->want_cost = lr; g->cost16 = 2L * cap * w * w < 65536; g->mask_cols = !lr;
+    const BMRoiRect q = bm_roi_rect(BMRoiGeom{W, H, D, minD, w / 2, lr, {0, 0, 0, 0}}, roi1, false);
+    g->vx0 = q.vx0; g->vx1 = q.vx1; g->vy0 = q.vy0; g->vy1 = q.vy1; g->cx0 = q.cx0; g->cx1 = q.cx1;
+    return q.any != 0;
+}
+
+static const char* const FORMS[] = {"scalar_u16", "scalar_i32", "vec_wave", "vec_half", "vec_half2", "packed"};
+
+static void lr_line(const int* v)
+{
+    const int W = v[0], H = v[1], D = v[2], w = v[3], cap = v[4], n = v[5], maxdiff = v[6], window = v[7], range = v[8], minD = v[9];
+    BMGeom g;
+    const bool any = geom_roi(W, H, D, w, cap, minD, maxdiff >= 0, v + 10, &g);
+    const bool speckle = range >= 0 && window > 0;                   // chunk_back's condition
+    printf("%dx%d D=%d w=%d cap=%d n=%d maxdiff=%d window=%d range=%d minD=%d roi=%d,%d,%d,%d: ", W, H, D, w, cap, n, maxdiff, window, range,
+           minD, v[10], v[11], v[12], v[13]);
+    if (!any || maxdiff < 0) { printf("lr: -\n"); return; }
+    const LrPlan p = plan_lrcheck(g, maxdiff, speckle ? range : 0, n, speckle, true);
+    printf("lr: form=%s init=%d threads=%u gy=%u gz=%u lds=%zu heads=%s block_rows=%d rect=%d,%d,%d,%d\n", FORMS[(int)p.form],
+           p.heads != SpkHeads::NONE, p.threads, p.gy, p.n, p.lds, HEADS[(int)p.heads], p.block_rows, g.vx0, g.vy0, g.vx1 - g.vx0, g.vy1 - g.vy0);
 }
 
 static void print_spk(const SpkPlan& s, int y_hi)
@@ -66,6 +99,14 @@ int main(int argc, char** argv)
         }
         return 0;
     }
+    if (mode == "lr" && (argc - 2) % 14 == 0) {
+        for (int a = 2; a < argc; a += 14) {
+            int v[14];
+            for (int k = 0; k < 14; ++k) v[k] = atoi(argv[a + k]);
+            lr_line(v);
+        }
+        return 0;
+    }
     if (mode == "sgm" && (argc - 2) % 3 == 0) {
         for (int a = 2; a < argc; a += 3) {
             const int W = atoi(argv[a]), H = atoi(argv[a + 1]), n = atoi(argv[a + 2]);
@@ -81,6 +122,7 @@ int main(int argc, char** argv)
                 for (int H : {w + 1, w + 3, 720}) bm_line(W, H, D, w, cap, n, 1, 100, 1);
         return 0;
     }
-    fprintf(stderr, "usage: %s bm {W H D w cap n disp12MaxDiff speckleWindowSize rows_aligned}... | sgm {W H n}... | sweep D w cap\n", argv[0]);
+    fprintf(stderr, "usage: %s bm {W H D w cap n disp12MaxDiff speckleWindowSize rows_aligned}... | sgm {W H n}... | sweep D w cap | "
+                    "lr {W H D w cap n disp12MaxDiff speckleWindowSize speckleRange minDisparity roi1x roi1y roi1w roi1h}...\n", argv[0]);
     return 2;
 }

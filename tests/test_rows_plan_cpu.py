@@ -1,13 +1,15 @@
 """What plan_lrcheck and plan_speckle (rt-depth-map_amd/csrc/k_rows.hip) plan for the left-right check and the speckle filter,
 through the stand-alone program tests/rows_plan_host.cpp: built with hipcc (host code only) into a temporary directory and
 linked against librtdm_hip.so, which loads without a device.  The rows are the route table of DESIGN.md ("K3 / K4: routes"),
-kept in tests/rows_cases.py; the environment hooks of a row go to the child process that plans it."""
+kept in tests/rows_cases.py; the environment hooks of a row go to the child process that plans it.  The cases of
+tests/lr_cases.py (any minDisparity, speckleRange and ROI1) are pinned to their kernel form through the program's lr mode."""
 import os
 import re
 import subprocess
 
 import pytest
 
+import lr_cases as LC
 import rows_cases as RC
 from conftest import PKG, ROOT
 
@@ -126,3 +128,50 @@ def test_frames_of_the_gpu_rows_are_live(oracle, synth, r):
         _, lr, spk, alive = RC.liveness(oracle, r, L, R)
         print(RC.assert_live(r, f, lr, spk, alive))
     assert n == 1 or RC.frames(r) == (0, n - 1)
+
+
+# ---- the cases of tests/lr_cases.py: any minDisparity, speckleRange and ROI1 (the program's lr mode) ---------------------------
+LR_STATE = re.compile(r"lr: form=(\w+) init=(\d) threads=(\d+) gy=(\d+) gz=(\d+) lds=(\d+) heads=(\w+) block_rows=(\d+) rect=(-?\d+),(-?\d+),(-?\d+),(-?\d+)$")
+
+
+def lr_args(c):
+    return [c["W"], c["H"], c["D"], c["w"], c["cap"], c["n"], c["M"], c["window"], c["range"], c["minD"]] + list(c["roi"] or (0, 0, 0, 0))
+
+
+@pytest.fixture(scope="module")
+def lr_lines(exe):
+    lines = run(exe, ["lr"] + [v for c in LC.CASES for v in lr_args(c)])
+    assert len(lines) == len(LC.CASES)
+    return {c["id"]: line for c, line in zip(LC.CASES, lines)}
+
+
+@pytest.mark.parametrize("c", LC.CASES, ids=lambda c: c["id"])
+def test_left_right_state_case_is_planned_on_its_form(lr_lines, oracle, c):
+    line = lr_lines[c["id"]]
+    m = LR_STATE.search(line)
+    assert m, line
+    form, init, threads, gy, gz, lds, heads, block_rows = m.group(1), int(m.group(2)), int(m.group(3)), int(m.group(4)), int(m.group(5)), \
+        int(m.group(6)), m.group(7), int(m.group(8))
+    assert (form, bool(init)) == (c["form"], c["init"]), line
+    assert gz == c["n"] and lds < 65536 and threads <= 512 and threads % 64 == 0, line
+    assert heads == ("NONE" if not init else "PIXEL" if form == "scalar_i32" else "CHUNK") and block_rows == (4 if form == "vec_half2" else 1), line
+    # the program's geometry is make_geom's: the valid rectangle is the oracle's
+    assert tuple(int(v) for v in m.groups()[8:]) == oracle.valid_rect(c["W"], c["H"], **LC.oracle_kw(c)), line
+
+
+def test_either_side_of_every_reachable_bound_of_the_packed_form(exe):
+    """two_ok_for_pk (k_rows.hip), one bound at a time around a shape that is packed: 2 cap w w < 32768, disp12MaxDiff <= 512,
+    speckleRange <= 4096, minDisparity >= -1024, minDisparity + numDisparities <= 1024.  (W + 2 < 16384 and the 64 KB of LDS lie
+    beyond the widest frame a handle accepts, 4096 columns: 24.6 KB.)"""
+    def form(W=1208, H=11, D=64, w=9, cap=31, M=1, window=2, rng=32, minD=0):
+        line, = run(exe, ["lr", W, H, D, w, cap, 1, M, window, rng, minD, 0, 0, 0, 0])
+        return LR_STATE.search(line).group(1)
+    assert form() == "packed"
+    assert (form(w=17, cap=56, H=19), form(w=17, cap=57, H=19)) == ("packed", "vec_half") and 2 * 56 * 17 * 17 < 32768 <= 2 * 57 * 17 * 17
+    assert (form(w=21, cap=37, H=23), form(w=21, cap=38, H=23)) == ("packed", "vec_half") and 2 * 37 * 21 * 21 < 32768 <= 2 * 38 * 21 * 21
+    assert (form(M=512), form(M=513)) == ("packed", "vec_half")
+    assert (form(rng=4096), form(rng=4097)) == ("packed", "vec_half")
+    assert (form(rng=4097, window=0), form(rng=-1)) == ("packed", "packed")          # the filter is off: its range is not read
+    assert (form(minD=-1024), form(minD=-1025)) == ("packed", "vec_half")
+    assert (form(W=2040, minD=960), form(W=2040, minD=961)) == ("packed", "vec_half")
+    assert form(W=4096, D=16, w=5, H=7, minD=0) == "vec_wave"                        # past eight half-waves the packed form is not planned
