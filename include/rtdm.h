@@ -302,8 +302,32 @@ int rtdm_sgm_compute_device_cn(rtdm_sgm* sg, int channels, int n, const uint8_t*
                                int16_t* d_disp, size_t disp_pitch, size_t disp_frame_stride, void* hip_stream);
 /* Diagnostic switch, process wide: 1 runs the 16-bit pixel-cost forms on gray frames as well (0, the default: only where a
  * pixel cost can pass 255).  Results never depend on it; it exists so that tests can hold the 16-bit forms against the 8-bit
- * ones. */
+ * ones.  There is no 16-bit census form: under RTDM_SGM_COST_CENSUS (below) the switch changes nothing. */
 void rtdm_debug_sgm_cost16(int on);
+/* The pixel cost of a handle, from the next compute call on (like rtdm_sgm_set_prefilter_cap; no allocation, no
+ * synchronisation).  RTDM_SGM_COST_BT, the default, is R1.  RTDM_SGM_COST_CENSUS is this project's own and has NO counterpart
+ * in cv::StereoSGBM (nothing to be at parity with): the census transform with a Hamming-distance cost, for pairs whose two
+ * cameras expose differently -- the result does not change under any strictly increasing intensity mapping of either image.
+ * How much a brightness difference costs the BT maps, and what census gains on real pairs, is unmeasured.  Rules (DESIGN.md
+ * section 4.20):
+ *   N1  descriptor of pixel (x, y) of a gray image I over an odd window census_width x census_height, width in {3, 5, 7, 9},
+ *       height in {3, 5, 7}: one bit per offset (i, j) != (0, 0), |i| <= width / 2, |j| <= height / 2, set where
+ *       I[clamp(y + j)][clamp(x + i)] < I[y][x] (strict; coordinates clamped into the frame): at most 62 bits
+ *   N2  cost(x, y, d) = popcount(descL(x, y) xor descR(x - d - minDisparity, y)) <= M = width * height - 1
+ *   N3  R1 is not used: no ftzero, no overwritten border columns; preFilterCap stays stored, has no effect while census is
+ *       selected and applies again once the cost is RTDM_SGM_COST_BT
+ *   N4  everything after the pixel cost (R3-R12: block sum, paths, saturating sum, winners, left-right check, median, speckle
+ *       filter, coerced knobs) is unchanged; where M * window^2 + P2 > 32767 the block costs are checked against 32767 - P2
+ *       and a frame that passes it is refused with RTDM_ERR_UNSUPPORTED, as under R1 with its own M
+ *   N5  gray only: a compute call with channels = 3 on a census handle returns RTDM_ERR_UNSUPPORTED before any device use
+ * sg NULL: RTDM_ERR_NULL; cost neither value, or census with a size outside the sets above: RTDM_ERR_BAD_PARAM (the handle
+ * keeps its setting); RTDM_SGM_COST_BT ignores the two sizes.  rtdm_sgm_get_cost: any out pointer may be NULL; the sizes are
+ * those of the last accepted census setting (9 x 7 before the first).  The setting is not part of rtdm_sgm_params: a caller
+ * that builds a right matcher (rtdm_sgm_right_params) copies it to the right handle, as the adapters do. */
+#define RTDM_SGM_COST_BT     0   /* R1, the default */
+#define RTDM_SGM_COST_CENSUS 1
+int rtdm_sgm_set_cost(rtdm_sgm* sg, int cost, int census_width, int census_height);
+int rtdm_sgm_get_cost(const rtdm_sgm* sg, int* cost, int* census_width, int* census_height);
 
 /* ---- the step after the matcher, kept on the device ------------
  * rtdm_bm_compute_depth <- estimator.cpp:56 + 75-77: bm->compute(...); left_disp /= 16.;

@@ -15,6 +15,7 @@ STATUS = {0: "RTDM_OK", -1: "RTDM_ERR_BAD_PARAM", -2: "RTDM_ERR_BAD_SIZE", -3: "
           -4: "RTDM_ERR_HIP", -5: "RTDM_ERR_NOMEM", -6: "RTDM_ERR_UNSUPPORTED", -7: "RTDM_ERR_NULL", -8: "RTDM_ERR_BAD_STREAM"}
 STAGES = ("prefilter", "search", "lrcheck", "speckle")
 PREFILTER_NORMALIZED_RESPONSE, PREFILTER_XSOBEL = 0, 1   # cv::StereoBM's values (RTDM_PREFILTER_* in rtdm.h)
+SGM_COST_BT, SGM_COST_CENSUS = 0, 1                      # RTDM_SGM_COST_* in rtdm.h
 
 
 class RtdmError(RuntimeError):
@@ -158,6 +159,8 @@ SIGNATURES = {          # every entry point of include/rtdm.h: (restype, argtype
     "rtdm_sgm_compute_cn": (C.c_int, [vp, C.c_int, u8p, sz, u8p, sz, C.c_int, C.c_int, i16p, sz]),
     "rtdm_sgm_compute_device_cn": (C.c_int, [vp, C.c_int, C.c_int, u8p, u8p, sz, sz, C.c_int, C.c_int, i16p, sz, sz, vp]),
     "rtdm_debug_sgm_cost16": (None, [C.c_int]),
+    "rtdm_sgm_set_cost": (C.c_int, [vp, C.c_int, C.c_int, C.c_int]),
+    "rtdm_sgm_get_cost": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "rtdm_bm_compute_depth": (C.c_int, [vp, u8p, sz, u8p, sz, C.c_int, C.c_int, C.POINTER(C.c_double), u8p, sz,
                                         C.POINTER(Region), C.c_int, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_int), i16p, sz]),
     "rtdm_depth_stats_device": (C.c_int, [C.c_int, i16p, sz, C.c_int, C.c_int, C.POINTER(C.c_double), u8p, sz,

@@ -12,6 +12,7 @@ struct rtdm_sgm {
     int16_t* dOut;
     SGMBuffers b;
     int prefilter_cap;             // rtdm_sgm_set_prefilter_cap: R1's ftzero = max(preFilterCap, 15) | 1
+    SgmCostKind cost;              // rtdm_sgm_set_cost: the pixel cost of the next call (R1, or census descriptors: N1-N5)
     int cost_limit;                // of the current call, > 0 where a block cost + P2 can pass 32767: a block cost above it would
                                    // wrap the library's 16-bit path costs (sgm_cost_limit)
     int32_t* hOvf;                 // page-locked copy of b.ovf
@@ -34,12 +35,14 @@ static int sgm_sweep_check(rtdm_sgm* sg)
     return RTDM_ERR_HIP;
 }
 
-// R1 generalised (oracle rule restated for colour in tests/sgm_cn_ref.py): a pixel cost is at most M = cn (2 ftzero + 63), a
-// block cost at most M blockSize^2; where that + P2 can pass 32767 the block costs are checked against 32767 - P2
+// R1 generalised (oracle rule restated for colour in tests/sgm_cn_ref.py): a pixel cost is at most M = cn (2 ftzero + 63) -- under
+// the census cost (N4) M = cw ch - 1 --, a block cost at most M blockSize^2; where that + P2 can pass 32767 the block costs are
+// checked against 32767 - P2
+static_assert(SGM_COST_BT == RTDM_SGM_COST_BT && SGM_COST_CENSUS == RTDM_SGM_COST_CENSUS, "the kernels' names for rtdm.h's values");
 static int sgm_ftzero(const rtdm_sgm* sg) { return std::max(sg->prefilter_cap, 15) | 1; }
 static int sgm_cost_limit(const rtdm_sgm* sg, int cn)
 {
-    const long M = (long)cn * (2 * sgm_ftzero(sg) + 63);
+    const long M = sg->cost.kind == SGM_COST_CENSUS ? (long)sg->cost.cw * sg->cost.ch - 1 : (long)cn * (2 * sgm_ftzero(sg) + 63);
     return M * sg->p.blockSize * sg->p.blockSize + sg->p.P2 > 32767 ? 32767 - sg->p.P2 : 0;
 }
 
@@ -108,6 +111,7 @@ int rtdm_sgm_create(const rtdm_sgm_params* params, int max_width, int max_height
     if (!sg) return RTDM_ERR_NOMEM;
     sg->p = p; sg->maxW = max_width; sg->maxH = max_height; sg->maxB = max_batch; sg->device = device;
     sg->path_variant = "";
+    sg->cost = SgmCostKind{SGM_COST_BT, 9, 7};
     const size_t px = (size_t)max_width * max_height * max_batch;
     // D <= 256: volumes on max_width columns, as always.  D > 256 (the wide path pass): on the widest column domain a frame can
     // have, W1max = max_width + min(minD, 0) - max(minD + D, 0) -- at D = 4080 on 4096 columns that is 16 columns instead of
@@ -169,7 +173,7 @@ static int sgm_chunk(rtdm_sgm* sg, int n, int cn, Plane8 L, Plane8 R, int W, int
     sg->lim.ring_words = b.ring_words;
     sg->path_variant = launch_sgm(L, R, disp, g, b, sg->lim, p.paths, n, s,
                                   SgmParams{p.blockSize, p.P1, p.P2, p.uniquenessRatio, p.disp12MaxDiff, p.speckleWindowSize,
-                                            p.speckleRange, sg->cost_limit, cn, sgm_ftzero(sg)});
+                                            p.speckleRange, sg->cost_limit, cn, sgm_ftzero(sg), sg->cost});
     HIPC(hipGetLastError());
     return RTDM_OK;
 }
@@ -182,6 +186,7 @@ int rtdm_sgm_compute_device_cn(rtdm_sgm* sg, int channels, int n, const uint8_t*
     if (channels != 1 && channels != 3) return RTDM_ERR_BAD_PARAM;
     if (n <= 0 || width <= 0 || height <= 0 || width > sg->maxW || height > sg->maxH) return RTDM_ERR_BAD_SIZE;
     if (pitch < (size_t)width * channels || disp_pitch < (size_t)width * 2 || (disp_pitch & 1) || (disp_frame_stride & 1)) return RTDM_ERR_BAD_SIZE;
+    if (channels == 3 && sg->cost.kind == SGM_COST_CENSUS) return RTDM_ERR_UNSUPPORTED;      // N5: the census cost is gray only
     HIPC(hipSetDevice(sg->device));
     if (channels == 3) { const int rc = sgm_colour_buffers(sg, false); if (rc) return rc; }
     sg->cost_limit = sgm_cost_limit(sg, channels);
@@ -213,6 +218,7 @@ int rtdm_sgm_compute_cn(rtdm_sgm* sg, int channels, const uint8_t* left, size_t 
     if (width <= 0 || height <= 0 || width > sg->maxW || height > sg->maxH) return RTDM_ERR_BAD_SIZE;
     const size_t row = (size_t)width * channels;
     if (left_pitch < row || right_pitch < row || disp_pitch < (size_t)width * 2) return RTDM_ERR_BAD_SIZE;
+    if (channels == 3 && sg->cost.kind == SGM_COST_CENSUS) return RTDM_ERR_UNSUPPORTED;      // N5
     HIPC(hipSetDevice(sg->device));
     if (channels == 3) { const int rc = sgm_colour_buffers(sg, true); if (rc) return rc; }
     sg->cost_limit = sgm_cost_limit(sg, channels);
@@ -244,6 +250,29 @@ int rtdm_sgm_set_prefilter_cap(rtdm_sgm* sg, int preFilterCap)
     if (!sg) return RTDM_ERR_NULL;
     if (preFilterCap >= 128) return RTDM_ERR_UNSUPPORTED;      // the library's 8-bit clip table wraps from here on
     sg->prefilter_cap = preFilterCap;
+    return RTDM_OK;
+}
+
+// No allocation, no synchronisation: the descriptors live where the bounds do (b.gl / b.gr), and a call in flight has read the
+// handle's setting when it was issued
+int rtdm_sgm_set_cost(rtdm_sgm* sg, int cost, int census_width, int census_height)
+{
+    if (!sg) return RTDM_ERR_NULL;
+    if (cost == RTDM_SGM_COST_BT) { sg->cost.kind = SGM_COST_BT; return RTDM_OK; }      // (the two sizes are ignored)
+    if (cost != RTDM_SGM_COST_CENSUS) return RTDM_ERR_BAD_PARAM;
+    const bool wok = census_width == 3 || census_width == 5 || census_width == 7 || census_width == 9;
+    const bool hok = census_height == 3 || census_height == 5 || census_height == 7;
+    if (!wok || !hok) return RTDM_ERR_BAD_PARAM;
+    sg->cost = SgmCostKind{SGM_COST_CENSUS, census_width, census_height};
+    return RTDM_OK;
+}
+
+int rtdm_sgm_get_cost(const rtdm_sgm* sg, int* cost, int* census_width, int* census_height)
+{
+    if (!sg) return RTDM_ERR_NULL;
+    if (cost) *cost = sg->cost.kind;
+    if (census_width) *census_width = sg->cost.cw;
+    if (census_height) *census_height = sg->cost.ch;
     return RTDM_OK;
 }
 

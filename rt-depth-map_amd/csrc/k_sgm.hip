@@ -233,7 +233,7 @@ static int sgm_issue(const SgmPlan& plan, const SgmCall& c)
 const char* launch_sgm(Plane8 L, Plane8 R, Plane16W disp, const SGMGeom& g, const SGMBuffers& b, const SgmLimits& lim, int paths,
                        int n, hipStream_t stream, SgmParams p)
 {
-    launch_sgm_cost(L, R, g, b, p.blockSize, p.cost_limit, p.cn, p.ftz, n, stream);
+    launch_sgm_cost(L, R, g, b, p.blockSize, p.cost_limit, p.cn, p.ftz, p.cost, n, stream);
     // (the right image's bounds are dead once the pixel costs exist: 8 bytes per pixel for the winners; C, S and S2 are whole
     // allocations: 16-byte aligned, as the packed loads and stores of the path passes need)
     const SgmCall c{g, b, p.P1, p.P2, p.uniq, n, (SgmWin*)b.gr, stream};

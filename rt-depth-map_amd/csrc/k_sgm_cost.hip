@@ -7,6 +7,9 @@
 //   k_sgm_pixbox Birchfield-Tomasi pixel cost (gradient + (intensity >> 2), u8, kept in LDS) and the blockSize x blockSize sum
 //                with clamped coordinates -> C (u16), windows <= 7; larger windows: k_sgm_pix (u8 volume) + k_sgm_box / _any
 //                (colour frames and ftzero >= 97, where a pixel cost passes 255: the u16 forms k_sgm_pixbox<Cost16>, k_sgm_pix16)
+//   k_sgm_census the other pixel cost (rtdm_sgm_set_cost, rules N1-N5 of DESIGN.md section 4.20; no library counterpart): a census
+//                descriptor per pixel and image instead of the bounds, in the same 8-byte records; the pixel cost is then the
+//                Hamming distance of two descriptors (CostCensus), through k_sgm_pixbox or k_sgm_pix_census + k_sgm_box / _any
 #include "rtdm_sgm.h"
 
 #include <atomic>
@@ -79,6 +82,60 @@ struct Cost16 {
     static __device__ __forceinline__ void widen(Word w, uint32_t& h0, uint32_t& h1) { h0 = w.x; h1 = w.y; }
 };
 
+// N1, the census descriptor of a (2 HW + 1) x (2 HH + 1) window: one bit per offset (i, j) != (0, 0), set where the neighbour at
+// clamped coordinates is strictly darker than the centre -- at most 62 bits, the low 32 in .x (bit order: row by row, the
+// centre skipped; only Hamming distances leave the cost stage, so the order is nobody else's business).  A workgroup owns a
+// tile of 64 x 16 pixels of one image of one frame: the tile and its halo go to LDS once (clamped coordinates, a byte per
+// lane and load), then every lane builds the words of four pixels of its column and stores them, 8 bytes each, where
+// k_sgm_bounds<1> stores its records.  1 byte read and 8 written per pixel and image, as there -- but it runs at 2 x that
+// kernel's time (9 x 7, 720p): up to 62 LDS byte reads and compares per pixel bind it, not HBM.
+template <int HW, int HH>
+__global__ __launch_bounds__(256) void k_sgm_census(Plane8 L, Plane8 R, uint2* cl, uint2* cr, int W, int H, int n)
+{
+    constexpr int TX = 64, TY = 16, LW = TX + 2 * HW, LH = TY + 2 * HH;
+    __shared__ uint8_t tile[LH][LW];
+    int f = blockIdx.z;
+    const bool right = f >= n;
+    if (right) f -= n;
+    const Plane8 S = right ? R : L;
+    const uint8_t* img = S.base + (size_t)f * S.frame;
+    const int x0 = blockIdx.x * TX, y0 = blockIdx.y * TY;
+    for (int i = threadIdx.x; i < LW * LH; i += 256) {
+        const int ty = i / LW, tx = i - ty * LW;
+        const int ys = min(max(y0 + ty - HH, 0), H - 1), xs = min(max(x0 + tx - HW, 0), W - 1);
+        tile[ty][tx] = img[(size_t)ys * S.pitch + xs];
+    }
+    __syncthreads();
+    const int tx = threadIdx.x % TX, x = x0 + tx;
+    if (x >= W) return;
+    uint2* out = (right ? cr : cl) + (size_t)f * H * W;
+#pragma unroll
+    for (int q = 0; q < TY / 4; ++q) {
+        const int ty = threadIdx.x / TX + 4 * q, y = y0 + ty;
+        if (y >= H) break;
+        const uint32_t c = tile[ty + HH][tx + HW];
+        uint32_t lo = 0u, hi = 0u;
+        int bit = 0;
+#pragma unroll
+        for (int j = 0; j <= 2 * HH; ++j) {
+#pragma unroll
+            for (int i = 0; i <= 2 * HW; ++i) {
+                if (i == HW && j == HH) continue;
+                const uint32_t b = (uint32_t)tile[ty + j][tx + i] < c ? 1u : 0u;
+                if (bit < 32) lo |= b << bit; else hi |= b << (bit - 32);
+                ++bit;
+            }
+        }
+        out[(size_t)y * W + x] = make_uint2(lo, hi);
+    }
+}
+
+// N2: the pixel cost of census descriptors, popcount(left xor right) <= M = cw ch - 1 <= 62, four consecutive disparities as
+// four u8 in a dword like Cost8 (whose widen it shares); block sums of the fused kernel's windows stay below 49 * 62: no check
+struct CostCensus : Cost8 {
+    static __device__ __forceinline__ Word cost(const uint2* cl, const uint2* cr, size_t row, int x, int xr) { return sgm_census_cost4(cl, cr, row, x, xr); }
+};
+
 // pixel cost, u8 volume: one thread per (x, four consecutive d); d fastest
 __global__ __launch_bounds__(256) void k_sgm_pix(const uint2* bl, const uint2* br, uint8_t* pix, SGMGeom g)
 {
@@ -90,6 +147,19 @@ __global__ __launch_bounds__(256) void k_sgm_pix(const uint2* bl, const uint2* b
     const int x = g.x0 + xi, xr = x - (d + g.minD);                     // element j pairs x with xr - j
     const size_t row = ((size_t)f * g.H + y) * g.W;
     *(uint32_t*)(pix + (((size_t)f * g.H + y) * g.W1 + xi) * g.D + d) = Cost8::cost(bl, br, row, x, xr);
+}
+
+// k_sgm_pix over census descriptors (N2): the same u8 volume, the same thread layout
+__global__ __launch_bounds__(256) void k_sgm_pix_census(const uint2* cl, const uint2* cr, uint8_t* pix, SGMGeom g)
+{
+    const int dq = g.D >> 2;
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;          // over W1 * D/4
+    if (idx >= (size_t)g.W1 * dq) return;
+    const int d = (int)(idx % dq) * 4, xi = (int)(idx / dq);
+    const int y = blockIdx.y, f = blockIdx.z;
+    const int x = g.x0 + xi, xr = x - (d + g.minD);                     // N2: xr - 3 >= 1 on the column domain
+    const size_t row = ((size_t)f * g.H + y) * g.W;
+    *(uint32_t*)(pix + (((size_t)f * g.H + y) * g.W1 + xi) * g.D + d) = CostCensus::cost(cl, cr, row, x, xr);
 }
 
 // k_sgm_pix with u16 pixel costs -> pix [n][H][W1][D] (it lives in S, dead until the first path pass writes it)
@@ -299,19 +369,39 @@ static void launch_box(const SGMGeom& g, const SGMBuffers& b, const T* pix, int 
     hipLaunchKernelGGL(k_sgm_box_any<T>, bgrid, blk, 0, stream, pix, b.C, g, Rw, rps, cost_limit, b.ovf);
 }
 
+// The descriptor kernel over the window (cw, ch) in {3, 5, 7, 9} x {3, 5, 7} (the caller has checked them)
+static void launch_census(Plane8 L, Plane8 R, const SGMGeom& g, const SGMBuffers& b, int cw, int ch, int n, hipStream_t stream)
+{
+    const dim3 grid((g.W + 63) / 64, (g.H + 15) / 16, 2 * n), blk(256);
+#define RTDM_CEN(HW, HH) hipLaunchKernelGGL((k_sgm_census<HW, HH>), grid, blk, 0, stream, L, R, (uint2*)b.gl, (uint2*)b.gr, g.W, g.H, n)
+#define RTDM_CENH(HW) do { switch (ch) { case 3: RTDM_CEN(HW, 1); break; case 5: RTDM_CEN(HW, 2); break; default: RTDM_CEN(HW, 3); break; } } while (0)
+    switch (cw) { case 3: RTDM_CENH(1); break; case 5: RTDM_CENH(2); break; case 7: RTDM_CENH(3); break; default: RTDM_CENH(4); break; }
+#undef RTDM_CENH
+#undef RTDM_CEN
+}
+
 // The whole cost stage: the bounds, then pixel cost and block sum -> b.C -- fused for windows <= 7 and D in {16, 32, 64, 128,
 // 256} (the u8 form: only where no block cost can pass cost_limit; the u16 form checks it itself), otherwise two kernels with
-// the pixel-cost volume between them (u8: b.pix; u16: b.S, which is not written before the first path pass)
-void launch_sgm_cost(Plane8 L, Plane8 R, const SGMGeom& g, const SGMBuffers& b, int blockSize, int cost_limit, int cn, int ftz, int n,
-                     hipStream_t stream)
+// the pixel-cost volume between them (u8: b.pix; u16: b.S, which is not written before the first path pass).  cost.kind ==
+// SGM_COST_CENSUS (gray only, N5: the caller has refused colour): descriptors instead of bounds and the u8 routes over
+// CostCensus; there is no 16-bit census form, rtdm_debug_sgm_cost16 changes nothing there.
+void launch_sgm_cost(Plane8 L, Plane8 R, const SGMGeom& g, const SGMBuffers& b, int blockSize, int cost_limit, int cn, int ftz,
+                     SgmCostKind cost, int n, hipStream_t stream)
 {
     const dim3 blk(256), bnd((g.W + 255) / 256, g.H, 2 * n);
-    if (cn == 3) hipLaunchKernelGGL(k_sgm_bounds<3>, bnd, blk, 0, stream, L, R, (uint2*)b.cl, (uint2*)b.cr, g.W, g.H, n, ftz);
-    else hipLaunchKernelGGL(k_sgm_bounds<1>, bnd, blk, 0, stream, L, R, (uint2*)b.gl, (uint2*)b.gr, g.W, g.H, n, ftz);
-    const uint2 *bl = (const uint2*)(cn == 3 ? b.cl : b.gl), *br = (const uint2*)(cn == 3 ? b.cr : b.gr);
     const int Rw = blockSize / 2, dq = g.D / 4;                         // D is a multiple of 16
     const bool fused = Rw <= 3 && (dq == 4 || dq == 8 || dq == 16 || dq == 32 || dq == 64);
     const dim3 xgrid((unsigned)(((size_t)g.W1 * dq + 255) / 256), g.H, n);
+    if (cost.kind == SGM_COST_CENSUS) {
+        launch_census(L, R, g, b, cost.cw, cost.ch, n, stream);
+        const uint2 *cl = (const uint2*)b.gl, *cr = (const uint2*)b.gr;
+        if (fused && !cost_limit) return launch_pixbox<CostCensus>(g, b, cl, cr, Rw, 0, n, stream);
+        hipLaunchKernelGGL(k_sgm_pix_census, xgrid, blk, 0, stream, cl, cr, b.pix, g);
+        return launch_box<uint8_t>(g, b, b.pix, Rw, cost_limit, n, stream);
+    }
+    if (cn == 3) hipLaunchKernelGGL(k_sgm_bounds<3>, bnd, blk, 0, stream, L, R, (uint2*)b.cl, (uint2*)b.cr, g.W, g.H, n, ftz);
+    else hipLaunchKernelGGL(k_sgm_bounds<1>, bnd, blk, 0, stream, L, R, (uint2*)b.gl, (uint2*)b.gr, g.W, g.H, n, ftz);
+    const uint2 *bl = (const uint2*)(cn == 3 ? b.cl : b.gl), *br = (const uint2*)(cn == 3 ? b.cr : b.gr);
     if (!sgm_cost16_needed(cn, ftz)) {
         if (fused && !cost_limit) return launch_pixbox<Cost8>(g, b, bl, br, Rw, 0, n, stream);
         hipLaunchKernelGGL(k_sgm_pix, xgrid, blk, 0, stream, bl, br, b.pix, g);

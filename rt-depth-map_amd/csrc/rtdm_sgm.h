@@ -103,6 +103,21 @@ __device__ __forceinline__ uint2 sgm_cost4(const uint2* bl, const uint2* br, siz
     return make_uint2(c0, c1);
 }
 
+// The census pixel cost (N2): Hamming distances of the 64-bit descriptor of left column x to those of right
+// columns xr, xr - 1, xr - 2, xr - 3 (disparities d .. d + 3), each <= 62, as four u8 in a dword, d in the low byte.  Two
+// popcounts per disparity, the second accumulating onto the first (v_bcnt_u32_b32).  row = (f * H + y) * W.
+__device__ __forceinline__ uint32_t sgm_census_cost4(const uint2* cl, const uint2* cr, size_t row, int x, int xr)
+{
+    const uint2 a = cl[row + x];
+    uint32_t w = 0u;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const uint2 b = cr[row + xr - j];
+        w |= (uint32_t)(__builtin_popcount(a.x ^ b.x) + __builtin_popcount(a.y ^ b.y)) << (8 * j);
+    }
+    return w;
+}
+
 // The path recurrence (R4) for one u16 pair of a line: L <- C + min(Lp[d], Lp[d -+ 1] + P1, min Lp + P2) - min Lp, with the
 // previous pixel's (previous, own, next) pairs, its line minimum mps and mpP2 = that + P2 in both halves of a dword
 __device__ __forceinline__ uint32_t sgm_pair_step(uint32_t prev, uint32_t own, uint32_t next, uint32_t c, uint32_t mps, uint32_t mpP2,

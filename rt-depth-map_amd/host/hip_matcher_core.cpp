@@ -261,6 +261,13 @@ int HIPSGMCore::setPreFilterCap(int preFilterCap)
     if (rc == RTDM_OK) preFilterCap_ = preFilterCap;
     return rc;
 }
+int HIPSGMCore::setCost(int cost, int cw, int ch)
+{
+    if (!sg_) return status_ != RTDM_OK ? status_ : RTDM_ERR_NO_DEVICE;
+    const int rc = rtdm_sgm_set_cost(sg_, cost, cw, ch);
+    if (rc == RTDM_OK) rtdm_sgm_get_cost(sg_, &cost_, &censusWidth_, &censusHeight_);
+    return rc;
+}
 
 HIPWLSCore::HIPWLSCore(const rtdm_wls_params& params, int maxWidth, int maxHeight, int device) : params_(params)
 {
@@ -343,6 +350,7 @@ HIPSGMCore* createRightMatcher(const HIPSGMCore& left)
     HIPSGMCore* m = new HIPSGMCore(p.blockSize, p.minDisparity, p.numDisparities, p.uniquenessRatio, p.speckleWindowSize,
                                    p.speckleRange, p.disp12MaxDiff, left.maxWidth(), left.maxHeight(), left.device(), p.paths);
     if (left.preFilterCap()) m->setPreFilterCap(left.preFilterCap());     // not part of rtdm_sgm_params (W1)
+    if (left.cost() != RTDM_SGM_COST_BT) m->setCost(left.cost(), left.censusWidth(), left.censusHeight());   // nor is the pixel cost
     return m;
 }
 

@@ -104,9 +104,16 @@ public:
                 int rows, int cols, int16_t* out, size_t outStep);
     // cv::StereoSGBM::setPreFilterCap (0 .. 127), from the next compute on
     int setPreFilterCap(int preFilterCap);
+    // rtdm_sgm_set_cost, from the next compute on: RTDM_SGM_COST_BT (cv::StereoSGBM's pixel cost, the default) or
+    // RTDM_SGM_COST_CENSUS over a cw x ch window (cw 3, 5, 7, 9; ch 3, 5, 7; gray frames only) -- the project's own cost for
+    // pairs whose cameras expose differently; the library has no counterpart
+    int setCost(int cost, int cw = 9, int ch = 7);
     int status() const { return status_; }
     const rtdm_sgm_params& params() const { return params_; }
     int preFilterCap() const { return preFilterCap_; }
+    int cost() const { return cost_; }
+    int censusWidth() const { return censusWidth_; }
+    int censusHeight() const { return censusHeight_; }
     int maxWidth() const { return maxWidth_; }
     int maxHeight() const { return maxHeight_; }
     int device() const { return device_; }
@@ -116,6 +123,7 @@ private:
     int status_ = RTDM_OK;
     rtdm_sgm_params params_;
     int preFilterCap_ = 0, maxWidth_ = 0, maxHeight_ = 0, device_ = 0;
+    int cost_ = RTDM_SGM_COST_BT, censusWidth_ = 9, censusHeight_ = 7;
 };
 
 // The disparity WLS post-filter (cv::ximgproc::DisparityWLSFilter, the reference's ENABLE_POST_FILTER block,

@@ -23,6 +23,9 @@ public:
 	~HIPSemiGlobalMatcher();
 	int compute(cv::InputArray left, cv::InputArray right, cv::OutputArray out);
 	int setPreFilterCap(int preFilterCap) { return core->setPreFilterCap(preFilterCap); }
+	/* RTDM_SGM_COST_BT (the library's cost, the default) or RTDM_SGM_COST_CENSUS over a cw x ch window: for two cameras with
+	 * their own auto-exposure; not a cv::StereoSGBM feature (include/rtdm.h, rtdm_sgm_set_cost).  CV_8UC1 pairs only. */
+	int setCost(int cost, int cw = 9, int ch = 7) { return core->setCost(cost, cw, ch); }
 	void setROI1(cv::Rect roi1) {}
 	void setROI2(cv::Rect roi2) {}
 	/* takes ownership of a core (createRightMatcher, wls-hip.cpp) */

@@ -168,15 +168,20 @@ class HIPSemiGlobalMatcher(Handle):
     preFilterCap is cv::StereoSGBM's (0 .. 127, setPreFilterCap); compute / compute_device take gray (H x W) or
     interleaved colour (H x W x 3) uint8 frames, as cv::StereoSGBM::compute takes CV_8UC1 and CV_8UC3.
     mode is cv::StereoSGBM::setMode's value (MODE_SGBM, MODE_HH, MODE_HH4; MODE_SGBM_3WAY is refused by the library with
-    RTDM_ERR_UNSUPPORTED); paths names the same thing by its direction count (5, 8, 4) and defaults to 8."""
+    RTDM_ERR_UNSUPPORTED); paths names the same thing by its direction count (5, 8, 4) and defaults to 8.
+    cost is the pixel cost: COST_BT (the default, cv::StereoSGBM's) or COST_CENSUS, the Hamming distance of census descriptors
+    over a census = (width, height) window, width in 3, 5, 7, 9 and height in 3, 5, 7 -- this project's own, with no library
+    counterpart, for pairs whose cameras expose differently (gray frames only; rtdm_sgm_set_cost in include/rtdm.h)."""
     _destroy = "rtdm_sgm_destroy"
+    COST_BT, COST_CENSUS = B.SGM_COST_BT, B.SGM_COST_CENSUS
+    _CENSUS_W, _CENSUS_H = (3, 5, 7, 9), (3, 5, 7)
 
     MODE_SGBM, MODE_HH, MODE_SGBM_3WAY, MODE_HH4 = 0, 1, 2, 3          # cv::StereoSGBM's values
     _MODE_PATHS = {MODE_SGBM: 5, MODE_HH: 8, MODE_SGBM_3WAY: 3, MODE_HH4: 4}
 
     def __init__(self, blockSize=5, minDisparity=0, numOfDisparities=128, uniquenessRatio=10, speckleWindowSize=100,
                  speckleRange=32, disp12MaxDiff=1, P1=600, P2=2400, width=1280, height=720, max_batch=1, device=0, paths=None,
-                 preFilterCap=0, mode=None):
+                 preFilterCap=0, mode=None, cost=COST_BT, census=(9, 7)):
         # paths: 5 = cv::StereoSGBM's default MODE_SGBM (what sgbm-sw.cpp:15 creates), 8 = MODE_HH (BASELINE config 5),
         # 4 = MODE_HH4 (the two horizontal and the two vertical directions)
         if mode is not None:
@@ -187,6 +192,7 @@ class HIPSemiGlobalMatcher(Handle):
             paths = self._MODE_PATHS[mode]
         elif paths is None:
             paths = 8
+        cost, census = self._check_cost(cost, census)
         self._h = C.c_void_p()
         self.params = B.SGMParams(blockSize, minDisparity, numOfDisparities, P1, P2, uniquenessRatio, speckleWindowSize,
                                   speckleRange, disp12MaxDiff, paths)
@@ -194,12 +200,42 @@ class HIPSemiGlobalMatcher(Handle):
         B.check(B.lib().rtdm_sgm_create(C.byref(self.params), width, height, max_batch, device, C.byref(self._h)),
                 "rtdm_sgm_create")
         self.preFilterCap = 0
-        if preFilterCap:
-            try:
+        try:
+            if preFilterCap:
                 self.setPreFilterCap(preFilterCap)
-            except B.RtdmError:
-                self.close()
-                raise
+            if cost != self.COST_BT:
+                self.setCost(cost, census)
+        except B.RtdmError:
+            self.close()
+            raise
+
+    @classmethod
+    def _check_cost(cls, cost, census):
+        """-> (cost, (width, height)) as ints, or ValueError: the checks of rtdm_sgm_set_cost, made before the library is asked"""
+        if isinstance(cost, bool) or cost not in (cls.COST_BT, cls.COST_CENSUS):
+            raise ValueError("cost must be COST_BT (0) or COST_CENSUS (1); got %r" % (cost,))
+        try:
+            cw, ch = census
+            ok = all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) for v in (cw, ch))
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError("census must be a (width, height) pair of ints; got %r" % (census,))
+        if cost == cls.COST_CENSUS and (cw not in cls._CENSUS_W or ch not in cls._CENSUS_H):
+            raise ValueError("census window must be width 3, 5, 7 or 9 by height 3, 5 or 7; got %r" % (census,))
+        return int(cost), (int(cw), int(ch))
+
+    def setCost(self, cost, census=(9, 7)):
+        """The pixel cost from the next compute call on: COST_BT, or COST_CENSUS over a census = (width, height) window
+        (rtdm_sgm_set_cost; COST_BT ignores census).  preFilterCap stays stored and has no effect under COST_CENSUS."""
+        cost, (cw, ch) = self._check_cost(cost, census)
+        B.check(B.lib().rtdm_sgm_set_cost(self._h, cost, cw, ch), "rtdm_sgm_set_cost")
+
+    def getCost(self):
+        """-> (cost, (width, height)); the window is that of the last census setting, (9, 7) before the first"""
+        c, w, h = C.c_int(), C.c_int(), C.c_int()
+        B.check(B.lib().rtdm_sgm_get_cost(self._h, C.byref(c), C.byref(w), C.byref(h)), "rtdm_sgm_get_cost")
+        return c.value, (w.value, h.value)
 
     def setPreFilterCap(self, preFilterCap):
         """cv::StereoSGBM::setPreFilterCap: applies from the next compute call; >= 128 is refused (RTDM_ERR_UNSUPPORTED)."""
@@ -288,5 +324,5 @@ def create_right_matcher(m):
                                     uniquenessRatio=rp.uniquenessRatio, speckleWindowSize=rp.speckleWindowSize,
                                     speckleRange=rp.speckleRange, disp12MaxDiff=rp.disp12MaxDiff, P1=rp.P1, P2=rp.P2,
                                     width=m.width, height=m.height, max_batch=m.max_batch, device=m.device, paths=rp.paths,
-                                    preFilterCap=m.preFilterCap)
+                                    preFilterCap=m.preFilterCap, cost=m.getCost()[0], census=m.getCost()[1])
     raise ValueError("create_right_matcher takes a HIPMatcher or a HIPSemiGlobalMatcher; got %s" % type(m).__name__)
