@@ -255,7 +255,8 @@ typedef struct rtdm_sgm_params {
                             * right, down, down-right, down-left); 8: MODE_HH, all eight neighbours (BASELINE config 5);
                             * 4: MODE_HH4 (OpenCV 3.4 / 4.x), left, right, down, up and no others (rule R4', DESIGN.md section 4
                             * "K6 for MODE_HH4"; restated from memory, parity with the library unpinned like R1-R12).
-                            * 3 (MODE_SGBM_3WAY): RTDM_ERR_UNSUPPORTED, valid for the library but not implemented.  Any other
+                            * 3 (MODE_SGBM_3WAY): RTDM_ERR_UNSUPPORTED at creation; the mode is served through
+                            * rtdm_sgm_set_mode on a live handle (below).  Any other
                             * value: RTDM_ERR_BAD_PARAM */
 } rtdm_sgm_params;
 typedef struct rtdm_sgm rtdm_sgm;
@@ -328,6 +329,37 @@ void rtdm_debug_sgm_cost16(int on);
 #define RTDM_SGM_COST_CENSUS 1
 int rtdm_sgm_set_cost(rtdm_sgm* sg, int cost, int census_width, int census_height);
 int rtdm_sgm_get_cost(const rtdm_sgm* sg, int* cost, int* census_width, int* census_height);
+/* cv::StereoSGBM::setMode / getMode on a live handle, with the library's values.  The mode holds from the next compute call on;
+ * the call allocates nothing and does not use the device, and a handle that never calls it launches what it launched before.
+ * MODE_SGBM, MODE_HH and MODE_HH4 plan exactly as a handle created with paths = 5, 8 or 4 plans with the buffers THIS handle
+ * owns: one created with paths = 4 has no edge ring, so its MODE_SGBM and MODE_HH calls run one pass per direction ("half").
+ * MODE_SGBM_3WAY is served through this call only -- rtdm_sgm_create with paths = 3 keeps returning RTDM_ERR_UNSUPPORTED -- by
+ * rules T1-T8, restated from memory of the library's computeDisparity3WAY (OpenCV 3.4 / 4.x); parity
+ * with the library is unpinned, as for R1-R12:
+ *   T1  always 4 row stripes, sz = (H + 3) / 4 rows each, ovl = (blockSize / 2 + 1) + (sz + 9) / 10; stripe s = 0 .. 3 has the
+ *       output rows [o, e) = [min(s sz, H), min((s + 1) sz, H)) and the first source row a = max(min(s sz - ovl, H), 0)
+ *   T2  R1-R3 unchanged except for T3's rows
+ *   T3  for y in [a, min(a + blockSize / 2, e)) the vertical window of R3 clamps at the top to row a, not to row 0 (C'); a = 0: C' = C
+ *   T4  (1, 0) and (-1, 0) over the whole frame (R4); (0, 1) per stripe, started at row a with L = C'(a); rows [a, o) serve the
+ *       recurrence only
+ *   T5  S = min(L-> + L<- + Ldown, 32767) on the output rows
+ *   T6  R6 and R8 unchanged (min S = 32767 is no winner); no votes (R7) and no left-right check (R9): disp12MaxDiff is
+ *       accepted and ignored
+ *   T7  R10-R12 unchanged
+ *   T8  where M window^2 + P2 > 32767 every block cost the mode reads, every C' included, is checked against 32767 - P2; a frame
+ *       that passes it is refused (RTDM_ERR_UNSUPPORTED)
+ * Under MODE_SGBM_3WAY rtdm_sgm_path_variant says "vert3" and rtdm_sgm_get_pass_stats does not move; RTDM_SGM_DUAL = 0 keeps its
+ * meaning (the second horizontal direction adds into S), RTDM_SGM_SWEEP and rtdm_debug_sgm_wide_paths are ignored.  A frame
+ * lower than about 6 (blockSize / 2) rows makes the first such call allocate a buffer for the C' (the call fails if that does).
+ * sg NULL (get: or mode NULL): RTDM_ERR_NULL; a value outside 0 .. 3: RTDM_ERR_BAD_PARAM; MODE_SGBM_3WAY on a handle whose
+ * numDisparities > 256: RTDM_ERR_UNSUPPORTED; a refused call leaves the mode as it was.  rtdm_sgm_right_params does not carry
+ * the mode: the caller copies it to the right handle, as with the cost setting (the adapters do). */
+#define RTDM_SGM_MODE_SGBM      0
+#define RTDM_SGM_MODE_HH        1
+#define RTDM_SGM_MODE_SGBM_3WAY 2
+#define RTDM_SGM_MODE_HH4       3
+int rtdm_sgm_set_mode(rtdm_sgm* sg, int mode);
+int rtdm_sgm_get_mode(const rtdm_sgm* sg, int* mode);
 
 /* ---- the step after the matcher, kept on the device ------------
  * rtdm_bm_compute_depth <- estimator.cpp:56 + 75-77: bm->compute(...); left_disp /= 16.;

@@ -161,6 +161,8 @@ SIGNATURES = {          # every entry point of include/rtdm.h: (restype, argtype
     "rtdm_debug_sgm_cost16": (None, [C.c_int]),
     "rtdm_sgm_set_cost": (C.c_int, [vp, C.c_int, C.c_int, C.c_int]),
     "rtdm_sgm_get_cost": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "rtdm_sgm_set_mode": (C.c_int, [vp, C.c_int]),
+    "rtdm_sgm_get_mode": (C.c_int, [vp, C.POINTER(C.c_int)]),
     "rtdm_bm_compute_depth": (C.c_int, [vp, u8p, sz, u8p, sz, C.c_int, C.c_int, C.POINTER(C.c_double), u8p, sz,
                                         C.POINTER(Region), C.c_int, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_int), i16p, sz]),
     "rtdm_depth_stats_device": (C.c_int, [C.c_int, i16p, sz, C.c_int, C.c_int, C.POINTER(C.c_double), u8p, sz,

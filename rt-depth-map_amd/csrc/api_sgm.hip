@@ -1,5 +1,6 @@
 // api_sgm.hip -- rtdm_sgm, the SWSemiGlobalMatcher (cv::StereoSGBM) counterpart.
 #include "rtdm_handles.h"
+#include "rtdm_sgm_stripes.h"
 
 using namespace rtdm;
 
@@ -11,6 +12,8 @@ struct rtdm_sgm {
     uint8_t *dInL3, *dInR3;        // colour staging of rtdm_sgm_compute_cn (allocated by the first colour call)
     int16_t* dOut;
     SGMBuffers b;
+    size_t pix_bytes;              // of b.pix
+    uint16_t* dWarm;               // MODE_SGBM_3WAY's warm-up costs C' where b.pix cannot hold them (allocated by the first such call)
     int prefilter_cap;             // rtdm_sgm_set_prefilter_cap: R1's ftzero = max(preFilterCap, 15) | 1
     SgmCostKind cost;              // rtdm_sgm_set_cost: the pixel cost of the next call (R1, or census descriptors: N1-N5)
     int cost_limit;                // of the current call, > 0 where a block cost + P2 can pass 32767: a block cost above it would
@@ -59,6 +62,24 @@ static int sgm_colour_buffers(rtdm_sgm* sg, bool host)
     return create_failed("StereoSGBM colour buffers", std::exchange(m.err, hipSuccess));     // (the next colour call asks again)
 }
 
+// MODE_SGBM_3WAY (T3): where the n frames' warm-up block costs C' go -- 3 stripes x min(blockSize / 2, H) rows of W1 x D u16 per
+// frame.  b.pix is dead once C exists and holds them where about 6 (blockSize / 2) <= H; a frame too low for that gets a buffer
+// of exactly the handle's largest such call, and a failed allocation is an error, never a silent other route.
+static int sgm_warm_buffer(rtdm_sgm* sg, const SGMGeom& g, int n)
+{
+    const size_t need = (size_t)n * (SGM3_STRIPES - 1) * sgm3_warm_rows(sg->p.blockSize, g.H) * g.W1 * g.D * sizeof(uint16_t);
+    if (need <= sg->pix_bytes) { sg->b.Cw = (uint16_t*)sg->b.pix; return RTDM_OK; }
+    if (!sg->dWarm) {
+        const long w1max = (long)sg->maxW + std::min(sg->p.minDisparity, 0) - std::max(sg->p.minDisparity + sg->p.numDisparities, 0);
+        const size_t most = (size_t)sg->maxB * (SGM3_STRIPES - 1) * sgm3_warm_rows(sg->p.blockSize, sg->maxH) * (size_t)w1max *
+                            sg->p.numDisparities * sizeof(uint16_t);
+        AllocList& m = sg->mem;
+        if (!m.dev(&sg->dWarm, most)) return create_failed("StereoSGBM MODE_SGBM_3WAY warm-up costs", std::exchange(m.err, hipSuccess));
+    }
+    sg->b.Cw = sg->dWarm;
+    return RTDM_OK;
+}
+
 // windows whose block cost + P2 can pass 32767: the frame is refused if it does (what is not restated is the wrap-around)
 static int sgm_overflow_check(rtdm_sgm* sg, hipStream_t s)
 {
@@ -85,8 +106,8 @@ int rtdm_sgm_create(const rtdm_sgm_params* params, int max_width, int max_height
     rtdm_sgm_params p = *params;
     if (p.numDisparities <= 0 || p.numDisparities % 16 != 0 || p.blockSize < 1) return RTDM_ERR_BAD_PARAM;
     if (p.uniquenessRatio > 100) return RTDM_ERR_BAD_PARAM;
-    // cv::StereoSGBM's modes by their direction count: 5 MODE_SGBM, 8 MODE_HH, 4 MODE_HH4 (R4'); 3 is MODE_SGBM_3WAY, which the
-    // library serves and this build does not
+    // cv::StereoSGBM's modes by their direction count: 5 MODE_SGBM, 8 MODE_HH, 4 MODE_HH4 (R4'); 3 is MODE_SGBM_3WAY, which this
+    // door keeps refusing: it is served through rtdm_sgm_set_mode on a live handle (DESIGN.md section 4.21 and "Known limits")
     if (p.paths == 3) return RTDM_ERR_UNSUPPORTED;
     if (p.paths != 4 && p.paths != 5 && p.paths != 8) return RTDM_ERR_BAD_PARAM;
     // cv::StereoSGBM never checks the parity of blockSize: its window is SADWindowSize / 2 either side, an even size runs as
@@ -124,6 +145,7 @@ int rtdm_sgm_create(const rtdm_sgm_params* params, int max_width, int max_height
     e = hipStreamCreateWithFlags(&sg->stream, hipStreamNonBlocking);
     m.dev(&sg->dInL, px); m.dev(&sg->dInR, px); m.dev(&sg->dOut, px * 2);
     m.dev(&sg->b.gl, px * 8); m.dev(&sg->b.gr, px * 8);
+    sg->pix_bytes = vol;
     m.dev(&sg->b.pix, vol); m.dev(&sg->b.C, vol * 2); m.dev(&sg->b.S, vol * 2);          // (vol == 0: skipped)
     m.dev(&sg->b.label, px * 4); m.dev(&sg->b.size, px * 4); m.dev(&sg->b.runs, px * 4);
     m.dev(&sg->b.rowcnt, (size_t)max_batch * max_height * 4); m.dev(&sg->b.headmap, px * 2);
@@ -166,6 +188,7 @@ static int sgm_chunk(rtdm_sgm* sg, int n, int cn, Plane8 L, Plane8 R, int W, int
     g.x0 = std::max(g.minD + g.D, 0);
     g.W1 = (W + std::min(g.minD, 0)) - g.x0;
     if (g.W1 <= 0) { launch_fill16(disp, 0, W, 0, H, n, (g.minD - 1) * 16, s); return RTDM_OK; }
+    if (p.paths == 3) { const int rc = sgm_warm_buffer(sg, g, n); if (rc) return rc; }
     const SGMBuffers& b = sg->b;
     if (!sg->caps_asked) { sgm_sweep_caps(g.D, p.paths, b.S2 != nullptr, sg->lim.cap); sg->caps_asked = true; }
     sg->lim.sweep = b.ring && b.ev_in && b.ev_out && b.abortf && *b.abortf == 0;
@@ -273,6 +296,27 @@ int rtdm_sgm_get_cost(const rtdm_sgm* sg, int* cost, int* census_width, int* cen
     if (cost) *cost = sg->cost.kind;
     if (census_width) *census_width = sg->cost.cw;
     if (census_height) *census_height = sg->cost.ch;
+    return RTDM_OK;
+}
+
+// cv::StereoSGBM::setMode on a live handle: the direction count of the next call's plan.  Nothing is allocated or freed and the
+// device is not used; the sweep capacities belong to the mode and are asked again by the next call.
+static_assert(RTDM_SGM_MODE_SGBM == 0 && RTDM_SGM_MODE_HH == 1 && RTDM_SGM_MODE_SGBM_3WAY == 2 && RTDM_SGM_MODE_HH4 == 3, "cv::StereoSGBM's values");
+int rtdm_sgm_set_mode(rtdm_sgm* sg, int mode)
+{
+    if (!sg) return RTDM_ERR_NULL;
+    if (mode < RTDM_SGM_MODE_SGBM || mode > RTDM_SGM_MODE_HH4) return RTDM_ERR_BAD_PARAM;
+    // (k_sgm_vert3 holds a line of at most 256 disparities; there is no wide form of it)
+    if (mode == RTDM_SGM_MODE_SGBM_3WAY && sg->p.numDisparities > 256) return RTDM_ERR_UNSUPPORTED;
+    static const int paths[4] = {5, 8, 3, 4};
+    if (sg->p.paths != paths[mode]) { sg->p.paths = paths[mode]; sg->caps_asked = false; }
+    return RTDM_OK;
+}
+
+int rtdm_sgm_get_mode(const rtdm_sgm* sg, int* mode)
+{
+    if (!sg || !mode) return RTDM_ERR_NULL;
+    *mode = sg->p.paths == 5 ? RTDM_SGM_MODE_SGBM : (sg->p.paths == 8 ? RTDM_SGM_MODE_HH : (sg->p.paths == 3 ? RTDM_SGM_MODE_SGBM_3WAY : RTDM_SGM_MODE_HH4));
     return RTDM_OK;
 }
 

@@ -12,6 +12,7 @@
 //
 //   k_sgm_lrfinal one workgroup per row: the votes of the integer winners (LDS, right-most voter wins ties: R7) and the
 //                always-on left-right check (R9)
+//   k_sgm_final3 MODE_SGBM_3WAY's final stage: neither of the two (T6)
 //   k_sgm_median 3x3 median with clamped coordinates (R10) + the speckle filter's per-row init
 #include "rtdm_sgm.h"
 
@@ -55,6 +56,20 @@ __global__ __launch_bounds__(256) void k_sgm_lrfinal(const SgmWin* win, Plane16W
     }
 }
 
+// MODE_SGBM_3WAY's final stage (T6): the winners' x16 disparities as they are -- no votes (R7) and no left-right check (R9)
+__global__ __launch_bounds__(256) void k_sgm_final3(const SgmWin* win, Plane16W disp, SGMGeom g)
+{
+    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y, f = blockIdx.z;
+    if (x >= g.W) return;
+    const int xi = x - g.x0;
+    int d1 = (g.minD - 1) * 16;
+    if (xi >= 0 && xi < g.W1) {
+        const SgmWin w = win[((size_t)f * g.H + y) * g.W1 + xi];
+        if (w.bd >= g.minD) d1 = w.d16;                       // (rejected by the uniqueness test or saturated: INV)
+    }
+    disp.base[(size_t)f * disp.frame_e + (size_t)y * disp.pitch_e + x] = (int16_t)d1;
+}
+
 // R10: medianBlur(disp, disp, 3) -- 3x3 median of the int16 map with clamped coordinates -- followed by the speckle
 // filter's per-row init on the filtered row.  One workgroup per row; the three source rows stream through L2.
 __device__ __forceinline__ void mnmx(int& a, int& b) { const int t = min(a, b); b = max(a, b); a = t; }
@@ -88,9 +103,10 @@ __global__ __launch_bounds__(256) void k_sgm_median(const int16_t* src, Plane16W
     }
 }
 
-// the winners' votes and left-right check (k_sgm_lrfinal: the last path pass decided them), the median and the speckle filter
+// the winners' votes and left-right check (k_sgm_lrfinal: the last path pass decided them; !votes, MODE_SGBM_3WAY: neither,
+// k_sgm_final3), the median and the speckle filter
 static void sgm_finish(Plane16W disp, const SGMGeom& g, const SGMBuffers& b, int disp12MaxDiff, int speckleWindowSize,
-                       int speckleRange, int n, hipStream_t stream, const SgmWin* win)
+                       int speckleRange, int n, hipStream_t stream, const SgmWin* win, bool votes)
 {
     dim3 blk(256);
     const bool speckle = speckleWindowSize > 0;                           // R11
@@ -98,7 +114,8 @@ static void sgm_finish(Plane16W disp, const SGMGeom& g, const SGMBuffers& b, int
     // select -> a temporary plane (the bounds buffer of the left image is free again), median -> the caller's plane
     int16_t* tmp = (int16_t*)b.gl;
     const Plane16W tplane{tmp, (size_t)g.W, (size_t)g.W * g.H};
-    hipLaunchKernelGGL(k_sgm_lrfinal, dim3(1, g.H, n), blk, lds, stream, win, tplane, g, disp12MaxDiff);
+    if (votes) hipLaunchKernelGGL(k_sgm_lrfinal, dim3(1, g.H, n), blk, lds, stream, win, tplane, g, disp12MaxDiff);
+    else hipLaunchKernelGGL(k_sgm_final3, dim3((g.W + 255) / 256, g.H, n), blk, 0, stream, win, tplane, g);
     const size_t mlds = (size_t)g.W * 6;
     const int INV = (g.minD - 1) * 16;
     if (speckle) {
@@ -142,6 +159,20 @@ SgmPlan plan_sgm(const SGMGeom& g, int paths, int n, const SgmLimits& lim, SgmDo
         p = SgmPass{step, k, k < 0 ? 0 : dirs[k][0], k < 0 ? 0 : dirs[k][1], k == 0, k == last_dir, s2, 0, 0, 0, 0, 0};
         return p;
     };
+    // MODE_SGBM_3WAY (T4, T5; D <= 256: rtdm_sgm_set_mode has refused the others): -> and <- over the whole frame as for
+    // MODE_HH4, then the striped downward pass, which decides the winners.  No sweep, no wide form: RTDM_SGM_SWEEP and
+    // rtdm_debug_sgm_wide_paths are not consulted; RTDM_SGM_DUAL = 0 keeps its meaning.
+    // RTDM_SGM_DUAL=0 (test hook): the two horizontal directions one after the other (the second adds to S) instead of side by
+    // side -- what runs without S2
+    static const int dual_env = env_int("RTDM_SGM_DUAL", 1);
+    if (paths == 3) {
+        const bool dual = dual_env && lim.s2;
+        add(SgmStep::PATH_H, 0, dual);
+        if (!dual) add(SgmStep::PATH_H, 1, false);
+        add(SgmStep::VERT3, 2, dual).last = true;
+        plan.variant = "vert3";
+        return plan;
+    }
     // D > 256 (or rtdm_debug_sgm_wide_paths): one wide pass per direction (k_sgm_wide.hip), the last one deciding the winners;
     // none of the forms below -- they hold at most 256 disparities per line -- and none of their hooks
     const int wide = sgm_wide_mode();
@@ -155,9 +186,6 @@ SgmPlan plan_sgm(const SGMGeom& g, int paths, int n, const SgmLimits& lim, SgmDo
     // RTDM_SGM_SWEEP=0 (test hook): one k_sgm_path_h pass per direction for those that advance a row per step as well -- what
     // runs after a sweep gave up or did not fit, and what k_sgm_vert is timed against
     static const int sweep_env = env_int("RTDM_SGM_SWEEP", 1);
-    // RTDM_SGM_DUAL=0 (test hook): the two horizontal directions one after the other (the second adds to S) instead of side by
-    // side -- what runs without S2
-    static const int dual_env = env_int("RTDM_SGM_DUAL", 1);
     if (paths == 4 && sweep_env) {
         // MODE_HH4: -> and <- (side by side into S and S2 where there is an S2), then the two vertical directions on the
         // column-parallel pass, the upward one deciding the winners -- no sweep, no ring, no epoch, no sweep stream
@@ -224,6 +252,7 @@ static int sgm_issue(const SgmPlan& plan, const SgmCall& c)
             case SgmStep::PATH_H: launch_path_h(p, c); break;
             case SgmStep::VERT: launch_vert(p, c); break;
             case SgmStep::ADD_S2: launch_sgm_add_s2(c); break;
+            case SgmStep::VERT3: launch_vert3(p, c); break;
             case SgmStep::SWEEP: if (!launch_sweep(p, c)) return i; break;
         }
     }
@@ -236,7 +265,8 @@ const char* launch_sgm(Plane8 L, Plane8 R, Plane16W disp, const SGMGeom& g, cons
     launch_sgm_cost(L, R, g, b, p.blockSize, p.cost_limit, p.cn, p.ftz, p.cost, n, stream);
     // (the right image's bounds are dead once the pixel costs exist: 8 bytes per pixel for the winners; C, S and S2 are whole
     // allocations: 16-byte aligned, as the packed loads and stores of the path passes need)
-    const SgmCall c{g, b, p.P1, p.P2, p.uniq, n, (SgmWin*)b.gr, stream};
+    if (paths == 3) launch_sgm_warm3(g, b, p.blockSize, p.cost_limit, p.cn, p.ftz, p.cost, n, stream);   // (reads the bounds: before b.gr is reused)
+    const SgmCall c{g, b, p.P1, p.P2, p.uniq, n, (SgmWin*)b.gr, stream, p.blockSize};
     SgmPlan plan = plan_sgm(g, paths, n, lim);
     const int issued = sgm_issue(plan, c);
     if (issued < plan.npasses) {                     // a refused sweep: the remainder without sweeps, which nothing can refuse
@@ -245,7 +275,7 @@ const char* launch_sgm(Plane8 L, Plane8 R, Plane16W disp, const SGMGeom& g, cons
         plan = plan_sgm(g, paths, n, rest, sgm_done(plan, issued));
         sgm_issue(plan, c);
     }
-    sgm_finish(disp, g, b, p.disp12MaxDiff, p.speckleWindowSize, p.speckleRange, n, stream, c.win);
+    sgm_finish(disp, g, b, p.disp12MaxDiff, p.speckleWindowSize, p.speckleRange, n, stream, c.win, paths != 3);
     return plan.variant;
 }
 

@@ -334,6 +334,51 @@ __global__ __launch_bounds__(256) void k_sgm_box_any(const T* pix, uint16_t* C, 
     }
 }
 
+// MODE_SGBM_3WAY's warm-up block costs (rule T3): for stripe s = 1 .. 3 with first source row a > 0 the
+// rows y in [a, min(a + R, e)) get C'(y) = sum over j = -R .. R of h(clamp(y + j, a, H - 1)) -- R3's window with its top clamped to
+// the stripe's first source row instead of the frame's.  thread = (x, four consecutive d) of one stripe of one frame, as in
+// k_sgm_box; h(r), the horizontal sum of row r's pixel costs (first and last column of the domain replicated), comes straight
+// from F::cost, so no cost volume is read and none of the kernels above changes.  C'(a) = (R + 1) h(a) + h(a + 1) + .. + h(a + R);
+// a row further down the window gains h(y + 1 + R) and loses one h(a).  At most 2 R rows of h per thread.  Sums are 32-bit; a
+// C' above cost_limit (> 0) sets *ovf and is stored truncated (T8: the caller refuses the frame).
+// Cw: [frame][stripe - 1][row - a, wrows of them][x - x0][d].
+template <typename F>
+__global__ __launch_bounds__(256) void k_sgm_warm3(const uint2* bl, const uint2* br, uint16_t* Cw, SGMGeom g, Sgm3Stripes st, int R,
+                                                   int wrows, int cost_limit, int32_t* ovf)
+{
+    const int dq = g.D >> 2;
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;          // over W1 * D/4
+    if (idx >= (size_t)g.W1 * dq) return;
+    const int d = (int)(idx % dq) * 4, xi = (int)(idx / dq);
+    const int f = blockIdx.z;
+    const Sgm3Stripe s = st.s[1 + blockIdx.y];
+    if (s.a <= 0 || s.o >= s.e) return;                                 // C' = C (T3), or an empty stripe
+    struct Sum4 { int v[4]; };
+    const auto hsum = [&](int y) -> Sum4 {
+        const size_t row = ((size_t)f * g.H + min(y, g.H - 1)) * g.W;
+        Sum4 h = {{0, 0, 0, 0}};
+        for (int k = -R; k <= R; ++k) {
+            const int x = g.x0 + min(max(xi + k, 0), g.W1 - 1);
+            uint32_t w0, w1;
+            F::widen(F::cost(bl, br, row, x, x - (d + g.minD)), w0, w1);
+            h.v[0] += (int)(w0 & 0xffffu); h.v[1] += (int)(w0 >> 16); h.v[2] += (int)(w1 & 0xffffu); h.v[3] += (int)(w1 >> 16);
+        }
+        return h;
+    };
+    const Sum4 ha = hsum(s.a);
+    int sum[4];
+    for (int j = 0; j < 4; ++j) sum[j] = (R + 1) * ha.v[j];
+    for (int k = 1; k <= R; ++k) { const Sum4 h = hsum(s.a + k); for (int j = 0; j < 4; ++j) sum[j] += h.v[j]; }
+    const int rows = min(wrows, s.e - s.a);
+    uint16_t* out = Cw + ((((size_t)f * (SGM3_STRIPES - 1) + blockIdx.y) * wrows) * g.W1 + xi) * g.D + d;
+    for (int k = 0; k < rows; ++k) {
+        *(uint2*)(out + (size_t)k * g.W1 * g.D) =
+            make_uint2((uint32_t)(sum[0] & 0xffff) | ((uint32_t)sum[1] << 16), (uint32_t)(sum[2] & 0xffff) | ((uint32_t)sum[3] << 16));
+        if (cost_limit > 0 && max(max(sum[0], sum[1]), max(sum[2], sum[3])) > cost_limit) *ovf = 1;
+        if (k + 1 < rows) { const Sum4 h = hsum(s.a + k + 1 + R); for (int j = 0; j < 4; ++j) sum[j] += h.v[j] - ha.v[j]; }
+    }
+}
+
 // rtdm_debug_sgm_cost16: the u16 cost forms for gray frames as well (they must give what the u8 forms give)
 static std::atomic<int> g_cost16{0};
 void sgm_cost16_set(int on) { g_cost16.store(on ? 1 : 0, std::memory_order_relaxed); }
@@ -414,6 +459,25 @@ void launch_sgm_cost(Plane8 L, Plane8 R, const SGMGeom& g, const SGMBuffers& b, 
         else hipLaunchKernelGGL(k_sgm_pix16<1>, xgrid, blk, 0, stream, bl, br, b.S, g);
         launch_box<uint16_t>(g, b, b.S, Rw, cost_limit, n, stream);
     }
+}
+
+// k_sgm_warm3 in the pixel-cost form launch_sgm_cost has just used for the same arguments, over the records it left in b.gl / b.gr
+// (colour: b.cl / b.cr) -> b.Cw.  blockSize 1: there is no C', nothing is launched.
+void launch_sgm_warm3(const SGMGeom& g, const SGMBuffers& b, int blockSize, int cost_limit, int cn, int ftz, SgmCostKind cost, int n,
+                      hipStream_t stream)
+{
+    const int Rw = blockSize / 2, wrows = sgm3_warm_rows(blockSize, g.H);
+    if (Rw == 0) return;
+    const Sgm3Stripes st = sgm3_stripes(g.H, blockSize);
+    const dim3 grid((unsigned)(((size_t)g.W1 * (g.D / 4) + 255) / 256), SGM3_STRIPES - 1, n), blk(256);
+    const bool census = cost.kind == SGM_COST_CENSUS;
+    const uint2 *bl = (const uint2*)(!census && cn == 3 ? b.cl : b.gl), *br = (const uint2*)(!census && cn == 3 ? b.cr : b.gr);
+#define RTDM_WARM3(F) hipLaunchKernelGGL((k_sgm_warm3<F>), grid, blk, 0, stream, bl, br, b.Cw, g, st, Rw, wrows, cost_limit, b.ovf)
+    if (census) RTDM_WARM3(CostCensus);
+    else if (!sgm_cost16_needed(cn, ftz)) RTDM_WARM3(Cost8);
+    else if (cn == 3) RTDM_WARM3(Cost16<3>);
+    else RTDM_WARM3(Cost16<1>);
+#undef RTDM_WARM3
 }
 
 }  // namespace rtdm

@@ -8,6 +8,8 @@
 //                the winners: wave minimum, uniqueness, quadratic sub-pixel) -> 8 bytes per pixel
 //   k_sgm_vert   MODE_HH4's two vertical directions, one pass each: a line per half-wave, neighbouring columns in neighbouring
 //                half-waves, no LDS, no barrier, no wait on another workgroup (the upward pass decides the winners)
+//   k_sgm_vert3  MODE_SGBM_3WAY's downward direction in four row stripes, k_sgm_vert's layout over (columns, frame, stripe);
+//                always the last pass
 #include "rtdm_sgm.h"
 
 #include <cstdlib>
@@ -389,6 +391,85 @@ __global__ __launch_bounds__(256) void k_sgm_vert(const uint16_t* C, uint16_t* S
     }
 }
 
+// MODE_SGBM_3WAY's vertical direction (rules T1, T4-T6): (0, 1) in four row stripes, each a chain of its
+// own that starts at the stripe's first source row a with L = C'(a).  k_sgm_vert's layout -- a line per half-wave, neighbouring
+// columns in neighbouring half-waves, sgm_line_step, PF rows requested ahead -- over a grid of (columns, frame, stripe); like
+// k_sgm_vert it has no LDS, no barrier and no wait on another workgroup in any form: the grid may be of any size and run in any
+// order.  Rows [a, o) serve the recurrence only: their block cost alone is loaded, C' (Cw, k_sgm_warm3) for the first ncw rows of
+// a stripe with a > 0 and C below them.  Rows [o, e) load C and S (ADD2: and S2, the other horizontal direction's L_r), form
+// min(S + L, 32767) (T5) and decide the winner in the lanes (sgm_wta_half): this is always the last pass, S is never written.
+template <int NP2, bool ADD2, int PF>
+__global__ __launch_bounds__(256) void k_sgm_vert3(const uint16_t* C, const uint16_t* Cw, const uint16_t* S, const uint16_t* S2, SGMGeom g,
+                                                   Sgm3Stripes st, int wrows, int P1, int P2, SgmWin* win, int uniq)
+{
+    const int lane = threadIdx.x & 63, hl = lane & 31;
+    const int D = g.D, W1 = g.W1, H = g.H;
+    const int col = blockIdx.x * (blockDim.x >> 5) + (threadIdx.x >> 5);
+    if ((col & ~1) >= W1) return;                                 // whole waves only
+    const bool ok = col < W1;                                     // (an odd W1's last wave: its second half repeats the last column)
+    const int xc = min(col, W1 - 1), f = blockIdx.y, si = blockIdx.z;
+    const Sgm3Stripe s = st.s[si];
+    if (s.o >= s.e) return;                                       // an empty stripe
+    const int a = s.a, nrows = s.e - a, nwarm = s.o - a;          // steps of the chain; those before the first output row
+    const int ncw = a > 0 ? min(wrows, nrows) : 0;                // steps whose block cost is C' (T3; a = 0: C' = C)
+    const int d0 = hl * 2 * NP2;
+    const bool live = d0 < D;                                     // D is a multiple of 16 = of 2 * NP2
+    const uint32_t P1s = (uint32_t)P1 * 0x10001u, P2s = (uint32_t)P2 * 0x10001u;
+    const size_t stride = (size_t)W1 * D;                         // one row, elements
+    const size_t loff = (size_t)xc * D + (live ? d0 : 0);
+    const size_t off0 = ((size_t)f * H + a) * stride + loff;
+    const uint16_t* cp = C + off0;
+    const uint16_t* wp = ncw ? Cw + ((size_t)f * (SGM3_STRIPES - 1) + (si - 1)) * wrows * stride + loff : cp;   // (a > 0: si >= 1)
+    const uint16_t* sp = S + off0;
+    const uint16_t* tp = ADD2 ? S2 + off0 : nullptr;
+    const auto ld_c = [&](int t) { return ld_w<NP2>((t < ncw ? wp : cp) + (size_t)t * stride); };
+    PackW<NP2> cr[PF], sr[PF], tr[ADD2 ? PF : 1];
+#pragma unroll
+    for (int k = 0; k < PF; ++k) {
+        sr[k] = PackW<NP2>{};                                     // (a warm-up row's S is never loaded and never used)
+        if (ADD2 || k == 0) tr[ADD2 ? k : 0] = PackW<NP2>{};
+        if (k < nrows) {
+            cr[k] = ld_c(k);
+            if (k >= nwarm) {
+                sr[k] = ld_w<NP2>(sp + (size_t)k * stride);
+                if constexpr (ADD2) tr[k] = ld_w<NP2>(tp + (size_t)k * stride);
+            }
+        }
+    }
+    uint32_t l[NP2], mps = 0;
+#pragma unroll
+    for (int r = 0; r < NP2; ++r) l[r] = 0xffffffffu;
+    for (int base = 0; base < nrows; base += PF) {
+#pragma unroll
+        for (int k = 0; k < PF; ++k) {
+            const int step = base + k;
+            if (step >= nrows) break;
+            const PackW<NP2> c = cr[k];
+            uint32_t o[NP2];
+#pragma unroll
+            for (int r = 0; r < NP2; ++r) o[r] = sr[k].w[r];
+            if constexpr (ADD2) {
+#pragma unroll
+                for (int r = 0; r < NP2; ++r) o[r] = pk_min_u(pk_add(o[r], tr[k].w[r]), 0x7fff7fffu);       // R5
+            }
+            if (step + PF < nrows) {
+                cr[k] = ld_c(step + PF);
+                if (step + PF >= nwarm) {
+                    sr[k] = ld_w<NP2>(sp + (size_t)(step + PF) * stride);
+                    if constexpr (ADD2) tr[k] = ld_w<NP2>(tp + (size_t)(step + PF) * stride);
+                }
+            }
+            sgm_line_step<NP2, true>(l, mps, l, mps, c.w, step == 0, live, hl, P1s, P2s);
+            if (step >= nwarm) {                                  // (grid-uniform per stripe: o is S only from here on)
+#pragma unroll
+                for (int r = 0; r < NP2; ++r) o[r] = pk_min_u(pk_add(o[r], l[r]), 0x7fff7fffu);              // T5
+                const SgmWin wv = sgm_wta_half<NP2>(o, live, lane, d0, D, uniq, g.minD);
+                if (hl == 0 && ok) win[((size_t)f * H + a + step) * W1 + xc] = wv;
+            }
+        }
+    }
+}
+
 // S = min(S + S2, 32767) (R5), two elements per thread: only where the two horizontal directions ran side by side into S and S2
 // and the sweep that was to add them up could not be launched after all
 __global__ __launch_bounds__(256) void k_sgm_add_s2(uint32_t* S, const uint32_t* S2, size_t npairs)
@@ -441,7 +522,7 @@ static int sweep_capacity(SweepKernel k)
 void sgm_sweep_caps(int D, int paths, bool s2, int cap[2][3][2])
 {
     for (int i = 0; i < 12; ++i) (&cap[0][0][0])[i] = 0;
-    if (paths == 4 || D > 256) return;
+    if (paths == 4 || paths == 3 || D > 256) return;              // (MODE_SGBM_3WAY runs no sweep either)
     for (int c = 0; c < 3; ++c) {
         for (int add2 = 0; add2 <= (s2 ? 1 : 0); ++add2) cap[paths == 5][c][add2] = sweep_capacity(sweep_kernel(sgm_np2(D), paths == 5, 1 << c, add2));
         if (paths == 8) cap[1][c][0] = sweep_capacity(sweep_kernel(sgm_np2(D), true, 1 << c, false));
@@ -509,6 +590,21 @@ void launch_vert(const SgmPass& p, const SgmCall& c)
                           else hipLaunchKernelGGL((k_sgm_vert<N, false, false, PF>), vgrid, blk, 0, c.stream, c.b.C, c.b.S, S2, g, p.dy, c.P1, c.P2, c.win, c.uniq); } while (0)
     switch (sgm_np2(g.D)) { case 1: RTDM_VERT(1); break; case 2: RTDM_VERT(2); break; default: RTDM_VERT(4); break; }
 #undef RTDM_VERT
+}
+
+// One k_sgm_vert3 launch: MODE_SGBM_3WAY's striped (0, 1), always last.  p.s2: S2 is added to S on the way.  Columns per
+// workgroup and rows of prefetch as launch_vert has them.
+void launch_vert3(const SgmPass& p, const SgmCall& c)
+{
+    constexpr int cols = 2, PF = 8;
+    const SGMGeom& g = c.g;
+    const Sgm3Stripes st = sgm3_stripes(g.H, c.blockSize);
+    const int wrows = sgm3_warm_rows(c.blockSize, g.H);
+    const dim3 vgrid((g.W1 + cols - 1) / cols, c.n, SGM3_STRIPES), blk(32 * cols);
+#define RTDM_VERT3(N) do { if (p.s2) hipLaunchKernelGGL((k_sgm_vert3<N, true, PF>), vgrid, blk, 0, c.stream, c.b.C, c.b.Cw, c.b.S, c.b.S2, g, st, wrows, c.P1, c.P2, c.win, c.uniq); \
+                           else hipLaunchKernelGGL((k_sgm_vert3<N, false, PF>), vgrid, blk, 0, c.stream, c.b.C, c.b.Cw, c.b.S, c.b.S2, g, st, wrows, c.P1, c.P2, c.win, c.uniq); } while (0)
+    switch (sgm_np2(g.D)) { case 1: RTDM_VERT3(1); break; case 2: RTDM_VERT3(2); break; default: RTDM_VERT3(4); break; }
+#undef RTDM_VERT3
 }
 
 void launch_sgm_add_s2(const SgmCall& c)

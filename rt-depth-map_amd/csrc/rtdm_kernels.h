@@ -243,6 +243,7 @@ struct SGMBuffers {
     uint8_t* pix;            // pixel cost                 [n][H][W1][D]
     uint16_t *C, *S;         // block cost, aggregated     [n][H][W1][D]
     uint16_t* S2;            // the (-1, 0) direction's path costs where the two horizontal directions run side by side (or null)
+    uint16_t* Cw;            // MODE_SGBM_3WAY: the warm-up block costs C' (T3)  [n][3][min(blockSize / 2, H)][W1][D], set per call
     int32_t *label, *size, *rowcnt; uint32_t* runs; int16_t* headmap;   // speckle filter workspace
     int32_t* ovf;            // set to 1 by the block-cost kernel where a block cost + P2 passes 32767 (windows > 17 only)
     // row-synchronous sweep (k_sgm_sweep): edge ring between neighbouring strips, give-up flag (page-locked, host readable),
@@ -268,15 +269,18 @@ void launch_sgm_cost(Plane8 L, Plane8 R, const SGMGeom& g, const SGMBuffers& b, 
                      SgmCostKind cost, int n, hipStream_t stream);
 // The path passes between the cost stage and the winners' left-right check.  plan_sgm (k_sgm.hip) decides, once per call and
 // without touching the runtime, what launch_sgm then issues; the route table is in DESIGN.md ("SGM: routes").  Directions are
-// indexed 0..7 = (1,0) (-1,0) (0,1) (0,-1) (1,1) (-1,1) (1,-1) (-1,-1): paths 4 runs 0..3, paths 5 those with dy >= 0, paths 8 all.
+// indexed 0..7 = (1,0) (-1,0) (0,1) (0,-1) (1,1) (-1,1) (1,-1) (-1,-1): paths 4 runs 0..3, paths 5 those with dy >= 0, paths 8 all,
+// paths 3 (MODE_SGBM_3WAY, through rtdm_sgm_set_mode only) 0..2 with (0,1) cut into stripes.
 //   WIDE    k_sgm_wide, one direction, `waves` (1 / 4) waves per line: D > 256 or rtdm_debug_sgm_wide_paths
 //   PATH_H  k_sgm_path_h, one direction; s2: (dx, 0) -> S and (-dx, 0) -> S2 side by side
 //   VERT    k_sgm_vert over (0, dy); s2: S2 is added to S on the way
 //   SWEEP   k_sgm_sweep over (0, dy), (+1, dy), (-1, dy), `cols` (1 / 2 / 4) columns per half-wave, `strips` strips per frame,
 //           `items` = n strips on `grid` workgroups; s2: S2 is added to S on the way
 //   ADD_S2  k_sgm_add_s2: S = min(S + S2, 32767)
+//   VERT3   k_sgm_vert3 over (0, 1) in the four row stripes of MODE_SGBM_3WAY (paths 3, rules T1-T8 of DESIGN.md section 4.21),
+//           always the last pass; s2: S2 is added to S on the way
 // first: S is written, not added to; last: the pass decides the winners instead of writing S.
-enum class SgmStep { WIDE, PATH_H, VERT, SWEEP, ADD_S2 };
+enum class SgmStep { WIDE, PATH_H, VERT, SWEEP, ADD_S2, VERT3 };
 struct SgmPass {
     SgmStep step;
     int dir, dx, dy;                       // direction index and vector (ADD_S2: -1, 0, 0)
@@ -286,7 +290,7 @@ struct SgmPass {
 };
 struct SgmPlan {
     SgmPass pass[8]; int npasses;
-    const char* variant;                   // "sweep", "half", "vert", "wide_w1", "wide_w4"
+    const char* variant;                   // "sweep", "half", "vert", "wide_w1", "wide_w4", "vert3"
 };
 // What a plan may use of the handle and the device, filled by the caller: sweep -- the handle may run k_sgm_sweep (edge ring
 // and both events there, give-up flag clear); s2 -- S2 exists; cap -- the workgroups the device holds at once of the

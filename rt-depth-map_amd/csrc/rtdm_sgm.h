@@ -6,6 +6,7 @@
 #include "rtdm_kernels.h"
 #include "rtdm_device.h"
 #include "rtdm_pk16.h"
+#include "rtdm_sgm_stripes.h"
 
 namespace rtdm {
 
@@ -188,10 +189,16 @@ __device__ __forceinline__ SgmWin sgm_win_record(int bd, int mins, int s_p, int 
 // issues the planned pass and decides nothing.
 static constexpr int SWEEP_RING = 4;                      // rows of edge data kept per (strip, side) of a k_sgm_sweep launch
 inline int sgm_np2(int D) { return D <= 64 ? 1 : (D <= 128 ? 2 : 4); }   // u16 pairs per lane of the half-wave forms
-struct SgmCall { const SGMGeom& g; const SGMBuffers& b; int P1, P2, uniq, n; SgmWin* win; hipStream_t stream; };
+struct SgmCall { const SGMGeom& g; const SGMBuffers& b; int P1, P2, uniq, n; SgmWin* win; hipStream_t stream; int blockSize; };   // (blockSize: VERT3 only)
 void launch_sgm_wide(const SgmPass& p, const SgmCall& c);
 void launch_path_h(const SgmPass& p, const SgmCall& c);
 void launch_vert(const SgmPass& p, const SgmCall& c);
+// MODE_SGBM_3WAY (T1-T8): the warm-up block costs C' of stripes 1 .. 3 -> b.Cw (k_sgm_cost.hip, after
+// launch_sgm_cost and with its arguments: the bounds or descriptors are still in place), and the striped vertical pass that
+// reads them and decides the winners (k_sgm_paths.hip).  Rows of C' kept per stripe: sgm3_warm_rows (rtdm_sgm_stripes.h).
+void launch_sgm_warm3(const SGMGeom& g, const SGMBuffers& b, int blockSize, int cost_limit, int cn, int ftz, SgmCostKind cost, int n,
+                      hipStream_t stream);
+void launch_vert3(const SgmPass& p, const SgmCall& c);
 // false: the runtime refused (device, sweep stream or event record) before anything was launched
 bool launch_sweep(const SgmPass& p, const SgmCall& c);
 void launch_sgm_add_s2(const SgmCall& c);

@@ -235,9 +235,10 @@ HIPSGMCore::HIPSGMCore(int blockSize, int minDisparity, int numOfDisparities, in
     rtdm_sgm_default_params(&p, numOfDisparities, blockSize);     // P1 = 8*3*5*5, P2 = 32*3*5*5 (sgbm-sw.cpp:17-18)
     p.minDisparity = minDisparity; p.uniquenessRatio = uniquenessRatio; p.speckleWindowSize = speckleWindowSize;
     p.speckleRange = speckleRange; p.disp12MaxDiff = disp12MaxDiff; p.paths = paths;
-    params_ = p; maxWidth_ = maxWidth; maxHeight_ = maxHeight; device_ = device;
+    params_ = p; maxWidth_ = maxWidth; maxHeight_ = maxHeight; device_ = device; createdPaths_ = paths;
     status_ = rtdm_sgm_create(&p, maxWidth, maxHeight, 1, device, &sg_);
     if (status_ != RTDM_OK) std::fprintf(stderr, "HIPSemiGlobalMatcher: %s\n", rtdm_strerror(status_));
+    else rtdm_sgm_get_mode(sg_, &mode_);
 }
 HIPSGMCore::~HIPSGMCore() { rtdm_sgm_destroy(sg_); }
 int HIPSGMCore::compute(const uint8_t* left, size_t leftStep, const uint8_t* right, size_t rightStep, int rows, int cols,
@@ -266,6 +267,14 @@ int HIPSGMCore::setCost(int cost, int cw, int ch)
     if (!sg_) return status_ != RTDM_OK ? status_ : RTDM_ERR_NO_DEVICE;
     const int rc = rtdm_sgm_set_cost(sg_, cost, cw, ch);
     if (rc == RTDM_OK) rtdm_sgm_get_cost(sg_, &cost_, &censusWidth_, &censusHeight_);
+    return rc;
+}
+
+int HIPSGMCore::setMode(int mode)
+{
+    if (!sg_) return status_ != RTDM_OK ? status_ : RTDM_ERR_NO_DEVICE;
+    const int rc = rtdm_sgm_set_mode(sg_, mode);
+    if (rc == RTDM_OK) { mode_ = mode; params_.paths = pathsForMode(mode); }
     return rc;
 }
 
@@ -347,10 +356,12 @@ HIPSGMCore* createRightMatcher(const HIPSGMCore& left)
 {
     rtdm_sgm_params p;
     rtdm_sgm_right_params(&left.params(), &p);
+    // (created as the left one was -- paths = 3 cannot be created --, the mode set on it since is copied below)
     HIPSGMCore* m = new HIPSGMCore(p.blockSize, p.minDisparity, p.numDisparities, p.uniquenessRatio, p.speckleWindowSize,
-                                   p.speckleRange, p.disp12MaxDiff, left.maxWidth(), left.maxHeight(), left.device(), p.paths);
+                                   p.speckleRange, p.disp12MaxDiff, left.maxWidth(), left.maxHeight(), left.device(), left.createdPaths());
     if (left.preFilterCap()) m->setPreFilterCap(left.preFilterCap());     // not part of rtdm_sgm_params (W1)
     if (left.cost() != RTDM_SGM_COST_BT) m->setCost(left.cost(), left.censusWidth(), left.censusHeight());   // nor is the pixel cost
+    if (left.mode() != m->mode()) m->setMode(left.mode());               // nor a mode set on the live matcher
     return m;
 }
 

@@ -86,7 +86,8 @@ private:
 // hard-codes them; setROI1/2 are no-ops there too.  paths = 8 (BASELINE config 5) or 5: the directions of
 // cv::StereoSGBM's default MODE_SGBM, which is what sgbm-sw.cpp:15 creates -- the adapter sgbm-hip.cpp passes 5 unless told
 // another mode; 4: MODE_HH4 (left, right, down, up).  pathsForMode maps cv::StereoSGBM::setMode's values to the direction
-// count; MODE_SGBM_3WAY maps to 3, which rtdm_sgm_create refuses (RTDM_ERR_UNSUPPORTED), anything else to 0 (RTDM_ERR_BAD_PARAM).
+// count; MODE_SGBM_3WAY maps to 3, which rtdm_sgm_create refuses (RTDM_ERR_UNSUPPORTED; setMode serves it), anything else to 0
+// (RTDM_ERR_BAD_PARAM).
 enum SGMMode { MODE_SGBM = 0, MODE_HH = 1, MODE_SGBM_3WAY = 2, MODE_HH4 = 3 };   // cv::StereoSGBM's values
 class HIPSGMCore {
 public:
@@ -108,6 +109,12 @@ public:
     // RTDM_SGM_COST_CENSUS over a cw x ch window (cw 3, 5, 7, 9; ch 3, 5, 7; gray frames only) -- the project's own cost for
     // pairs whose cameras expose differently; the library has no counterpart
     int setCost(int cost, int cw = 9, int ch = 7);
+    // cv::StereoSGBM::setMode on the live matcher (rtdm_sgm_set_mode), from the next compute on: MODE_SGBM, MODE_HH, MODE_HH4 or
+    // MODE_SGBM_3WAY -- the one door to the last (rules T1-T8; numOfDisparities <= 256); params().paths
+    // follows it (3 under MODE_SGBM_3WAY), createdPaths() stays what the matcher was created with
+    int setMode(int mode);
+    int mode() const { return mode_; }
+    int createdPaths() const { return createdPaths_; }
     int status() const { return status_; }
     const rtdm_sgm_params& params() const { return params_; }
     int preFilterCap() const { return preFilterCap_; }
@@ -124,6 +131,7 @@ private:
     rtdm_sgm_params params_;
     int preFilterCap_ = 0, maxWidth_ = 0, maxHeight_ = 0, device_ = 0;
     int cost_ = RTDM_SGM_COST_BT, censusWidth_ = 9, censusHeight_ = 7;
+    int mode_ = MODE_HH, createdPaths_ = 8;
 };
 
 // The disparity WLS post-filter (cv::ximgproc::DisparityWLSFilter, the reference's ENABLE_POST_FILTER block,

@@ -167,8 +167,9 @@ class HIPSemiGlobalMatcher(Handle):
     any multiple of 16, as in cv::StereoSGBM (above 256 the path passes run on the wide-line kernel); the library checks it.
     preFilterCap is cv::StereoSGBM's (0 .. 127, setPreFilterCap); compute / compute_device take gray (H x W) or
     interleaved colour (H x W x 3) uint8 frames, as cv::StereoSGBM::compute takes CV_8UC1 and CV_8UC3.
-    mode is cv::StereoSGBM::setMode's value (MODE_SGBM, MODE_HH, MODE_HH4; MODE_SGBM_3WAY is refused by the library with
-    RTDM_ERR_UNSUPPORTED); paths names the same thing by its direction count (5, 8, 4) and defaults to 8.
+    mode is cv::StereoSGBM::setMode's value (MODE_SGBM, MODE_HH, MODE_HH4; MODE_SGBM_3WAY is refused at creation with
+    RTDM_ERR_UNSUPPORTED and served by setMode on the live matcher); paths names the same thing by its direction count (5, 8, 4)
+    and defaults to 8.
     cost is the pixel cost: COST_BT (the default, cv::StereoSGBM's) or COST_CENSUS, the Hamming distance of census descriptors
     over a census = (width, height) window, width in 3, 5, 7, 9 and height in 3, 5, 7 -- this project's own, with no library
     counterpart, for pairs whose cameras expose differently (gray frames only; rtdm_sgm_set_cost in include/rtdm.h)."""
@@ -199,6 +200,7 @@ class HIPSemiGlobalMatcher(Handle):
         self.width, self.height, self.max_batch, self.device = width, height, max_batch, device
         B.check(B.lib().rtdm_sgm_create(C.byref(self.params), width, height, max_batch, device, C.byref(self._h)),
                 "rtdm_sgm_create")
+        self._created_paths = paths         # what create_right_matcher creates with, whatever setMode has said since
         self.preFilterCap = 0
         try:
             if preFilterCap:
@@ -236,6 +238,22 @@ class HIPSemiGlobalMatcher(Handle):
         c, w, h = C.c_int(), C.c_int(), C.c_int()
         B.check(B.lib().rtdm_sgm_get_cost(self._h, C.byref(c), C.byref(w), C.byref(h)), "rtdm_sgm_get_cost")
         return c.value, (w.value, h.value)
+
+    def setMode(self, mode):
+        """cv::StereoSGBM::setMode on the live matcher, from the next compute call on (rtdm_sgm_set_mode): MODE_SGBM, MODE_HH,
+        MODE_HH4 or MODE_SGBM_3WAY -- the one door to the last (rules T1-T8; numOfDisparities <= 256).
+        The mode property and params.paths follow it."""
+        if isinstance(mode, bool) or not isinstance(mode, (int, np.integer)) or int(mode) not in self._MODE_PATHS:
+            raise ValueError("mode must be MODE_SGBM (0), MODE_HH (1), MODE_SGBM_3WAY (2) or MODE_HH4 (3); got %r" % (mode,))
+        mode = int(mode)
+        B.check(B.lib().rtdm_sgm_set_mode(self._h, mode), "rtdm_sgm_set_mode")
+        self.params.paths = self._MODE_PATHS[mode]
+
+    def getMode(self):
+        """cv::StereoSGBM::getMode, as the library holds it (rtdm_sgm_get_mode)"""
+        v = C.c_int()
+        B.check(B.lib().rtdm_sgm_get_mode(self._h, C.byref(v)), "rtdm_sgm_get_mode")
+        return v.value
 
     def setPreFilterCap(self, preFilterCap):
         """cv::StereoSGBM::setPreFilterCap: applies from the next compute call; >= 128 is refused (RTDM_ERR_UNSUPPORTED)."""
@@ -292,7 +310,7 @@ class HIPSemiGlobalMatcher(Handle):
 
     @property
     def path_variant(self):
-        """the path-pass form of the last call: "sweep", "vert", "half", "wide_w1", "wide_w4" -- rtdm_sgm_path_variant"""
+        """the path-pass form of the last call: "sweep", "vert", "half", "wide_w1", "wide_w4", "vert3" -- rtdm_sgm_path_variant"""
         return B.lib().rtdm_sgm_path_variant(self._h).decode()
 
     def compute_device(self, d_left, d_right, d_disp, stream=None):
@@ -320,9 +338,17 @@ def create_right_matcher(m):
     if isinstance(m, HIPSemiGlobalMatcher):
         rp = B.SGMParams()
         B.check(B.lib().rtdm_sgm_right_params(C.byref(m.params), C.byref(rp)), "rtdm_sgm_right_params")
-        return HIPSemiGlobalMatcher(blockSize=rp.blockSize, minDisparity=rp.minDisparity, numOfDisparities=rp.numDisparities,
-                                    uniquenessRatio=rp.uniquenessRatio, speckleWindowSize=rp.speckleWindowSize,
-                                    speckleRange=rp.speckleRange, disp12MaxDiff=rp.disp12MaxDiff, P1=rp.P1, P2=rp.P2,
-                                    width=m.width, height=m.height, max_batch=m.max_batch, device=m.device, paths=rp.paths,
-                                    preFilterCap=m.preFilterCap, cost=m.getCost()[0], census=m.getCost()[1])
+        # (the mode is not part of what rtdm_sgm_right_params carries over: created as the left one was, then set as it is set)
+        r = HIPSemiGlobalMatcher(blockSize=rp.blockSize, minDisparity=rp.minDisparity, numOfDisparities=rp.numDisparities,
+                                 uniquenessRatio=rp.uniquenessRatio, speckleWindowSize=rp.speckleWindowSize,
+                                 speckleRange=rp.speckleRange, disp12MaxDiff=rp.disp12MaxDiff, P1=rp.P1, P2=rp.P2,
+                                 width=m.width, height=m.height, max_batch=m.max_batch, device=m.device, paths=m._created_paths,
+                                 preFilterCap=m.preFilterCap, cost=m.getCost()[0], census=m.getCost()[1])
+        if m.params.paths != m._created_paths:
+            try:
+                r.setMode(m.mode)
+            except B.RtdmError:
+                r.close()
+                raise
+        return r
     raise ValueError("create_right_matcher takes a HIPMatcher or a HIPSemiGlobalMatcher; got %s" % type(m).__name__)
