@@ -17,7 +17,7 @@ struct rtdm_sgm {
     int prefilter_cap;             // rtdm_sgm_set_prefilter_cap: R1's ftzero = max(preFilterCap, 15) | 1
     SgmCostKind cost;              // rtdm_sgm_set_cost: the pixel cost of the next call (R1, or census descriptors: N1-N5)
     int cost_limit;                // of the current call, > 0 where a block cost + P2 can pass 32767: a block cost above it would
-                                   // wrap the library's 16-bit path costs (sgm_cost_limit)
+                                   // wrap the library's 16-bit path costs (sgm_block_cost_limit, rtdm_sgm_cost_plan.h)
     int32_t* hOvf;                 // page-locked copy of b.ovf
     uint32_t sweep_epoch;          // launches of k_sgm_sweep (tags of its edge ring)
     SgmLimits lim;                 // cap: workgroups the device holds at once per sweep form, asked by the first call (caps_asked)
@@ -38,16 +38,9 @@ static int sgm_sweep_check(rtdm_sgm* sg)
     return RTDM_ERR_HIP;
 }
 
-// R1 generalised (oracle rule restated for colour in tests/sgm_cn_ref.py): a pixel cost is at most M = cn (2 ftzero + 63) -- under
-// the census cost (N4) M = cw ch - 1 --, a block cost at most M blockSize^2; where that + P2 can pass 32767 the block costs are
-// checked against 32767 - P2
 static_assert(SGM_COST_BT == RTDM_SGM_COST_BT && SGM_COST_CENSUS == RTDM_SGM_COST_CENSUS, "the kernels' names for rtdm.h's values");
 static int sgm_ftzero(const rtdm_sgm* sg) { return std::max(sg->prefilter_cap, 15) | 1; }
-static int sgm_cost_limit(const rtdm_sgm* sg, int cn)
-{
-    const long M = sg->cost.kind == SGM_COST_CENSUS ? (long)sg->cost.cw * sg->cost.ch - 1 : (long)cn * (2 * sgm_ftzero(sg) + 63);
-    return M * sg->p.blockSize * sg->p.blockSize + sg->p.P2 > 32767 ? 32767 - sg->p.P2 : 0;
-}
+static int sgm_cost_limit(const rtdm_sgm* sg, int cn) { return sgm_block_cost_limit(sg->cost, cn, sgm_ftzero(sg), sg->p.blockSize, sg->p.P2); }
 
 // colour frames: the 24-byte bounds records (and, for the host entry point, the staging of the interleaved input)
 static int sgm_colour_buffers(rtdm_sgm* sg, bool host)
@@ -196,7 +189,7 @@ static int sgm_chunk(rtdm_sgm* sg, int n, int cn, Plane8 L, Plane8 R, int W, int
     sg->lim.ring_words = b.ring_words;
     sg->path_variant = launch_sgm(L, R, disp, g, b, sg->lim, p.paths, n, s,
                                   SgmParams{p.blockSize, p.P1, p.P2, p.uniquenessRatio, p.disp12MaxDiff, p.speckleWindowSize,
-                                            p.speckleRange, sg->cost_limit, cn, sgm_ftzero(sg), sg->cost});
+                                            p.speckleRange, cn, sgm_ftzero(sg), sg->cost});
     HIPC(hipGetLastError());
     return RTDM_OK;
 }

@@ -5,7 +5,7 @@
 // cv::StereoSGBM is unpinned).  Cost volumes live on the column domain [x0, x1) = [minD+D, W+min(minD,0)) and are laid
 // out [frame][y][x - x0][d] with d fastest, so a wavefront's lanes = consecutive disparities = one coalesced line per pixel.
 //
-//   k_sgm_cost.hip   the two frames -> the block costs C (launch_sgm_cost)
+//   k_sgm_cost.hip   the two frames -> the block costs C (plan_sgm_cost / launch_sgm_cost)
 //   k_sgm_paths.hip  the path passes over lines of at most 256 disparities: C -> S, the last pass -> the winners
 //   k_sgm_wide.hip   the path pass for wider lines
 //   here             the schedule of the passes (plan_sgm / launch_sgm) and what follows the winners:
@@ -262,10 +262,9 @@ static int sgm_issue(const SgmPlan& plan, const SgmCall& c)
 const char* launch_sgm(Plane8 L, Plane8 R, Plane16W disp, const SGMGeom& g, const SGMBuffers& b, const SgmLimits& lim, int paths,
                        int n, hipStream_t stream, SgmParams p)
 {
-    launch_sgm_cost(L, R, g, b, p.blockSize, p.cost_limit, p.cn, p.ftz, p.cost, n, stream);
-    // (the right image's bounds are dead once the pixel costs exist: 8 bytes per pixel for the winners; C, S and S2 are whole
+    launch_sgm_cost(plan_sgm_cost(g.D, g.H, p.blockSize, p.P2, p.cn, p.ftz, p.cost, paths, sgm_cost16_forced()), L, R, g, b, n, stream);
+    // (the right image's bounds are dead once the cost stage is through: 8 bytes per pixel for the winners; C, S and S2 are whole
     // allocations: 16-byte aligned, as the packed loads and stores of the path passes need)
-    if (paths == 3) launch_sgm_warm3(g, b, p.blockSize, p.cost_limit, p.cn, p.ftz, p.cost, n, stream);   // (reads the bounds: before b.gr is reused)
     const SgmCall c{g, b, p.P1, p.P2, p.uniq, n, (SgmWin*)b.gr, stream, p.blockSize};
     SgmPlan plan = plan_sgm(g, paths, n, lim);
     const int issued = sgm_issue(plan, c);

@@ -5,11 +5,12 @@
 //   k_sgm_bounds x-Sobel (vertical edge replication) clipped to +-ftzero, + ftzero, and the BT bounds of it and of the
 //                intensity (border columns overwritten with ftzero, R1), per pixel and channel  (HBM bound)
 //   k_sgm_pixbox Birchfield-Tomasi pixel cost (gradient + (intensity >> 2), u8, kept in LDS) and the blockSize x blockSize sum
-//                with clamped coordinates -> C (u16), windows <= 7; larger windows: k_sgm_pix (u8 volume) + k_sgm_box / _any
-//                (colour frames and ftzero >= 97, where a pixel cost passes 255: the u16 forms k_sgm_pixbox<Cost16>, k_sgm_pix16)
+//                with clamped coordinates -> C (u16), windows <= 7; larger windows: k_sgm_pix<F> (a volume) + k_sgm_box / _any
+//                (colour frames and ftzero >= 97, where a pixel cost passes 255: the u16 forms Cost16<CN> of both)
 //   k_sgm_census the other pixel cost (rtdm_sgm_set_cost, rules N1-N5 of DESIGN.md section 4.20; no library counterpart): a census
 //                descriptor per pixel and image instead of the bounds, in the same 8-byte records; the pixel cost is then the
-//                Hamming distance of two descriptors (CostCensus), through k_sgm_pixbox or k_sgm_pix_census + k_sgm_box / _any
+//                Hamming distance of two descriptors (CostCensus), through k_sgm_pixbox or k_sgm_pix + k_sgm_box / _any
+//   k_sgm_warm3  MODE_SGBM_3WAY's warm-up block costs C'.  Which of them a call runs: plan_sgm_cost (DESIGN.md "SGM: cost routes")
 #include "rtdm_sgm.h"
 
 #include <atomic>
@@ -66,6 +67,7 @@ __global__ __launch_bounds__(256) void k_sgm_bounds(Plane8 L, Plane8 R, uint2* b
 //               sums are checked against cost_limit (> 0 where a block cost + P2 can pass 32767); Cost8's stay below it.
 struct Cost8 {
     typedef uint32_t Word;
+    typedef uint8_t Elem;                                  // of a volume of such costs
     static constexpr bool CHECK = false, ROLL_P = false;
     static __device__ __forceinline__ Word cost(const uint2* bl, const uint2* br, size_t row, int x, int xr)
     { const uint2 c = sgm_cost4<1>(bl, br, row, x, xr); return __builtin_amdgcn_perm(c.y, c.x, 0x06040200u); }
@@ -75,6 +77,7 @@ struct Cost8 {
 template <int CN>
 struct Cost16 {
     typedef uint2 Word;
+    typedef uint16_t Elem;
     // (colour: the fused kernel's p loop stays rolled, or the whole body of its unrolled k loop grows past what the compiler
     // unrolls, and then ring[][k] goes to scratch)
     static constexpr bool CHECK = true, ROLL_P = CN != 1;
@@ -136,44 +139,27 @@ struct CostCensus : Cost8 {
     static __device__ __forceinline__ Word cost(const uint2* cl, const uint2* cr, size_t row, int x, int xr) { return sgm_census_cost4(cl, cr, row, x, xr); }
 };
 
-// pixel cost, u8 volume: one thread per (x, four consecutive d); d fastest
-__global__ __launch_bounds__(256) void k_sgm_pix(const uint2* bl, const uint2* br, uint8_t* pix, SGMGeom g)
+// The item of a thread of the kernels below whose grid.x covers W1 * D/4: column xi of the domain and the four consecutive
+// disparities d .. d + 3 (d fastest).  false: the thread is past the last item.
+__device__ __forceinline__ bool sgm_item(const SGMGeom& g, int& xi, int& d)
 {
     const int dq = g.D >> 2;
-    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;          // over W1 * D/4
-    if (idx >= (size_t)g.W1 * dq) return;
-    const int d = (int)(idx % dq) * 4, xi = (int)(idx / dq);
-    const int y = blockIdx.y, f = blockIdx.z;
-    const int x = g.x0 + xi, xr = x - (d + g.minD);                     // element j pairs x with xr - j
-    const size_t row = ((size_t)f * g.H + y) * g.W;
-    *(uint32_t*)(pix + (((size_t)f * g.H + y) * g.W1 + xi) * g.D + d) = Cost8::cost(bl, br, row, x, xr);
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (size_t)g.W1 * dq) return false;
+    d = (int)(idx % dq) * 4; xi = (int)(idx / dq);
+    return true;
 }
 
-// k_sgm_pix over census descriptors (N2): the same u8 volume, the same thread layout
-__global__ __launch_bounds__(256) void k_sgm_pix_census(const uint2* cl, const uint2* cr, uint8_t* pix, SGMGeom g)
+// pixel cost -> the volume pix [n][H][W1][D] of F::Elem (u8: b.pix; u16: it lives in S, dead until the first path pass writes it)
+template <typename F>
+__global__ __launch_bounds__(256) void k_sgm_pix(const uint2* bl, const uint2* br, typename F::Elem* pix, SGMGeom g)
 {
-    const int dq = g.D >> 2;
-    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;          // over W1 * D/4
-    if (idx >= (size_t)g.W1 * dq) return;
-    const int d = (int)(idx % dq) * 4, xi = (int)(idx / dq);
+    int xi, d;
+    if (!sgm_item(g, xi, d)) return;
     const int y = blockIdx.y, f = blockIdx.z;
-    const int x = g.x0 + xi, xr = x - (d + g.minD);                     // N2: xr - 3 >= 1 on the column domain
+    const int x = g.x0 + xi, xr = x - (d + g.minD);                     // element j pairs x with xr - j (N2: xr - 3 >= 1 on the domain)
     const size_t row = ((size_t)f * g.H + y) * g.W;
-    *(uint32_t*)(pix + (((size_t)f * g.H + y) * g.W1 + xi) * g.D + d) = CostCensus::cost(cl, cr, row, x, xr);
-}
-
-// k_sgm_pix with u16 pixel costs -> pix [n][H][W1][D] (it lives in S, dead until the first path pass writes it)
-template <int CN>
-__global__ __launch_bounds__(256) void k_sgm_pix16(const uint2* bl, const uint2* br, uint16_t* pix, SGMGeom g)
-{
-    const int dq = g.D >> 2;
-    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;          // over W1 * D/4
-    if (idx >= (size_t)g.W1 * dq) return;
-    const int d = (int)(idx % dq) * 4, xi = (int)(idx / dq);
-    const int y = blockIdx.y, f = blockIdx.z;
-    const int x = g.x0 + xi, xr = x - (d + g.minD);
-    const size_t row = ((size_t)f * g.H + y) * g.W;
-    *(uint2*)(pix + (((size_t)f * g.H + y) * g.W1 + xi) * g.D + d) = sgm_cost4<CN>(bl, br, row, x, xr);
+    *(typename F::Word*)(pix + (((size_t)f * g.H + y) * g.W1 + xi) * g.D + d) = F::cost(bl, br, row, x, xr);
 }
 
 // four consecutive pixel costs (u8 volume: one dword, u16 volume: one qword) added to s[0..3]
@@ -182,23 +168,24 @@ __device__ __forceinline__ void sgm_acc4(const uint8_t* p, int* s)
 __device__ __forceinline__ void sgm_acc4(const uint16_t* p, int* s)
 { const uint2 w = *(const uint2*)p; s[0] += w.x & 0xffff; s[1] += w.x >> 16; s[2] += w.y & 0xffff; s[3] += w.y >> 16; }
 
+// The four 32-bit sums of an item.  (Packing, storing and checking them stays written out in k_sgm_box, which stores them
+// unmasked, and in k_sgm_box_any and k_sgm_warm3, which truncate: a shared helper changes the instruction streams of all three.)
+struct Sum4 { int v[4]; };
+
 // block cost: thread = (x, four consecutive d); walks down a strip of rows keeping the last 2R+1 horizontal sums in
 // registers, so every pixel-cost element is read (2R+1) times instead of (2R+1)^2 times.  T: the pixel-cost volume's type
 // (uint8_t, or uint16_t where a pixel cost can pass 255: colour, preFilterCap >= 96)
 template <int R, typename T>
 __global__ __launch_bounds__(256) void k_sgm_box(const T* pix, uint16_t* C, SGMGeom g, int rows_per_strip, int cost_limit, int32_t* ovf)
 {
-    const int dq = g.D >> 2;
-    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;          // over W1 * D/4
-    if (idx >= (size_t)g.W1 * dq) return;
-    const int d = (int)(idx % dq) * 4, xi = (int)(idx / dq);
+    int xi, d;
+    if (!sgm_item(g, xi, d)) return;
     const int f = blockIdx.z;
     const int y0 = blockIdx.y * rows_per_strip, y1 = min(y0 + rows_per_strip, g.H);
     const T* base = pix + (size_t)f * g.H * g.W1 * g.D + d;
     int xs[2 * R + 1];
 #pragma unroll
     for (int k = 0; k <= 2 * R; ++k) xs[k] = min(max(xi + k - R, 0), g.W1 - 1) * g.D;
-    struct Sum4 { int v[4]; };
     const auto hsum = [&](int y) -> Sum4 {
         const T* row = base + (size_t)min(max(y, 0), g.H - 1) * g.W1 * g.D;
         Sum4 s = {{0, 0, 0, 0}};
@@ -308,14 +295,11 @@ __global__ __launch_bounds__(256) void k_sgm_pixbox(const uint2* bl, const uint2
 template <typename T>
 __global__ __launch_bounds__(256) void k_sgm_box_any(const T* pix, uint16_t* C, SGMGeom g, int R, int rows_per_strip, int cost_limit, int32_t* ovf)
 {
-    const int dq = g.D >> 2;
-    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;          // over W1 * D/4
-    if (idx >= (size_t)g.W1 * dq) return;
-    const int d = (int)(idx % dq) * 4, xi = (int)(idx / dq);
+    int xi, d;
+    if (!sgm_item(g, xi, d)) return;
     const int f = blockIdx.z;
     const int y0 = blockIdx.y * rows_per_strip, y1 = min(y0 + rows_per_strip, g.H);
     const T* base = pix + (size_t)f * g.H * g.W1 * g.D + d;
-    struct Sum4 { int v[4]; };
     const auto hsum = [&](int y) -> Sum4 {
         const T* row = base + (size_t)min(max(y, 0), g.H - 1) * g.W1 * g.D;
         Sum4 s = {{0, 0, 0, 0}};
@@ -346,14 +330,11 @@ template <typename F>
 __global__ __launch_bounds__(256) void k_sgm_warm3(const uint2* bl, const uint2* br, uint16_t* Cw, SGMGeom g, Sgm3Stripes st, int R,
                                                    int wrows, int cost_limit, int32_t* ovf)
 {
-    const int dq = g.D >> 2;
-    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;          // over W1 * D/4
-    if (idx >= (size_t)g.W1 * dq) return;
-    const int d = (int)(idx % dq) * 4, xi = (int)(idx / dq);
+    int xi, d;
+    if (!sgm_item(g, xi, d)) return;
     const int f = blockIdx.z;
     const Sgm3Stripe s = st.s[1 + blockIdx.y];
     if (s.a <= 0 || s.o >= s.e) return;                                 // C' = C (T3), or an empty stripe
-    struct Sum4 { int v[4]; };
     const auto hsum = [&](int y) -> Sum4 {
         const size_t row = ((size_t)f * g.H + min(y, g.H - 1)) * g.W;
         Sum4 h = {{0, 0, 0, 0}};
@@ -382,102 +363,72 @@ __global__ __launch_bounds__(256) void k_sgm_warm3(const uint2* bl, const uint2*
 // rtdm_debug_sgm_cost16: the u16 cost forms for gray frames as well (they must give what the u8 forms give)
 static std::atomic<int> g_cost16{0};
 void sgm_cost16_set(int on) { g_cost16.store(on ? 1 : 0, std::memory_order_relaxed); }
-bool sgm_cost16_needed(int cn, int ftz) { return cn != 1 || 2 * ftz + 63 > 255 || g_cost16.load(std::memory_order_relaxed); }
+bool sgm_cost16_forced() { return g_cost16.load(std::memory_order_relaxed) != 0; }
 
-// The fused kernel over (form, R, DQ)
-template <typename F>
-static void launch_pixbox(const SGMGeom& g, const SGMBuffers& b, const uint2* bl, const uint2* br, int Rw, int cost_limit, int n, hipStream_t stream)
+// The one step from a plan's form to its type: fn is called with a value of Cost8, Cost16<1>, Cost16<3> or CostCensus
+template <typename Fn>
+static void with_cost_form(SgmCostForm form, Fn&& fn)
 {
-    const int dq = g.D / 4, rps = 48, strips = (g.H + rps - 1) / rps, tx = 4 * (256 / dq);
-    const dim3 pgrid((g.W1 + tx - 1) / tx, strips, n), blk(256);
-#define RTDM_PB(RR, QQ) hipLaunchKernelGGL((k_sgm_pixbox<F, RR, QQ>), pgrid, blk, 0, stream, bl, br, b.C, g, rps, cost_limit, b.ovf)
-#define RTDM_PBQ(RR) do { switch (dq) { case 4: RTDM_PB(RR, 4); break; case 8: RTDM_PB(RR, 8); break; case 16: RTDM_PB(RR, 16); break; \
-                                       case 32: RTDM_PB(RR, 32); break; default: RTDM_PB(RR, 64); break; } } while (0)
-    switch (Rw) { case 0: RTDM_PBQ(0); break; case 1: RTDM_PBQ(1); break; case 2: RTDM_PBQ(2); break; default: RTDM_PBQ(3); break; }
-#undef RTDM_PBQ
-#undef RTDM_PB
-}
-
-// The block sum over a pixel-cost volume of type T: the row sums of a strip stay in registers for windows <= 17 (u8) / <= 13
-// (u16: the register ring of k_sgm_box<R> holds 64-bit loads as well; above it would spill), k_sgm_box_any above
-template <typename T>
-static void launch_box(const SGMGeom& g, const SGMBuffers& b, const T* pix, int Rw, int cost_limit, int n, hipStream_t stream)
-{
-    constexpr int RMAX = sizeof(T) == 1 ? 8 : 6;
-    const int rps = 48, strips = (g.H + rps - 1) / rps;
-    const dim3 bgrid((unsigned)(((size_t)g.W1 * (g.D / 4) + 255) / 256), strips, n), blk(256);
-    switch (Rw) {                                       // a case above RMAX launches nothing and leaves the switch for k_sgm_box_any
-#define RTDM_BOX(RR) case RR: if constexpr (RR <= RMAX) { hipLaunchKernelGGL((k_sgm_box<RR, T>), bgrid, blk, 0, stream, pix, b.C, g, rps, cost_limit, b.ovf); return; } break;
-        RTDM_BOX(0) RTDM_BOX(1) RTDM_BOX(2) RTDM_BOX(3) RTDM_BOX(4) RTDM_BOX(5) RTDM_BOX(6) RTDM_BOX(7) RTDM_BOX(8)
-#undef RTDM_BOX
+    switch (form) {
+        case SgmCostForm::BT8: return fn(Cost8{});
+        case SgmCostForm::BT16_GRAY: return fn(Cost16<1>{});
+        case SgmCostForm::BT16_COLOUR: return fn(Cost16<3>{});
+        case SgmCostForm::CENSUS: return fn(CostCensus{});
     }
-    hipLaunchKernelGGL(k_sgm_box_any<T>, bgrid, blk, 0, stream, pix, b.C, g, Rw, rps, cost_limit, b.ovf);
+}
+// ... and from a run-time value to a template argument: fn(std::integral_constant<int, V>) for the V of the list that v equals,
+// for the last one if it equals none (the plan sends no such value)
+template <int V0, int... V, typename Fn>
+static void with_int(int v, Fn&& fn)
+{
+    if (sizeof...(V) == 0 || v == V0) fn(std::integral_constant<int, V0>{});
+    else if constexpr (sizeof...(V) != 0) with_int<V...>(v, fn);
 }
 
-// The descriptor kernel over the window (cw, ch) in {3, 5, 7, 9} x {3, 5, 7} (the caller has checked them)
-static void launch_census(Plane8 L, Plane8 R, const SGMGeom& g, const SGMBuffers& b, int cw, int ch, int n, hipStream_t stream)
+// The whole cost stage as plan_sgm_cost planned it ("SGM: cost routes"): the bounds or the descriptors, the pixel-cost
+// volume where the plan has one, the block sum -> b.C, and last MODE_SGBM_3WAY's warm-up costs -> b.Cw: they read the records
+// before the caller reuses b.gr for the winners, and b.Cw may alias b.pix, which is dead only once C exists.
+void launch_sgm_cost(const SgmCostPlan& p, Plane8 L, Plane8 R, const SGMGeom& g, const SGMBuffers& b, int n, hipStream_t stream)
 {
-    const dim3 grid((g.W + 63) / 64, (g.H + 15) / 16, 2 * n), blk(256);
-#define RTDM_CEN(HW, HH) hipLaunchKernelGGL((k_sgm_census<HW, HH>), grid, blk, 0, stream, L, R, (uint2*)b.gl, (uint2*)b.gr, g.W, g.H, n)
-#define RTDM_CENH(HW) do { switch (ch) { case 3: RTDM_CEN(HW, 1); break; case 5: RTDM_CEN(HW, 2); break; default: RTDM_CEN(HW, 3); break; } } while (0)
-    switch (cw) { case 3: RTDM_CENH(1); break; case 5: RTDM_CENH(2); break; case 7: RTDM_CENH(3); break; default: RTDM_CENH(4); break; }
-#undef RTDM_CENH
-#undef RTDM_CEN
-}
-
-// The whole cost stage: the bounds, then pixel cost and block sum -> b.C -- fused for windows <= 7 and D in {16, 32, 64, 128,
-// 256} (the u8 form: only where no block cost can pass cost_limit; the u16 form checks it itself), otherwise two kernels with
-// the pixel-cost volume between them (u8: b.pix; u16: b.S, which is not written before the first path pass).  cost.kind ==
-// SGM_COST_CENSUS (gray only, N5: the caller has refused colour): descriptors instead of bounds and the u8 routes over
-// CostCensus; there is no 16-bit census form, rtdm_debug_sgm_cost16 changes nothing there.
-void launch_sgm_cost(Plane8 L, Plane8 R, const SGMGeom& g, const SGMBuffers& b, int blockSize, int cost_limit, int cn, int ftz,
-                     SgmCostKind cost, int n, hipStream_t stream)
-{
-    const dim3 blk(256), bnd((g.W + 255) / 256, g.H, 2 * n);
-    const int Rw = blockSize / 2, dq = g.D / 4;                         // D is a multiple of 16
-    const bool fused = Rw <= 3 && (dq == 4 || dq == 8 || dq == 16 || dq == 32 || dq == 64);
-    const dim3 xgrid((unsigned)(((size_t)g.W1 * dq + 255) / 256), g.H, n);
-    if (cost.kind == SGM_COST_CENSUS) {
-        launch_census(L, R, g, b, cost.cw, cost.ch, n, stream);
-        const uint2 *cl = (const uint2*)b.gl, *cr = (const uint2*)b.gr;
-        if (fused && !cost_limit) return launch_pixbox<CostCensus>(g, b, cl, cr, Rw, 0, n, stream);
-        hipLaunchKernelGGL(k_sgm_pix_census, xgrid, blk, 0, stream, cl, cr, b.pix, g);
-        return launch_box<uint8_t>(g, b, b.pix, Rw, cost_limit, n, stream);
-    }
-    if (cn == 3) hipLaunchKernelGGL(k_sgm_bounds<3>, bnd, blk, 0, stream, L, R, (uint2*)b.cl, (uint2*)b.cr, g.W, g.H, n, ftz);
-    else hipLaunchKernelGGL(k_sgm_bounds<1>, bnd, blk, 0, stream, L, R, (uint2*)b.gl, (uint2*)b.gr, g.W, g.H, n, ftz);
-    const uint2 *bl = (const uint2*)(cn == 3 ? b.cl : b.gl), *br = (const uint2*)(cn == 3 ? b.cr : b.gr);
-    if (!sgm_cost16_needed(cn, ftz)) {
-        if (fused && !cost_limit) return launch_pixbox<Cost8>(g, b, bl, br, Rw, 0, n, stream);
-        hipLaunchKernelGGL(k_sgm_pix, xgrid, blk, 0, stream, bl, br, b.pix, g);
-        launch_box<uint8_t>(g, b, b.pix, Rw, cost_limit, n, stream);
-    } else if (fused) {
-        if (cn == 3) launch_pixbox<Cost16<3>>(g, b, bl, br, Rw, cost_limit, n, stream);
-        else launch_pixbox<Cost16<1>>(g, b, bl, br, Rw, cost_limit, n, stream);
+    const dim3 blk(256);
+    const int rps = 48, strips = (g.H + rps - 1) / rps, tx = 4 * (256 / (g.D / 4));     // rows per strip, columns per tile, of the block sums
+    const auto items = [&](int rows) { return dim3((unsigned)(((size_t)g.W1 * (g.D / 4) + 255) / 256), rows, n); };   // a thread per sgm_item
+    uint2 *bl = (uint2*)(p.colour_records ? b.cl : b.gl), *br = (uint2*)(p.colour_records ? b.cr : b.gr);
+    if (p.form == SgmCostForm::CENSUS) {                     // the window (cw, ch) in {3, 5, 7, 9} x {3, 5, 7}: the caller has checked it
+        const dim3 grid((g.W + 63) / 64, (g.H + 15) / 16, 2 * n);
+        with_int<3, 5, 7, 9>(p.cw, [&](auto cw) { with_int<3, 5, 7>(p.ch, [&](auto ch) {
+            hipLaunchKernelGGL((k_sgm_census<decltype(cw)::value / 2, decltype(ch)::value / 2>), grid, blk, 0, stream, L, R, bl, br, g.W, g.H, n);
+        }); });
     } else {
-        if (cn == 3) hipLaunchKernelGGL(k_sgm_pix16<3>, xgrid, blk, 0, stream, bl, br, b.S, g);
-        else hipLaunchKernelGGL(k_sgm_pix16<1>, xgrid, blk, 0, stream, bl, br, b.S, g);
-        launch_box<uint16_t>(g, b, b.S, Rw, cost_limit, n, stream);
+        const dim3 grid((g.W + 255) / 256, g.H, 2 * n);
+        if (p.colour_records) hipLaunchKernelGGL(k_sgm_bounds<3>, grid, blk, 0, stream, L, R, bl, br, g.W, g.H, n, p.ftz);
+        else hipLaunchKernelGGL(k_sgm_bounds<1>, grid, blk, 0, stream, L, R, bl, br, g.W, g.H, n, p.ftz);
     }
-}
-
-// k_sgm_warm3 in the pixel-cost form launch_sgm_cost has just used for the same arguments, over the records it left in b.gl / b.gr
-// (colour: b.cl / b.cr) -> b.Cw.  blockSize 1: there is no C', nothing is launched.
-void launch_sgm_warm3(const SGMGeom& g, const SGMBuffers& b, int blockSize, int cost_limit, int cn, int ftz, SgmCostKind cost, int n,
-                      hipStream_t stream)
-{
-    const int Rw = blockSize / 2, wrows = sgm3_warm_rows(blockSize, g.H);
-    if (Rw == 0) return;
-    const Sgm3Stripes st = sgm3_stripes(g.H, blockSize);
-    const dim3 grid((unsigned)(((size_t)g.W1 * (g.D / 4) + 255) / 256), SGM3_STRIPES - 1, n), blk(256);
-    const bool census = cost.kind == SGM_COST_CENSUS;
-    const uint2 *bl = (const uint2*)(!census && cn == 3 ? b.cl : b.gl), *br = (const uint2*)(!census && cn == 3 ? b.cr : b.gr);
-#define RTDM_WARM3(F) hipLaunchKernelGGL((k_sgm_warm3<F>), grid, blk, 0, stream, bl, br, b.Cw, g, st, Rw, wrows, cost_limit, b.ovf)
-    if (census) RTDM_WARM3(CostCensus);
-    else if (!sgm_cost16_needed(cn, ftz)) RTDM_WARM3(Cost8);
-    else if (cn == 3) RTDM_WARM3(Cost16<3>);
-    else RTDM_WARM3(Cost16<1>);
-#undef RTDM_WARM3
+    with_cost_form(p.form, [&](auto form) {
+        using F = decltype(form); using T = typename F::Elem;
+        T* vol = p.volume == SgmCostVolume::PIX ? (T*)b.pix : (T*)b.S;
+        if (p.volume != SgmCostVolume::NONE) hipLaunchKernelGGL(k_sgm_pix<F>, items(g.H), blk, 0, stream, bl, br, vol, g);
+        switch (p.sum) {
+            case SgmCostSum::FUSED:                          // R <= 3 and D / 4 in {4, 8, 16, 32, 64}
+                with_int<0, 1, 2, 3>(p.R, [&](auto r) { with_int<4, 8, 16, 32, 64>(g.D / 4, [&](auto dq) {
+                    hipLaunchKernelGGL((k_sgm_pixbox<F, decltype(r)::value, decltype(dq)::value>), dim3((g.W1 + tx - 1) / tx, strips, n), blk, 0,
+                                       stream, bl, br, b.C, g, rps, p.cost_limit, b.ovf);
+                }); });
+                break;
+            case SgmCostSum::BOX:                            // R <= 8 on a u8 volume, <= 6 on a u16 one: above, the register ring would spill
+                with_int<0, 1, 2, 3, 4, 5, 6, 7, 8>(p.R, [&](auto r) {
+                    if constexpr (decltype(r)::value <= (sizeof(T) == 1 ? 8 : 6))
+                        hipLaunchKernelGGL((k_sgm_box<decltype(r)::value, T>), items(strips), blk, 0, stream, vol, b.C, g, rps, p.cost_limit, b.ovf);
+                });
+                break;
+            case SgmCostSum::BOX_ANY:
+                hipLaunchKernelGGL(k_sgm_box_any<T>, items(strips), blk, 0, stream, vol, b.C, g, p.R, rps, p.cost_limit, b.ovf);
+                break;
+        }
+        if (p.warm)
+            hipLaunchKernelGGL(k_sgm_warm3<F>, items(SGM3_STRIPES - 1), blk, 0, stream, bl, br, b.Cw, g, sgm3_stripes(g.H, 2 * p.R + 1), p.R,
+                               p.wrows, p.cost_limit, b.ovf);
+    });
 }
 
 }  // namespace rtdm

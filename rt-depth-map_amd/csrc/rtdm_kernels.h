@@ -9,6 +9,8 @@
 #include <atomic>
 #include <vector>
 
+#include "rtdm_sgm_cost_plan.h"
+
 namespace rtdm {
 
 // Process-wide state shared BETWEEN handles (two handles may be driven from two host threads): environment switches (test
@@ -258,15 +260,9 @@ size_t sgm_ring_words(int maxW, int D, int max_batch);
 struct SgmWin { int16_t d16, bd; uint16_t mins, pad; };
 void sgm_wide_set_mode(int m);     // rtdm_debug_sgm_wide_paths
 int sgm_wide_mode();
-// The pixel cost of a call (rtdm_sgm_set_cost): kind SGM_COST_BT (R1; cw, ch unused) or SGM_COST_CENSUS -- Hamming distance of
-// cw x ch census descriptors, cw in {3, 5, 7, 9}, ch in {3, 5, 7}, gray frames only.  The values
-// are RTDM_SGM_COST_* of include/rtdm.h.
-enum { SGM_COST_BT = 0, SGM_COST_CENSUS = 1 };
-struct SgmCostKind { int kind, cw, ch; };
-// The cost stage (k_sgm_cost.hip): bounds (census: descriptors, in b.gl / b.gr as well), pixel cost and block sum of n pairs
-// -> b.C; cost_limit, cn, ftz as for launch_sgm.
-void launch_sgm_cost(Plane8 L, Plane8 R, const SGMGeom& g, const SGMBuffers& b, int blockSize, int cost_limit, int cn, int ftz,
-                     SgmCostKind cost, int n, hipStream_t stream);
+// The cost stage (k_sgm_cost.hip) of n pairs as plan_sgm_cost (rtdm_sgm_cost_plan.h; DESIGN.md "SGM: cost routes") planned it:
+// bounds or census descriptors, pixel cost and block sum -> b.C, under MODE_SGBM_3WAY the warm-up costs -> b.Cw as well
+void launch_sgm_cost(const SgmCostPlan& p, Plane8 L, Plane8 R, const SGMGeom& g, const SGMBuffers& b, int n, hipStream_t stream);
 // The path passes between the cost stage and the winners' left-right check.  plan_sgm (k_sgm.hip) decides, once per call and
 // without touching the runtime, what launch_sgm then issues; the route table is in DESIGN.md ("SGM: routes").  Directions are
 // indexed 0..7 = (1,0) (-1,0) (0,1) (0,-1) (1,1) (-1,1) (1,-1) (-1,-1): paths 4 runs 0..3, paths 5 those with dy >= 0, paths 8 all,
@@ -301,17 +297,15 @@ void sgm_sweep_caps(int D, int paths, bool s2, int cap[2][3][2]);   // asks the 
 // not been added to S; swept -- a sweep ran.
 struct SgmDone { unsigned dirs; bool s2_pending, swept; };
 SgmPlan plan_sgm(const SGMGeom& g, int paths, int n, const SgmLimits& lim, SgmDone done = SgmDone{0, false, false});
-// cost_limit > 0: block costs above it set *b.ovf (the caller reads it back: api_sgm.hip).  cn: 1 (gray) or 3 (interleaved
-// colour, reads b.cl / b.cr); ftz: R1's ftzero = max(preFilterCap, 15) | 1, at most 127.  Where a pixel cost can pass 255
-// (sgm_cost16_needed: colour, ftz >= 97, or rtdm_debug_sgm_cost16) the cost stage runs on u16 pixel costs.  cost: the pixel
-// cost; under SGM_COST_CENSUS ftz is not read and cn is 1.
-struct SgmParams { int blockSize, P1, P2, uniq, disp12MaxDiff, speckleWindowSize, speckleRange, cost_limit, cn, ftz; SgmCostKind cost; };
-// Cost stage, the passes of plan_sgm, sgm_finish.  Returns the plan's variant.  A sweep that the runtime refuses before
+// cn: 1 (gray) or 3 (interleaved colour, reads b.cl / b.cr); ftz: R1's ftzero = max(preFilterCap, 15) | 1, at most 127; cost: the pixel
+// cost; under SGM_COST_CENSUS ftz is not read and cn is 1.  What the cost stage makes of them, its limit included: plan_sgm_cost.
+struct SgmParams { int blockSize, P1, P2, uniq, disp12MaxDiff, speckleWindowSize, speckleRange, cn, ftz; SgmCostKind cost; };
+// The cost stage of plan_sgm_cost, the passes of plan_sgm, sgm_finish.  Returns the plan's variant.  A sweep that the runtime refuses before
 // anything was launched: the remainder runs as plan_sgm plans it without sweeps.
 const char* launch_sgm(Plane8 L, Plane8 R, Plane16W disp, const SGMGeom& g, const SGMBuffers& b, const SgmLimits& lim, int paths,
                        int n, hipStream_t stream, SgmParams p);
-bool sgm_cost16_needed(int cn, int ftz);
-void sgm_cost16_set(int on);
+void sgm_cost16_set(int on);       // rtdm_debug_sgm_cost16
+bool sgm_cost16_forced();
 
 // Depth statistics after the matcher (estimator.cpp:75-77, 206-263).  q = the 4x4 reprojection matrix Q, row major.
 struct DepthQ { double q[16]; };

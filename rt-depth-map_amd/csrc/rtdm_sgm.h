@@ -193,11 +193,8 @@ struct SgmCall { const SGMGeom& g; const SGMBuffers& b; int P1, P2, uniq, n; Sgm
 void launch_sgm_wide(const SgmPass& p, const SgmCall& c);
 void launch_path_h(const SgmPass& p, const SgmCall& c);
 void launch_vert(const SgmPass& p, const SgmCall& c);
-// MODE_SGBM_3WAY (T1-T8): the warm-up block costs C' of stripes 1 .. 3 -> b.Cw (k_sgm_cost.hip, after
-// launch_sgm_cost and with its arguments: the bounds or descriptors are still in place), and the striped vertical pass that
-// reads them and decides the winners (k_sgm_paths.hip).  Rows of C' kept per stripe: sgm3_warm_rows (rtdm_sgm_stripes.h).
-void launch_sgm_warm3(const SGMGeom& g, const SGMBuffers& b, int blockSize, int cost_limit, int cn, int ftz, SgmCostKind cost, int n,
-                      hipStream_t stream);
+// MODE_SGBM_3WAY (T1-T8): the striped vertical pass that reads the warm-up block costs C' of stripes
+// 1 .. 3 (b.Cw: the cost stage's last kernel) and decides the winners.  Rows of C' kept per stripe: sgm3_warm_rows (rtdm_sgm_stripes.h).
 void launch_vert3(const SgmPass& p, const SgmCall& c);
 // false: the runtime refused (device, sweep stream or event record) before anything was launched
 bool launch_sweep(const SgmPass& p, const SgmCall& c);

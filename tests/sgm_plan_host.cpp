@@ -25,7 +25,8 @@ static void print_plan(const long long* v)
     for (int i = 0; i < 12; ++i) (&lim.cap[0][0][0])[i] = (int)v[11 + i];
     sgm_wide_set_mode((int)v[7]);
     const SgmPlan p = plan_sgm(g, (int)v[1], (int)v[3], lim, SgmDone{(unsigned)v[8], v[9] != 0, v[10] != 0});
-    static const char* const kinds[] = {"WIDE", "PATH_H", "VERT", "SWEEP", "ADD_S2"};
+    static const char* const kinds[] = {"WIDE", "PATH_H", "VERT", "SWEEP", "ADD_S2", "VERT3"};
+    static_assert(sizeof kinds / sizeof *kinds == (int)SgmStep::VERT3 + 1, "a name per SgmStep");
     for (int i = 0; i < p.npasses; ++i) {
         const SgmPass& q = p.pass[i];
         printf("%s %s (%d,%d) first=%d last=%d s2=%d", p.variant, kinds[(int)q.step], q.dx, q.dy, (int)q.first, (int)q.last, (int)q.s2);

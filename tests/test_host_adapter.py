@@ -46,7 +46,8 @@ def test_makefile_build_hip_rule_compiles_a_kernel_for_gfx950(tmp_path):
     csrc = os.path.join(ROOT, "rt-depth-map_amd", "csrc")
     inc = tmp_path / "include"
     inc.mkdir()
-    shutil.copy(os.path.join(csrc, "rtdm_kernels.h"), inc / "rtdm_kernels.h")
+    for h in ("rtdm_kernels.h", "rtdm_sgm_cost_plan.h"):                              # (the second: included by the first)
+        shutil.copy(os.path.join(csrc, h), inc / h)
     src = open(os.path.join(csrc, "k_synth.hip")).read().replace('#include "rtdm_kernels.h"', '#include <rtdm_kernels.h>')
     (mod / "k_synth.hip").write_text(src)
     dry = subprocess.run(["make", "-n", "_all"], cwd=tmp_path, capture_output=True, text=True)

@@ -60,6 +60,10 @@ def WD(k, waves, last=0):
     return "WIDE (%d,%d) first=%d last=%d s2=0 waves=%d" % (DIRS[k][0], DIRS[k][1], k == 0, last, waves)
 
 
+def V3(s2=0):
+    return "VERT3 (0,1) first=0 last=1 s2=%d" % s2
+
+
 ADD = "ADD_S2 (0,0) first=0 last=0 s2=0"
 
 # W1 = 61: 8 / 4 / 2 strips of 8 / 16 / 32 columns.  (number of the row in DESIGN.md, configuration, hooks, variant, passes)
@@ -100,6 +104,13 @@ ROUTES = [
     (30, Cfg(paths=8, s2=0, sweep=0, done=(0b11, 0, 0)), {}, "half", [H(k, last=k == 7) for k in range(2, 8)]),
     (31, Cfg(paths=5, sweep=0, done=(0b11, 1, 0)), {}, "half", [ADD, H(2), H(4), H(5, last=1)]),
     (32, Cfg(paths=8, sweep=0, done=(0b00110111, 0, 1)), {}, "sweep", [H(3), H(6), H(7, last=1)]),
+    # MODE_SGBM_3WAY: with S2, without it or under RTDM_SGM_DUAL=0 (two configurations of row 34), and under the hook and the
+    # debug switch that it does not consult (two of row 35)
+    (33, Cfg(paths=3), {}, "vert3", [H(0, s2=1), V3(s2=1)]),
+    (34, Cfg(paths=3, s2=0), {}, "vert3", [H(0), H(1), V3()]),
+    (34, Cfg(paths=3), {"RTDM_SGM_DUAL": "0"}, "vert3", [H(0), H(1), V3()]),
+    (35, Cfg(paths=3), {"RTDM_SGM_SWEEP": "0"}, "vert3", [H(0, s2=1), V3(s2=1)]),
+    (35, Cfg(paths=3, wide=4, sweep=0, ring=0), {}, "vert3", [H(0, s2=1), V3(s2=1)]),
 ]
 
 
@@ -141,14 +152,15 @@ def test_the_command_line_form_prints_the_same(exe):
     assert subprocess.run([exe, "1", "2"], capture_output=True).returncode == 2
 
 
-@pytest.mark.parametrize("row", ROUTES, ids=lambda r: "row%d" % r[0])
+@pytest.mark.parametrize("row", ROUTES, ids=["row%d%s" % (r[0], "b" if i and ROUTES[i - 1][0] == r[0] else "") for i, r in enumerate(ROUTES)])
 def test_route_table(exe, row):
     num, cfg, hooks, variant, passes = row
     assert run(exe, [cfg], hooks) == [(variant, passes)], num
 
 
 def test_route_rows_are_numbered_in_order_and_fit_a_plan():
-    assert [r[0] for r in ROUTES] == list(range(1, len(ROUTES) + 1))
+    nums = [r[0] for r in ROUTES]                         # (rows 34 and 35 name two configurations each)
+    assert nums == sorted(nums) and sorted(set(nums)) == list(range(1, 36))
     assert all(1 <= len(r[4]) <= 8 for r in ROUTES)
 
 
@@ -186,6 +198,11 @@ def model_sweep(c, hooks, last, add2, probe=False, refused=False):
 
 def model(c, hooks, refuse=None):
     """-> (variant, passes) of a whole call"""
+    if c.paths == 3:
+        # MODE_SGBM_3WAY (DESIGN.md section 4.21, T4 / T5; newer than the launcher restated below): the horizontal pair as for
+        # MODE_HH4, then the striped downward pass; no sweep, no wide form, RTDM_SGM_DUAL = 0 keeps its meaning
+        dual = bool(int(hooks.get("RTDM_SGM_DUAL", 1)) and c.s2)
+        return "vert3", [H(0, s2=dual)] + ([] if dual else [H(1)]) + [V3(s2=dual)]
     last_dir = {4: 3, 5: 5, 8: 7}[c.paths]
     if c.D > 256 or c.wide:
         waves = 4 if (c.wide == 4 or c.D > 1024) else 1

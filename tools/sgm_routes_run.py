@@ -5,7 +5,10 @@ sum of the results.  Meant to run under `rocprofv3 --kernel-trace` on two trees 
 (profiles/sgm_plan_launches.txt):
     python tools/sgm_routes_run.py [TREE]          TREE: the checkout whose package is loaded (default: this one)
     python tools/sgm_routes_run.py TREE first      instead: wall time of the first and the second `compute` of a fresh
-                                                   MODE_HH handle (1280x720, D = 128) in a process that has run the mode before"""
+                                                   MODE_HH handle (1280x720, D = 128) in a process that has run the mode before
+    python tools/sgm_routes_run.py TREE cost       instead: the rows of the cost-route table ("SGM: cost routes"), one small call
+                                                   pair per case of tests/sgm_cost_routes.py (this checkout's, whatever TREE
+                                                   is); compared in profiles/sgm_cost_plan_launches.txt"""
 import importlib, os, sys, time
 tree = os.path.abspath(sys.argv[1]) if len(sys.argv) > 1 else os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, tree)
@@ -26,6 +29,28 @@ if len(sys.argv) > 2 and sys.argv[2] == "first":
             t0 = time.perf_counter(); sg.compute(L, R); t.append((time.perf_counter() - t0) * 1e3)
         print("fresh MODE_HH handle %d: first compute %.3f ms, second %.3f ms (%s)" % (k, t[0], t[1], sg.path_variant), flush=True)
         sg.close()
+    sys.exit(0)
+
+if len(sys.argv) > 2 and sys.argv[2] == "cost":
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import sgm_cost_routes as routes
+    M = pkg.HIPSemiGlobalMatcher
+    st = torch.cuda.current_stream().cuda_stream
+    for c in routes.CASES:
+        frames = c.frames()
+        Ls, Rs = np.stack([f[0] for f in frames]), np.stack([f[1] for f in frames])
+        pkg.binding.lib().rtdm_debug_sgm_cost16(c.f16)
+        sg = M(numOfDisparities=c.D, blockSize=c.bs, P1=routes.P1, P2=c.P2, width=c.W, height=c.H, max_batch=3, preFilterCap=c.cap,
+               paths=5 if c.paths == 3 else c.paths, **(dict(cost=M.COST_CENSUS, census=c.census) if c.census else {}))
+        if c.paths == 3: sg.setMode(M.MODE_SGBM_3WAY)
+        one = sg.compute(Ls[0], Rs[0])
+        dD = torch.zeros((3, c.H, c.W), dtype=torch.int16, device="cuda")
+        sg.compute_device(torch.from_numpy(Ls).cuda(), torch.from_numpy(Rs).cuda(), dD, st)
+        torch.cuda.synchronize()
+        print("%s (%s) paths %d: %s sums %d %d" % (c.name, routes.ROWS[c.row], c.paths, sg.path_variant,
+                                                   int(one.astype(np.int64).sum()), int(dD.cpu().numpy().astype(np.int64).sum())), flush=True)
+        sg.close()
+        pkg.binding.lib().rtdm_debug_sgm_cost16(0)
     sys.exit(0)
 
 # (paths, D, W - D, H)
